@@ -85,7 +85,18 @@ def parse():
     ap.add_argument("--side-runner", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-extras", action="store_true",
                     help="bursts workload: skip the measurements after the timed region (planar layout, the other decoder)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="bursts workload: after the timed steps, write what the last timed step returned (l2, crc, conv, toa, "
+                         "freq_err, rv per burst, and burst_index) as DIR/<name>.npy in float32 / float64, at most 64 MB in all "
+                         "(a fixed, seeded sample of the bursts beyond that); rank 0's batch when N > 1.  bench_outputs/ is "
+                         "git-ignored")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.workload != "bursts":
+        ap.error("--dump-outputs is implemented for the headline workload (bursts) only")
     # read by the library on first use and by tests/oracle_lib.py when it loads the oracle; inherited by spawned ranks
     os.environ["GMR1_HIP_CONV_DECODER"] = args.conv_decoder
     os.environ["ORC_CONV_MODE"] = "1" if args.conv_decoder == "acc" else "0"
@@ -120,6 +131,23 @@ def emit(out, **kw):
         if lib and "prof" in os.path.basename(lib):
             out["config"]["profiling_build"] = True
     print(json.dumps(out), **kw)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: {name: (array with one row per burst, float dtype that holds its values exactly)} -> DIR/<name>.npy.
+    Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of the bursts is written, the same one in every run with the same
+    arguments; burst_index.npy says which bursts the rows are."""
+    n = len(next(iter(arrays.values()))[0])
+    per_burst = 8 + sum(a.size // n * np.dtype(t).itemsize for a, t in arrays.values())     # 8: burst_index
+    keep = min(n, (DUMP_LIMIT_BYTES - 4096) // per_burst)          # 4096: the .npy headers
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "burst_index.npy"), idx.astype(np.float64))
+    for name, (a, t) in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a[idx].astype(t))
 
 
 def preroll(step, seconds):
@@ -1491,6 +1519,12 @@ def main():
         clock["compute_units"] = props.multi_processor_count
     except Exception as e:
         clock["error"] = repr(e)
+    # what the last timed step returned, taken behind the clock probe (which writes none of
+    # them) and before anything else after the timed region launches into the same buffers
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"l2": (l2.cpu().numpy(), np.float32), "crc": (crc.cpu().numpy(), np.float64),
+                                         "conv": (conv.cpu().numpy(), np.float64), "toa": (toa.cpu().numpy(), np.float32),
+                                         "freq_err": (ferr.cpu().numpy(), np.float32), "rv": (rv.cpu().numpy(), np.float64)})
 
     if grouped:
         import torch.distributed as dist

@@ -1,6 +1,7 @@
-"""Reads the integer tables of the reference's C sources as TEXT (container only: /root/reference does not exist
-on the GPU box, tests using this skip there).  Nothing is copied into the repo: the tables are parsed at test time
-and compared with the oracle's and the product's own transcriptions.
+"""Reads the integer tables of the reference's C sources as TEXT, and compares them with the oracle's and the product's own
+transcriptions.  Where the reference's sources are not on the machine (the GPU box, a fresh checkout elsewhere), what the
+parsers return comes from tests/golden/ref_tables.json instead: the same parse, written by tests/golden/make_ref_tables.py
+as data only (integer tables, names, formula checks), and pinned to the files by test_ref_tables.py wherever they exist.
 
   conv.c    every `next_output` / `next_state` array, every `struct osmo_conv_code` initialiser, and the generator
             polynomials written in the comment above each code (reference src/l1/conv.c)
@@ -9,14 +10,48 @@ and compared with the oracle's and the product's own transcriptions.
 """
 from __future__ import annotations
 
+import functools
+import json
 import os
 import re
+import sys
 
 REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_tables.json")
+PARSERS = {}                 # golden key -> the parser reading the reference's files
+
+
+def live() -> bool:
+    """The reference's sources are here: the parsers read them."""
+    return os.path.isfile(os.path.join(REF, "src", "l1", "conv.c"))
 
 
 def available() -> bool:
-    return os.path.isfile(os.path.join(REF, "src", "l1", "conv.c"))
+    return live() or os.path.isfile(GOLDEN)
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def _or_golden(key, restore=lambda v: v):
+    """The parser when the reference's files are here, else its result as stored in the golden file (`restore` turns the
+    JSON lists back into the tuples the parser returns)."""
+    def wrap(parse):
+        PARSERS[key] = parse
+
+        @functools.wraps(parse)
+        def get():
+            return parse() if live() else restore(_golden()[key])
+        return get
+    return wrap
+
+
+def parse_all():
+    """Every parser's result, as tests/golden/ref_tables.json holds it."""
+    return json.loads(json.dumps({k: f() for k, f in PARSERS.items()}))
 
 
 def _read(rel):
@@ -39,6 +74,7 @@ def _const_expr(s):
     return int(eval(s, {"__builtins__": {}}))
 
 
+@_or_golden("conv")
 def parse_conv():
     """-> {code name: dict(N, K, next_output [[o0, o1]...], next_state [[s0, s1]...], polys_comment [int...])}.
     polys_comment: the g_i(D) of the comment above the code's output table as masks, bit i = D^i;
@@ -99,6 +135,7 @@ def trellis_from_polys(N, K, polys):
     return out, nxt
 
 
+@_or_golden("punct")
 def parse_punct():
     """-> {name: dict(r, L, N, mask [0/1...])}, in file order."""
     src = _strip_comments(_read("src/l1/punct.c"))
@@ -150,6 +187,14 @@ def puncturer_generate(N, coded_len, pre, main, post, repeat):
     return p
 
 
+def _restore_nb(bursts):
+    for b in bursts.values():
+        b["sync"] = [[(p, syms) for p, syms in seq] for seq in b["sync"]]
+        b["data"] = [tuple(c) for c in b["data"]]
+    return bursts
+
+
+@_or_golden("nb", _restore_nb)
 def parse_nb():
     """-> {burst name ('bcch', 'dc2', ...): dict(mod, guard_pre, guard_post, len, ebits, sync [[(pos, [syms])...]...],
     data [(pos, len)...])}."""
@@ -184,6 +229,7 @@ def parse_nb():
     return bursts
 
 
+@_or_golden("modulations")
 def parse_modulations():
     """-> {'gmr1_pi4cqpsk': dict(rotation_expr, nbits, syms [(idx, data bits..., re, im)])} from src/sdr/pi4cxpsk.c:71-115."""
     src = _strip_comments(_read("src/sdr/pi4cxpsk.c"))
@@ -194,3 +240,52 @@ def parse_modulations():
         nbits = int(re.search(r"\.nbits\s*=\s*(\d+)", body).group(1))
         mods[m.group(1)] = dict(rotation_expr=rot, nbits=nbits)
     return mods
+
+
+@_or_golden("punct_declared")
+def parse_punct_declared():
+    """The puncturer names include/osmocom/gmr1/l1/punct.h declares (punct.h:54-106), in order."""
+    return re.findall(r"extern const struct gmr1_puncturer (\w+);", _read("include/osmocom/gmr1/l1/punct.h"))
+
+
+@_or_golden("scramb")
+def parse_scramb():
+    """src/l1/scramb.c: the register's initial value (:39) and whether the step is b = bit 14 ^ bit 0, shifted in at
+    the bottom (:47-48)."""
+    src = _read("src/l1/scramb.c")
+    init = int(re.search(r"#define GMR1_SCRAMBLE_REG_INIT\s+(0x[0-9a-fA-F]+)", src).group(1), 16)
+    step = re.search(r"b = \(\(reg_val >> 14\) \^ reg_val\) & 1;\s*\*reg = \(reg_val << 1\) \| b;", src)
+    return dict(reg_init=init, step_bit14_xor_bit0=bool(step))
+
+
+@_or_golden("interleave")
+def parse_interleave():
+    """src/l1/interleave.c:46-87: whether the intra-burst index is formed from ((5 * kc) & 7)."""
+    isrc = _read("src/l1/interleave.c")
+    return dict(index_5kc_and_7=bool(re.search(r"\(\s*\(\s*5\s*\*\s*\w+\s*\)\s*&\s*7\s*\)", isrc)
+                                     or "5 * kc" in isrc or "5*kc" in isrc))
+
+
+@_or_golden("crc", lambda d: {k: tuple(v) for k, v in d.items()})
+def parse_crc():
+    """src/l1/crc.c: {code name: (bits, poly, init, remainder)}."""
+    src = _strip_comments(_read("src/l1/crc.c"))
+    got = {}
+    for m in re.finditer(r"const struct osmo_crc\d+gen_code (\w+)\s*=\s*\{(.*?)\};", src, flags=re.S):
+        f = {k: int(v, 0) for k, v in re.findall(r"\.(\w+)\s*=\s*(0x[0-9a-fA-F]+|\d+)", m.group(2))}
+        got[m.group(1)] = (f["bits"], f["poly"], f["init"], f["remainder"])
+    return got
+
+
+@_or_golden("gmr1_rx_identifiers")
+def parse_gmr1_rx_identifiers():
+    """Every gmr1_* identifier the reference's application src/gmr1_rx.c names, sorted."""
+    return sorted(set(re.findall(r"\b(gmr1_[a-z0-9_]+)\b", _read("src/gmr1_rx.c"))))
+
+
+@_or_golden("ambe_codebooks", lambda d: {k: tuple(v) for k, v in d.items()})
+def parse_ambe_codebooks():
+    """src/codec/tables.c (+ rho of synth.c) through tools/gen_ambe_tables.py: {short name: (dims, kind, words)}."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import gen_ambe_tables
+    return gen_ambe_tables.parse(os.path.join(REF, "src", "codec", "tables.c"))

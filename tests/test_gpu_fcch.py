@@ -124,7 +124,7 @@ def test_fcch_rough_multi(gpu_api, orc, pkg):
     assert g == orc.fcch_rough_multi(noise, SPS)[0]
 
 
-def test_folded_sweep_fallback_and_dc_offset(gpu_api, orc, pkg):
+def test_folded_sweep_fallback_and_dc_offset(gpu_api, orc, pkg, tmp_path):
     """The folded rough sweep (k_fcch_sweep<NT, true>: a tile finishes its own lags once every tile of the stream has published
     its statistics) and its fallback.  (1) Streams with a DC offset much larger than the signal -- the mean's contribution to
     every lag, the one thing a tile cannot know by itself, decides the peak here -- give the oracle's toa.  (2) The profiling
@@ -150,11 +150,12 @@ def test_folded_sweep_fallback_and_dc_offset(gpu_api, orc, pkg):
     prof = os.path.join(root, "osmo-gmr_amd", "libgmr1_hip_prof.so")
     if not os.path.exists(prof):
         pytest.skip("the profiling build (python osmo-gmr_amd/build.py --profile) is not there")
-    np.save("/tmp/_fold_streams.npy", x)
+    f_in = str(tmp_path / "fold_streams.npy")
+    np.save(f_in, x)
     code = ("import sys, json, numpy as np; sys.path.insert(0, %r); from __graft_entry__ import load_package; pkg = load_package(); "
-            "import torch; torch.cuda.init(); pkg.api.load(); pkg.api.init(0); x = np.load('/tmp/_fold_streams.npy'); "
+            "import torch; torch.cuda.init(); pkg.api.load(); pkg.api.init(0); x = np.load(%r); "
             "toa, rv = pkg.api.fcch_rough_batch(x, (np.arange(%d) * %d).astype(np.uint64), %d, sps=%d); "
-            "print(json.dumps([int(t) for t in toa] + [int(r) for r in rv]))" % (root, n, ns, ns, SPS))
+            "print(json.dumps([int(t) for t in toa] + [int(r) for r in rv]))" % (root, f_in, n, ns, ns, SPS))
     for switch in ("GMR1_HIP_FCCH_FOLD_POLLS", "GMR1_HIP_FCCH_UNFOLDED"):
         env = dict(os.environ, GMR1_HIP_LIBRARY=prof)
         env[switch] = "0" if switch.endswith("POLLS") else "1"

@@ -1,10 +1,12 @@
 """The integer tables of the reference, read from its own source files, against the oracle's and the product's.
 
-Container only (skipped where /root/reference is absent, i.e. on the GPU box): tests/ref_parse.py parses
+tests/ref_parse.py parses
 src/l1/conv.c (every trellis table + the polynomials in its comments), src/l1/punct.c (all 51 masks),
 src/sdr/nb.c (all 10 burst formats) and the formulas of scramb.c / interleave.c are restated from the cited lines.
 This replaces hand-typed spot rows as the pin of every integer table on the path: the oracle's (oracle/orc_*.c)
-and the product's (host tables, encoder plans, exported description objects) are compared entry by entry.
+and the product's (host tables, encoder plans, exported description objects) are compared entry by entry.  Where the
+reference's sources are absent, the parse stored in tests/golden/ref_tables.json stands in (the first test below pins
+that file to the sources wherever they are present).
 """
 import ctypes as C
 import os
@@ -14,7 +16,7 @@ import pytest
 
 import ref_parse
 
-pytestmark = pytest.mark.skipif(not ref_parse.available(), reason="/root/reference is not present on this machine")
+pytestmark = pytest.mark.skipif(not ref_parse.available(), reason="neither the reference's sources nor tests/golden/ref_tables.json")
 
 
 class OrcCode(C.Structure):
@@ -30,6 +32,14 @@ def _orc_code(orc, fn, which):
     f = getattr(orc.lib(), fn)
     f.restype = C.POINTER(OrcCode)
     return f(C.c_int(which)).contents
+
+
+@pytest.mark.skipif(not ref_parse.live(), reason="the reference's sources are not on this machine")
+def test_golden_parse_equals_the_reference_files():
+    """tests/golden/ref_tables.json (what the tests below read where the sources are absent) is the parse of the files."""
+    import json
+    with open(ref_parse.GOLDEN) as f:
+        assert json.load(f) == ref_parse.parse_all()
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -135,9 +145,7 @@ def test_all_masks_parse_and_are_self_consistent():
     masks = ref_parse.parse_punct()
     assert len(masks) == 51          # punct.h:54-106 declares 51 (SURVEY.md counts 53)
     # the names punct.h declares (reference include/osmocom/gmr1/l1/punct.h:54-106) are exactly these
-    import re
-    with open(os.path.join(ref_parse.REF, "include/osmocom/gmr1/l1/punct.h")) as f:
-        declared = re.findall(r"extern const struct gmr1_puncturer (\w+);", f.read())
+    declared = ref_parse.parse_punct_declared()
     assert declared == list(masks)
     for name, m in masks.items():
         assert len(m["mask"]) == m["L"] * m["N"], name
@@ -201,10 +209,9 @@ def test_all_10_burst_formats_equal_nb_c(pkg, orc):
 # scramb.c / interleave.c / crc.c: formulas and parameters as the files state them
 # ---------------------------------------------------------------------------------------------------------------
 def test_scrambler_and_interleavers_follow_the_reference_formulas(pkg, orc):
-    import re
-    src = open(os.path.join(ref_parse.REF, "src/l1/scramb.c")).read()
-    init = int(re.search(r"#define GMR1_SCRAMBLE_REG_INIT\s+(0x[0-9a-fA-F]+)", src).group(1), 16)     # scramb.c:39
-    assert re.search(r"b = \(\(reg_val >> 14\) \^ reg_val\) & 1;\s*\*reg = \(reg_val << 1\) \| b;", src)  # :47-48
+    scramb = ref_parse.parse_scramb()
+    init = scramb["reg_init"]                             # scramb.c:39
+    assert scramb["step_bit14_xor_bit0"]                  # :47-48
     r, bits = init, []
     for _ in range(662):                                  # longest burst (NT9)
         b = ((r >> 14) ^ r) & 1
@@ -214,8 +221,7 @@ def test_scrambler_and_interleavers_follow_the_reference_formulas(pkg, orc):
     got = orc.scramble_sbit(ones)
     assert np.array_equal(got < 0, np.array(bits, bool))
     # intra-burst (de)interleaver, interleave.c:46-87: kep = N * ((5 * kc) & 7) + (kc >> 3)
-    isrc = open(os.path.join(ref_parse.REF, "src/l1/interleave.c")).read()
-    assert re.search(r"\(\s*\(\s*5\s*\*\s*\w+\s*\)\s*&\s*7\s*\)", isrc) or "5 * kc" in isrc or "5*kc" in isrc
+    assert ref_parse.parse_interleave()["index_5kc_and_7"]
     for N in (12, 14, 33, 53, 80, 81):
         x = np.random.default_rng(N).integers(0, 256, 8 * N).astype(np.uint8)
         kc = np.arange(8 * N)
@@ -223,12 +229,7 @@ def test_scrambler_and_interleavers_follow_the_reference_formulas(pkg, orc):
 
 
 def test_crc_parameters_equal_crc_c(orc):
-    import re
-    src = ref_parse._strip_comments(open(os.path.join(ref_parse.REF, "src/l1/crc.c")).read())
-    got = {}
-    for m in re.finditer(r"const struct osmo_crc\d+gen_code (\w+)\s*=\s*\{(.*?)\};", src, flags=re.S):
-        f = {k: int(v, 0) for k, v in re.findall(r"\.(\w+)\s*=\s*(0x[0-9a-fA-F]+|\d+)", m.group(2))}
-        got[m.group(1)] = (f["bits"], f["poly"], f["init"], f["remainder"])
+    got = ref_parse.parse_crc()
     assert got == {"gmr1_crc8": (8, 0x9b, 0, 0), "gmr1_crc12": (12, 0x80f, 0, 0), "gmr1_crc16": (16, 0x1021, 0, 0)}
 
     class Crc(C.Structure):
