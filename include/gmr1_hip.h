@@ -83,7 +83,8 @@ struct gmr1_hip_burst_flat {
  * they take turns.  The host part of such a call runs under a per-device lock (a second thread waits), and a call
  * on another stream first makes its stream wait, on the device, for the previous user's kernels; nothing is
  * refused and no result depends on the interleaving (tests/test_gpu_threads.py).  They do not run in PARALLEL
- * with each other on one device: one receiver per GPU, as in the reference (one process per capture). */
+ * with each other on one device: one receiver per GPU, as in the reference (one process per capture).  The streaming
+ * channelizer (gmr1_hip_chan_stream_*) does not use the workspace: its handles own their memory and run concurrently. */
 int         gmr1_hip_init(int device);          /* optional; selects the HIP device     */
 const char *gmr1_hip_last_error(void);
 const char *gmr1_hip_version(void);
@@ -392,6 +393,31 @@ int gmr1_hip_channelize(double samp_rate, int sps, const float *wide, uint64_t n
 int gmr1_hip_channelize_planar_dev(void *stream, double samp_rate, int sps, const float *wide, uint64_t n_in,
                                    float rotation, int n_sel, const int32_t *chan_idx,
                                    float *out_planes, uint64_t out_stride, uint64_t plane_stride, uint64_t *n_out);
+
+/* Streaming form of the two front ends above, for a capture that arrives in pieces (an SDR read loop, a file read block by
+ * block): a handle, created once per (mode, sample rate, sps, selection) on the current device, carries the filters'
+ * history, the resamplers' phases and the direct mode's decimation and mixer phases from one push to the next.  A push of
+ * the next n_in wideband samples writes, per selected stream, exactly the outputs that have become computable:
+ * n_out(N + n_in) - n_out(N), N = samples pushed before, n_out() the one-shot count (gmr1_hip_channelize_plan /
+ * gmr1_hip_ddc_plan).  The outputs of any sequence of pushes, concatenated, are IDENTICAL to one gmr1_hip_channelize /
+ * gmr1_hip_ddc call on the same samples (any chunk sizes, 0 included; no flush is needed: every output is causal).
+ * Creation refuses what the one-shot calls refuse (-EINVAL).  gmr1_hip_chan_stream_out_len: the count the next push of
+ * n_in samples will write (host arithmetic).  _push_dev enqueues on `stream` and returns (wide, out: device memory the
+ * caller keeps alive until the stream has run); pushes on one handle are ordered, from any thread and any stream (a push
+ * on another stream than the previous one waits for it); a refused push (-EINVAL) leaves the handle as it was.  The handle
+ * owns its device memory (the input's tail, grow-only intermediate streams): after the first push of a size, pushes
+ * allocate nothing.  _push: host arrays, synchronous.  _destroy waits for the handle's last push. */
+struct gmr1_hip_chan_stream;
+int gmr1_hip_channelize_stream_create(double samp_rate, int sps, float rotation, int n_sel, const int32_t *chan_idx,
+                                      struct gmr1_hip_chan_stream **h);
+int gmr1_hip_ddc_stream_create(double samp_rate, int sps, int n_sel, const double *freq_hz,
+                               struct gmr1_hip_chan_stream **h);
+int gmr1_hip_chan_stream_out_len(const struct gmr1_hip_chan_stream *h, uint64_t n_in, uint64_t *n_out);
+int gmr1_hip_chan_stream_push_dev(void *stream, struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in,
+                                  float *out, uint64_t out_stride, uint64_t *n_out);
+int gmr1_hip_chan_stream_push(struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in,
+                              float *out, uint64_t out_stride, uint64_t *n_out);
+int gmr1_hip_chan_stream_destroy(struct gmr1_hip_chan_stream *h);
 
 /* ------------------------------------------------------------------------
  * The gmr1_rx receive loop over many BCCH carriers (reference src/gmr1_rx.c:605-895 and

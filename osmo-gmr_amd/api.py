@@ -60,6 +60,8 @@ EXPORTED_FUNCTIONS = [
     "gmr1_interleave_inter", "gmr1_deinterleave_inter",
     "gmr1_puncturer_generate",
     "gmr1_hip_ddc_plan", "gmr1_hip_ddc_dev", "gmr1_hip_ddc",
+    "gmr1_hip_channelize_stream_create", "gmr1_hip_ddc_stream_create", "gmr1_hip_chan_stream_out_len",
+    "gmr1_hip_chan_stream_push_dev", "gmr1_hip_chan_stream_push", "gmr1_hip_chan_stream_destroy",
     "gmr1_hip_shard_unique_id", "gmr1_hip_shard_create", "gmr1_hip_shard_adopt", "gmr1_hip_shard_destroy",
     "gmr1_hip_rx_run_sharded", "gmr1_hip_rx_run_sharded_resident",
     "gmr1_codec_alloc", "gmr1_codec_release", "gmr1_codec_decode_frame", "gmr1_codec_decode_dtx",
@@ -1024,6 +1026,74 @@ def channelize_planar_dev(stream, wide_ptr, n_in, samp_rate, channels, out_ptr, 
            C.c_uint64(plane_stride), C.byref(no))
     _check(rc, "gmr1_hip_channelize_planar_dev")
     return no.value
+
+
+class ChanStream:
+    """gmr1_hip_chan_stream_*: the channelizer (or, from ChanStream.direct, the direct mode) over a capture pushed piece
+    by piece.  Each push returns the outputs that have become computable; all pushes' outputs, concatenated per stream, are
+    identical to one channelize() / ddc() call on the samples pushed so far."""
+
+    def __init__(self, samp_rate, channels, sps=4, rotation=0.0, _handle=None, _n_sel=None):
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h, self.n_sel = _handle, _n_sel
+            return
+        ch, p_ch = _np(channels, np.int32)
+        f = load().gmr1_hip_channelize_stream_create
+        f.restype = C.c_int
+        _check(f(C.c_double(samp_rate), C.c_int(sps), C.c_float(rotation), C.c_int(ch.size), p_ch, C.byref(self._h)),
+               "gmr1_hip_channelize_stream_create")
+        self.n_sel = ch.size
+
+    @classmethod
+    def direct(cls, samp_rate, freqs_hz, sps=4):
+        """gmr1_hip_ddc_stream_create: the recorder script's direct mode, carriers at freqs_hz from the centre."""
+        freqs, p_f = _np(freqs_hz, np.float64)
+        h = C.c_void_p()
+        _check(load().gmr1_hip_ddc_stream_create(C.c_double(samp_rate), C.c_int(sps), C.c_int(freqs.size), p_f, C.byref(h)),
+               "gmr1_hip_ddc_stream_create")
+        return cls(None, None, _handle=h, _n_sel=freqs.size)
+
+    def out_len(self, n_in):
+        """outputs per stream the next push of n_in samples will give"""
+        n = C.c_uint64()
+        _check(load().gmr1_hip_chan_stream_out_len(self._h, C.c_uint64(n_in), C.byref(n)), "gmr1_hip_chan_stream_out_len")
+        return n.value
+
+    def push(self, wide):
+        """host complex64 samples -> (n_sel, n_new) complex64"""
+        wide, p_w = _np(np.asarray(wide).reshape(-1), np.complex64)
+        n_new = self.out_len(wide.size)
+        out = np.zeros((self.n_sel, max(n_new, 1)), np.complex64)
+        got = C.c_uint64()
+        _check(load().gmr1_hip_chan_stream_push(self._h, p_w, C.c_uint64(wide.size), out.ctypes.data_as(C.c_void_p),
+                                                C.c_uint64(out.shape[1]), C.byref(got)), "gmr1_hip_chan_stream_push")
+        return out[:, :got.value]
+
+    def push_dev(self, stream, wide_ptr, n_in, out_ptr, out_stride):
+        """device pointers, enqueued on `stream` (not waited for) -> outputs written per stream"""
+        got = C.c_uint64()
+        _check(load().gmr1_hip_chan_stream_push_dev(C.c_void_p(stream) if stream else None, self._h, C.c_void_p(wide_ptr),
+                                                    C.c_uint64(n_in), C.c_void_p(out_ptr), C.c_uint64(out_stride),
+                                                    C.byref(got)), "gmr1_hip_chan_stream_push_dev")
+        return got.value
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, C.c_void_p()
+            _check(load().gmr1_hip_chan_stream_destroy(h), "gmr1_hip_chan_stream_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------------------

@@ -4,8 +4,10 @@
 
 #include "capi_common.h"
 
+#include <algorithm>
 #include <cmath>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -83,6 +85,13 @@ std::vector<float> design_rrc(double gain, double fs, double sym_rate, double al
 }
 
 long long gcdll(long long a, long long b) { return b ? gcdll(b, a % b) : a; }
+
+// outputs of the arbitrary resampler (filter j0 first, phase step num / den in 1 / 32 input samples) over T inputs
+uint64_t resamp_out(int j0, long long num, long long den, uint64_t T)
+{
+	const long long v = ((long long)T * kNfilt - j0) * den;
+	return v > 0 ? (uint64_t)(v / num) : 0;
+}
 size_t up_to(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct ChanPlan {
@@ -349,6 +358,37 @@ int get_ddc_plan(double samp_rate, int sps, const DdcPlan **out)
 	return 0;
 }
 
+// freq_xlating_fir_filter_ccc: the low-pass turned up to the carrier, taps[k] e^{+j 2 pi f k / fs}; the output is
+// turned back by e^{-j 2 pi f m d1 / fs}
+void ddc_carrier_taps(const DdcPlan &p, int n_sel, const double *freq_hz, std::vector<float2> &t1, std::vector<double> &rot)
+{
+	const int nt1 = (int)p.taps1.size();
+	t1.resize((size_t)n_sel * nt1);
+	rot.resize((size_t)n_sel);
+	for (int c = 0; c < n_sel; c++) {
+		const double fn = freq_hz[c] / p.samp_rate;
+		for (int k = 0; k < nt1; k++) {
+			const double ph = 2.0 * M_PI * std::fmod(fn * k, 1.0);
+			t1[(size_t)c * nt1 + k] = make_float2((float)(p.taps1[k] * std::cos(ph)), (float)(p.taps1[k] * std::sin(ph)));
+		}
+		rot[c] = fn * p.d1;
+	}
+}
+
+// the slot of every channel (-1: not kept) for a selection, refusing indices outside the plan and repeats
+int select_channels(int nch, int n_sel, const int32_t *chan_idx, std::vector<int32_t> &slot)
+{
+	slot.assign(nch, -1);
+	for (int i = 0; i < n_sel; i++) {
+		if (chan_idx[i] < 0 || chan_idx[i] >= nch)
+			return fail(-EINVAL, "channelize: channel index %d outside 0..%d", chan_idx[i], nch - 1);
+		if (slot[chan_idx[i]] >= 0)
+			return fail(-EINVAL, "channelize: channel %d selected twice", chan_idx[i]);
+		slot[chan_idx[i]] = i;
+	}
+	return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -367,11 +407,8 @@ int gmr1_hip_ddc_plan(double samp_rate, int sps, uint64_t n_in, int32_t *decim1,
 	if (decim1) *decim1 = p->d1;
 	if (decim2) *decim2 = p->d2;
 	if (resamp) *resamp = p->resamp;
-	if (n_out) {
-		const uint64_t n2 = n_in / (uint64_t)p->d1 / (uint64_t)p->d2;
-		const long long v = ((long long)n2 * kNfilt - p->j0) * p->den;
-		*n_out = v > 0 ? (uint64_t)(v / p->num) : 0;
-	}
+	if (n_out)
+		*n_out = resamp_out(p->j0, p->num, p->den, n_in / (uint64_t)p->d1 / (uint64_t)p->d2);
 	return 0;
 }
 
@@ -412,18 +449,9 @@ int gmr1_hip_ddc_dev(void *stream, double samp_rate, int sps, const float *wide,
 	double *d_rot = reinterpret_cast<double *>(w + b_t1);
 	float2 *d_y1 = reinterpret_cast<float2 *>(w + b_t1 + b_rot);
 	float2 *d_y2 = p->d2 > 1 ? reinterpret_cast<float2 *>(w + b_t1 + b_rot + b_y1) : d_y1;
-	// freq_xlating_fir_filter_ccc: the low-pass turned up to the carrier, taps[k] e^{+j 2 pi f k / fs}; the output is
-	// turned back by e^{-j 2 pi f m d1 / fs}
-	std::vector<float2> t1((size_t)n_sel * nt1);
-	std::vector<double> rot((size_t)n_sel);
-	for (int c = 0; c < n_sel; c++) {
-		const double fn = freq_hz[c] / samp_rate;
-		for (int k = 0; k < nt1; k++) {
-			const double ph = 2.0 * M_PI * std::fmod(fn * k, 1.0);
-			t1[(size_t)c * nt1 + k] = make_float2((float)(p->taps1[k] * std::cos(ph)), (float)(p->taps1[k] * std::sin(ph)));
-		}
-		rot[c] = fn * p->d1;
-	}
+	std::vector<float2> t1;
+	std::vector<double> rot;
+	ddc_carrier_taps(*p, n_sel, freq_hz, t1, rot);
 	HIP_TRY(hipMemcpyAsync(d_t1, t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(d_rot, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipStreamSynchronize(st));       // t1 / rot are host temporaries
@@ -492,10 +520,7 @@ int gmr1_hip_channelize_plan(double samp_rate, int sps, uint64_t n_in,
 	const uint64_t T = p->mid_samples(n_in) / (uint64_t)(p->n_chans / 2);
 	if (n_chans) *n_chans = p->n_chans;
 	if (n_mid) *n_mid = T;
-	if (n_out) {
-		const long long v = ((long long)T * kNfilt - p->j0) * p->den;
-		*n_out = v > 0 ? (uint64_t)(v / p->num) : 0;
-	}
+	if (n_out) *n_out = resamp_out(p->j0, p->num, p->den, T);
 	return 0;
 }
 
@@ -520,14 +545,9 @@ static int channelize_dev_impl(void *stream, double samp_rate, int sps, const fl
 	const ChanPlan *p;
 	r = get_plan(samp_rate, sps, &p);
 	if (r) return r;
-	std::vector<int32_t> slot(nch, -1);
-	for (int i = 0; i < n_sel; i++) {
-		if (chan_idx[i] < 0 || chan_idx[i] >= nch)
-			return fail(-EINVAL, "channelize: channel index %d outside 0..%d", chan_idx[i], nch - 1);
-		if (slot[chan_idx[i]] >= 0)
-			return fail(-EINVAL, "channelize: channel %d selected twice", chan_idx[i]);
-		slot[chan_idx[i]] = i;
-	}
+	std::vector<int32_t> slot;
+	if ((r = select_channels(nch, n_sel, chan_idx, slot)))
+		return r;
 	hipStream_t st = (hipStream_t)stream;
 	DevState *s;
 	r = dev_state(&s);
@@ -619,6 +639,438 @@ int gmr1_hip_channelize(double samp_rate, int sps, const float *wide, uint64_t n
 	if (r) return r;
 	HIP_TRY(hipStreamSynchronize(nullptr));
 	HIP_TRY(hipMemcpy(out, d_o.p, (size_t)n_sel * out_stride * 8, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+}  // extern "C"
+
+// ---- streaming: the same channelizer / direct mode over a capture that arrives in pieces --------------------------------
+// Every output of both chains is causal -- filterbank instant t reads input up to sample (n_chans / 2) t, resampler output n
+// inputs below its plan's T, direct-mode output m input up to m d1 -- and every kernel computes phases, rotations and
+// filter positions from GLOBAL indices (StreamIdx, gmr1_dev.h).  So a handle keeps, per stage, only the history the next
+// outputs reach back into: the last Lx wideband samples, and each intermediate stream as [retained tail | this push's new
+// samples] in one buffer it owns.  A push computes exactly the outputs that have become computable, identical to a one-shot
+// call's.
+namespace {
+
+// an intermediate stream of the handle: `rows` rows of `cap` complex samples, the first L the retained tail
+struct StageBuf {
+	float2 *p = nullptr;
+	long long cap = 0;
+	int L = 0, rows = 0;
+	~StageBuf() { if (p) (void)hipFree(p); }
+};
+
+// zeroed: global indices before the stream's start read as zeros, as in a one-shot call
+int stage_init(StageBuf &b, int L, int rows)
+{
+	b.L = L;
+	b.rows = rows;
+	b.cap = L;
+	HIP_TRY(hipMalloc(&b.p, (size_t)(rows > 0 ? rows : 1) * L * sizeof(float2)));
+	HIP_TRY(hipMemsetAsync(b.p, 0, (size_t)(rows > 0 ? rows : 1) * L * sizeof(float2), nullptr));
+	return 0;
+}
+
+// room for n_new samples behind the tail (grow-only: the tails move over, on `st`, before the old buffer goes)
+int stage_reserve(StageBuf &b, long long n_new, hipStream_t st)
+{
+	if (b.L + n_new <= b.cap)
+		return 0;
+	const long long cap = up_to((size_t)(b.L + n_new), 256);
+	float2 *p = nullptr;
+	HIP_TRY(hipMalloc(&p, (size_t)(b.rows > 0 ? b.rows : 1) * cap * sizeof(float2)));
+	if (b.rows > 0)
+		HIP_TRY(hipMemcpy2DAsync(p, cap * sizeof(float2), b.p, b.cap * sizeof(float2), b.L * sizeof(float2), b.rows,
+		                         hipMemcpyDeviceToDevice, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipFree(b.p));
+	b.p = p;
+	b.cap = cap;
+	return 0;
+}
+
+// the last L samples of each row's [tail | n_new] to the front (a job of the push's k_keep_tail launch)
+void stage_keep(KeepTailArgs &k, StageBuf &b, long long n_new)
+{
+	if (n_new <= 0 || b.rows <= 0)
+		return;
+	KeepTail &j = k.job[k.n++];
+	j.dst = b.p; j.a = b.p; j.b = nullptr;
+	j.dst_stride = b.cap; j.a_stride = b.cap; j.b_stride = 0; j.na = b.L + n_new; j.nb = 0;
+	j.L = b.L; j.rows = b.rows;
+}
+
+// history a k_resamp instantiation of `taps` taps reads behind its first new output: the taps, the input step of one
+// output (num / (32 den) samples) and the rounding of both ends (capi_chan.cpp, resamp_out)
+int resamp_history(int taps, long long num, long long den)
+{
+	return (int)up_to((size_t)(taps + num / (kNfilt * den) + 3), 64);
+}
+
+// a host array's grow-only device copy (gmr1_hip_chan_stream_push)
+struct GrowBuf {
+	void *p = nullptr;
+	size_t bytes = 0;
+	~GrowBuf() { if (p) (void)hipFree(p); }
+	int reserve(size_t n)
+	{
+		if (n <= bytes)
+			return 0;
+		if (p) {
+			HIP_TRY(hipFree(p));
+			p = nullptr;
+			bytes = 0;
+		}
+		HIP_TRY(hipMalloc(&p, n));
+		bytes = n;
+		return 0;
+	}
+};
+
+}  // namespace
+
+struct gmr1_hip_chan_stream {
+	mutable std::mutex mu;               // one push at a time
+	int device = -1;
+	bool direct = false;                 // gmr1_hip_ddc_stream_create
+	int n_sel = 0;
+	float rotation = 0.0f;
+	const ChanPlan *cp = nullptr;
+	const DdcPlan *dp = nullptr;
+	uint64_t N = 0;                      // wideband samples pushed so far
+	StageBuf xt;                         // the last Lx wideband samples (one row)
+	StageBuf pre, mid;                   // channelizer: the pre-resampled capture (off the grid), the 2x channel streams
+	StageBuf y1, y2;                     // direct mode: the two decimating FIRs' outputs
+	int32_t *d_slot = nullptr;           // channelizer: slot table, then the selection
+	float2 *d_t1 = nullptr;              // direct mode: per-carrier stage-1 taps, then their rotation steps
+	double *d_rot = nullptr;
+	hipEvent_t ev = nullptr;             // recorded behind the last push
+	hipStream_t last = nullptr;
+	bool pushed = false;
+	GrowBuf h_in, h_out;                 // gmr1_hip_chan_stream_push's device copies
+	~gmr1_hip_chan_stream()
+	{
+		if (d_slot) (void)hipFree(d_slot);
+		if (d_t1) (void)hipFree(d_t1);
+		if (d_rot) (void)hipFree(d_rot);
+		if (ev) (void)hipEventDestroy(ev);
+	}
+};
+
+namespace {
+
+// global counts after n wideband samples: the first stage's, the second's (the filterbank's instants / stage 2 of the
+// direct mode; = the first's where there is no second) and the outputs
+struct StreamCounts {
+	uint64_t a, b, out;
+};
+StreamCounts stream_counts(const gmr1_hip_chan_stream *h, uint64_t n)
+{
+	StreamCounts c;
+	if (h->direct) {
+		c.a = n / (uint64_t)h->dp->d1;
+		c.b = c.a / (uint64_t)h->dp->d2;
+		c.out = resamp_out(h->dp->j0, h->dp->num, h->dp->den, c.b);
+	} else {
+		c.a = h->cp->mid_samples(n);
+		c.b = c.a / (uint64_t)(h->cp->n_chans / 2);
+		c.out = resamp_out(h->cp->j0, h->cp->num, h->cp->den, c.b);
+	}
+	return c;
+}
+
+int stream_finish_create(gmr1_hip_chan_stream *h, gmr1_hip_chan_stream **out)
+{
+	HIP_TRY(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
+	HIP_TRY(hipStreamSynchronize(nullptr));     // the zeroed tails and uploaded tables are in place before any stream uses them
+	*out = h;
+	return 0;
+}
+
+// the device part of a push; the caller holds h->mu and has validated everything
+int stream_push(hipStream_t st, gmr1_hip_chan_stream *h, const float2 *wide, uint64_t n_in, float2 *out, uint64_t out_stride)
+{
+	const uint64_t N0 = h->N, N1 = N0 + n_in;
+	const StreamCounts c0 = stream_counts(h, N0), c1 = stream_counts(h, N1);
+	if (h->pushed && st != h->last)
+		HIP_TRY(hipStreamWaitEvent(st, h->ev, 0));
+	const long long na = (long long)(c1.a - c0.a), nb = (long long)(c1.b - c0.b);
+	StreamIdx in;                        // the wideband chunk behind the retained samples
+	std::memset(&in, 0, sizeof(in));
+	in.xt = h->xt.p; in.xt0 = (long long)N0 - h->xt.L; in.x0 = (long long)N0;
+	const bool outs = h->n_sel > 0 && c1.out > c0.out;
+	StageBuf *rs_in = nullptr;           // what the resampler reads
+	if (!h->direct) {
+		const ChanPlan &p = *h->cp;
+		int r;
+		if (p.pre && (r = stage_reserve(h->pre, na, st))) return r;
+		if ((r = stage_reserve(h->mid, nb, st))) return r;
+		PfbArgs pa;
+		std::memset(&pa, 0, sizeof(pa));
+		pa.x = wide; pa.st = in; pa.rotation = h->rotation;
+		if (p.pre && na > 0) {
+			ResampArgs rp;
+			std::memset(&rp, 0, sizeof(rp));
+			rp.n_slots = 1; rp.nfilt = kNfilt; rp.tpf = 30; rp.j0 = p.pre_j0; rp.num = p.pre_num; rp.den = p.pre_den;
+			rp.T = (long long)N1; rp.n_out = (long long)c1.a; rp.out_stride = h->pre.cap;
+			rp.y = wide; rp.bank = p.d_pre_bank; rp.out = h->pre.p + h->pre.L; rp.rotation = h->rotation;
+			rp.st = in; rp.st.o0 = (long long)c0.a;
+			HIP_TRY(launch_resamp(rp, st));
+		}
+		if (p.pre) {
+			pa.x = h->pre.p + h->pre.L; pa.rotation = 0.0f;
+			pa.st.xt = h->pre.p; pa.st.xt0 = (long long)c0.a - h->pre.L; pa.st.x0 = (long long)c0.a;
+		}
+		if (h->n_sel > 0 && nb > 0) {
+			pa.n_chans = p.n_chans; pa.n_blocks = p.n_blocks; pa.ntaps = p.ntaps;
+			pa.n_in = (long long)c1.a; pa.T = (long long)c1.b;
+			pa.taps = p.d_taps; pa.slot = h->d_slot; pa.sel = h->d_slot + kPfbMaxChans; pa.n_sel = h->n_sel;
+			pa.y = h->mid.p + h->mid.L; pa.st.o0 = (long long)c0.b; pa.st.y_stride = h->mid.cap;
+			HIP_TRY(launch_pfb(pa, st));
+		}
+		rs_in = &h->mid;
+	} else {
+		const DdcPlan &p = *h->dp;
+		int r;
+		if ((r = stage_reserve(h->y1, na, st))) return r;
+		if (p.d2 > 1 && (r = stage_reserve(h->y2, nb, st))) return r;
+		if (h->n_sel > 0 && na > 0) {
+			DdcFirArgs f1;
+			std::memset(&f1, 0, sizeof(f1));
+			f1.n_sel = h->n_sel; f1.decim = p.d1; f1.ntaps = (int)p.taps1.size(); f1.n_in = (long long)N1; f1.n_out = (long long)c1.a;
+			f1.x = wide; f1.taps = h->d_t1; f1.rot = h->d_rot; f1.y = h->y1.p + h->y1.L;
+			f1.st = in; f1.st.o0 = (long long)c0.a; f1.st.y_stride = h->y1.cap;
+			HIP_TRY(launch_ddc_fir(f1, st));
+		}
+		if (p.d2 > 1 && nb > 0) {
+			// (carrier by carrier on the one row of real taps, as the one-shot call launches them)
+			for (int k = 0; k < h->n_sel; k++) {
+				DdcFirArgs f2;
+				std::memset(&f2, 0, sizeof(f2));
+				f2.n_sel = 1; f2.decim = p.d2; f2.ntaps = (int)p.taps2.size(); f2.n_in = (long long)c1.a; f2.n_out = (long long)c1.b;
+				f2.x = h->y1.p + (size_t)k * h->y1.cap + h->y1.L; f2.taps = p.d_taps2; f2.rot = nullptr;
+				f2.y = h->y2.p + (size_t)k * h->y2.cap + h->y2.L;
+				f2.st.xt = h->y1.p + (size_t)k * h->y1.cap; f2.st.xt0 = (long long)c0.a - h->y1.L; f2.st.x0 = (long long)c0.a;
+				f2.st.o0 = (long long)c0.b; f2.st.y_stride = h->y2.cap;
+				HIP_TRY(launch_ddc_fir(f2, st));
+			}
+		}
+		rs_in = p.d2 > 1 ? &h->y2 : &h->y1;
+	}
+	if (outs) {
+		const int tpf = h->direct ? h->dp->bank_tpf : h->cp->tpf, j0 = h->direct ? h->dp->j0 : h->cp->j0;
+		ResampArgs ra;
+		std::memset(&ra, 0, sizeof(ra));
+		ra.n_slots = h->n_sel; ra.nfilt = kNfilt; ra.tpf = tpf; ra.j0 = j0;
+		ra.num = h->direct ? h->dp->num : h->cp->num; ra.den = h->direct ? h->dp->den : h->cp->den;
+		ra.T = (long long)c1.b; ra.n_out = (long long)c1.out; ra.out_stride = (long long)out_stride;
+		ra.y = rs_in->p + rs_in->L; ra.bank = h->direct ? h->dp->d_bank : h->cp->d_bank; ra.out = out;
+		ra.st.xt = rs_in->p; ra.st.xt0 = (long long)c0.b - rs_in->L; ra.st.x0 = (long long)c0.b; ra.st.o0 = (long long)c0.out;
+		ra.st.x_stride = rs_in->cap;
+		HIP_TRY(launch_resamp(ra, st));
+	}
+	// what the next push reaches back into: the input's last Lx samples, each stage's last L
+	KeepTailArgs keep;
+	std::memset(&keep, 0, sizeof(keep));
+	if (n_in > 0) {
+		KeepTail &j = keep.job[keep.n++];
+		j.dst = h->xt.p; j.a = h->xt.p; j.b = wide; j.na = h->xt.L; j.nb = (long long)n_in; j.L = h->xt.L; j.rows = 1;
+	}
+	if (!h->direct) {
+		if (h->cp->pre)
+			stage_keep(keep, h->pre, na);
+		stage_keep(keep, h->mid, nb);
+	} else {
+		stage_keep(keep, h->y1, na);
+		if (h->dp->d2 > 1)
+			stage_keep(keep, h->y2, nb);
+	}
+	HIP_TRY(launch_keep_tail(keep, st));
+	HIP_TRY(hipEventRecord(h->ev, st));
+	h->last = st;
+	h->pushed = true;
+	h->N = N1;
+	return 0;
+}
+
+// the checks every push makes before it touches the handle: -EINVAL leaves the stream as it was
+int stream_check(gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in, const float *out, uint64_t out_stride,
+                 uint64_t *n_new)
+{
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	if (!h)
+		return fail(-EINVAL, "chan_stream: no handle");
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	if (dev != h->device)
+		return fail(-EINVAL, "chan_stream: the handle belongs to device %d, the current device is %d", h->device, dev);
+	if (!wide)
+		return fail(-EINVAL, "chan_stream: wide is required");
+	if (n_in > (uint64_t)1 << 40)
+		return fail(-EINVAL, "chan_stream: %llu samples in one push", (unsigned long long)n_in);
+	*n_new = stream_counts(h, h->N + n_in).out - stream_counts(h, h->N).out;
+	if (h->n_sel > 0 && *n_new > 0) {
+		if (!out)
+			return fail(-EINVAL, "chan_stream: out is required");
+		if (out_stride < *n_new)
+			return fail(-EINVAL, "chan_stream: out_stride %llu < %llu new output samples per stream",
+			            (unsigned long long)out_stride, (unsigned long long)*n_new);
+	}
+	return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmr1_hip_channelize_stream_create(double samp_rate, int sps, float rotation, int n_sel, const int32_t *chan_idx,
+                                      struct gmr1_hip_chan_stream **out)
+{
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	if (!out || n_sel < 0 || (n_sel && !chan_idx))
+		return fail(-EINVAL, "channelize_stream: chan_idx / handle are required");
+	int32_t nch;
+	if ((r = gmr1_hip_channelize_plan(samp_rate, sps, 0, &nch, nullptr, nullptr)))
+		return r;
+	const ChanPlan *p;
+	if ((r = get_plan(samp_rate, sps, &p)))
+		return r;
+	std::vector<int32_t> slot;
+	if ((r = select_channels(nch, n_sel, chan_idx, slot)))
+		return r;
+	std::unique_ptr<gmr1_hip_chan_stream> h(new gmr1_hip_chan_stream);
+	HIP_TRY(hipGetDevice(&h->device));
+	h->n_sel = n_sel; h->rotation = rotation; h->cp = p;
+	// history: the filterbank reaches ntaps + n_chans / 2 inputs behind its first new instant (n_blocks n_chans + n_chans
+	// covers it); the pre-resampler its taps and one step
+	const int l_pfb = (p->n_blocks + 1) * p->n_chans;
+	const int lx = p->pre ? resamp_history(30, p->pre_num, p->pre_den) : l_pfb;
+	if ((r = stage_init(h->xt, lx, 1)) || (p->pre && (r = stage_init(h->pre, l_pfb, 1))) ||
+	    (r = stage_init(h->mid, resamp_history(p->tpf, p->num, p->den), n_sel)))
+		return r;
+	std::vector<int32_t> tab(2 * kPfbMaxChans, -1);
+	std::copy(slot.begin(), slot.end(), tab.begin());
+	std::copy(chan_idx, chan_idx + n_sel, tab.begin() + kPfbMaxChans);
+	HIP_TRY(hipMalloc(&h->d_slot, tab.size() * sizeof(int32_t)));
+	HIP_TRY(hipMemcpy(h->d_slot, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+	if ((r = stream_finish_create(h.get(), out)))
+		return r;
+	h.release();
+	return 0;
+}
+
+int gmr1_hip_ddc_stream_create(double samp_rate, int sps, int n_sel, const double *freq_hz, struct gmr1_hip_chan_stream **out)
+{
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	if (!out || n_sel < 0 || (n_sel && !freq_hz))
+		return fail(-EINVAL, "ddc_stream: freq_hz / handle are required");
+	if ((r = gmr1_hip_ddc_plan(samp_rate, sps, 0, nullptr, nullptr, nullptr, nullptr)))
+		return r;
+	const DdcPlan *p;
+	if ((r = get_ddc_plan(samp_rate, sps, &p)))
+		return r;
+	std::unique_ptr<gmr1_hip_chan_stream> h(new gmr1_hip_chan_stream);
+	HIP_TRY(hipGetDevice(&h->device));
+	h->direct = true; h->n_sel = n_sel; h->dp = p;
+	const int l_rs = resamp_history(p->bank_tpf, p->num, p->den);
+	const int l_fir1 = (int)p->taps1.size() + p->d1 + 1;
+	if ((r = stage_init(h->xt, (int)up_to((size_t)l_fir1, 64), 1)) ||
+	    (r = stage_init(h->y1, p->d2 > 1 ? (int)up_to(p->taps2.size() + p->d2 + 1, 64) : l_rs, n_sel)) ||
+	    (p->d2 > 1 && (r = stage_init(h->y2, l_rs, n_sel))))
+		return r;
+	std::vector<float2> t1;
+	std::vector<double> rot;
+	ddc_carrier_taps(*p, n_sel, freq_hz, t1, rot);
+	HIP_TRY(hipMalloc(&h->d_t1, (t1.empty() ? 1 : t1.size()) * sizeof(float2)));
+	HIP_TRY(hipMalloc(&h->d_rot, (rot.empty() ? 1 : rot.size()) * sizeof(double)));
+	HIP_TRY(hipMemcpy(h->d_t1, t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(h->d_rot, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice));
+	if ((r = stream_finish_create(h.get(), out)))
+		return r;
+	h.release();
+	return 0;
+}
+
+int gmr1_hip_chan_stream_out_len(const struct gmr1_hip_chan_stream *h, uint64_t n_in, uint64_t *n_out)
+{
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	if (!h || !n_out)
+		return fail(-EINVAL, "chan_stream_out_len: handle / n_out are required");
+	std::lock_guard<std::mutex> lk(h->mu);
+	*n_out = stream_counts(h, h->N + n_in).out - stream_counts(h, h->N).out;
+	return 0;
+}
+
+int gmr1_hip_chan_stream_push_dev(void *stream, struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in,
+                                  float *out, uint64_t out_stride, uint64_t *n_out)
+{
+	std::unique_lock<std::mutex> lk;
+	if (h)
+		lk = std::unique_lock<std::mutex>(h->mu);
+	uint64_t n_new = 0;
+	int r = stream_check(h, wide, n_in, out, out_stride, &n_new);
+	if (r) return r;
+	if ((r = stream_push((hipStream_t)stream, h, reinterpret_cast<const float2 *>(wide), n_in, reinterpret_cast<float2 *>(out),
+	                     out_stride)))
+		return r;
+	if (n_out) *n_out = n_new;
+	return 0;
+}
+
+int gmr1_hip_chan_stream_push(struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in, float *out,
+                              uint64_t out_stride, uint64_t *n_out)
+{
+	std::unique_lock<std::mutex> lk;
+	if (h)
+		lk = std::unique_lock<std::mutex>(h->mu);
+	uint64_t n_new = 0;
+	int r = stream_check(h, wide, n_in, out, out_stride, &n_new);
+	if (r) return r;
+	const size_t out_rows = h->n_sel > 0 && n_new > 0 ? (size_t)h->n_sel : 0;
+	if ((r = h->h_in.reserve(n_in * sizeof(float2))) || (r = h->h_out.reserve(out_rows * n_new * sizeof(float2))))
+		return r;
+	if (n_in)
+		HIP_TRY(hipMemcpyAsync(h->h_in.p, wide, n_in * sizeof(float2), hipMemcpyHostToDevice, nullptr));
+	if ((r = stream_push(nullptr, h, static_cast<const float2 *>(h->h_in.p ? h->h_in.p : h->xt.p), n_in,
+	                     static_cast<float2 *>(h->h_out.p), n_new)))
+		return r;
+	if (out_rows)
+		HIP_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float2), h->h_out.p, n_new * sizeof(float2), n_new * sizeof(float2),
+		                         out_rows, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	if (n_out) *n_out = n_new;
+	return 0;
+}
+
+int gmr1_hip_chan_stream_destroy(struct gmr1_hip_chan_stream *h)
+{
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	if (!h)
+		return 0;
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	const int own = h->device;
+	if (dev != own)
+		HIP_TRY(hipSetDevice(own));          // its memory is freed on its own device
+	{
+		std::lock_guard<std::mutex> lk(h->mu);
+		if (h->pushed)
+			(void)hipEventSynchronize(h->ev);      // nothing of the handle's is still in use when it goes
+	}
+	delete h;
+	if (dev != own)
+		HIP_TRY(hipSetDevice(dev));
 	return 0;
 }
 

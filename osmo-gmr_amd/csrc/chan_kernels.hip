@@ -44,6 +44,8 @@ static constexpr float kPif = 3.14159265358979323846f;
 static constexpr int kPfbSteps = 64;        // output instants per wavefront (32 new blocks; 128 / 256: 5 / 22 % slower, r06aq)
 static constexpr int kPfbTile = 16;         // instants per LDS transpose tile
 static constexpr int kPfbWb = 4;            // tile reads answered together in k_pfb64's write-out
+// a streamed push is a small grid: its time is one wave's walk, not the machine's throughput -- one tile per wave there
+static constexpr int kPfbStepsStream = 16;
 
 // (every lane of these permutations has a source lane: no "old" value is needed, and none is set up)
 template <int CTRL>
@@ -61,6 +63,15 @@ __device__ __forceinline__ float lane_xor(float v)
 	else if constexpr (X == 4) return dppf<0x1B>(dppf<0x141>(v));   // half mirror, then quad reverse
 	else if constexpr (X == 2) return dppf<0x4E>(v);
 	else return dppf<0xB1>(v);
+}
+
+// sample s (global index) of a streamed stage's input row: the retained tail below st.x0, the new samples from there, zeros
+// outside [st.xt0, end) (gmr1_dev.h, StreamIdx)
+__device__ __forceinline__ float2 stream_ld(const float2 *x, const float2 *xt, const StreamIdx &st, long long s, long long end)
+{
+	if (s < st.xt0 || s >= end)
+		return make_float2(0.f, 0.f);
+	return s < st.x0 ? xt[s - st.xt0] : x[s - st.x0];
 }
 
 // ---- packed single precision (v_pk_*_f32: two multiply-adds per lane and instruction, the rate the vector peak is quoted
@@ -135,12 +146,14 @@ __device__ __forceinline__ pf_v2f pf_partner(pf_v2f v)
 	return (pf_v2f){lane_xor<SPAN>(v.x), lane_xor<SPAN>(v.y)};
 }
 
-template <bool ROT>
+// STREAM: the instants [st.o0, T) of a streamed run (the waves start at the even instant at or below st.o0)
+template <bool ROT, bool STREAM>
 __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 {
 	__shared__ float2 tile[64 * (kPfbTile + 1)];
 	const int r = threadIdx.x;
-	const long long t0 = (long long)blockIdx.x * kPfbSteps;       // first instant of this wave (even)
+	constexpr int kSteps = STREAM ? kPfbStepsStream : kPfbSteps;
+	const long long t0 = (STREAM ? (a.st.o0 & ~1LL) : 0) + (long long)blockIdx.x * kSteps;          // first instant of this wave (even)
 	const int NB = a.n_blocks;
 
 	// taps of this branch: even instants h[64 q - r], odd instants h[64 q + 32 - r]
@@ -179,8 +192,11 @@ __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 	auto load_block = [&](long long b) -> pf_v2f {
 		const long long s = 64 * b + r;
 		float2 v = make_float2(0.f, 0.f);
-		if (b >= 0 && s < a.n_in) {
-			v = a.x[s];
+		if (STREAM || (b >= 0 && s < a.n_in)) {
+			if constexpr (STREAM)
+				v = stream_ld(a.x, a.st.xt, a.st, s, a.n_in);
+			else
+				v = a.x[s];
 			if (ROT) {
 				// e^{j rotation s}: the angle reduced in double so that long captures keep their phase
 				const double ph = (double)a.rotation * (double)s;
@@ -199,7 +215,7 @@ __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 	// (two blocks on their way: at half the instruction count a block's arithmetic no longer covers a trip to memory)
 	pf_v2f nxt = load_block(b0), nxt2 = load_block(b0 + 1);
 	constexpr int kBlk = kPfbTile / 2;           // new blocks per tile
-	for (int tt = 0; tt < kPfbSteps; tt += kPfbTile) {
+	for (int tt = 0; tt < kSteps; tt += kPfbTile) {
 		// The tile's eight blocks unrolled over ONE register array W: the window of block k is W[kBlk - 1 - k + q], the new
 		// block goes to W[kBlk - 1 - k] -- static indices, nothing is shifted per block; the window moves back up once per tile.
 		pf_v2f W[kBlk + kPfbMaxBlocks - 1];
@@ -243,7 +259,8 @@ __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 		{
 			const int u = r & 15, hq = r >> 4;
 			const long long t = t0 + tt + u;
-			const bool tin = t < a.T;
+			const bool tin = t < a.T && (!STREAM || t >= a.st.o0);
+			const long long yo = STREAM ? t - a.st.o0 : t, ys = STREAM ? a.st.y_stride : a.T;
 			const float2 *row = &tile[(16 * hq) * (kPfbTile + 1) + (hq >> 1) + u];      // channel 16 hq + i is (kPfbTile + 1) i on
 			// (the slots looked at afresh per tile: sixteen store addresses carried across the loop are 32 registers and a wave)
 #pragma unroll
@@ -262,7 +279,7 @@ __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 					// (streamed past the caches: nothing of it is read again before the launch is over -- with ordinary stores the
 					// 640 MB evict the input still to be read and are written back under the next kernel; A/B profiles/r06am)
 					if (sl != 0xffu && tin)
-						__builtin_nontemporal_store((pf_v2f){v[k].x, v[k].y}, reinterpret_cast<pf_v2f *>(&a.y[(long long)sl * a.T + t]));
+						__builtin_nontemporal_store((pf_v2f){v[k].x, v[k].y}, reinterpret_cast<pf_v2f *>(&a.y[(long long)sl * ys + yo]));
 				}
 			}
 		}
@@ -282,7 +299,7 @@ __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 static constexpr int kAnyTile = 16;          // instants per work-group
 static constexpr int kAnyThreads = 256;
 
-template <bool ROT>
+template <bool ROT, bool STREAM>
 __global__ __launch_bounds__(kAnyThreads) void k_pfb_any(PfbArgs a)
 {
 	extern __shared__ float2 lds_any[];
@@ -290,7 +307,7 @@ __global__ __launch_bounds__(kAnyThreads) void k_pfb_any(PfbArgs a)
 	float2 *v = lds_any;                       // kAnyTile x (M + 1)
 	float2 *tw = lds_any + kAnyTile * ld;      // M twiddles e^{-j 2 pi i / M}
 	const int tid = threadIdx.x;
-	const long long t0 = (long long)blockIdx.x * kAnyTile;
+	const long long t0 = (STREAM ? a.st.o0 : 0) + (long long)blockIdx.x * kAnyTile;
 
 	for (int i = tid; i < M; i += kAnyThreads) {
 		float sn, cs;
@@ -312,7 +329,9 @@ __global__ __launch_bounds__(kAnyThreads) void k_pfb_any(PfbArgs a)
 					break;
 				if (sidx >= a.n_in)
 					continue;
-				float2 x = a.x[sidx];
+				if (STREAM && sidx < a.st.xt0)
+					break;
+				float2 x = STREAM ? stream_ld(a.x, a.st.xt, a.st, sidx, a.n_in) : a.x[sidx];
 				if (ROT) {
 					const double ph = (double)a.rotation * (double)sidx;
 					const float fr = (float)(ph - 6.283185307179586 * rint(ph * 0.15915494309189535));
@@ -344,30 +363,48 @@ __global__ __launch_bounds__(kAnyThreads) void k_pfb_any(PfbArgs a)
 			idx += k;
 			idx = idx >= M ? idx - M : idx;
 		}
-		a.y[(long long)c * a.T + t] = make_float2(yr, yi);
+		if constexpr (STREAM)
+			a.y[(long long)c * a.st.y_stride + (t - a.st.o0)] = make_float2(yr, yi);
+		else
+			a.y[(long long)c * a.T + t] = make_float2(yr, yi);
 	}
 }
 
 hipError_t launch_pfb(const PfbArgs &a, hipStream_t stream)
 {
-	if (a.T <= 0)
+	const bool strm = a.st.xt != nullptr;
+	const long long t_lo = strm ? a.st.o0 : 0;
+	if (a.T <= t_lo)
 		return hipSuccess;
+	if (t_lo < 0)
+		return hipErrorInvalidValue;
 	if (a.n_chans != 64) {
 		if (a.n_chans < 2 || a.n_chans > kPfbMaxChans || (a.n_chans & 1) || !a.sel || a.n_sel <= 0)
 			return hipErrorInvalidValue;
-		const long long grid = (a.T + kAnyTile - 1) / kAnyTile;
+		const long long grid = (a.T - t_lo + kAnyTile - 1) / kAnyTile;
 		const size_t lds = (size_t)(kAnyTile * (a.n_chans + 1) + a.n_chans) * sizeof(float2);
-		if (a.rotation != 0.0f)
-			hipLaunchKernelGGL(k_pfb_any<true>, dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
+		const bool rot = a.rotation != 0.0f;
+		if (strm && rot)
+			hipLaunchKernelGGL((k_pfb_any<true, true>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
+		else if (strm)
+			hipLaunchKernelGGL((k_pfb_any<false, true>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
+		else if (rot)
+			hipLaunchKernelGGL((k_pfb_any<true, false>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
 		else
-			hipLaunchKernelGGL(k_pfb_any<false>, dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
+			hipLaunchKernelGGL((k_pfb_any<false, false>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
 		return hipGetLastError();
 	}
-	const long long grid = (a.T + kPfbSteps - 1) / kPfbSteps;
-	if (a.rotation != 0.0f)
-		hipLaunchKernelGGL(k_pfb64<true>, dim3((unsigned)grid), dim3(64), 0, stream, a);
+	const int steps = strm ? kPfbStepsStream : kPfbSteps;
+	const long long grid = (a.T - (t_lo & ~1LL) + steps - 1) / steps;
+	const bool rot = a.rotation != 0.0f;
+	if (strm && rot)
+		hipLaunchKernelGGL((k_pfb64<true, true>), dim3((unsigned)grid), dim3(64), 0, stream, a);
+	else if (strm)
+		hipLaunchKernelGGL((k_pfb64<false, true>), dim3((unsigned)grid), dim3(64), 0, stream, a);
+	else if (rot)
+		hipLaunchKernelGGL((k_pfb64<true, false>), dim3((unsigned)grid), dim3(64), 0, stream, a);
 	else
-		hipLaunchKernelGGL(k_pfb64<false>, dim3((unsigned)grid), dim3(64), 0, stream, a);
+		hipLaunchKernelGGL((k_pfb64<false, false>), dim3((unsigned)grid), dim3(64), 0, stream, a);
 	return hipGetLastError();
 }
 
@@ -386,6 +423,7 @@ hipError_t launch_pfb(const PfbArgs &a, hipStream_t stream)
 // resamples DOWN (rate 0.468) and its root-raised cosine is 95 taps per phase long -- a second instantiation
 static constexpr int kRsTapsShort = 30, kRsTapsLong = 96;
 static constexpr int kRsPeriods = 32;        // periods one wave walks
+static constexpr int kRsPeriodsStream = 4;   // ... in a streamed push (a small grid: the walk is the push's time)
 static constexpr int kRsRing = 8;            // k_resamp2: ring slots of one period's window each (seven periods in flight)
 static constexpr int kRsWinTight = 128, kRsWinShort = 256, kRsWinLong = 512;     // LDS window (samples) per wave, >= span
 
@@ -419,12 +457,14 @@ __device__ __forceinline__ void rs_mac2(rs_v2f &acc0, rs_v2f &acc1, rs_v2f e0, r
 }
 
 // EXT: the instantiation that can rotate its input (the pre-resampler of an off-grid capture) and write polyphase-planar
-// output; the plain one does neither and keeps its registers
+// output; the plain one does neither and keeps its registers.  STREAM: the outputs [st.o0, n_out) of a streamed run (the
+// streaming path's one resampler form: a lane owns one output, so partial periods at either end are no more than the
+// store's range test -- k_resamp2's pairs and clamped ring would need both ends handled again)
 // (the 30-tap instantiations are compiled for at least five waves per SIMD: the compiler otherwise keeps all thirty samples
 // of a period in flight at once)
 template <int kRsTaps, bool EXT>
 constexpr int kRsWaves = kRsTaps <= 32 ? 5 : 2;
-template <int kRsTaps, int kRsWin, bool EXT = false>
+template <int kRsTaps, int kRsWin, bool EXT = false, bool STREAM = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRsWaves<kRsTaps, EXT>)))
 void k_resamp(ResampArgs a, long long P, long long Q, int span)
 {
@@ -459,19 +499,24 @@ void k_resamp(ResampArgs a, long long P, long long Q, int span)
 		const float2 b0 = a.bank[j * kRsTaps + k], b1 = a.bank[j * kRsTaps + k + 1];
 		e2[k / 2] = (rs_v2f){fmaf(frac, b0.y, b0.x), fmaf(frac, b1.y, b1.x)};
 	}
-	const float2 *__restrict__ y = a.y + (long long)sl * a.T;
+	const float2 *__restrict__ y = a.y + (long long)sl * (STREAM ? a.st.x_stride : a.T);
+	const float2 *__restrict__ yt = STREAM ? a.st.xt + (long long)sl * a.st.x_stride : nullptr;
 	float2 *__restrict__ out = a.out + (long long)sl * a.out_stride;
-	const long long m0 = (long long)blockIdx.z * kRsPeriods;
+	constexpr int kPer = STREAM ? kRsPeriodsStream : kRsPeriods;
+	const long long m0 = (STREAM ? a.st.o0 / P : 0) + (long long)blockIdx.z * kPer;
 
 	// window of period m: inputs i_first + m Q + [0, span)
-	static_assert(kRsPeriods % D == 0, "the period loop runs in blocks of D");
+	static_assert(kPer % D == 0, "the period loop runs in blocks of D");
 	float2 ring[D][NH];
 	auto fetch = [&](long long m, float2 (&nx)[NH]) {
 #pragma unroll
 		for (int h = 0; h < NH; h++) {
 			const int w = lane + 64 * h;
 			const long long s = i_first + m * Q + w;
-			nx[h] = (w < span && s >= 0 && s < a.T) ? y[s] : make_float2(0.f, 0.f);
+			if constexpr (STREAM)
+				nx[h] = w < span ? stream_ld(y, yt, a.st, s, a.T) : make_float2(0.f, 0.f);
+			else
+				nx[h] = (w < span && s >= 0 && s < a.T) ? y[s] : make_float2(0.f, 0.f);
 			if (EXT && a.rotation != 0.0f) {
 				// e^{j rotation s}, the angle reduced in double as in k_pfb64 (long captures keep their phase)
 				const double ph = (double)a.rotation * (double)s;
@@ -496,7 +541,7 @@ void k_resamp(ResampArgs a, long long P, long long Q, int span)
 #pragma unroll
 	for (int d = 0; d < D; d++)
 		fetch(m0 + d, ring[d]);
-	for (int mm = 0; mm < kRsPeriods; mm += D) {
+	for (int mm = 0; mm < kPer; mm += D) {
 		if ((m0 + mm) * P >= a.n_out)
 			return;
 		WSYNC();
@@ -507,7 +552,7 @@ void k_resamp(ResampArgs a, long long P, long long Q, int span)
 				if (lane + 64 * h < span)
 					xsb[d][lane + 64 * h] = ring[d][h];
 		WSYNC();
-		if (mm + D < kRsPeriods) {
+		if (mm + D < kPer) {
 #pragma unroll
 			for (int d = 0; d < D; d++)
 				fetch(m0 + mm + D + d, ring[d]);    // the next block's windows travel during this block's arithmetic
@@ -529,8 +574,10 @@ void k_resamp(ResampArgs a, long long P, long long Q, int span)
 #pragma unroll
 		for (int d = 0; d < D; d++) {
 			const long long n = (m0 + mm + d) * P + p;
-			if (live && n < a.n_out) {
-				if (EXT && a.planar_sps > 0)
+			if (live && n < a.n_out && (!STREAM || n >= a.st.o0)) {
+				if (STREAM)
+					out[n - a.st.o0] = make_float2(res[d].x, res[d].y);
+				else if (EXT && a.planar_sps > 0)
 					a.out[(long long)pl_r * a.plane_stride + pl_q] = make_float2(res[d].x, res[d].y);
 				else
 					out[n] = make_float2(res[d].x, res[d].y);
@@ -1032,25 +1079,30 @@ void k_resamp2w(ResampArgs a, long long P, long long Q, int nch)
 // every thread then runs its own dot product out of LDS.  Stage 1 reads the one wideband stream for every carrier
 // with that carrier's complex taps  taps[k] exp(+j 2 pi f k / fs)  and turns the output by exp(-j 2 pi f m D / fs)
 // (freq_xlating_fir_filter_ccc: the same as mixing x down by f first), the angle reduced in double so that a minute
-// of capture keeps its phase; stage 2 has real taps and no rotation.
+// of capture keeps its phase; stage 2 has real taps and no rotation.  STREAM: the outputs [st.o0, n_out) of a streamed run.
 // ---------------------------------------------------------------------------
 static constexpr int kDdcOut = 256;
 
+template <bool STREAM>
 __global__ __launch_bounds__(256) void k_ddc_fir(DdcFirArgs a)
 {
 	extern __shared__ __align__(16) unsigned char ddc_lds[];
 	float2 *tp = reinterpret_cast<float2 *>(ddc_lds);                     // ntaps
 	float2 *xs = tp + a.ntaps;                                           // kDdcOut * decim + ntaps
 	const int s = blockIdx.y, tid = threadIdx.x;
-	const long long m0 = (long long)blockIdx.x * kDdcOut;
+	const long long m0 = (STREAM ? a.st.o0 : 0) + (long long)blockIdx.x * kDdcOut;
 	const float2 *__restrict__ x = a.x + (long long)s * a.in_stride;
+	const float2 *__restrict__ xt = STREAM ? a.st.xt + (long long)s * a.in_stride : nullptr;
 	const int span = kDdcOut * a.decim + a.ntaps;
 	const long long first = m0 * a.decim - (a.ntaps - 1);                 // oldest sample the block touches
 	for (int i = tid; i < a.ntaps; i += 256)
 		tp[i] = a.taps[(long long)s * a.ntaps + i];
 	for (int i = tid; i < span; i += 256) {
 		const long long n = first + i;
-		xs[i] = (n >= 0 && n < a.n_in) ? x[n] : make_float2(0.f, 0.f);
+		if constexpr (STREAM)
+			xs[i] = stream_ld(x, xt, a.st, n, a.n_in);
+		else
+			xs[i] = (n >= 0 && n < a.n_in) ? x[n] : make_float2(0.f, 0.f);
 	}
 	__syncthreads();
 	const long long m = m0 + tid;
@@ -1073,26 +1125,82 @@ __global__ __launch_bounds__(256) void k_ddc_fir(DdcFirArgs a)
 		ar = r;
 		ai = q;
 	}
-	a.y[(long long)s * a.n_out + m] = make_float2(ar, ai);
+	if constexpr (STREAM)
+		a.y[(long long)s * a.st.y_stride + (m - a.st.o0)] = make_float2(ar, ai);
+	else
+		a.y[(long long)s * a.n_out + m] = make_float2(ar, ai);
+}
+
+// ---------------------------------------------------------------------------
+// k_keep_tail -- what a streamed run keeps between pushes: per job and row, the last L samples of (a[0, na) ++ b[0, nb)) go
+// to dst[0, L) (L <= na + nb).  One work-group per row reads them all into LDS before it writes, so dst may be a itself
+// (the stage buffers' [tail | new samples] moved to the front).  O(L) per row: the history a stage needs, never a chunk.
+// All of a push's stages in one launch (blockIdx.y: the job): each launch is ~4 us of a push that is 20-70 us.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_keep_tail(KeepTailArgs ka)
+{
+	extern __shared__ float2 keep_lds[];
+	const KeepTail &j = ka.job[blockIdx.y];
+	const long long row = blockIdx.x, g0 = j.na + j.nb - j.L;
+	if (row >= j.rows)
+		return;
+	for (int i = threadIdx.x; i < j.L; i += 256) {
+		const long long g = g0 + i;
+		keep_lds[i] = g < j.na ? j.a[row * j.a_stride + g] : j.b[row * j.b_stride + (g - j.na)];
+	}
+	__syncthreads();
+	for (int i = threadIdx.x; i < j.L; i += 256)
+		j.dst[row * j.dst_stride + i] = keep_lds[i];
+}
+
+hipError_t launch_keep_tail(const KeepTailArgs &a, hipStream_t stream)
+{
+	if (a.n < 0 || a.n > kKeepJobs)
+		return hipErrorInvalidValue;
+	int rows = 0, L = 0;
+	for (int i = 0; i < a.n; i++) {
+		const KeepTail &j = a.job[i];
+		if (j.L < 0 || j.L > kKeepTailMax || j.rows < 0 || j.na < 0 || j.nb < 0 || j.na + j.nb < j.L || (j.nb > 0 && !j.b))
+			return hipErrorInvalidValue;
+		rows = j.rows > rows ? j.rows : rows;
+		L = j.L > L ? j.L : L;
+	}
+	if (rows == 0 || L == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_keep_tail, dim3((unsigned)rows, (unsigned)a.n), dim3(256), (size_t)L * sizeof(float2), stream, a);
+	return hipGetLastError();
 }
 
 hipError_t launch_ddc_fir(const DdcFirArgs &a, hipStream_t stream)
 {
-	if (a.n_out <= 0 || a.n_sel <= 0)
+	const bool strm = a.st.xt != nullptr;
+	const long long m_lo = strm ? a.st.o0 : 0;
+	if (a.n_out <= m_lo || a.n_sel <= 0)
 		return hipSuccess;
+	if (m_lo < 0)
+		return hipErrorInvalidValue;
 	if (a.ntaps < 1 || a.ntaps > kDdcMaxTaps || a.decim < 1 || a.decim > 64)
 		return hipErrorInvalidValue;
 	const size_t lds = ((size_t)a.ntaps + (size_t)kDdcOut * a.decim + a.ntaps) * sizeof(float2);
 	if (lds > 150 * 1024)
 		return hipErrorInvalidValue;
+	const void *fn = strm ? reinterpret_cast<const void *>(k_ddc_fir<true>) : reinterpret_cast<const void *>(k_ddc_fir<false>);
 	if (lds > 64 * 1024)
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ddc_fir), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	hipLaunchKernelGGL(k_ddc_fir, dim3((unsigned)((a.n_out + kDdcOut - 1) / kDdcOut), (unsigned)a.n_sel), dim3(256), lds, stream, a);
+		(void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+	const dim3 grid((unsigned)((a.n_out - m_lo + kDdcOut - 1) / kDdcOut), (unsigned)a.n_sel);
+	if (strm)
+		hipLaunchKernelGGL(k_ddc_fir<true>, grid, dim3(256), lds, stream, a);
+	else
+		hipLaunchKernelGGL(k_ddc_fir<false>, grid, dim3(256), lds, stream, a);
 	return hipGetLastError();
 }
 
+static hipError_t launch_resamp_stream(const ResampArgs &a, hipStream_t stream);
+
 hipError_t launch_resamp(const ResampArgs &a, hipStream_t stream)
 {
+	if (a.st.xt)
+		return launch_resamp_stream(a, stream);
 	if (a.n_out <= 0 || a.n_slots <= 0)
 		return hipSuccess;
 	const bool lng = a.tpf == kRsTapsLong;
@@ -1172,6 +1280,39 @@ hipError_t launch_resamp(const ResampArgs &a, hipStream_t stream)
 		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight>), dim3(gx, (unsigned)a.n_slots, gz), dim3(64), 0, stream, a, P, Q, span);
 	else
 		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort>), dim3(gx, (unsigned)a.n_slots, gz), dim3(64), 0, stream, a, P, Q, span);
+	return hipGetLastError();
+}
+
+// the outputs [st.o0, n_out) of a streamed run: k_resamp's STREAM instantiations, periods from the one st.o0 falls in
+static hipError_t launch_resamp_stream(const ResampArgs &a, hipStream_t stream)
+{
+	if (a.n_out <= a.st.o0 || a.n_slots <= 0)
+		return hipSuccess;
+	const bool lng = a.tpf == kRsTapsLong;
+	if ((a.tpf != kRsTapsShort && !lng) || a.st.o0 < 0 || a.planar_sps > 0)
+		return hipErrorInvalidValue;
+	const int taps = lng ? kRsTapsLong : kRsTapsShort, win = lng ? kRsWinLong : kRsWinShort;
+	long long g = a.num, b = a.den * a.nfilt;
+	while (b) { const long long t = g % b; g = b; b = t; }
+	const long long P = a.den * a.nfilt / g, Q = a.num / g;
+	const int span = (int)((63 * a.num) / (a.den * a.nfilt)) + taps + 2;
+	if (span > win)
+		return hipErrorInvalidValue;
+	const long long periods = (a.n_out + P - 1) / P - a.st.o0 / P;
+	const dim3 grid((unsigned)((P + 63) / 64), (unsigned)a.n_slots, (unsigned)((periods + kRsPeriodsStream - 1) / kRsPeriodsStream));
+	const bool rot = a.rotation != 0.0f;
+	if (lng && rot)
+		return hipErrorInvalidValue;
+	if (lng)
+		hipLaunchKernelGGL((k_resamp<kRsTapsLong, kRsWinLong, false, true>), grid, dim3(64), 0, stream, a, P, Q, span);
+	else if (rot && span <= kRsWinTight)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, true, true>), grid, dim3(64), 0, stream, a, P, Q, span);
+	else if (rot)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, true, true>), grid, dim3(64), 0, stream, a, P, Q, span);
+	else if (span <= kRsWinTight)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, false, true>), grid, dim3(64), 0, stream, a, P, Q, span);
+	else
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, false, true>), grid, dim3(64), 0, stream, a, P, Q, span);
 	return hipGetLastError();
 }
 

@@ -278,6 +278,18 @@ struct A5Args {
 };
 
 // wideband -> per-ARFCN channelizer (chan_kernels.hip)
+// A streamed run (gmr1_hip_chan_stream_*): every sample, instant and output index of a stage is GLOBAL -- counted from the
+// start of the stream -- so that phases, rotations and filter positions are the one-shot run's.  A stage's input comes
+// from two places: its retained tail `xt` (global samples [xt0, x0)) and the new samples `x` (global [x0, end)); outside
+// [xt0, end) it reads zeros.  Outputs [o0, end) are stored at element (index - o0) of their row.  Only the kernels'
+// STREAM instantiations read these fields (a launcher takes them when xt is set); the one-shot ones do not.
+struct StreamIdx {
+	const float2 *xt;          // retained tail of the input, x_stride apart per row like x
+	long long xt0, x0;         // global index of xt[0] and of x[0]
+	long long o0;              // global index of the first output stored
+	long long x_stride;        // complex samples between input rows (resampler)
+	long long y_stride;        // ... between output rows (filterbank, decimating FIR; the resampler has out_stride)
+};
 constexpr int kPfbMaxBlocks = 11;        // prototype taps / n_chans, rounded up, + 1
 static constexpr int kPfbMaxChans = 256;
 struct PfbArgs {
@@ -293,6 +305,7 @@ struct PfbArgs {
 	float2 *y;                 // n_slots x T, 2x oversampled channel streams
 	const int32_t *sel;        // n_sel selected channel indices (slot order), used by the generic kernel
 	int n_sel;
+	StreamIdx st;              // streamed run: n_in and T are global ends
 };
 struct ResampArgs {
 	int n_slots;
@@ -309,6 +322,7 @@ struct ResampArgs {
 	                           // of an off-grid capture: the script rotates first, utils/gmr1_rx_sdr.py:444-461)
 	int planar_sps;            // > 0: `out` is polyphase-planar -- sample g = slot out_stride + n of the flat output array
 	long long plane_stride;    // goes to out[(g % planar_sps) * plane_stride + g / planar_sps] (include/gmr1_hip.h)
+	StreamIdx st;              // streamed run (never planar): T and n_out are global ends
 };
 hipError_t launch_pfb(const PfbArgs &a, hipStream_t stream);
 hipError_t launch_resamp(const ResampArgs &a, hipStream_t stream);
@@ -325,8 +339,23 @@ struct DdcFirArgs {
 	const float2 *taps;        // n_sel x ntaps complex taps (stage 1: the low-pass turned to the carrier; stage 2: real taps, im = 0)
 	const double *rot;         // optional, n_sel: output m is multiplied by exp(-j 2 pi frac(m rot[s])) (stage 1)
 	float2 *y;                 // n_sel x n_out
+	StreamIdx st;              // streamed run: n_in and n_out are global ends
 };
 hipError_t launch_ddc_fir(const DdcFirArgs &a, hipStream_t stream);
+// a streamed run's retained history, all of a push's stages in one launch: per job and row r < rows, the last L samples of
+// (a[r a_stride + [0, na)] ++ b[r b_stride + [0, nb)]) to dst[r dst_stride + [0, L)]; dst may be a
+constexpr int kKeepTailMax = 4096, kKeepJobs = 3;
+struct KeepTail {
+	float2 *dst;
+	const float2 *a, *b;
+	long long dst_stride, a_stride, b_stride, na, nb;
+	int L, rows;
+};
+struct KeepTailArgs {
+	KeepTail job[kKeepJobs];
+	int n;
+};
+hipError_t launch_keep_tail(const KeepTailArgs &a, hipStream_t stream);
 
 hipError_t launch_dkab(const DkabArgs &a, hipStream_t stream);
 hipError_t launch_a5(const A5Args &a, hipStream_t stream);
