@@ -101,8 +101,23 @@ int rough_dev(hipStream_t st, int tab, int n, int sps, int len, const float *iq,
 			// Profiling build: GMR1_HIP_FCCH_FOLD_POLLS=0 makes every tile give up at once -- the fallback path, for the tests)
 			static const int polls = [] { const char *e = profile_env("GMR1_HIP_FCCH_FOLD_POLLS"); return e ? atoi(e) : 1 << 14; }();
 			a.fold_polls = polls;
+			// (profiling build: GMR1_HIP_FCCH_FOLD_GIVEUP=k,r makes the tiles with tile % k == r give up as if their wait had run
+			// out, the others fold -- a stream whose tiles did not start together; a negative r counts from the stream's end)
+			static const std::pair<int, int> giveup = [] {
+				const char *e = profile_env("GMR1_HIP_FCCH_FOLD_GIVEUP");
+				int k = 0, r = 0;
+				if (!e || sscanf(e, "%d,%d", &k, &r) != 2 || k < 1) k = r = 0;
+				return std::make_pair(k, r);
+			}();
+			a.fold_giveup_k = giveup.first;
+			a.fold_giveup_r = giveup.second;
 		}
 	}
+	// (profiling build: GMR1_HIP_FCCH_POISON=1 fills the lag / sample scratch with 0x4f bytes, about 3.5e9 a float, first: a lag
+	// that no tile wrote then decides the pick, whatever earlier calls left there)
+	static const bool poison = [] { const char *e = profile_env("GMR1_HIP_FCCH_POISON"); return e && atoi(e) != 0; }();
+	if (poison)
+		HIP_TRY(hipMemsetAsync(a.dec, 0x4f, b_dec, st));
 	HIP_TRY(launch_fcch_rough_tail(a, ntaps, tl, st));
 	return 0;
 }
@@ -284,7 +299,10 @@ int fcch_rough_multi_tail(hipStream_t stream, int fcch_type, int n, int sps, int
 	// the energy plane lives behind the rough sweep's own scratch: ask for both at once
 	const int ndec = len / sps;
 	const size_t b_dec = (size_t)n * ((((size_t)ndec + 15) & ~(size_t)15) * 8);
-	const size_t b_par = (((size_t)n * fcch_stat_tiles(len) * 16) + 255) & ~(size_t)255;
+	// (the statistics partials sized exactly as rough_dev sizes them -- per lag tile in the one-pass form, more of them than
+	// kStatSpan tiles below 4 samples a symbol -- or the energy plane would start inside rough_dev's tile results)
+	const int n_stat_tiles = fcch_one_pass() ? fcch_lag_tiles(nlags) : fcch_stat_tiles(len);
+	const size_t b_par = (((size_t)n * n_stat_tiles * 16) + 255) & ~(size_t)255;
 	const size_t b_best = (((size_t)n * fcch_lag_tiles(nlags) * 32) + 255) & ~(size_t)255;
 	const size_t b_rough = b_dec + b_par + b_best;
 	void *ws;

@@ -535,6 +535,12 @@ __global__ __launch_bounds__(256) void k_fcch_sweep(FcchRoughArgs a)
 					break;
 				__builtin_amdgcn_s_sleep(4);
 			}
+#ifdef GMR1_HIP_PROFILE
+			// GMR1_HIP_FCCH_FOLD_GIVEUP=k,r: the tile gives up whatever its records say (a negative r counts from the stream's end)
+			if (a.fold_giveup_k > 0 && (tile - (a.fold_giveup_r < 0 ? a.fold_giveup_r + a.n_lag_tiles : a.fold_giveup_r)) %
+			                               a.fold_giveup_k == 0)
+				have = false;
+#endif
 			// (k_fcch_energy's sums: lane t holds tile t's partial, the rest zero; the same butterfly in double)
 			double dr = lane < a.n_stat_tiles ? (double)r.sr : 0.0, di = lane < a.n_stat_tiles ? (double)r.si : 0.0,
 			       dq = lane < a.n_stat_tiles ? (double)r.sq : 0.0;
@@ -650,6 +656,13 @@ __global__ __launch_bounds__(256) void k_fcch_sweep(FcchRoughArgs a)
 					for (int k = 0; k < 5; k++)
 						o[2 + k] = en[bi - m0 + k];
 				}
+				// and the raw correlation of the tile's first four lags all the same (lane 0 of wave 0: 32 bytes; here, where no
+				// barrier waits for the stores): the previous tile's windows reach them, and if that tile gave up, k_fcch_energy
+				// reads them from here -- this tile's, as in the two-kernel form, never what the workspace held before
+#pragma unroll
+				for (int v = 0; v < 4; v++)
+					if (m0 + v < nlags)
+						acc[m0 + v] = make_float2(dr0[v], di0[v]);
 			}
 		}
 	}

@@ -181,6 +181,7 @@ struct FcchRoughArgs {
 	// sum |x|^2, epoch, -, -} in a buffer only these kernels write: a word whose epoch is THIS launch's was written by this launch
 	float *fold_partial;  uint32_t epoch;
 	int fold_polls;                          // how often a tile looks for the stream's records before it gives up
+	int fold_giveup_k, fold_giveup_r;        // profiling build: tiles with tile % k == r give up all the same (k 0: none)
 };
 
 struct FcchMultiArgs {
