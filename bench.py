@@ -9,6 +9,12 @@ path (gmr1_hip_rx_bcch_ccch_batch_dev) over the whole batch, inputs resident in
 HBM.  With N GPUs every rank processes its own batch (bursts are independent:
 weak scaling, no data-path collective).
 
+A plain run does only what the headline figure needs: it sets up, warms up, times the steps, writes --dump-outputs and
+prints the line.  --full adds everything else the headline line can carry, all of it after the timed region: the CPU
+oracle's baselines and its comparison with the GPU's results, the legacy one-burst calls, the planar layout and the other
+Viterbi decoder timed on the same bursts, every other BASELINE config (`side`) and, with N > 1, the sharded config-4
+exchange (`sharded_rx`).  A --workload line is a side measurement asked for by name and keeps its checks either way.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -50,10 +56,17 @@ def parse():
                     help="untimed seconds of the same step before the warm-up steps: brings the GPU out of its idle clocks "
                          "(a cold launch of this 0.3 ms kernel runs about 20 %% slower); 0 disables")
     ap.add_argument("--bursts", type=int, default=100_000, help="bursts per GPU per step")
-    ap.add_argument("--cpu-sample", type=int, default=100_000, help="bursts timed on the CPU oracle (rank 0, N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="bursts workload: after the timed region, also run the CPU oracle baselines and comparisons, the "
+                         "legacy one-burst calls, the planar layout and the other Viterbi decoder, every other BASELINE config "
+                         "(`side`) and, with N > 1, the sharded config-4 exchange; --no-cpu, --no-extras and --no-shard leave "
+                         "out parts of it.  Off: set up, warm up, time the steps, dump the outputs, print the line")
+    ap.add_argument("--cpu-sample", type=int, default=100_000, help="bursts timed on the CPU oracle (rank 0, N=1; with --full)")
     ap.add_argument("--cpu-passes", type=int, default=3,
-                    help="bursts workload: passes of the CPU oracle over its sample (3 x 100k bursts = about 11 s of CPU work)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="bursts workload with --full: passes of the CPU oracle over its sample (3 x 100k bursts = about 11 s "
+                         "of CPU work)")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="no CPU oracle leg (bursts workload: with --full; --workload lines: their CPU baseline and oracle checks)")
     ap.add_argument("--nt3-two-launches", action="store_true",
                     help="nt3 workload: demodulate and decode the speech bursts with the two separate calls")
     ap.add_argument("--workload", default="bursts", choices=["bursts", "fcch", "tch3", "nt3", "rx", "chan", "ambe"],
@@ -67,11 +80,11 @@ def parse():
     ap.add_argument("--streams", type=int, default=1024, help="fcch workload: 1-s streams per GPU")
     ap.add_argument("--channels", type=int, default=8192, help="ambe workload: voice channels per GPU")
     ap.add_argument("--frames", type=int, default=100, help="ambe workload: 20 ms frames per channel and step")
-    ap.add_argument("--shard-arfcns", type=int, default=64, help="N > 1: carriers of the sharded config-4 run (extra keys)")
-    ap.add_argument("--shard-seconds", type=float, default=60.0, help="N > 1: capture length of the sharded config-4 run")
-    ap.add_argument("--no-shard", action="store_true", help="N > 1: skip the sharded config-4 run")
+    ap.add_argument("--shard-arfcns", type=int, default=64, help="N > 1 with --full: carriers of the sharded config-4 run (extra keys)")
+    ap.add_argument("--shard-seconds", type=float, default=60.0, help="N > 1 with --full: capture length of the sharded config-4 run")
+    ap.add_argument("--no-shard", action="store_true", help="N > 1 with --full: skip the sharded config-4 run")
     ap.add_argument("--shard-timeout", type=float, default=240.0,
-                    help="N > 1: if the sharded config-4 run has not finished after this many seconds, the headline line is "
+                    help="N > 1 with --full: if the sharded config-4 run has not finished after this many seconds, the headline line is "
                          "printed without it (with the reason) instead of hanging the job")
     ap.add_argument("--conv-decoder", default="acc", choices=["generic", "acc"],
                     help="which libosmocore Viterbi decoder the layer-1 chains reproduce (gmr1_hip_set_conv_decoder): "
@@ -79,12 +92,12 @@ def parse():
                          "codes) or its generic one; the CPU oracle beside it runs the same one")
     ap.add_argument("--layout", default="interleaved", choices=["interleaved", "planar"],
                     help="bursts workload: sample layout the TIMED step reads. interleaved (default) is the layout BASELINE "
-                         "describes and the one `value` is quoted on; the default run also times the opt-in polyphase-planar "
+                         "describes and the one `value` is quoted on; a --full run also times the opt-in polyphase-planar "
                          "entry point afterwards and reports it as `roofline_planar`. --layout planar makes the planar call the "
                          "timed step itself (a side measurement for the profiler: config.layout says so)")
     ap.add_argument("--side-runner", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-extras", action="store_true",
-                    help="bursts workload: skip the measurements after the timed region (planar layout, the other decoder)")
+                    help="bursts workload with --full: skip the planar layout and the other decoder after the timed region")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="bursts workload: after the timed steps, write what the last timed step returned (l2, crc, conv, toa, "
                          "freq_err, rv per burst, and burst_index) as DIR/<name>.npy in float32 / float64, at most 64 MB in all "
@@ -97,6 +110,9 @@ def parse():
         ap.error("--warmup must not be negative")
     if args.dump_outputs and args.workload != "bursts":
         ap.error("--dump-outputs is implemented for the headline workload (bursts) only")
+    if args.full and args.workload != "bursts":
+        ap.error("--full is an option of the headline workload (bursts): a --workload line always runs its own checks "
+                 "(--no-cpu leaves out their CPU legs)")
     # read by the library on first use and by tests/oracle_lib.py when it loads the oracle; inherited by spawned ranks
     os.environ["GMR1_HIP_CONV_DECODER"] = args.conv_decoder
     os.environ["ORC_CONV_MODE"] = "1" if args.conv_decoder == "acc" else "0"
@@ -1397,12 +1413,16 @@ def main():
         return run_ambe_workload(args)
     if args.workload != "bursts":
         return run_side_workload(args)
+    # what a --full run adds after the timed region (a plain run leaves all of it out)
+    with_extras = args.full and not args.no_extras
+    with_cpu = args.full and not args.no_cpu
+    with_shard = args.full and not args.no_shard
     # every other BASELINE config goes into the same record (`side`): their runner starts now, before the GPU is touched
     side_runner = None
     # (not under a profiler: its preloaded library initialises the GPU in every process before main(), and a process that has
     # done so must not start children that exec)
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if (env_world is None and args.gpus == 1 and not args.no_extras and not args.no_cpu and not profiled
+    if (env_world is None and args.gpus == 1 and with_extras and with_cpu and not profiled
             and not os.environ.get("GMR1_BENCH_FORCE_GROUP")):
         side_runner = start_side_runner(args)
     import torch
@@ -1436,7 +1456,7 @@ def main():
     # the same samples polyphase-planar (sample s at planes[(s & 3) * P + (s >> 2)]): what the opt-in entry point reads
     n_samp = wl["iq"].size
     P = -(-n_samp // 4)
-    want_planar = args.layout == "planar" or not args.no_extras
+    want_planar = args.layout == "planar" or with_extras
     planes = None
     if want_planar:
         planes = torch.zeros(4 * P * 2, dtype=torch.float32, device=dev)
@@ -1553,7 +1573,7 @@ def main():
 
     # ---- after the timed region, outside `value`: the opt-in planar layout and the other Viterbi decoder ----------
     extras = {}
-    if not args.no_extras and args.layout == "interleaved":
+    if with_extras and args.layout == "interleaved":
         h_all = [t.cpu().numpy().copy() for t in (crc, conv, toa, ferr, rv)]
         ms_pl = time_steps(step_planar, args.steps)
         same = bool(np.array_equal(l2.cpu().numpy(), h_l2) and
@@ -1573,7 +1593,7 @@ def main():
     # does not come back (a collective that hangs must not cost the measurement that is already taken).
     sharded = None
     line = {}
-    if grouped and not args.no_shard:
+    if grouped and with_shard:
         import threading
 
         def give_up():
@@ -1684,7 +1704,7 @@ def main():
                                         "one box do not)"}
 
     # ---- CPU baseline: the oracle (a port, 1 core) on a bounded sample ----------------------
-    if world == 1 and not args.no_cpu:
+    if world == 1 and with_cpu:
         import oracle_lib
         m = min(n, args.cpu_sample)
         end = int(wl["offset"][m]) if m < n else wl["iq"].size

@@ -132,7 +132,7 @@ def test_bench_configs4_gpus2_over_gloo_on_one_gpu(workload):
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_bench_gpus2_over_gloo_on_one_gpu():
-    """`GMR1_BENCH_BACKEND=gloo python bench.py --gpus 2`: two ranks share the one MI355X, the exchanges run over
+    """`GMR1_BENCH_BACKEND=gloo python bench.py --gpus 2 --full`: two ranks share the one MI355X, the exchanges run over
     gloo.  One JSON line with n_gpus 2, and the sharded config-4 keys (scatter, receive loop, gather; carrier 0's
     frames identical to the oracle's loop).  Child processes are started only while this process has not brought
     up the GPU (this file sorts first in the suite)."""
@@ -142,7 +142,7 @@ def test_bench_gpus2_over_gloo_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["GMR1_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--bursts", "7000",
-                        "--preroll-s", "0", "--shard-arfcns", "5", "--shard-seconds", "4"],
+                        "--preroll-s", "0", "--shard-arfcns", "5", "--shard-seconds", "4", "--full"],
                        capture_output=True, text=True, timeout=550, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -162,6 +162,60 @@ def test_bench_gpus2_over_gloo_on_one_gpu():
     assert sh["resident"]["records_identical_to_scattered_run"] and sh["resident"]["rx_loop_ms"] > 0
     lo, hi = sh["rx_loop_ms_per_rank_min_max"]
     assert 0 < lo <= hi
+
+
+FULL_ONLY_KEYS = ("roofline_planar", "other_decoder", "cpu_baseline", "cpu_baseline_all_cores", "legacy_one_burst_calls", "side",
+                  "sharded_rx")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_line_and_full_line(tmp_path):
+    """A plain `bench.py` line is the headline alone: none of the keys that take runs of their own after the timed region.
+    `--full` adds them, checked here in two halves (`--no-cpu`: the planar layout and the other decoder; `--no-extras`: the
+    CPU oracle's baselines and comparison; everything at once also starts every other BASELINE config at its full size).
+    What the last timed step computed (`--dump-outputs`) is the same in all three runs."""
+    import numpy as np
+    import torch
+    if torch.cuda.is_initialized():
+        pytest.skip("this process has already initialised the GPU: not starting child processes from it")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    runs = {"plain": ([], ()),
+            "full_no_cpu": (["--full", "--no-cpu"], ("roofline_planar", "other_decoder")),
+            "full_no_extras": (["--full", "--no-extras"], ("cpu_baseline", "cpu_baseline_all_cores", "legacy_one_burst_calls"))}
+    dumps = {}
+    for name, (extra, present) in runs.items():
+        dumps[name] = tmp_path / name
+        r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--bursts", "7000", "--preroll-s", "0",
+                            "--dump-outputs", str(dumps[name])] + extra, capture_output=True, text=True, timeout=170, env=env)
+        assert r.returncode == 0, (name, r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, (name, r.stdout)
+        out = json.loads(lines[0])
+        assert out["unit"] == "Mbursts/s" and out["higher_is_better"] is True and out["dtype"] == "f32+i32", name
+        assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["config"]["bursts_per_gpu"] == 7000
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["roofline"]["kernel_ms"] > 0
+        assert out["checks"]["payloads_match_sent"] and out["checks"]["crc_pass_frac"] > 0.9
+        assert sorted(k for k in FULL_ONLY_KEYS if k in out) == sorted(present), name
+        if "roofline_planar" in present:
+            assert out["roofline_planar"]["outputs_bit_identical_to_interleaved"] and out["other_decoder"]["kernel_ms"] > 0
+        if "cpu_baseline" in present:
+            assert out["checks"]["gpu_vs_oracle_crc_identical"] and out["checks"]["gpu_vs_oracle_payloads_identical"]
+            assert out["legacy_one_burst_calls"]["identical_to_oracle"]
+        else:
+            assert "gpu_vs_oracle_crc_identical" not in out["checks"]
+    names = sorted(os.listdir(dumps["plain"]))
+    assert names == ["burst_index.npy", "conv.npy", "crc.npy", "freq_err.npy", "l2.npy", "rv.npy", "toa.npy"]
+    for name in runs:
+        assert sorted(os.listdir(dumps[name])) == names
+        for f in names:
+            assert np.array_equal(np.load(dumps[name] / f), np.load(dumps["plain"] / f)), (name, f)
+
+
+def test_full_is_refused_for_a_side_workload():
+    r = subprocess.run([sys.executable, BENCH, "--workload", "fcch", "--full"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full is an option of the headline workload" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
 def test_side_runner_protocol():

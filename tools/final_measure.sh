@@ -13,15 +13,15 @@ bash tools/traffic_nt3.sh $t > $o/traffic_nt3.log 2>&1
 cp gpurun_out/hbm_traffic_nt3.json $o/hbm_traffic_nt3.json; cp gpurun_out/hbm_traffic_nt3.json profiles/hbm_traffic_nt3.json
 echo "traffic done"
 # 2. the bench lines
-python3 bench.py > $o/bench_100k.json 2> $o/bench_100k.err
-python3 bench.py --conv-decoder generic > $o/bench_100k_generic.json 2> $o/bench_100k_generic.err
+python3 bench.py --full > $o/bench_100k.json 2> $o/bench_100k.err
+python3 bench.py --full --conv-decoder generic > $o/bench_100k_generic.json 2> $o/bench_100k_generic.err
 for w in nt3 tch3 fcch rx chan ambe; do python3 bench.py --workload $w > $o/bench_$w.json 2> $o/bench_$w.err; done
 for w in nt3 tch3 rx; do python3 bench.py --workload $w --conv-decoder generic --no-cpu > $o/bench_${w}_generic.json 2> $o/bench_${w}_generic.err; done
 python3 bench.py --workload rx --arfcns 512 --seconds 20 --no-cpu > $o/bench_rx_512x20s.json 2> $o/bench_rx_512.err
 python3 bench.py --workload nt3 --no-cpu --nt3-two-launches > $o/bench_nt3_two_launches.json 2> $o/bench_nt3_two.err
 echo "benches done"
 # 3. rocprofv3 kernel statistics of the same commands
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_bench -- python3 bench.py --no-cpu > $o/bench_100k_under_profiler.json 2> $o/stats_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_bench -- python3 bench.py --full --no-cpu > $o/bench_100k_under_profiler.json 2> $o/stats_bench.err
 cp $(ls $o/stats_bench/*/*kernel_stats.csv | head -1) $o/kernel_stats_bench100k.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_nt3 -- python3 bench.py --workload nt3 --no-cpu --steps 20 > /dev/null 2> $o/stats_nt3.err
 cp $(ls $o/stats_nt3/*/*kernel_stats.csv | head -1) $o/kernel_stats_nt3_1M.csv

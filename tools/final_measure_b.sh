@@ -20,9 +20,9 @@ python3 tools/time_legacy.py > $o/legacy_one_burst_calls.json 2> $o/legacy.err
 echo "pmc done"
 timeout -k 10 900 python3 -m pytest tests -q -m gpu > $o/gpu_tests.log 2>&1; tail -3 $o/gpu_tests.log
 # 5. the N > 1 paths rehearsed on the one GPU: two gloo ranks (headline with the sharded receive loop, configs[4] both ways), RCCL with one rank
-GMR1_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 20 --warmup 5 --shard-arfcns 16 --shard-seconds 20 > $o/bench_gloo2_one_gpu.json 2> $o/bench_gloo2.err
+GMR1_BENCH_BACKEND=gloo python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --shard-arfcns 16 --shard-seconds 20 > $o/bench_gloo2_one_gpu.json 2> $o/bench_gloo2.err
 GMR1_BENCH_BACKEND=gloo python3 bench.py --workload nt3 --gpus 2 --steps 20 --warmup 5 --no-cpu > $o/bench_nt3_gloo2_one_gpu.json 2> $o/bench_nt3_gloo2.err
 GMR1_BENCH_BACKEND=gloo python3 bench.py --workload tch3 --gpus 2 --steps 20 --warmup 5 --no-cpu > $o/bench_tch3_gloo2_one_gpu.json 2> $o/bench_tch3_gloo2.err
-GMR1_BENCH_FORCE_GROUP=1 python3 bench.py --no-cpu --steps 20 --shard-arfcns 16 --shard-seconds 20 > $o/bench_rccl_one_rank.json 2> $o/bench_rccl1.err
+GMR1_BENCH_FORCE_GROUP=1 python3 bench.py --full --no-cpu --steps 20 --shard-arfcns 16 --shard-seconds 20 > $o/bench_rccl_one_rank.json 2> $o/bench_rccl1.err
 rm -rf gpurun_out/traffic_${t}_* gpurun_out/pmc_${t}_* gpurun_out/pmc2_${t}_*
 ls -la $o | head -80

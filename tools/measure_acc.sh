@@ -5,11 +5,11 @@ t=$1
 o=gpurun_out/$t
 mkdir -p $o
 for m in generic acc; do
-  python3 bench.py --conv-decoder $m > $o/${m}_bench_100k.json 2> $o/${m}_bench_100k.err
+  python3 bench.py --full --conv-decoder $m > $o/${m}_bench_100k.json 2> $o/${m}_bench_100k.err
   for w in nt3 tch3 rx; do python3 bench.py --workload $w --conv-decoder $m > $o/${m}_bench_$w.json 2> $o/${m}_bench_$w.err; done
   echo "$m benches done"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_bench -- python3 bench.py --no-cpu --conv-decoder acc > /dev/null 2> $o/stats_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_bench -- python3 bench.py --full --no-cpu --conv-decoder acc > /dev/null 2> $o/stats_bench.err
 cp $(ls $o/stats_bench/*/*kernel_stats.csv | head -1) $o/acc_kernel_stats_bench100k.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_nt3 -- python3 bench.py --workload nt3 --no-cpu --steps 20 --conv-decoder acc > /dev/null 2> $o/stats_nt3.err
 cp $(ls $o/stats_nt3/*/*kernel_stats.csv | head -1) $o/acc_kernel_stats_nt3_1M.csv

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 t=$1
 o=gpurun_out/$t
 mkdir -p $o
-python3 bench.py --no-cpu > $o/bench_100k_nocpu.json 2> $o/bench.err
+python3 bench.py --full --no-cpu > $o/bench_100k_nocpu.json 2> $o/bench.err
 bash tools/measure_traffic.sh $t > $o/traffic.log 2>&1
 cp gpurun_out/hbm_traffic.json $o/hbm_traffic.json
 for lay in interleaved planar; do for m in acc generic; do
