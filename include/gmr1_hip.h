@@ -460,6 +460,40 @@ int gmr1_hip_rx_run(int n_arfcn, int sps, const float *iq, uint64_t iq_len,
                     struct gmr1_hip_rx_record *out, int max_records, int *n_records,
                     int32_t *status, int32_t *n_chains);
 
+/* The receive loop over a capture pushed piece by piece: gmr1_hip_rx_run for a live receiver, with bounded memory and no
+ * capture-length limit.  Carrier i's next n complex64 samples are iq[2*(i*iq_stride + k)], k < n -- the layout of a
+ * gmr1_hip_chan_stream push's `out`, which can go straight in on the same HIP stream.  last != 0: these are the capture's
+ * final samples (n may be 0).  arfcn may be NULL (records carry the carrier index); sps 1..16 as for gmr1_hip_rx_run.
+ *  - Each push returns exactly the records that became final in it, ordered by carrier, chain, time.  The records of any
+ *    sequence of pushes ending with `last`, concatenated and stable-sorted by (carrier, chain), are byte-identical to one
+ *    gmr1_hip_rx_run call on the whole capture (every field, conv included), for any push sizes (0 included) and in both
+ *    Viterbi decoder modes; after the last push _status's status / n_chains equal that call's.
+ *  - The FCCH acquisition runs once 8000 + 330 ms + 650 ms + 3 FCCH bursts of samples are in (earlier on `last`); before
+ *    that a carrier keeps everything, after it what its chains can still reach: from 2 frames before the earliest chain,
+ *    a carrier whose acquisition failed nothing.  _status reports, per carrier, status (0 while undecided or fine),
+ *    chains followed and the samples the handle retains.
+ *  - A push with max_records below gmr1_hip_rx_stream_max_records(h, n) (host arithmetic) is refused with -EINVAL, as
+ *    are bad arguments and a push after `last`; a refused push leaves the handle as it was.  -EIO: the handle failed and
+ *    takes no further pushes.
+ *  - `out` takes what gmr1_hip_rx_run_dev's does.  A push is synchronous: it returns when its records are in `out`.
+ *    _push_dev: iq is device memory, read on `stream`; _push: host memory.  Pushes on one handle are ordered, from any
+ *    thread or stream; independent handles may be pushed concurrently (they take turns on the device's workspace).  A
+ *    handle belongs to the device current when it was created: a push from a thread whose current device is another
+ *    one is refused (-EINVAL).
+ *  - A chain whose walk outgrows the loop's buffers stops for good and its carrier's status becomes -EIO, as in
+ *    gmr1_hip_rx_run; the carrier's other chains go on.
+ *  - TCH3 / TCH9 follow-ups are not performed.  Without a GPU every entry point returns -ENODEV. */
+struct gmr1_hip_rx_stream;
+int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struct gmr1_hip_rx_stream **h);
+int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_records);
+int gmr1_hip_rx_stream_push_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride,
+                                uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records);
+int gmr1_hip_rx_stream_push(struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n,
+                            int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records);
+int gmr1_hip_rx_stream_status(const struct gmr1_hip_rx_stream *h, int32_t *status, int32_t *n_chains,
+                              uint64_t *retained);
+int gmr1_hip_rx_stream_destroy(struct gmr1_hip_rx_stream *h);
+
 /* The same with the TCH3 follow-up (gmr1_rx's optional tch.cfile and key arguments, gmr1_rx.c:355-600,
  * 897-975): tch holds, for every carrier, the traffic carrier an IMMEDIATE ASSIGNMENT on its CCCH points
  * to -- same offset[] / length[] layout and timing as iq; kc = n_arfcn x 8 key bytes (NULL: the all-zero

@@ -62,6 +62,8 @@ EXPORTED_FUNCTIONS = [
     "gmr1_hip_ddc_plan", "gmr1_hip_ddc_dev", "gmr1_hip_ddc",
     "gmr1_hip_channelize_stream_create", "gmr1_hip_ddc_stream_create", "gmr1_hip_chan_stream_out_len",
     "gmr1_hip_chan_stream_push_dev", "gmr1_hip_chan_stream_push", "gmr1_hip_chan_stream_destroy",
+    "gmr1_hip_rx_stream_create", "gmr1_hip_rx_stream_max_records", "gmr1_hip_rx_stream_push_dev",
+    "gmr1_hip_rx_stream_push", "gmr1_hip_rx_stream_status", "gmr1_hip_rx_stream_destroy",
     "gmr1_hip_shard_unique_id", "gmr1_hip_shard_create", "gmr1_hip_shard_adopt", "gmr1_hip_shard_destroy",
     "gmr1_hip_rx_run_sharded", "gmr1_hip_rx_run_sharded_resident",
     "gmr1_codec_alloc", "gmr1_codec_release", "gmr1_codec_decode_frame", "gmr1_codec_decode_dtx",
@@ -1082,6 +1084,89 @@ class ChanStream:
         if self._h:
             h, self._h = self._h, C.c_void_p()
             _check(load().gmr1_hip_chan_stream_destroy(h), "gmr1_hip_chan_stream_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RxStream:
+    """gmr1_hip_rx_stream_*: the receive loop (rx_run) over a capture pushed piece by piece.  Each push returns the records
+    that became final in it; all pushes' records up to the `last` one, stable-sorted by (carrier, chain), are identical to
+    one rx_run() call on the whole capture."""
+
+    def __init__(self, n_arfcn, sps=4, arfcn=None):
+        self._h = C.c_void_p()
+        self.n = int(n_arfcn)
+        p_arfcn = None
+        if arfcn is not None:
+            self._arfcn, p_arfcn = _np(arfcn, np.uint16)
+        f = load().gmr1_hip_rx_stream_create
+        f.restype = C.c_int
+        _check(f(C.c_int(self.n), C.c_int(sps), p_arfcn, C.byref(self._h)), "gmr1_hip_rx_stream_create")
+
+    def max_records(self, n):
+        """the most records the next push of n samples per carrier can return"""
+        m = C.c_int()
+        _check(load().gmr1_hip_rx_stream_max_records(self._h, C.c_uint64(n), C.byref(m)), "gmr1_hip_rx_stream_max_records")
+        return m.value
+
+    def _out(self, n, out):
+        m = self.max_records(n)
+        if out is None:
+            out = np.empty(max(m, 1), RX_RECORD)
+        elif out.dtype != RX_RECORD or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous RX_RECORD array")
+        return out
+
+    def push(self, iq, last=False, out=None):
+        """host (n_arfcn, n) complex64 -> the records that became final (RX_RECORD[])"""
+        iq = np.ascontiguousarray(np.asarray(iq, np.complex64).reshape(self.n, -1))
+        n = iq.shape[1]
+        out = self._out(n, out)
+        got = C.c_int()
+        _check(load().gmr1_hip_rx_stream_push(self._h, iq.ctypes.data_as(C.c_void_p), C.c_uint64(n), C.c_uint64(n),
+                                              C.c_int(1 if last else 0), out.ctypes.data_as(C.c_void_p), C.c_int(out.size),
+                                              C.byref(got)), "gmr1_hip_rx_stream_push")
+        return out[:got.value]
+
+    def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None):
+        """device samples (carrier i at iq_ptr + 8 * i * iq_stride), read on `stream` -> the records (synchronous).
+        out: a host RX_RECORD array, or None; out_ptr (device / pinned) goes through push_dev_raw."""
+        out = self._out(n, out)
+        got = self.push_dev_raw(stream, iq_ptr, iq_stride, n, last, out.ctypes.data, out.size)
+        return out[:got]
+
+    def push_dev_raw(self, stream, iq_ptr, iq_stride, n, last, out_ptr, max_records):
+        """gmr1_hip_rx_stream_push_dev with a caller's record buffer (any memory rx_run_dev takes) -> records written"""
+        got = C.c_int()
+        _check(load().gmr1_hip_rx_stream_push_dev(C.c_void_p(stream) if stream else None, self._h,
+                                                  C.c_void_p(iq_ptr) if iq_ptr else None, C.c_uint64(iq_stride),
+                                                  C.c_uint64(n), C.c_int(1 if last else 0), C.c_void_p(out_ptr),
+                                                  C.c_int(max_records), C.byref(got)), "gmr1_hip_rx_stream_push_dev")
+        return got.value
+
+    def status(self):
+        """(status[n], n_chains[n], retained[n]) per carrier"""
+        st = np.zeros(self.n, np.int32)
+        nc = np.zeros(self.n, np.int32)
+        ret = np.zeros(self.n, np.uint64)
+        _check(load().gmr1_hip_rx_stream_status(self._h, st.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
+                                                ret.ctypes.data_as(C.c_void_p)), "gmr1_hip_rx_stream_status")
+        return st, nc, ret
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, C.c_void_p()
+            _check(load().gmr1_hip_rx_stream_destroy(h), "gmr1_hip_rx_stream_destroy")
 
     def __enter__(self):
         return self

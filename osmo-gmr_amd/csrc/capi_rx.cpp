@@ -21,10 +21,12 @@
 
 #include "capi_common.h"
 #include "fcch_acq.h"
+#include "rx_stream.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 #include "../../include/gmr1_hip.h"
@@ -53,6 +55,7 @@ struct RxChain {
 	int fn, delay, stn;
 	float bcch_energy;
 	bool done;
+	bool outgrew = false;                // its walk outgrew the loop's buffers (the carrier's status is -EIO)
 	std::vector<gmr1_hip_rx_record> rec;
 	int n_rec = 0;                       // records of the chain when they went straight to the caller (RxRun::direct)
 	std::vector<int> rec_frame;          // frame (index into log) each record belongs to
@@ -193,6 +196,9 @@ struct RxRun {
 	int max_records = 0;
 	bool direct = false;
 	int direct_total = 0;
+	// the streaming loop (gmr1_hip_rx_stream_*): the chains' states live in this device array across pushes -- the walk
+	// starts from and writes back to it, nothing is uploaded
+	RxLoopState *loop_state = nullptr;
 
 	int acquire();        // fcch_single_init + fcch_multi_process
 	int frame_loop();     // process_bcch: BCCH / CCCH, in rounds
@@ -526,7 +532,10 @@ int RxRun::frame_loop()
 	}
 	static const bool timing = profile_env("GMR1_HIP_RX_TIMING") != nullptr;
 	const auto t_a = std::chrono::steady_clock::now();
-	HIP_TRY(hipMemcpyAsync(la.state, st0.data(), (size_t)nc * sizeof(RxLoopState), hipMemcpyHostToDevice, st));
+	if (loop_state)
+		la.state = loop_state;
+	else
+		HIP_TRY(hipMemcpyAsync(la.state, st0.data(), (size_t)nc * sizeof(RxLoopState), hipMemcpyHostToDevice, st));
 	const auto t_b = std::chrono::steady_clock::now();
 	r = rx_loop_dev_impl(st, nc, sps, iq, la);
 	if (r) return r;
@@ -537,7 +546,12 @@ int RxRun::frame_loop()
 	}
 	if (pack) {
 		// counters and states first (a few KB), then exactly the records there are
-		HIP_TRY(hipMemcpyAsync(h + o_cnt, d + o_cnt, cnt_bytes + st_bytes, hipMemcpyDeviceToHost, st));
+		if (loop_state) {
+			HIP_TRY(hipMemcpyAsync(h + o_cnt, d + o_cnt, cnt_bytes, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(h + o_st, loop_state, (size_t)nc * sizeof(RxLoopState), hipMemcpyDeviceToHost, st));
+		} else {
+			HIP_TRY(hipMemcpyAsync(h + o_cnt, d + o_cnt, cnt_bytes + st_bytes, hipMemcpyDeviceToHost, st));
+		}
 		HIP_TRY(hipStreamSynchronize(st));
 		t_chain_us = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_start).count() / 1e3;
 		const int n_total = reinterpret_cast<const int32_t *>(h + o_cnt)[3 * nc];
@@ -579,6 +593,7 @@ int RxRun::frame_loop()
 			     c.a, h_nr[ci], h_nrec[ci], h_nfr[ci]);
 			stat[c.a] = -EIO;
 			c.done = true;
+			c.outgrew = true;
 			continue;
 		}
 		const gmr1_hip_rx_record *rp = reinterpret_cast<const gmr1_hip_rx_record *>(h) + (size_t)ci * rec_stride;
@@ -1362,6 +1377,438 @@ int gmr1_hip_gsmtap_pack_big(const struct gmr1_hip_rx_big_record *rec, int with_
 	if (!rec || !buf)
 		return fail(-EINVAL, "gsmtap_pack: rec / buf are required");
 	return gsmtap_pack_any(rec->arfcn, rec->type, rec->fn, rec->tn, rec->l2, rec->len, 64, with_arfcn, buf, buf_len);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The streaming receive loop (gmr1_hip_rx_stream_*): gmr1_hip_rx_run over a capture pushed piece by piece.
+//
+// A handle holds, per carrier, the samples it still needs in one buffer of a device ping-pong pair, and every chain's
+// RxLoopState in device memory.  A push stages [kept tail | new chunk] into the other buffer (k_rx_stage, which also
+// rebases the states), runs the acquisition once enough samples are there (rx_stream_acq_need), then walks every chain
+// with the one-shot loop (RxRun::frame_loop) up to the samples available.  A walk only ever processes a frame after
+// rx_loop_advance's check `align + 2 * frame_len <= len` admitted it, and every window of such a frame ends before
+// align + 2 * frame_len, so a walk to H samples does exactly what the one-shot walk does up to there; the only thing the
+// horizon adds is a stop that the next push may lift (rx_stream_next_done).  A carrier then keeps its samples from
+// rx_stream_keep_from(min chain align): no window of the next walk starts before that (rx_stream_reach_back).
+// ---------------------------------------------------------------------------------------------------------------------
+static_assert(kStartDiscard == kRxStartDiscard, "one start discard");
+
+struct gmr1_hip_rx_stream {
+	mutable std::mutex mu;               // one push at a time
+	int device = -1;
+	int A = 0, sps = 0;
+	std::vector<uint16_t> arfcn;         // empty: records carry the carrier index
+	uint64_t N = 0;                      // samples pushed per carrier so far
+	bool acquired = false, ended = false, broken = false;
+	std::vector<int32_t> stat, nch;
+	std::vector<int32_t> acq_stat;       // per carrier: status the acquisition left (the loop may set stat to -EIO later)
+	std::vector<long long> held;         // per carrier: samples in the current buffer
+	std::vector<long long> keep;         // per carrier: first of them the next push keeps (held: none)
+	std::vector<int> rebased;            // per carrier: 1 once samples were dropped
+	std::vector<RxChain> chains;         // host mirror of the chains (carrier by carrier, chain by chain)
+	std::vector<int> c0;                 // per carrier: its first chain (A + 1 entries)
+	float2 *buf[2] = {nullptr, nullptr};
+	int cur = 0;
+	long long stride = 0;                // samples per carrier in each buffer (a multiple of kRxKeepAlign)
+	RxLoopState *d_state = nullptr;
+	RxStageCarrier *d_car = nullptr;
+	int32_t *d_err = nullptr;
+	RxStageCarrier *h_car = nullptr;     // pinned: the staging parameters go up from here
+	int32_t *h_err = nullptr;
+	float *h_in = nullptr;               // pinned: gmr1_hip_rx_stream_push's host chunk (grow-only)
+	size_t h_in_bytes = 0;
+	float *d_in = nullptr;
+	size_t d_in_bytes = 0;
+	~gmr1_hip_rx_stream()
+	{
+		for (float2 *p : buf)
+			if (p) (void)hipFree(p);
+		if (d_state) (void)hipFree(d_state);
+		if (d_car) (void)hipFree(d_car);
+		if (d_err) (void)hipFree(d_err);
+		if (d_in) (void)hipFree(d_in);
+		if (h_car) (void)hipHostFree(h_car);
+		if (h_err) (void)hipHostFree(h_err);
+		if (h_in) (void)hipHostFree(h_in);
+	}
+};
+
+namespace {
+
+// a carrier keeps nothing once its acquisition failed, or when none of its chains is left to walk (none found, or every
+// one outgrew the loop's buffers; as in the one-shot call, the others of a carrier go on when one does)
+bool rx_stream_dead(const gmr1_hip_rx_stream *h, int i)
+{
+	if (!h->acquired)
+		return false;
+	if (h->acq_stat[i] != 0)
+		return true;
+	for (int k = h->c0[i]; k < h->c0[i + 1]; k++)
+		if (!h->chains[k].outgrew)
+			return false;
+	return true;
+}
+
+// samples carrier i holds after a push of n
+long long rx_stream_next_held(const gmr1_hip_rx_stream *h, int i, uint64_t n)
+{
+	if (rx_stream_dead(h, i))
+		return 0;
+	return h->held[i] - h->keep[i] + (long long)n;
+}
+
+long long rx_stream_bound(const gmr1_hip_rx_stream *h, uint64_t n)
+{
+	if (h->ended)
+		return 0;
+	long long chains = 0, len = 0;
+	for (int i = 0; i < h->A; i++) {
+		if (rx_stream_dead(h, i))
+			continue;
+		chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
+		len = std::max(len, rx_stream_next_held(h, i, n));
+	}
+	return chains ? chains * rx_stream_rec_per_chain(len, h->sps) : 0;
+}
+
+int rx_stream_check(const gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n, int last,
+                    const gmr1_hip_rx_record *out, int max_records, const int *n_records)
+{
+	if (!h || !n_records || max_records < 0 || (max_records > 0 && !out) || (n > 0 && !iq))
+		return fail(-EINVAL, "rx_stream_push: handle / n_records (and iq when n > 0, out when max_records > 0) are required");
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	if (dev != h->device)
+		return fail(-EINVAL, "rx_stream_push: the handle belongs to device %d, the current device is %d", h->device, dev);
+	if (h->broken)
+		return fail(-EIO, "rx_stream_push: the handle failed in an earlier push");
+	if (h->ended)
+		return fail(-EINVAL, "rx_stream_push: the last push has been made");
+	if (h->A > 1 && n > 0 && iq_stride < n)
+		return fail(-EINVAL, "rx_stream_push: iq_stride %llu < n %llu", (unsigned long long)iq_stride, (unsigned long long)n);
+	if (n > 0x7fffffffull)
+		return fail(-EINVAL, "rx_stream_push: n above 2^31-1");
+	for (int i = 0; i < h->A; i++)
+		if (rx_stream_next_held(h, i, n) > 0x7fffffffll)
+			return fail(-EINVAL, "rx_stream_push: carrier %d would hold more than 2^31-1 samples", i);
+	const long long bound = rx_stream_bound(h, n);
+	if ((long long)max_records < bound)
+		return fail(-EINVAL, "rx_stream_push: max_records %d below the bound %lld", max_records, bound);
+	(void)last;
+	return 0;
+}
+
+// the device part of a push; the caller holds h->mu and the workspace lease, and has validated everything
+int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, uint64_t iq_stride, uint64_t n, int last,
+                        gmr1_hip_rx_record *out, int max_records, int *n_records)
+{
+	const int A = h->A, sps = h->sps;
+	// 1. staging: [kept tail | chunk] -> the other buffer, states rebased
+	std::vector<long long> next((size_t)A);
+	long long need = 0, max_pairs = 0;
+	for (int i = 0; i < A; i++) {
+		next[i] = rx_stream_next_held(h, i, n);
+		need = std::max(need, next[i]);
+	}
+	need = (need + kRxKeepAlign - 1) / kRxKeepAlign * kRxKeepAlign;
+	float2 *src = h->buf[h->cur];
+	const long long src_stride = h->stride;
+	float2 *fresh = nullptr;
+	if (need > h->stride) {
+		// grow-only: a new pair; the old current buffer is the source of this one staging and then goes
+		HIP_TRY(hipMalloc(&fresh, (size_t)A * (size_t)need * sizeof(float2)));
+		if (h->buf[1 - h->cur]) {
+			(void)hipFree(h->buf[1 - h->cur]);
+			h->buf[1 - h->cur] = nullptr;
+		}
+		h->buf[1 - h->cur] = fresh;
+		h->stride = need;
+	} else if (!h->buf[1 - h->cur] && need > 0) {
+		HIP_TRY(hipMalloc(&h->buf[1 - h->cur], (size_t)A * (size_t)h->stride * sizeof(float2)));
+	}
+	float2 *dst = h->buf[1 - h->cur];
+	for (int i = 0; i < A; i++) {
+		RxStageCarrier &c = h->h_car[i];
+		const bool dead = rx_stream_dead(h, i);
+		c.src = (uint64_t)((long long)i * src_stride + h->keep[i]);
+		c.dst = (uint64_t)((long long)i * h->stride);
+		c.iq = (long long)i * (long long)iq_stride;
+		c.kept = dead ? 0 : (int32_t)(h->held[i] - h->keep[i]);
+		c.n_new = dead ? 0 : (int32_t)n;
+		c.shift = dead ? 0 : (int32_t)h->keep[i];
+		c.c0 = h->c0.empty() ? 0 : h->c0[i];
+		c.c1 = h->c0.empty() ? 0 : h->c0[i + 1];
+		if (c.shift > 0) h->rebased[i] = 1;
+		c.rebased = h->rebased[i];
+		max_pairs = std::max(max_pairs, ((long long)c.kept + c.n_new + 1) / 2);
+	}
+	*h->h_err = 0;
+	HIP_TRY(hipMemcpyAsync(h->d_car, h->h_car, (size_t)A * sizeof(RxStageCarrier), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(h->d_err, h->h_err, 4, hipMemcpyHostToDevice, st));
+	if (dst) {
+		RxStageArgs sa;
+		std::memset(&sa, 0, sizeof(sa));
+		sa.n_carriers = A; sa.sps = sps; sa.last = last ? 1 : 0;
+		sa.max_pairs = (int)std::min<long long>(max_pairs, 0x7fffffff);
+		sa.src = src ? src : dst;
+		sa.dst = dst;
+		sa.iq = iq ? iq : dst;
+		sa.car = h->d_car;
+		sa.state = h->d_state;
+		sa.err = h->d_err;
+		HIP_TRY(launch_rx_stage(sa, st));
+	}
+	if (fresh && src) {
+		HIP_TRY(hipStreamSynchronize(st));     // the staging has read the old buffer
+		(void)hipFree(src);
+		h->buf[h->cur] = nullptr;
+	}
+	h->cur = 1 - h->cur;
+	for (int i = 0; i < A; i++) {
+		const bool dead = rx_stream_dead(h, i);
+		if (!dead) {
+			for (int k = h->c0.empty() ? 0 : h->c0[i]; k < (h->c0.empty() ? 0 : h->c0[i + 1]); k++)
+				h->chains[k].align -= (int)h->keep[i];
+		}
+		h->held[i] = next[i];
+		h->keep[i] = 0;
+	}
+	h->N += n;
+	if (last) h->ended = true;
+
+	RxRun run;
+	run.st = st; run.sps = sps; run.iq = reinterpret_cast<const float *>(h->buf[h->cur]);
+	run.tch = nullptr; run.csd = nullptr; run.kc = nullptr;
+	run.arfcn = h->arfcn.empty() ? nullptr : h->arfcn.data();
+	run.A = A;
+	run.out = out; run.max_records = max_records;
+	run.flen = kFcchLen * sps;
+	run.stat = h->stat; run.nch = h->nch;
+	std::vector<uint64_t> offset((size_t)A), length((size_t)A);
+	for (int i = 0; i < A; i++) {
+		offset[i] = (uint64_t)((long long)i * h->stride);
+		length[i] = (uint64_t)h->held[i];
+	}
+	run.offset = offset.data(); run.length = length.data();
+	int r = 0;
+
+	// 2. the acquisition, once every carrier holds what it reads (nothing has been dropped yet: coordinates are absolute)
+	if (!h->acquired && ((long long)h->N >= rx_stream_acq_need(sps) || last)) {
+		run.align.assign(A, kStartDiscard); run.base_align.assign(A, 0);
+		run.ferr.assign(A, 0.0f);
+		if ((r = run.acquire())) return r;
+		h->stat = run.stat; h->nch = run.nch;
+		h->acq_stat = run.stat;
+		h->chains = std::move(run.chains);
+		run.chains.clear();
+		h->c0.assign((size_t)A + 1, 0);
+		for (const RxChain &c : h->chains)
+			h->c0[c.a + 1]++;
+		for (int i = 0; i < A; i++)
+			h->c0[i + 1] += h->c0[i];
+		const int nc = (int)h->chains.size();
+		if (nc) {
+			HIP_TRY(hipMalloc(&h->d_state, (size_t)nc * sizeof(RxLoopState)));
+			std::vector<RxLoopState> s0((size_t)nc);
+			for (int k = 0; k < nc; k++) {
+				const RxChain &c = h->chains[k];
+				s0[k] = {c.base, c.len, c.align, c.freq_err, c.fn, c.delay, c.stn, kRxDoneUnstarted, c.bcch_energy,
+				         (uint16_t)(run.arfcn ? run.arfcn[c.a] : (uint16_t)c.a), (uint16_t)c.chain};
+				s0[k].done = rx_stream_next_done(kRxDoneUnstarted, c.align, c.len, sps, last);
+			}
+			HIP_TRY(hipMemcpyAsync(h->d_state, s0.data(), (size_t)nc * sizeof(RxLoopState), hipMemcpyHostToDevice, st));
+		}
+		h->acquired = true;
+	}
+
+	// 3. the walk up to the samples available
+	if (h->acquired && !h->chains.empty()) {
+		run.chains = std::move(h->chains);
+		for (RxChain &c : run.chains) {
+			c.base = offset[c.a];
+			c.len = (int)h->held[c.a];
+		}
+		run.loop_state = h->d_state;
+		r = run.frame_loop();
+		h->chains = std::move(run.chains);
+		if (r) return r;
+		h->stat = run.stat;
+		for (int k = 0; k < (int)h->chains.size(); k++)
+			if (h->chains[k].outgrew) {
+				// stopped for good, as in the one-shot call
+				static const int32_t fin = kRxDoneFinal;
+				HIP_TRY(hipMemcpyAsync(&h->d_state[k].done, &fin, 4, hipMemcpyHostToDevice, st));
+			}
+	}
+	HIP_TRY(hipMemcpyAsync(h->h_err, h->d_err, 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	if (*h->h_err) {
+		h->broken = true;
+		return fail(-EIO, "rx_stream_push: a chain could reach before its carrier's kept samples");
+	}
+	*n_records = run.direct ? run.direct_total : 0;
+
+	// 4. what each carrier keeps for the next push
+	for (int i = 0; i < A; i++) {
+		if (h->ended || rx_stream_dead(h, i)) {
+			h->keep[i] = h->held[i];
+			continue;
+		}
+		if (!h->acquired) {
+			h->keep[i] = 0;
+			continue;
+		}
+		long long lo = h->held[i];
+		for (int k = h->c0[i]; k < h->c0[i + 1]; k++)
+			if (!h->chains[k].outgrew)
+				lo = std::min<long long>(lo, h->chains[k].align);
+		h->keep[i] = std::min(h->held[i], rx_stream_keep_from(lo, sps));
+	}
+	return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struct gmr1_hip_rx_stream **out)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (!out)
+		return fail(-EINVAL, "rx_stream_create: h is required");
+	*out = nullptr;
+	if (n_arfcn < 1 || n_arfcn > 65535)
+		return fail(-EINVAL, "rx_stream_create: n_arfcn=%d (1..65535)", n_arfcn);
+	if (sps < 1 || sps > 16)                  // gmr1_rx.c:919-922
+		return fail(-EINVAL, "rx_stream_create: sps=%d unsupported (1..16)", sps);
+	std::unique_ptr<gmr1_hip_rx_stream> h(new gmr1_hip_rx_stream);
+	HIP_TRY(hipGetDevice(&h->device));
+	h->A = n_arfcn;
+	h->sps = sps;
+	if (arfcn)
+		h->arfcn.assign(arfcn, arfcn + n_arfcn);
+	h->stat.assign(n_arfcn, 0);
+	h->nch.assign(n_arfcn, 0);
+	h->held.assign(n_arfcn, 0);
+	h->keep.assign(n_arfcn, 0);
+	h->rebased.assign(n_arfcn, 0);
+	HIP_TRY(hipMalloc(&h->d_car, (size_t)n_arfcn * sizeof(RxStageCarrier)));
+	HIP_TRY(hipMalloc(&h->d_err, 4));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_car), (size_t)n_arfcn * sizeof(RxStageCarrier), hipHostMallocDefault));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_err), 4, hipHostMallocDefault));
+	*out = h.release();
+	return 0;
+}
+
+int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_records)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (!h || !max_records)
+		return fail(-EINVAL, "rx_stream_max_records: handle / max_records are required");
+	std::lock_guard<std::mutex> lk(h->mu);
+	const long long b = rx_stream_bound(h, n);
+	if (b > 0x7fffffffll)
+		return fail(-EINVAL, "rx_stream_max_records: %lld records do not fit an int", b);
+	*max_records = (int)b;
+	return 0;
+}
+
+int gmr1_hip_rx_stream_push_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n,
+                                int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (n_records) *n_records = 0;
+	std::unique_lock<std::mutex> lk;
+	if (h)
+		lk = std::unique_lock<std::mutex>(h->mu);
+	if ((r = rx_stream_check(h, iq, iq_stride, n, last, out, max_records, n_records)))
+		return r;
+	hipStream_t st = (hipStream_t)stream;
+	// the loop holds the device's workspace, side stream and events: pushes of other handles wait their turn
+	WsLease lease;
+	if ((r = lease.acquire(ds, st))) return r;
+	r = rx_stream_push_impl(st, h, reinterpret_cast<const float2 *>(iq), iq_stride, n, last, out, max_records, n_records);
+	if (r) h->broken = true;
+	return r;
+}
+
+int gmr1_hip_rx_stream_push(struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n, int last,
+                            struct gmr1_hip_rx_record *out, int max_records, int *n_records)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (n_records) *n_records = 0;
+	std::unique_lock<std::mutex> lk;
+	if (h)
+		lk = std::unique_lock<std::mutex>(h->mu);
+	if ((r = rx_stream_check(h, iq, iq_stride, n, last, out, max_records, n_records)))
+		return r;
+	// the chunk goes up packed (stride n) through the handle's pinned block
+	const size_t bytes = (size_t)h->A * (size_t)n * sizeof(float2);
+	if (bytes > h->h_in_bytes) {
+		if (h->h_in) (void)hipHostFree(h->h_in);
+		if (h->d_in) (void)hipFree(h->d_in);
+		h->h_in = nullptr; h->d_in = nullptr; h->h_in_bytes = h->d_in_bytes = 0;
+		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_in), bytes, hipHostMallocDefault));
+		h->h_in_bytes = bytes;
+		HIP_TRY(hipMalloc(&h->d_in, bytes));
+		h->d_in_bytes = bytes;
+	}
+	for (int i = 0; i < h->A && n > 0; i++)
+		std::memcpy(h->h_in + (size_t)i * n * 2, iq + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
+	WsLease lease;
+	if ((r = lease.acquire(ds, nullptr))) return r;
+	if (bytes)
+		HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, bytes, hipMemcpyHostToDevice, nullptr));
+	r = rx_stream_push_impl(nullptr, h, reinterpret_cast<const float2 *>(h->d_in), n, n, last, out, max_records, n_records);
+	if (r) h->broken = true;
+	return r;
+}
+
+int gmr1_hip_rx_stream_status(const struct gmr1_hip_rx_stream *h, int32_t *status, int32_t *n_chains, uint64_t *retained)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (!h)
+		return fail(-EINVAL, "rx_stream_status: handle is required");
+	std::lock_guard<std::mutex> lk(h->mu);
+	for (int i = 0; i < h->A; i++) {
+		if (status) status[i] = h->stat[i];
+		if (n_chains) n_chains[i] = h->nch[i];
+		if (retained) retained[i] = (uint64_t)(h->held[i] - h->keep[i]);
+	}
+	return 0;
+}
+
+int gmr1_hip_rx_stream_destroy(struct gmr1_hip_rx_stream *h)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (!h)
+		return 0;
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	const int own = h->device;
+	if (dev != own)
+		HIP_TRY(hipSetDevice(own));          // its memory is freed on its own device
+	{
+		std::lock_guard<std::mutex> lk(h->mu);    // a push in progress on another thread finishes first (pushes are synchronous)
+	}
+	delete h;
+	if (dev != own)
+		HIP_TRY(hipSetDevice(dev));
+	return 0;
 }
 
 }  // extern "C"

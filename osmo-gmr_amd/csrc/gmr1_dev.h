@@ -358,6 +358,29 @@ struct KeepTailArgs {
 };
 hipError_t launch_keep_tail(const KeepTailArgs &a, hipStream_t stream);
 
+// The streaming receive loop's staging (k_rx_stage, rx_stream_kernels.hip): per carrier, [kept tail of the source
+// buffer | the caller's chunk] -> the destination buffer, and the carrier's chain states rebased onto it.
+struct RxStageCarrier {
+	uint64_t src;                  // first kept sample in the source buffer
+	uint64_t dst;                  // the carrier's first sample in the destination buffer
+	long long iq;                  // its first chunk sample in the caller's array (complex samples)
+	int32_t kept, n_new;           // samples carried over, samples of the chunk appended
+	int32_t shift;                 // samples dropped from the front by this push (chain aligns move back by it)
+	int32_t c0, c1;                // its chains in the state array
+	int32_t rebased;               // 1 once any sample of the carrier has been dropped
+};
+struct RxStageArgs {
+	int n_carriers, sps, last;
+	int max_pairs;                 // most (kept + n_new + 1) / 2 of any carrier
+	const float2 *src;
+	float2 *dst;
+	const float2 *iq;
+	const RxStageCarrier *car;
+	RxLoopState *state;
+	int32_t *err;                  // set to 1 when a chain about to walk could reach before its carrier's kept samples
+};
+hipError_t launch_rx_stage(const RxStageArgs &a, hipStream_t stream);
+
 hipError_t launch_dkab(const DkabArgs &a, hipStream_t stream);
 hipError_t launch_a5(const A5Args &a, hipStream_t stream);
 // NT9 bursts: FACCH9 and the three TCH9 modes share one decoder kernel (nt9_kernels.hip)

@@ -1,0 +1,66 @@
+// rx_stream.h -- the integer arithmetic of the streaming receive loop (gmr1_hip_rx_stream_*, capi_rx.cpp): when the
+// acquisition may run, what a carrier keeps between pushes, how the chain states move with it.  Host-callable (tests,
+// sizing) and used by the staging kernel (rx_stream_kernels.hip).  No signal arithmetic here.
+#pragma once
+
+#include <stdint.h>
+
+#include "rx_loop.h"
+
+namespace gmr1 {
+
+constexpr int kRxStartDiscard = 8000;      // gmr1_rx.c:52
+constexpr int kRxKeepAlign = 64;           // a carrier drops whole multiples of this many samples
+
+// chain states between pushes (RxLoopState::done): 0 walking, 1 stopped by rx_loop_advance's check against the samples
+// available (provisional until the last push), 2 acquired but not yet started, 3 stopped for good (outgrew its buffers)
+constexpr int kRxDoneStopped = 1, kRxDoneUnstarted = 2, kRxDoneFinal = 3;
+
+GMR1_HD int rx_stream_frame_len(int sps) { return sps * 24 * 39; }
+
+// Samples a carrier needs before its FCCH acquisition (RxRun::acquire) decides as it would on any longer capture.
+// Every bound check there compares an end position with the carrier's length, and every sweep reads inside a window a
+// check admitted.  With wl1 = 330 ms, wl3 = 650 ms, flen = 117 sps, toa1 <= wl1 - flen (the rough sweep's last lag),
+// |ftoa|, |ctoa| < flen (the fine stage's chirp offset: at most 58 bins / 2 over the chirp rate, 91 sps) and rough-multi
+// peaks <= wl3 - flen, the largest end any check compares is
+//   kStartDiscard + toa1 + ftoa - flen + peak + ctoa + flen  <=  kStartDiscard + wl1 + wl3 - flen + flen
+// and H_acq adds three FCCH lengths of margin on top of that.
+GMR1_HD long long rx_stream_acq_need(int sps)
+{
+	const long long wl1 = (330LL * 23400 * sps) / 1000, wl3 = (650LL * 23400 * sps) / 1000, flen = 117LL * sps;
+	return kRxStartDiscard + wl1 + wl3 + 3 * flen;
+}
+
+// How far back of a chain's align a window of the walk can start: a window begins at most 10 sps before align
+// (burst_map's etoa), and over any stretch of frames bcch_tdma_align's shifts (stn_old - stn_new) * 39 * sps telescope to
+// at most 31 * 39 * sps (stn is a 5-bit field) while every frame adds frame_len and a BCCH correction takes at most 10 sps
+// of it back.  The handle keeps 2 * frame_len > (31 * 39 + 10) * sps before the earliest align.
+GMR1_HD int rx_stream_reach_back(int sps) { return (31 * 39 + 10) * sps; }
+
+// First sample a carrier keeps, given the smallest align of its chains (its own coordinates)
+GMR1_HD long long rx_stream_keep_from(long long min_align, int sps)
+{
+	long long k = min_align - 2LL * rx_stream_frame_len(sps);
+	if (k < 0) k = 0;
+	return k - k % kRxKeepAlign;
+}
+
+// What the loop may do with a chain once its carrier holds `len` samples: a chain that has not started walks only when
+// its first frame passes rx_loop_advance's check (or on the last push, as gmr1_rx processes the first frame unchecked);
+// a stopped one resumes only when the frame it stopped at passes it.
+GMR1_HD int rx_stream_next_done(int done, int align, int len, int sps, int last)
+{
+	const bool fits = (long long)align + 2LL * rx_stream_frame_len(sps) <= (long long)len;
+	if (done == kRxDoneUnstarted && (last || fits)) return 0;
+	if (done == kRxDoneStopped && fits) return 0;
+	return done;
+}
+
+// Records a walk over `len` samples can hand back per chain: the per-chain record buffer of RxRun::frame_loop
+GMR1_HD long long rx_stream_rec_per_chain(long long len, int sps)
+{
+	const long long max_frames = len / rx_stream_frame_len(sps) + 2;
+	return (max_frames / 7 + 8) * kLoopPerRound;
+}
+
+}  // namespace gmr1

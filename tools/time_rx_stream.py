@@ -1,0 +1,155 @@
+"""Times the streaming receive loop (gmr1_hip_rx_stream_*) against one gmr1_hip_rx_run_dev call: 64 BCCH carriers of
+--seconds at sps 4 (8 synthetic carriers, each used for 8 ARFCNs), device-resident, pushed through one handle in 10 ms,
+100 ms and 1 s pushes (push_dev, one stream).  Reports per push the host wall time around the call (a push is
+synchronous: that includes its host work and its copies back) and the device time on its stream (events recorded before and
+after the call: from its first device operation to its last, gaps where the stream waits for the push's host part
+included); median and p99 over the last three quarters of the pushes, the maximum over all; then the total of a pass against the one-shot call, and the
+real-time factor (capture seconds per second of the pass).  Then the chained pipeline: a wideband capture through
+ChanStream.push_dev -> RxStream.push_dev on one stream, against channelize + rx_run.  Checks the records are identical.
+
+    python tools/time_rx_stream.py [--seconds 60] [--pushes 0.01,0.1,1] [--out result.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def _sorted(rec, arfcn):
+    pos = {int(a): i for i, a in enumerate(arfcn)}
+    key = np.array([pos[int(a)] * 256 + int(c) for a, c in zip(rec["arfcn"], rec["chain"])], np.int64)
+    return rec[np.argsort(key, kind="stable")] if len(rec) else rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=60.0)
+    ap.add_argument("--pushes", default="0.01,0.1,1", help="push lengths in seconds")
+    ap.add_argument("--wide-seconds", type=float, default=10.0, help="length of the chained pipeline's wideband capture")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import workloads
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    api = pkg.api
+    torch.cuda.init()
+    api.load()
+    api.init(0)
+    sps, A, rate = 4, 64, 23400 * 4
+    base = [workloads.bcch_carrier(pkg, 900 + k, seconds=args.seconds, sps=sps, stn=(7 * k) % 32, delay=k % 8,
+                                   cfo_hz=40.0 * k - 150.0, esn0_db=10.0 + k)[0] for k in range(8)]
+    n = min(x.size for x in base)
+    x = np.stack([base[i % 8][:n] for i in range(A)]).astype(np.complex64)
+    arfcn = np.arange(A, dtype=np.uint16) + 100
+    d = torch.from_numpy(x.view(np.float32).reshape(A, -1)).cuda()
+    stream = torch.cuda.current_stream()
+    st = stream.cuda_stream
+    offset = np.arange(A, dtype=np.uint64) * np.uint64(n)
+    length = np.full(A, n, np.uint64)
+    res = {"carriers": A, "capture_s": n / rate, "sps": sps}
+    out = np.empty(1 << 21, api.RX_RECORD)
+    api.rx_run_dev(st, d.data_ptr(), offset, length, sps=sps, arfcn=arfcn, out=out)      # warm-up
+    t = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ref, rst, rch, _ = api.rx_run_dev(st, d.data_ptr(), offset, length, sps=sps, arfcn=arfcn, out=out)
+        t.append(time.perf_counter() - t0)
+    ref = ref.copy()
+    res["one_shot_ms"] = 1e3 * min(t)
+    res["records"] = int(len(ref))
+    for p_s in [float(v) for v in args.pushes.split(",")]:
+        p = int(round(p_s * rate))
+        best = None
+        for _ in range(2):
+            per, got, evs = [], [], []
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with api.RxStream(A, sps=sps, arfcn=arfcn) as s:
+                at = 0
+                buf = np.empty(max(s.max_records(p), 1), api.RX_RECORD)
+                while at < n:
+                    k = min(p, n - at)
+                    if s.max_records(k) > buf.size:
+                        buf = np.empty(s.max_records(k), api.RX_RECORD)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    q0 = time.perf_counter()
+                    r = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf)
+                    per.append(time.perf_counter() - q0)
+                    e1.record(stream)
+                    evs.append((e0, e1))
+                    got.append(r.copy())
+                    at += k
+            total = time.perf_counter() - t0
+            torch.cuda.synchronize()
+            dev = [a.elapsed_time(b) for a, b in evs]
+            if best is None or total < best[0]:
+                best = (total, per, got, dev)
+        total, per, got, dev = best
+        same = _sorted(np.concatenate(got), arfcn).tobytes() == ref.tobytes()
+        per_ms = np.array(per) * 1e3
+        dev_ms = np.array(dev)
+        steady = per_ms[len(per_ms) // 4:] if len(per_ms) > 8 else per_ms
+        steady_dev = dev_ms[len(dev_ms) // 4:] if len(dev_ms) > 8 else dev_ms
+        res["push_%gs" % p_s] = {"pushes": len(per), "total_ms": 1e3 * total, "vs_one_shot": total * 1e3 / res["one_shot_ms"],
+                                 "rtf": (n / rate) / total, "push_wall_ms_median": float(np.median(steady)),
+                                 "push_wall_ms_p99": float(np.percentile(steady, 99)), "push_wall_ms_max": float(per_ms.max()),
+                                 "push_dev_ms_median": float(np.median(steady_dev)),
+                                 "push_dev_ms_p99": float(np.percentile(steady_dev, 99)),
+                                 "push_dev_ms_max": float(dev_ms.max()), "identical": bool(same)}
+        print(json.dumps({("push_%gs" % p_s): res["push_%gs" % p_s]}), flush=True)
+    # the chained pipeline
+    fs = 2.0e6
+    carriers = tuple((c, dict(stn=(3 * c) % 32, delay=c % 8, cfo_hz=float(c))) for c in (3, 17, 33, 60))
+    wide, _ = workloads.wideband_capture(pkg, 5, seconds=args.wide_seconds, carriers=carriers)
+    chans = [c for c, _ in carriers]
+    nb = api.channelize(wide, fs, chans)
+    wa = np.asarray(chans, np.uint16)
+    nn = nb.shape[1]
+    ref2, _, _, _ = api.rx_run(np.ascontiguousarray(nb).reshape(-1), np.arange(len(chans), dtype=np.uint64) * np.uint64(nn),
+                               np.full(len(chans), nn, np.uint64), sps=4, arfcn=wa, max_records=1 << 20)
+    w = torch.from_numpy(wide.view(np.float32)).cuda()
+    for p_s in (0.01, 0.1):
+        p = int(round(p_s * fs))
+        got = []
+        cs = api.ChanStream(fs, chans)
+        rs = api.RxStream(len(chans), sps=4, arfcn=wa)
+        o = torch.empty((len(chans), 2 * (cs.out_len(p) + 64)), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        at = 0
+        while at < wide.size:
+            k = min(p, wide.size - at)
+            m = cs.out_len(k)
+            cs.push_dev(st, w.data_ptr() + 8 * at, k, o.data_ptr(), o.shape[1] // 2)
+            got.append(rs.push_dev(st, o.data_ptr(), o.shape[1] // 2, m, last=at + k >= wide.size).copy())
+            at += k
+        total = time.perf_counter() - t0
+        cs.close()
+        rs.close()
+        same = _sorted(np.concatenate(got), wa).tobytes() == ref2.tobytes()
+        res["pipeline_%gs" % p_s] = {"carriers": len(chans), "capture_s": wide.size / fs, "total_ms": 1e3 * total,
+                                     "rtf": (wide.size / fs) / total, "identical": bool(same)}
+        print(json.dumps({("pipeline_%gs" % p_s): res["pipeline_%gs" % p_s]}), flush=True)
+    try:
+        core, _ = api.clock_probe_dev(st, 2000)
+        res["core_mhz"] = core
+    except Exception:       # noqa: BLE001
+        pass
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
