@@ -47,6 +47,14 @@ int fail(int code, const char *fmt, ...)
 
 const char *last_error() { return t_err; }
 
+int bursts_fit(int n, const uint64_t *offset, int in_len, uint64_t iq_len)
+{
+	for (int i = 0; i < n; i++)
+		if (offset[i] + (uint64_t)in_len > iq_len)
+			return fail(-EINVAL, "burst %d runs past the end of iq", i);
+	return 0;
+}
+
 namespace {
 std::atomic<int> g_conv_decoder{-1};       // -1: not chosen yet (the environment decides on first use)
 }
@@ -405,9 +413,7 @@ static int demod_host_impl(int type, const DevBurst &ht, const DevBurst *custom,
 	if (r) return r;
 	if (n <= 0)
 		return 0;
-	for (int i = 0; i < n; i++)
-		if (offset[i] + (uint64_t)in_len > iq_len)
-			return fail(-EINVAL, "burst %d runs past the end of iq", i);
+	if ((r = bursts_fit(n, offset, in_len, iq_len))) return r;
 	hipStream_t st = nullptr;
 	// a caller-defined description occupies the one spare table slot for the duration of the call: two threads
 	// demodulating different custom formats must not interleave upload and launch
@@ -416,35 +422,21 @@ static int demod_host_impl(int type, const DevBurst &ht, const DevBurst *custom,
 		lk.lock();
 		HIP_TRY(upload_types(custom, kCustomSlot, 1, st));
 	}
-	DBuf d_iq, d_off, d_fs, d_eb, d_sid, d_toa, d_fe, d_ss, d_rv;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(d_off.alloc((size_t)n * 8));
-	HIP_TRY(d_rv.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, offset, (size_t)n * 8, hipMemcpyHostToDevice));
-	if (freq_shift) {
-		HIP_TRY(d_fs.alloc((size_t)n * 4));
-		HIP_TRY(hipMemcpy(d_fs.p, freq_shift, (size_t)n * 4, hipMemcpyHostToDevice));
-	}
-	if (ebits) HIP_TRY(d_eb.alloc((size_t)n * ebits_stride));
-	if (sync_id) HIP_TRY(d_sid.alloc((size_t)n * 4));
-	if (toa) HIP_TRY(d_toa.alloc((size_t)n * 4));
-	if (freq_err) HIP_TRY(d_fe.alloc((size_t)n * 4));
-	if (ssyms) HIP_TRY(d_ss.alloc((size_t)n * ht.len * 4));
-	r = demod_dev_impl(st, type, ht, n, sps, in_len, d_iq.as<float>(), d_off.as<uint64_t>(),
-	                   freq_shift ? d_fs.as<float>() : nullptr, ebits ? d_eb.as<int8_t>() : nullptr,
-	                   ebits_stride, sync_id ? d_sid.as<int32_t>() : nullptr,
-	                   toa ? d_toa.as<float>() : nullptr, freq_err ? d_fe.as<float>() : nullptr,
-	                   ssyms ? d_ss.as<float>() : nullptr, d_rv.as<int32_t>());
+	Stage sg(st);
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const uint64_t *d_off = sg.in(offset, (size_t)n);
+	const float *d_fs = sg.in(freq_shift, (size_t)n);
+	int32_t *d_rv = sg.out(rv, (size_t)n);
+	int8_t *d_eb = sg.out(ebits, (size_t)n * ebits_stride);
+	int32_t *d_sid = sg.out(sync_id, (size_t)n);
+	float *d_toa = sg.out(toa, (size_t)n);
+	float *d_fe = sg.out(freq_err, (size_t)n);
+	float *d_ss = sg.out(ssyms, (size_t)n * ht.len);
+	if ((r = sg.err())) return r;
+	r = demod_dev_impl(st, type, ht, n, sps, in_len, d_iq, d_off, d_fs, d_eb, ebits_stride, d_sid, d_toa, d_fe, d_ss,
+	                   d_rv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(st));
-	HIP_TRY(hipMemcpy(rv, d_rv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (ebits) HIP_TRY(hipMemcpy(ebits, d_eb.p, (size_t)n * ebits_stride, hipMemcpyDeviceToHost));
-	if (sync_id) HIP_TRY(hipMemcpy(sync_id, d_sid.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (toa) HIP_TRY(hipMemcpy(toa, d_toa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (freq_err) HIP_TRY(hipMemcpy(freq_err, d_fe.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (ssyms) HIP_TRY(hipMemcpy(ssyms, d_ss.p, (size_t)n * ht.len * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 // host pointers: staged through HBM
@@ -461,44 +453,24 @@ int gmr1_hip_tch3_rx_batch(int n, int sps, int in_len,
 		return 0;
 	if (!iq || !offset || !rv || !frames)
 		return fail(-EINVAL, "tch3 rx: n/iq/offset/rv/frames are required");
-	for (int i = 0; i < n; i++)
-		if (offset[i] + (uint64_t)in_len > iq_len)
-			return fail(-EINVAL, "burst %d runs past the end of iq", i);
-	DBuf d_iq, d_off, d_fs, d_ci, d_eb, d_sid, d_toa, d_rv, d_fr, d_s, d_conv;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(d_off.alloc((size_t)n * 8));
-	HIP_TRY(d_rv.alloc((size_t)n * 4));
-	HIP_TRY(d_fr.alloc((size_t)n * 20));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, offset, (size_t)n * 8, hipMemcpyHostToDevice));
-	if (freq_shift) {
-		HIP_TRY(d_fs.alloc((size_t)n * 4));
-		HIP_TRY(hipMemcpy(d_fs.p, freq_shift, (size_t)n * 4, hipMemcpyHostToDevice));
-	}
-	if (ciph) {
-		HIP_TRY(d_ci.alloc((size_t)n * 208));
-		HIP_TRY(hipMemcpy(d_ci.p, ciph, (size_t)n * 208, hipMemcpyHostToDevice));
-	}
-	if (ebits) HIP_TRY(d_eb.alloc((size_t)n * 212));
-	if (sync_id) HIP_TRY(d_sid.alloc((size_t)n * 4));
-	if (toa) HIP_TRY(d_toa.alloc((size_t)n * 4));
-	if (bits_s) HIP_TRY(d_s.alloc((size_t)n * 4));
-	if (conv) HIP_TRY(d_conv.alloc((size_t)n * 8));
-	r = gmr1_hip_tch3_rx_batch_dev(nullptr, n, sps, in_len, d_iq.as<float>(), d_off.as<uint64_t>(),
-	                               freq_shift ? d_fs.as<float>() : nullptr, m, ciph ? d_ci.as<uint8_t>() : nullptr,
-	                               ebits ? d_eb.as<int8_t>() : nullptr, sync_id ? d_sid.as<int32_t>() : nullptr,
-	                               toa ? d_toa.as<float>() : nullptr, d_rv.as<int32_t>(), d_fr.as<uint8_t>(),
-	                               bits_s ? d_s.as<uint8_t>() : nullptr, conv ? d_conv.as<int32_t>() : nullptr);
+	if ((r = bursts_fit(n, offset, in_len, iq_len))) return r;
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const uint64_t *d_off = sg.in(offset, (size_t)n);
+	const float *d_fs = sg.in(freq_shift, (size_t)n);
+	const uint8_t *d_ci = sg.in(ciph, (size_t)n * 208);
+	int32_t *d_rv = sg.out(rv, (size_t)n);
+	uint8_t *d_fr = sg.out(frames, (size_t)n * 20);
+	int8_t *d_eb = sg.out(ebits, (size_t)n * 212);
+	int32_t *d_sid = sg.out(sync_id, (size_t)n);
+	float *d_toa = sg.out(toa, (size_t)n);
+	uint8_t *d_s = sg.out(bits_s, (size_t)n * 4);
+	int32_t *d_conv = sg.out(conv, (size_t)n * 2);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_tch3_rx_batch_dev(nullptr, n, sps, in_len, d_iq, d_off, d_fs, m, d_ci, d_eb, d_sid, d_toa, d_rv, d_fr,
+	                               d_s, d_conv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(rv, d_rv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(frames, d_fr.p, (size_t)n * 20, hipMemcpyDeviceToHost));
-	if (ebits) HIP_TRY(hipMemcpy(ebits, d_eb.p, (size_t)n * 212, hipMemcpyDeviceToHost));
-	if (sync_id) HIP_TRY(hipMemcpy(sync_id, d_sid.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (toa) HIP_TRY(hipMemcpy(toa, d_toa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (bits_s) HIP_TRY(hipMemcpy(bits_s, d_s.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (conv) HIP_TRY(hipMemcpy(conv, d_conv.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int gmr1_hip_demod_batch(int burst_id, int n, int sps, int in_len,
@@ -536,57 +508,38 @@ int gmr1_hip_demod_taps(int burst_id, int sps, int in_len, const float *iq, floa
 	DevState *s;
 	r = dev_state(&s);
 	if (r) return r;
-	DBuf d_iq, d_off, d_fs, d_eb, d_sid, d_toa, d_fe, d_ss, d_rv, d_taps;
+	Stage sg;
 	const uint64_t zero = 0;
 	const size_t n_taps = (size_t)w + 2 * (size_t)in_len + 4 * (size_t)ht.len;     // floats: corr, burst, align, final
-	HIP_TRY(d_iq.alloc((size_t)in_len * 8));
-	HIP_TRY(d_off.alloc(8));
-	HIP_TRY(d_fs.alloc(4));
-	HIP_TRY(d_eb.alloc(ht.ebits));
-	HIP_TRY(d_sid.alloc(4));
-	HIP_TRY(d_toa.alloc(4));
-	HIP_TRY(d_fe.alloc(4));
-	HIP_TRY(d_ss.alloc((size_t)ht.len * 4));
-	HIP_TRY(d_rv.alloc(4));
-	HIP_TRY(d_taps.alloc(n_taps * 4 + 16));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, (size_t)in_len * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, &zero, 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_fs.p, &freq_shift, 4, hipMemcpyHostToDevice));
 	RxArgs a;
 	std::memset(&a, 0, sizeof(a));
 	a.n = 1; a.sps = sps; a.in_len[0] = a.in_len[1] = in_len;
 	a.fixed_type = burst_id;
 	a.ebits_stride = ht.ebits;
 	a.ssyms_stride = ht.len;
-	a.iq = d_iq.as<float2>();
-	a.offset = d_off.as<uint64_t>();
-	a.freq_shift = d_fs.as<float>();
-	a.ebits = d_eb.as<int8_t>();
-	a.sync_id = d_sid.as<int32_t>();
-	a.toa = d_toa.as<float>();
-	a.freq_err = d_fe.as<float>();
-	a.ssyms = d_ss.as<float>();
-	a.rv = d_rv.as<int32_t>();
+	a.iq = reinterpret_cast<const float2 *>(sg.in(iq, (size_t)in_len * 2));
+	a.offset = sg.in(&zero, 1);
+	a.freq_shift = sg.in(&freq_shift, 1);
+	a.ebits = sg.out_always(ebits, (size_t)ht.ebits);
+	a.sync_id = sg.out_always(sync_id, 1);
+	a.toa = sg.out_always(toa, 1);
+	a.freq_err = sg.out_always(freq_err, 1);
+	a.ssyms = sg.out_always(ssyms, (size_t)ht.len);
+	a.rv = sg.out(rv, 1);
 	// (burst / align / final are complex: they come first so that they sit on 8-byte boundaries)
-	float *t = d_taps.as<float>();
+	float *t = sg.dev<float>(n_taps + 4);
+	if ((r = sg.err())) return r;
 	RxTapsOut o;
 	o.burst = reinterpret_cast<float2 *>(t);
 	o.align = o.burst + in_len;
 	o.final_ = o.align + ht.len;
 	o.corr = reinterpret_cast<float *>(o.final_ + ht.len);
+	sg.back(corr, o.corr, (size_t)w);
+	sg.back(burst, reinterpret_cast<float *>(o.burst), (size_t)in_len * 2);
+	sg.back(align, reinterpret_cast<float *>(o.align), (size_t)ht.len * 2);
+	sg.back(final_, reinterpret_cast<float *>(o.final_), (size_t)ht.len * 2);
 	HIP_TRY(launch_rx_taps(a, o, nullptr));
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(rv, d_rv.p, 4, hipMemcpyDeviceToHost));
-	if (corr) HIP_TRY(hipMemcpy(corr, o.corr, (size_t)w * 4, hipMemcpyDeviceToHost));
-	if (burst) HIP_TRY(hipMemcpy(burst, o.burst, (size_t)in_len * 8, hipMemcpyDeviceToHost));
-	if (align) HIP_TRY(hipMemcpy(align, o.align, (size_t)ht.len * 8, hipMemcpyDeviceToHost));
-	if (final_) HIP_TRY(hipMemcpy(final_, o.final_, (size_t)ht.len * 8, hipMemcpyDeviceToHost));
-	if (ebits) HIP_TRY(hipMemcpy(ebits, d_eb.p, ht.ebits, hipMemcpyDeviceToHost));
-	if (sync_id) HIP_TRY(hipMemcpy(sync_id, d_sid.p, 4, hipMemcpyDeviceToHost));
-	if (toa) HIP_TRY(hipMemcpy(toa, d_toa.p, 4, hipMemcpyDeviceToHost));
-	if (freq_err) HIP_TRY(hipMemcpy(freq_err, d_fe.p, 4, hipMemcpyDeviceToHost));
-	if (ssyms) HIP_TRY(hipMemcpy(ssyms, d_ss.p, (size_t)ht.len * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 // ---------------------------------------------------------------------------
@@ -865,19 +818,15 @@ static int l1_host(int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *
 	int r = dev_state(&s);
 	if (r) return r;
 	if (n <= 0) return 0;
-	DBuf d_eb, d_l2, d_crc, d_conv;
-	HIP_TRY(d_eb.alloc((size_t)n * neb));
-	HIP_TRY(d_l2.alloc((size_t)n * 24));
-	HIP_TRY(d_crc.alloc((size_t)n * 4));
-	HIP_TRY(d_conv.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_eb.p, ebits, (size_t)n * neb, hipMemcpyHostToDevice));
-	r = l1_dev(nullptr, chain, n, d_eb.as<int8_t>(), d_l2.as<uint8_t>(), d_crc.as<int32_t>(), d_conv.as<int32_t>());
+	Stage sg;
+	const int8_t *d_eb = sg.in(ebits, (size_t)n * neb);
+	uint8_t *d_l2 = sg.out(l2, (size_t)n * 24);
+	int32_t *d_crc = sg.out(crc, (size_t)n);
+	int32_t *d_conv = sg.out(conv, (size_t)n);
+	if ((r = sg.err())) return r;
+	r = l1_dev(nullptr, chain, n, d_eb, d_l2, d_crc, d_conv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(l2, d_l2.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(crc, d_crc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(conv, d_conv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int gmr1_hip_bcch_decode_batch_dev(void *stream, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv)
@@ -1117,40 +1066,24 @@ int gmr1_hip_rx_bcch_ccch_batch(int n, int sps,
 		if (offset[i] + len > iq_len)
 			return fail(-EINVAL, "burst %d runs past the end of iq", i);
 	}
-	DBuf d_iq, d_off, d_kind, d_fs, d_l2, d_crc, d_conv, d_toa, d_fe, d_eb, d_ss, d_rv;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(d_off.alloc((size_t)n * 8));
-	HIP_TRY(d_kind.alloc((size_t)n));
-	HIP_TRY(d_l2.alloc((size_t)n * 24));
-	HIP_TRY(d_crc.alloc((size_t)n * 4));
-	HIP_TRY(d_conv.alloc((size_t)n * 4));
-	HIP_TRY(d_toa.alloc((size_t)n * 4));
-	HIP_TRY(d_fe.alloc((size_t)n * 4));
-	HIP_TRY(d_rv.alloc((size_t)n * 4));
-	if (freq_shift) HIP_TRY(d_fs.alloc((size_t)n * 4));
-	if (ebits) HIP_TRY(d_eb.alloc((size_t)n * 432));
-	if (ssyms) HIP_TRY(d_ss.alloc((size_t)n * 234 * 4));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, offset, (size_t)n * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_kind.p, kind, (size_t)n, hipMemcpyHostToDevice));
-	if (freq_shift) HIP_TRY(hipMemcpy(d_fs.p, freq_shift, (size_t)n * 4, hipMemcpyHostToDevice));
-	r = gmr1_hip_rx_bcch_ccch_batch_dev(nullptr, n, sps, d_iq.as<float>(), d_off.as<uint64_t>(), d_kind.as<uint8_t>(),
-	                                    freq_shift ? d_fs.as<float>() : nullptr,
-	                                    d_l2.as<uint8_t>(), d_crc.as<int32_t>(), d_conv.as<int32_t>(),
-	                                    d_toa.as<float>(), d_fe.as<float>(),
-	                                    ebits ? d_eb.as<int8_t>() : nullptr, ssyms ? d_ss.as<float>() : nullptr,
-	                                    d_rv.as<int32_t>());
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const uint64_t *d_off = sg.in(offset, (size_t)n);
+	const uint8_t *d_kind = sg.in(kind, (size_t)n);
+	const float *d_fs = sg.in(freq_shift, (size_t)n);
+	uint8_t *d_l2 = sg.out(l2, (size_t)n * 24);
+	int32_t *d_crc = sg.out(crc, (size_t)n);
+	int32_t *d_conv = sg.out(conv, (size_t)n);
+	int32_t *d_rv = sg.out(rv, (size_t)n);
+	float *d_toa = sg.out_always(toa, (size_t)n);
+	float *d_fe = sg.out_always(freq_err, (size_t)n);
+	int8_t *d_eb = sg.out(ebits, (size_t)n * 432);
+	float *d_ss = sg.out(ssyms, (size_t)n * 234);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_rx_bcch_ccch_batch_dev(nullptr, n, sps, d_iq, d_off, d_kind, d_fs, d_l2, d_crc, d_conv, d_toa, d_fe,
+	                                    d_eb, d_ss, d_rv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(l2, d_l2.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(crc, d_crc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(conv, d_conv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(rv, d_rv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (toa) HIP_TRY(hipMemcpy(toa, d_toa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (freq_err) HIP_TRY(hipMemcpy(freq_err, d_fe.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (ebits) HIP_TRY(hipMemcpy(ebits, d_eb.p, (size_t)n * 432, hipMemcpyDeviceToHost));
-	if (ssyms) HIP_TRY(hipMemcpy(ssyms, d_ss.p, (size_t)n * 234 * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 }  // extern "C"

@@ -322,26 +322,21 @@ int gmr1_hip_codec_decode_batch(int n_ch, int n_frames, const uint8_t *frames, i
 	if (!frames || !pcm)
 		return fail(-EINVAL, "codec: frames / pcm are required");
 	const size_t nf = (size_t)n_ch * n_frames;
-	DBuf d_fr, d_pcm, d_rv, d_st;
-	HIP_TRY(d_fr.alloc(nf * kAmbeFrameBytes));
-	HIP_TRY(d_pcm.alloc(nf * kAmbeFrameSamples * 2));
-	HIP_TRY(d_rv.alloc(nf * 4));
-	HIP_TRY(d_st.alloc((size_t)n_ch * sizeof(AmbeState)));
-	HIP_TRY(hipMemcpy(d_fr.p, frames, nf * kAmbeFrameBytes, hipMemcpyHostToDevice));
-	if (state && !(flags & GMR1_HIP_CODEC_FRESH))
-		HIP_TRY(hipMemcpy(d_st.p, state, (size_t)n_ch * sizeof(AmbeState), hipMemcpyHostToDevice));
-	else {
-		r = init_dev(nullptr, n_ch, d_st.p, flags & GMR1_HIP_CODEC_CLEARED);
+	Stage sg;
+	AmbeState *h_st = static_cast<AmbeState *>(state);
+	const bool carry = state && !(flags & GMR1_HIP_CODEC_FRESH);
+	const uint8_t *d_fr = sg.in(frames, nf * kAmbeFrameBytes);
+	int16_t *d_pcm = sg.out(pcm, nf * kAmbeFrameSamples);
+	int32_t *d_rv = sg.out_always(rv, nf);
+	AmbeState *d_st = carry ? sg.inout(h_st, (size_t)n_ch) : sg.out_always(h_st, (size_t)n_ch);
+	if ((r = sg.err())) return r;
+	if (!carry) {
+		r = init_dev(nullptr, n_ch, d_st, flags & GMR1_HIP_CODEC_CLEARED);
 		if (r) return r;
 	}
-	r = decode_dev(nullptr, n_ch, n_frames, d_fr.as<uint8_t>(), d_pcm.as<int16_t>(), kAmbeFrameSamples, d_rv.as<int32_t>(),
-	               d_st.p, kAmbeFrameSamples);
+	r = decode_dev(nullptr, n_ch, n_frames, d_fr, d_pcm, kAmbeFrameSamples, d_rv, d_st, kAmbeFrameSamples);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(pcm, d_pcm.p, nf * kAmbeFrameSamples * 2, hipMemcpyDeviceToHost));
-	if (rv) HIP_TRY(hipMemcpy(rv, d_rv.p, nf * 4, hipMemcpyDeviceToHost));
-	if (state) HIP_TRY(hipMemcpy(state, d_st.p, (size_t)n_ch * sizeof(AmbeState), hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 // ---- the reference's own calls (include/osmocom/gmr1/codec/codec.h:37-45) ----

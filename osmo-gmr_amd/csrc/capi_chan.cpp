@@ -495,15 +495,13 @@ int gmr1_hip_ddc(double samp_rate, int sps, const float *wide, uint64_t n_in, in
 	if (!n_sel || !n_out) return 0;
 	if (out_stride < n_out)
 		return fail(-EINVAL, "ddc: out_stride too small");
-	DBuf d_w, d_o;
-	HIP_TRY(d_w.alloc(n_in * 8));
-	HIP_TRY(d_o.alloc((size_t)n_sel * out_stride * 8));
-	HIP_TRY(hipMemcpy(d_w.p, wide, n_in * 8, hipMemcpyHostToDevice));
-	r = gmr1_hip_ddc_dev(nullptr, samp_rate, sps, d_w.as<float>(), n_in, n_sel, freq_hz, d_o.as<float>(), out_stride, nullptr);
+	Stage sg;
+	const float *d_w = sg.in(wide, (size_t)n_in * 2);
+	float *d_o = sg.out(out, (size_t)n_sel * out_stride * 2);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_ddc_dev(nullptr, samp_rate, sps, d_w, n_in, n_sel, freq_hz, d_o, out_stride, nullptr);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(out, d_o.p, (size_t)n_sel * out_stride * 8, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int gmr1_hip_channelize_plan(double samp_rate, int sps, uint64_t n_in,
@@ -630,16 +628,13 @@ int gmr1_hip_channelize(double samp_rate, int sps, const float *wide, uint64_t n
 	if (!n_sel || !n_out) return 0;
 	if (out_stride < n_out)
 		return fail(-EINVAL, "channelize: out_stride too small");
-	DBuf d_w, d_o;
-	HIP_TRY(d_w.alloc(n_in * 8));
-	HIP_TRY(d_o.alloc((size_t)n_sel * out_stride * 8));
-	HIP_TRY(hipMemcpy(d_w.p, wide, n_in * 8, hipMemcpyHostToDevice));
-	r = gmr1_hip_channelize_dev(nullptr, samp_rate, sps, d_w.as<float>(), n_in, rotation, n_sel, chan_idx,
-	                            d_o.as<float>(), out_stride, nullptr);
+	Stage sg;
+	const float *d_w = sg.in(wide, (size_t)n_in * 2);
+	float *d_o = sg.out(out, (size_t)n_sel * out_stride * 2);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_channelize_dev(nullptr, samp_rate, sps, d_w, n_in, rotation, n_sel, chan_idx, d_o, out_stride, nullptr);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(out, d_o.p, (size_t)n_sel * out_stride * 8, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,8 @@ namespace gmr1 {
 
 int fail(int code, const char *fmt, ...);
 const char *last_error();
+// -EINVAL if one of n windows of in_len samples, window i at offset[i], does not lie within the iq_len samples of iq
+int bursts_fit(int n, const uint64_t *offset, int in_len, uint64_t iq_len);
 // 1 when the layer-1 chains follow libosmocore's accelerated Viterbi decoder (gmr1_hip_set_conv_decoder), else 0
 int conv_acc();
 
@@ -94,12 +97,123 @@ int demod_dev_energy(hipStream_t st, int burst_id, int n, int sps, int in_len, c
                      const uint64_t *offset, const float *freq_shift, int8_t *ebits, int ebits_stride,
                      int32_t *sync_id, float *toa, float *energy, int32_t *rv);
 
-// RAII device buffer for the host-pointer variants
-struct DBuf {
-	void *p = nullptr;
-	~DBuf() { if (p) (void)hipFree(p); }
-	hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-	template <typename T> T *as() { return static_cast<T *>(p); }
+// Device scratch of a traffic pass: one carve-up of the grow-only device workspace (none of the kernels the
+// passes launch uses it) instead of dozens of hipMalloc / hipFree pairs per call.
+struct Arena {
+	unsigned char *base = nullptr;
+	size_t cap = 0, off = 0;
+	int init(size_t bytes)
+	{
+		DevState *ds;
+		int r = dev_state(&ds);
+		if (r) return r;
+		void *ws;
+		r = dev_workspace(ds, bytes + 256, &ws);
+		if (r) return r;
+		base = reinterpret_cast<unsigned char *>(((uintptr_t)ws + 127) & ~(uintptr_t)127);
+		cap = bytes;
+		off = 0;
+		return 0;
+	}
+	void *take(size_t n)
+	{
+		n = ((n ? n : 1) + 127) & ~(size_t)127;
+		if (off + n > cap)
+			return nullptr;
+		void *p = base + off;
+		off += n;
+		return p;
+	}
+};
+
+// The device copies of one call's host buffers.  Counts are elements of T, so a buffer's size is written once.
+// in() and out() turn a null host pointer into a null device pointer and allocate nothing.  The first HIP error is
+// kept and everything after it does nothing: the caller asks err() once before it launches and returns what fetch()
+// returns, both with HIP_TRY's codes.  Plain: hipMalloc and blocking copies, freed on scope exit.  On an Arena:
+// memory from it and hipMemcpyAsync on the stream.
+class Stage {
+public:
+	explicit Stage(hipStream_t st = nullptr, Arena *arena = nullptr) : st_(st), arena_(arena) {}
+	Stage(const Stage &) = delete;
+	Stage &operator=(const Stage &) = delete;
+	~Stage() { for (void *p : owned_) (void)hipFree(p); }
+
+	// n elements that only the device sees
+	template <typename T> T *dev(size_t n) { return static_cast<T *>(take(n * sizeof(T))); }
+	// uploaded
+	template <typename T> const T *in(const T *h, size_t n)
+	{
+		T *d = h ? dev<T>(n) : nullptr;
+		if (d) copy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
+		return d;
+	}
+	// copied back by fetch()
+	template <typename T> T *out(T *h, size_t n) { return h ? out_always(h, n) : nullptr; }
+	// an output the kernel writes whether the caller wants it or not: copied back by fetch() if h is not null
+	template <typename T> T *out_always(T *h, size_t n)
+	{
+		T *d = dev<T>(n);
+		back(h, d, n);
+		return d;
+	}
+	// uploaded, and copied back by fetch()
+	template <typename T> T *inout(T *h, size_t n)
+	{
+		T *d = const_cast<T *>(in(h, n));
+		back(h, d, n);
+		return d;
+	}
+	// fetch() copies the n elements at d, which lie in a buffer of this stage, to h (nothing if h is null)
+	template <typename T> void back(T *h, const T *d, size_t n) { if (h && d) backs_.push_back({h, d, n * sizeof(T)}); }
+
+	int err() const
+	{
+		return e_ == hipSuccess ? 0 : fail(e_ == hipErrorNoDevice ? -ENODEV : -EIO, "%s: %s", what_, hipGetErrorString(e_));
+	}
+	// on an Arena: queues the copies back booked so far and does not wait; a later fetch() waits for them
+	void queue_backs()
+	{
+		for (const Back &b : backs_)
+			copy(b.h, b.d, b.bytes, hipMemcpyDeviceToHost);
+		backs_.clear();
+	}
+	// one synchronisation of the stream, ahead of the blocking copies back and behind the queued ones
+	int fetch()
+	{
+		if (!arena_) note("hipStreamSynchronize", hipStreamSynchronize(st_));
+		queue_backs();
+		if (arena_ && e_ == hipSuccess) note("hipStreamSynchronize", hipStreamSynchronize(st_));
+		return err();
+	}
+
+private:
+	struct Back { void *h; const void *d; size_t bytes; };
+	void note(const char *what, hipError_t e) { if (e_ == hipSuccess && e != hipSuccess) { e_ = e; what_ = what; } }
+	void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+	{
+		if (e_ != hipSuccess) return;
+		if (arena_) note("hipMemcpyAsync", hipMemcpyAsync(dst, src, bytes, kind, st_));
+		else note("hipMemcpy", hipMemcpy(dst, src, bytes, kind));
+	}
+	void *take(size_t bytes)
+	{
+		void *p = nullptr;
+		if (e_ != hipSuccess) return p;
+		if (arena_) {
+			p = arena_->take(bytes);
+			note("the traffic pass's arena", p ? hipSuccess : hipErrorOutOfMemory);
+		} else {
+			note("hipMalloc", hipMalloc(&p, bytes ? bytes : 1));
+			if (p) owned_.push_back(p);
+		}
+		return p;
+	}
+	hipStream_t st_;
+	Arena *arena_;
+	hipError_t e_ = hipSuccess;
+	const char *what_ = "";
+	std::vector<void *> owned_;
+	std::vector<Back> backs_;
 };
 
 }  // namespace gmr1

@@ -116,26 +116,17 @@ static int detect_host_impl(int n_types, const int *slots, const DevBurst *const
 	if (n <= 0) return 0;
 	if (!iq || !offset || !rv)
 		return fail(-EINVAL, "detect: NULL argument");
-	for (int i = 0; i < n; i++)
-		if (offset[i] + (uint64_t)in_len > iq_len)
-			return fail(-EINVAL, "burst %d runs past the end of iq", i);
-	DBuf d_iq, d_off, d_fs, d_et, d_bt, d_sid, d_toa, d_rv;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(d_off.alloc((size_t)n * 8));
-	HIP_TRY(d_bt.alloc((size_t)n * 4));
-	HIP_TRY(d_sid.alloc((size_t)n * 4));
-	HIP_TRY(d_toa.alloc((size_t)n * 4));
-	HIP_TRY(d_rv.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, offset, (size_t)n * 8, hipMemcpyHostToDevice));
-	if (freq_shift) {
-		HIP_TRY(d_fs.alloc((size_t)n * 4));
-		HIP_TRY(hipMemcpy(d_fs.p, freq_shift, (size_t)n * 4, hipMemcpyHostToDevice));
-	}
-	if (e_toa) {
-		HIP_TRY(d_et.alloc((size_t)n * 4));
-		HIP_TRY(hipMemcpy(d_et.p, e_toa, (size_t)n * 4, hipMemcpyHostToDevice));
-	}
+	if ((r = bursts_fit(n, offset, in_len, iq_len))) return r;
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const uint64_t *d_off = sg.in(offset, (size_t)n);
+	const float *d_fs = sg.in(freq_shift, (size_t)n);
+	const float *d_et = sg.in(e_toa, (size_t)n);
+	int32_t *d_rv = sg.out(rv, (size_t)n);
+	int32_t *d_bt = sg.out_always(bt_id, (size_t)n);
+	int32_t *d_sid = sg.out_always(sync_id, (size_t)n);
+	float *d_toa = sg.out_always(toa, (size_t)n);
+	if ((r = sg.err())) return r;
 	// caller-defined descriptors share the spare table slots process-wide: uploads, launches and completion under one lock
 	bool any_custom = false;
 	for (int i = 0; i < n_types; i++)
@@ -143,18 +134,10 @@ static int detect_host_impl(int n_types, const int *slots, const DevBurst *const
 	std::unique_lock<std::mutex> lk(custom_slots_mutex(), std::defer_lock);
 	if (any_custom)
 		lk.lock();
-	r = detect_dev_impl(nullptr, n_types, slots, hts, customs, n, sps, in_len, d_iq.as<float>(), d_off.as<uint64_t>(),
-	                    freq_shift ? d_fs.as<float>() : nullptr, e_toa ? d_et.as<float>() : nullptr,
-	                    d_bt.as<int32_t>(), d_sid.as<int32_t>(), d_toa.as<float>(), d_rv.as<int32_t>());
+	r = detect_dev_impl(nullptr, n_types, slots, hts, customs, n, sps, in_len, d_iq, d_off, d_fs, d_et, d_bt, d_sid, d_toa,
+	                    d_rv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	if (lk.owns_lock())
-		lk.unlock();
-	HIP_TRY(hipMemcpy(rv, d_rv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (bt_id) HIP_TRY(hipMemcpy(bt_id, d_bt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (sync_id) HIP_TRY(hipMemcpy(sync_id, d_sid.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (toa) HIP_TRY(hipMemcpy(toa, d_toa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int gmr1_hip_detect_batch(int n_types, const int *burst_ids, int n, int sps, int in_len,
@@ -196,25 +179,16 @@ int gmr1_hip_mod_order_batch(int n, int sps, int in_len, const float *iq, uint64
 	if (n <= 0) return 0;
 	if (!iq || !offset || !order)
 		return fail(-EINVAL, "mod_order: NULL argument");
-	for (int i = 0; i < n; i++)
-		if (offset[i] + (uint64_t)in_len > iq_len)
-			return fail(-EINVAL, "burst %d runs past the end of iq", i);
-	DBuf d_iq, d_off, d_fs, d_o;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(d_off.alloc((size_t)n * 8));
-	HIP_TRY(d_o.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, offset, (size_t)n * 8, hipMemcpyHostToDevice));
-	if (freq_shift) {
-		HIP_TRY(d_fs.alloc((size_t)n * 4));
-		HIP_TRY(hipMemcpy(d_fs.p, freq_shift, (size_t)n * 4, hipMemcpyHostToDevice));
-	}
-	r = gmr1_hip_mod_order_batch_dev(nullptr, n, sps, in_len, d_iq.as<float>(), d_off.as<uint64_t>(),
-	                                 freq_shift ? d_fs.as<float>() : nullptr, d_o.as<int32_t>());
+	if ((r = bursts_fit(n, offset, in_len, iq_len))) return r;
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const uint64_t *d_off = sg.in(offset, (size_t)n);
+	const float *d_fs = sg.in(freq_shift, (size_t)n);
+	int32_t *d_o = sg.out(order, (size_t)n);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_mod_order_batch_dev(nullptr, n, sps, in_len, d_iq, d_off, d_fs, d_o);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(order, d_o.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 // ---- reference-compatible single calls (pi4cxpsk.h:107-113) -------------------------------

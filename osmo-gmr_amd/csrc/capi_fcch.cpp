@@ -144,23 +144,20 @@ int fine_dev(hipStream_t st, int tab, int mode, int n, int sps, const float *iq,
 	return 0;
 }
 
-// shared host staging: copies iq + offsets (+ freq_shift) in, runs `body`, copies results out
+// shared host staging: iq + offsets (+ freq_shift) in; the callers add their outputs to `sg`
 struct Staged {
-	DBuf iq, off, fs;
+	Stage sg;
+	const float *iq = nullptr, *fs = nullptr;
+	const uint64_t *off = nullptr;
 	int stage(int n, const float *h_iq, uint64_t iq_len, const uint64_t *h_off, const float *h_fs,
 	          uint64_t need)
 	{
 		for (int i = 0; i < n; i++)
 			if (h_off[i] + need > iq_len)
 				return fail(-EINVAL, "window %d runs past the end of iq", i);
-		HIP_TRY(iq.alloc(iq_len * 8));
-		HIP_TRY(off.alloc((size_t)n * 8));
-		HIP_TRY(hipMemcpy(iq.p, h_iq, iq_len * 8, hipMemcpyHostToDevice));
-		HIP_TRY(hipMemcpy(off.p, h_off, (size_t)n * 8, hipMemcpyHostToDevice));
-		if (h_fs) {
-			HIP_TRY(fs.alloc((size_t)n * 4));
-			HIP_TRY(hipMemcpy(fs.p, h_fs, (size_t)n * 4, hipMemcpyHostToDevice));
-		}
+		iq = sg.in(h_iq, (size_t)iq_len * 2);
+		off = sg.in(h_off, (size_t)n);
+		fs = sg.in(h_fs, (size_t)n);
 		return 0;
 	}
 };
@@ -189,16 +186,12 @@ int gmr1_hip_fcch_rough_batch(int fcch_type, int n, int sps, int len,
 	Staged st;
 	r = st.stage(n, iq, iq_len, offset, freq_shift, (uint64_t)len);
 	if (r) return r;
-	DBuf d_toa, d_rv;
-	HIP_TRY(d_toa.alloc((size_t)n * 4));
-	HIP_TRY(d_rv.alloc((size_t)n * 4));
-	r = rough_dev(nullptr, fcch_type, n, sps, len, st.iq.as<float>(), st.off.as<uint64_t>(),
-	              freq_shift ? st.fs.as<float>() : nullptr, d_toa.as<int32_t>(), d_rv.as<int32_t>(), nullptr, 0);
+	int32_t *d_toa = st.sg.out(toa, (size_t)n);
+	int32_t *d_rv = st.sg.out_always(rv, (size_t)n);
+	if ((r = st.sg.err())) return r;
+	r = rough_dev(nullptr, fcch_type, n, sps, len, st.iq, st.off, st.fs, d_toa, d_rv, nullptr, 0);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(toa, d_toa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (rv) HIP_TRY(hipMemcpy(rv, d_rv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return st.sg.fetch();
 }
 
 int gmr1_hip_fcch_fine_batch_dev(void *stream, int fcch_type, int n, int sps,
@@ -228,16 +221,12 @@ int gmr1_hip_fcch_fine_batch(int fcch_type, int n, int sps,
 	Staged st;
 	r = st.stage(n, iq, iq_len, offset, freq_shift, (uint64_t)kFcchBuiltin[fcch_type]->len * sps);
 	if (r) return r;
-	DBuf d_toa, d_fe;
-	HIP_TRY(d_toa.alloc((size_t)n * 4));
-	HIP_TRY(d_fe.alloc((size_t)n * 4));
-	r = fine_dev(nullptr, fcch_type, 0, n, sps, st.iq.as<float>(), st.off.as<uint64_t>(),
-	             freq_shift ? st.fs.as<float>() : nullptr, d_toa.as<int32_t>(), d_fe.as<float>(), nullptr);
+	int32_t *d_toa = st.sg.out(toa, (size_t)n);
+	float *d_fe = st.sg.out(freq_error, (size_t)n);
+	if ((r = st.sg.err())) return r;
+	r = fine_dev(nullptr, fcch_type, 0, n, sps, st.iq, st.off, st.fs, d_toa, d_fe, nullptr);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(toa, d_toa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(freq_error, d_fe.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return st.sg.fetch();
 }
 
 int gmr1_hip_fcch_snr_batch(int fcch_type, int n, int sps,
@@ -253,14 +242,11 @@ int gmr1_hip_fcch_snr_batch(int fcch_type, int n, int sps,
 	Staged st;
 	r = st.stage(n, iq, iq_len, offset, freq_shift, (uint64_t)kFcchBuiltin[fcch_type]->len * sps);
 	if (r) return r;
-	DBuf d_snr;
-	HIP_TRY(d_snr.alloc((size_t)n * 4));
-	r = fine_dev(nullptr, fcch_type, 1, n, sps, st.iq.as<float>(), st.off.as<uint64_t>(),
-	             freq_shift ? st.fs.as<float>() : nullptr, nullptr, nullptr, d_snr.as<float>());
+	float *d_snr = st.sg.out(snr, (size_t)n);
+	if ((r = st.sg.err())) return r;
+	r = fine_dev(nullptr, fcch_type, 1, n, sps, st.iq, st.off, st.fs, nullptr, nullptr, d_snr);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(snr, d_snr.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return st.sg.fetch();
 }
 
 }  // extern "C"
@@ -353,18 +339,13 @@ int gmr1_hip_fcch_rough_multi_batch(int fcch_type, int n, int sps, int len,
 	Staged st;
 	r = st.stage(n, iq, iq_len, offset, freq_shift, (uint64_t)len);
 	if (r) return r;
-	DBuf d_toa, d_cnt;
-	HIP_TRY(d_toa.alloc((size_t)n * N * 4));
-	HIP_TRY(d_cnt.alloc((size_t)n * 4));
-	HIP_TRY(hipMemset(d_toa.p, 0, (size_t)n * N * 4));
-	r = gmr1_hip_fcch_rough_multi_batch_dev(nullptr, fcch_type, n, sps, len, st.iq.as<float>(), st.off.as<uint64_t>(),
-	                                        freq_shift ? st.fs.as<float>() : nullptr, d_toa.as<int32_t>(), N,
-	                                        d_cnt.as<int32_t>());
+	int32_t *d_toa = st.sg.out(peaks_toa, (size_t)n * N);
+	int32_t *d_cnt = st.sg.out(count, (size_t)n);
+	if ((r = st.sg.err())) return r;
+	HIP_TRY(hipMemset(d_toa, 0, (size_t)n * N * 4));
+	r = gmr1_hip_fcch_rough_multi_batch_dev(nullptr, fcch_type, n, sps, len, st.iq, st.off, st.fs, d_toa, N, d_cnt);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(peaks_toa, d_toa.p, (size_t)n * N * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(count, d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return st.sg.fetch();
 }
 
 // ---- reference-compatible single calls (fcch.h:47-61) ---------------------------------------

@@ -31,26 +31,17 @@ int gmr1_hip_facch3_decode_batch(int n, const int8_t *ebits, const uint8_t *ciph
 	if (n <= 0) return 0;
 	if (!ebits || !l2 || !crc || !conv)
 		return fail(-EINVAL, "facch3 decode: NULL argument");
-	DBuf d_eb, d_ci, d_l2, d_s, d_crc, d_conv;
-	HIP_TRY(d_eb.alloc((size_t)n * 416));
-	HIP_TRY(d_l2.alloc((size_t)n * 10));
-	HIP_TRY(d_s.alloc((size_t)n * 32));
-	HIP_TRY(d_crc.alloc((size_t)n * 4));
-	HIP_TRY(d_conv.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_eb.p, ebits, (size_t)n * 416, hipMemcpyHostToDevice));
-	if (ciph) {
-		HIP_TRY(d_ci.alloc((size_t)n * 384));
-		HIP_TRY(hipMemcpy(d_ci.p, ciph, (size_t)n * 384, hipMemcpyHostToDevice));
-	}
-	r = gmr1_hip_facch3_decode_batch_dev(nullptr, n, d_eb.as<int8_t>(), ciph ? d_ci.as<uint8_t>() : nullptr,
-	                                     d_l2.as<uint8_t>(), d_s.as<uint8_t>(), d_crc.as<int32_t>(), d_conv.as<int32_t>());
+	Stage sg;
+	const int8_t *d_eb = sg.in(ebits, (size_t)n * 416);
+	const uint8_t *d_ci = sg.in(ciph, (size_t)n * 384);
+	uint8_t *d_l2 = sg.out(l2, (size_t)n * 10);
+	uint8_t *d_s = sg.out_always(bits_s, (size_t)n * 32);
+	int32_t *d_crc = sg.out(crc, (size_t)n);
+	int32_t *d_conv = sg.out(conv, (size_t)n);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_facch3_decode_batch_dev(nullptr, n, d_eb, d_ci, d_l2, d_s, d_crc, d_conv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(l2, d_l2.p, (size_t)n * 10, hipMemcpyDeviceToHost));
-	if (bits_s) HIP_TRY(hipMemcpy(bits_s, d_s.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(crc, d_crc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(conv, d_conv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int gmr1_hip_tch3_decode_batch_dev(void *stream, int n, int m, const int8_t *ebits, const uint8_t *ciph,
@@ -76,24 +67,16 @@ int gmr1_hip_tch3_decode_batch(int n, int m, const int8_t *ebits, const uint8_t 
 	if (n <= 0) return 0;
 	if (!ebits || !frames)
 		return fail(-EINVAL, "tch3 decode: NULL argument");
-	DBuf d_eb, d_ci, d_fr, d_s, d_conv;
-	HIP_TRY(d_eb.alloc((size_t)n * 212));
-	HIP_TRY(d_fr.alloc((size_t)n * 20));
-	HIP_TRY(d_s.alloc((size_t)n * 4));
-	HIP_TRY(d_conv.alloc((size_t)n * 8));
-	HIP_TRY(hipMemcpy(d_eb.p, ebits, (size_t)n * 212, hipMemcpyHostToDevice));
-	if (ciph) {
-		HIP_TRY(d_ci.alloc((size_t)n * 208));
-		HIP_TRY(hipMemcpy(d_ci.p, ciph, (size_t)n * 208, hipMemcpyHostToDevice));
-	}
-	r = gmr1_hip_tch3_decode_batch_dev(nullptr, n, m, d_eb.as<int8_t>(), ciph ? d_ci.as<uint8_t>() : nullptr,
-	                                   d_fr.as<uint8_t>(), d_s.as<uint8_t>(), d_conv.as<int32_t>());
+	Stage sg;
+	const int8_t *d_eb = sg.in(ebits, (size_t)n * 212);
+	const uint8_t *d_ci = sg.in(ciph, (size_t)n * 208);
+	uint8_t *d_fr = sg.out(frames, (size_t)n * 20);
+	uint8_t *d_s = sg.out_always(bits_s, (size_t)n * 4);
+	int32_t *d_conv = sg.out_always(conv, (size_t)n * 2);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_tch3_decode_batch_dev(nullptr, n, m, d_eb, d_ci, d_fr, d_s, d_conv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(frames, d_fr.p, (size_t)n * 20, hipMemcpyDeviceToHost));
-	if (bits_s) HIP_TRY(hipMemcpy(bits_s, d_s.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (conv) HIP_TRY(hipMemcpy(conv, d_conv.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 // ---- reference-compatible single calls ---------------------------------------------------------

@@ -180,28 +180,18 @@ int nt9_host(int kind, int n, int seq_len, const int8_t *ebits, const uint8_t *c
 	if (kind < 0 || kind > 3)
 		return fail(-EINVAL, "nt9: mode %d unknown", kind);
 	const int nb = kKinds[kind].l2_bytes;
-	DBuf d_e, d_c, d_l2, d_sa, d_st, d_crc, d_cv;
-	HIP_TRY(d_e.alloc((size_t)n * 662));
-	HIP_TRY(d_l2.alloc((size_t)n * nb));
-	HIP_TRY(d_sa.alloc((size_t)n * 10));
-	HIP_TRY(d_st.alloc((size_t)n * 4));
-	HIP_TRY(d_crc.alloc((size_t)n * 4));
-	HIP_TRY(d_cv.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_e.p, ebits, (size_t)n * 662, hipMemcpyHostToDevice));
-	if (ciph) {
-		HIP_TRY(d_c.alloc((size_t)n * 658));
-		HIP_TRY(hipMemcpy(d_c.p, ciph, (size_t)n * 658, hipMemcpyHostToDevice));
-	}
-	r = nt9_dev(nullptr, kind, n, seq_len, d_e.as<int8_t>(), ciph ? d_c.as<uint8_t>() : nullptr, d_l2.as<uint8_t>(),
-	            d_sa.as<int8_t>(), d_st.as<int8_t>(), d_crc.as<int32_t>(), d_cv.as<int32_t>());
+	Stage sg;
+	const int8_t *d_e = sg.in(ebits, (size_t)n * 662);
+	const uint8_t *d_c = sg.in(ciph, (size_t)n * 658);
+	uint8_t *d_l2 = sg.out(l2, (size_t)n * nb);
+	int8_t *d_sa = sg.out_always(sacch, (size_t)n * 10);
+	int8_t *d_st = sg.out_always(status, (size_t)n * 4);
+	int32_t *d_crc = sg.out_always(crc, (size_t)n);
+	int32_t *d_cv = sg.out_always(conv, (size_t)n);
+	if ((r = sg.err())) return r;
+	r = nt9_dev(nullptr, kind, n, seq_len, d_e, d_c, d_l2, d_sa, d_st, d_crc, d_cv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(l2, d_l2.p, (size_t)n * nb, hipMemcpyDeviceToHost));
-	if (sacch) HIP_TRY(hipMemcpy(sacch, d_sa.p, (size_t)n * 10, hipMemcpyDeviceToHost));
-	if (status) HIP_TRY(hipMemcpy(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (crc) HIP_TRY(hipMemcpy(crc, d_crc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (conv) HIP_TRY(hipMemcpy(conv, d_cv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 }  // namespace

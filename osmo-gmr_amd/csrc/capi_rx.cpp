@@ -132,45 +132,6 @@ int host_log(size_t bytes, unsigned char **out)
 }
 
 
-// Device scratch of a traffic pass: one carve-up of the grow-only device workspace (none of the kernels the
-// passes launch uses it) instead of dozens of hipMalloc / hipFree pairs per call.
-struct Arena {
-	unsigned char *base = nullptr;
-	size_t cap = 0, off = 0;
-	int init(size_t bytes)
-	{
-		DevState *ds;
-		int r = dev_state(&ds);
-		if (r) return r;
-		void *ws;
-		r = dev_workspace(ds, bytes + 256, &ws);
-		if (r) return r;
-		base = reinterpret_cast<unsigned char *>(((uintptr_t)ws + 127) & ~(uintptr_t)127);
-		cap = bytes;
-		off = 0;
-		return 0;
-	}
-	void *take(size_t n)
-	{
-		n = up128(n ? n : 1);
-		if (off + n > cap)
-			return nullptr;
-		void *p = base + off;
-		off += n;
-		return p;
-	}
-};
-thread_local Arena *g_arena = nullptr;
-struct ABuf {                      // DBuf's interface on the current arena
-	void *p = nullptr;
-	hipError_t alloc(size_t n)
-	{
-		p = g_arena ? g_arena->take(n) : nullptr;
-		return p ? hipSuccess : hipErrorOutOfMemory;
-	}
-	template <typename T> T *as() { return static_cast<T *>(p); }
-};
-
 // One call of gmr1_hip_rx_run*: what the phases share.  The phases run in the order the reference's main()
 // runs them (gmr1_rx.c:897-975); each is one member function below.
 struct RxRun {
@@ -662,8 +623,7 @@ int RxRun::tch3_pass()
 			// step A needs 376 B per frame, the decodes of step C at most 866 B per frame
 			Arena arena;
 			if ((r = arena.init((size_t)nt * 1300 + 64 * 1024))) return r;
-			g_arena = &arena;
-			struct Reset { ~Reset() { g_arena = nullptr; } } reset;
+			Stage sg(st, &arena);
 			std::vector<uint64_t> t_off(nt);
 			std::vector<float> t_fs(nt), t_et(nt);
 			std::vector<int32_t> t_p(nt);
@@ -675,49 +635,41 @@ int RxRun::tch3_pass()
 				t_et[k] = (float)t_etoa;
 				t_p[k] = titems[k].p;
 			}
-			ABuf d_off2, d_fs2, d_et, d_pp, d_feb, d_fsid, d_frv, d_en, d_seb, d_srv, d_bt, d_dsid, d_dtoa, d_drv, d_krv, d_ftoa;
-			HIP_TRY(d_off2.alloc((size_t)nt * 8)); HIP_TRY(d_fs2.alloc((size_t)nt * 4)); HIP_TRY(d_et.alloc((size_t)nt * 4));
-			HIP_TRY(d_pp.alloc((size_t)nt * 4)); HIP_TRY(d_feb.alloc((size_t)nt * 104)); HIP_TRY(d_fsid.alloc((size_t)nt * 4));
-			HIP_TRY(d_frv.alloc((size_t)nt * 4)); HIP_TRY(d_en.alloc((size_t)nt * 4)); HIP_TRY(d_seb.alloc((size_t)nt * 212));
-			HIP_TRY(d_srv.alloc((size_t)nt * 4)); HIP_TRY(d_bt.alloc((size_t)nt * 4)); HIP_TRY(d_dsid.alloc((size_t)nt * 4));
-			HIP_TRY(d_dtoa.alloc((size_t)nt * 4)); HIP_TRY(d_drv.alloc((size_t)nt * 4)); HIP_TRY(d_krv.alloc((size_t)nt * 4));
-			HIP_TRY(d_ftoa.alloc((size_t)nt * 4));
-			HIP_TRY(hipMemcpyAsync(d_off2.p, t_off.data(), (size_t)nt * 8, hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(d_fs2.p, t_fs.data(), (size_t)nt * 4, hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(d_et.p, t_et.data(), (size_t)nt * 4, hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(d_pp.p, t_p.data(), (size_t)nt * 4, hipMemcpyHostToDevice, st));
-
-			// A. speculative per-frame work
-			r = demod_dev_energy(st, GMR1_HIP_NT3_FACCH, nt, sps, t_in_len, tch, d_off2.as<uint64_t>(), d_fs2.as<float>(),
-			                     d_feb.as<int8_t>(), 104, d_fsid.as<int32_t>(), d_ftoa.as<float>(), d_en.as<float>(),
-			                     d_frv.as<int32_t>());
-			if (r) return r;
-			r = demod_dev_energy(st, GMR1_HIP_NT3_SPEECH, nt, sps, t_in_len, tch, d_off2.as<uint64_t>(), d_fs2.as<float>(),
-			                     d_seb.as<int8_t>(), 212, nullptr, nullptr, nullptr, d_srv.as<int32_t>());
-			if (r) return r;
-			{
-				const int ids[2] = {GMR1_HIP_NT3_FACCH, GMR1_HIP_NT3_SPEECH};     // gmr1_rx.c:534-538
-				r = gmr1_hip_detect_batch_dev(st, 2, ids, nt, sps, t_in_len, tch, d_off2.as<uint64_t>(), d_fs2.as<float>(),
-				                              d_et.as<float>(), d_bt.as<int32_t>(), d_dsid.as<int32_t>(), d_dtoa.as<float>(),
-				                              d_drv.as<int32_t>());
-				if (r) return r;
-			}
-			r = gmr1_hip_dkab_demod_batch_dev(st, nt, sps, t_in_len, tch, d_off2.as<uint64_t>(), d_fs2.as<float>(),
-			                                  d_pp.as<int32_t>(), nullptr, nullptr, d_krv.as<int32_t>());
-			if (r) return r;
 			std::vector<int8_t> h_feb((size_t)nt * 104), h_seb((size_t)nt * 212);
 			std::vector<int32_t> h_fsid(nt), h_frv(nt), h_srv(nt), h_bt(nt), h_drv(nt), h_krv(nt);
 			std::vector<float> h_en(nt);
-			HIP_TRY(hipMemcpyAsync(h_feb.data(), d_feb.p, (size_t)nt * 104, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_seb.data(), d_seb.p, (size_t)nt * 212, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_fsid.data(), d_fsid.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_frv.data(), d_frv.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_srv.data(), d_srv.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_bt.data(), d_bt.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_drv.data(), d_drv.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_krv.data(), d_krv.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_en.data(), d_en.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipStreamSynchronize(st));
+			const uint64_t *d_off2 = sg.in(t_off.data(), (size_t)nt);
+			const float *d_fs2 = sg.in(t_fs.data(), (size_t)nt);
+			const float *d_et = sg.in(t_et.data(), (size_t)nt);
+			const int32_t *d_pp = sg.in(t_p.data(), (size_t)nt);
+			int8_t *d_feb = sg.out(h_feb.data(), (size_t)nt * 104);
+			int8_t *d_seb = sg.out(h_seb.data(), (size_t)nt * 212);
+			int32_t *d_fsid = sg.out(h_fsid.data(), (size_t)nt);
+			int32_t *d_frv = sg.out(h_frv.data(), (size_t)nt);
+			int32_t *d_srv = sg.out(h_srv.data(), (size_t)nt);
+			int32_t *d_bt = sg.out(h_bt.data(), (size_t)nt);
+			int32_t *d_drv = sg.out(h_drv.data(), (size_t)nt);
+			int32_t *d_krv = sg.out(h_krv.data(), (size_t)nt);
+			float *d_en = sg.out(h_en.data(), (size_t)nt);
+			int32_t *d_dsid = sg.dev<int32_t>((size_t)nt);
+			float *d_dtoa = sg.dev<float>((size_t)nt), *d_ftoa = sg.dev<float>((size_t)nt);
+			if ((r = sg.err())) return r;
+
+			// A. speculative per-frame work
+			r = demod_dev_energy(st, GMR1_HIP_NT3_FACCH, nt, sps, t_in_len, tch, d_off2, d_fs2, d_feb, 104, d_fsid, d_ftoa, d_en,
+			                     d_frv);
+			if (r) return r;
+			r = demod_dev_energy(st, GMR1_HIP_NT3_SPEECH, nt, sps, t_in_len, tch, d_off2, d_fs2, d_seb, 212, nullptr, nullptr,
+			                     nullptr, d_srv);
+			if (r) return r;
+			{
+				const int ids[2] = {GMR1_HIP_NT3_FACCH, GMR1_HIP_NT3_SPEECH};     // gmr1_rx.c:534-538
+				r = gmr1_hip_detect_batch_dev(st, 2, ids, nt, sps, t_in_len, tch, d_off2, d_fs2, d_et, d_bt, d_dsid, d_dtoa, d_drv);
+				if (r) return r;
+			}
+			r = gmr1_hip_dkab_demod_batch_dev(st, nt, sps, t_in_len, tch, d_off2, d_fs2, d_pp, nullptr, nullptr, d_krv);
+			if (r) return r;
+			if ((r = sg.fetch())) return r;
 
 
 			// B. the state machine of rx_tch3 (gmr1_rx.c:531-600) and its helpers, chain by chain
@@ -815,23 +767,22 @@ int RxRun::tch3_pass()
 					if (kc) std::memcpy(&keys[(size_t)i * 8], kc + (size_t)chains[j.chain_idx].a * 8, 8);
 					fns[i] = (uint32_t)j.fn;
 				}
-				ABuf d_eb, d_k, d_fn, d_ks, d_fr, d_cv;
-				HIP_TRY(d_eb.alloc(eb.size())); HIP_TRY(d_k.alloc(keys.size())); HIP_TRY(d_fn.alloc((size_t)ns * 4));
-				HIP_TRY(d_ks.alloc((size_t)ns * 208)); HIP_TRY(d_fr.alloc((size_t)ns * 20)); HIP_TRY(d_cv.alloc((size_t)ns * 8));
-				HIP_TRY(hipMemcpyAsync(d_eb.p, eb.data(), eb.size(), hipMemcpyHostToDevice, st));
-				HIP_TRY(hipMemcpyAsync(d_k.p, keys.data(), keys.size(), hipMemcpyHostToDevice, st));
-				HIP_TRY(hipMemcpyAsync(d_fn.p, fns.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st));
-				r = gmr1_hip_a5_batch_dev(st, ns, 1, 208, d_k.as<uint8_t>(), d_fn.as<uint32_t>(), d_ks.as<uint8_t>(), nullptr);
+				const int8_t *d_eb = sg.in(eb.data(), eb.size());
+				const uint8_t *d_k = sg.in(keys.data(), keys.size());
+				const uint32_t *d_fn = sg.in(fns.data(), (size_t)ns);
+				uint8_t *d_ks = sg.dev<uint8_t>((size_t)ns * 208), *d_fr = sg.dev<uint8_t>((size_t)ns * 20);
+				int32_t *d_cv = sg.dev<int32_t>((size_t)ns * 2);
+				if ((r = sg.err())) return r;
+				r = gmr1_hip_a5_batch_dev(st, ns, 1, 208, d_k, d_fn, d_ks, nullptr);
 				if (r) return r;
 				for (int v = 0; v < 2; v++) {
-					r = gmr1_hip_tch3_decode_batch_dev(st, ns, 0, d_eb.as<int8_t>(), v ? d_ks.as<uint8_t>() : nullptr,
-					                                   d_fr.as<uint8_t>(), nullptr, d_cv.as<int32_t>());
+					r = gmr1_hip_tch3_decode_batch_dev(st, ns, 0, d_eb, v ? d_ks : nullptr, d_fr, nullptr, d_cv);
 					if (r) return r;
 					s_fr[v].resize((size_t)ns * 20);
 					s_conv[v].resize((size_t)ns * 2);
-					HIP_TRY(hipMemcpyAsync(s_fr[v].data(), d_fr.p, (size_t)ns * 20, hipMemcpyDeviceToHost, st));
-					HIP_TRY(hipMemcpyAsync(s_conv[v].data(), d_cv.p, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
-					HIP_TRY(hipStreamSynchronize(st));
+					sg.back(s_fr[v].data(), d_fr, (size_t)ns * 20);
+					sg.back(s_conv[v].data(), d_cv, (size_t)ns * 2);
+					if ((r = sg.fetch())) return r;
 				}
 			}
 			if (nf) {
@@ -846,27 +797,25 @@ int RxRun::tch3_pass()
 						fns[(size_t)i * 4 + b] = j.bi_fn[b];
 					}
 				}
-				ABuf d_eb, d_k, d_fn, d_ks, d_l2, d_crc, d_cv;
-				HIP_TRY(d_eb.alloc(eb.size())); HIP_TRY(d_k.alloc(keys.size())); HIP_TRY(d_fn.alloc((size_t)nf * 16));
-				HIP_TRY(d_ks.alloc((size_t)nf * 384)); HIP_TRY(d_l2.alloc((size_t)nf * 10)); HIP_TRY(d_crc.alloc((size_t)nf * 4));
-				HIP_TRY(d_cv.alloc((size_t)nf * 4));
-				HIP_TRY(hipMemcpyAsync(d_eb.p, eb.data(), eb.size(), hipMemcpyHostToDevice, st));
-				HIP_TRY(hipMemcpyAsync(d_k.p, keys.data(), keys.size(), hipMemcpyHostToDevice, st));
-				HIP_TRY(hipMemcpyAsync(d_fn.p, fns.data(), (size_t)nf * 16, hipMemcpyHostToDevice, st));
+				const int8_t *d_eb = sg.in(eb.data(), eb.size());
+				const uint8_t *d_k = sg.in(keys.data(), keys.size());
+				const uint32_t *d_fn = sg.in(fns.data(), (size_t)nf * 4);
+				uint8_t *d_ks = sg.dev<uint8_t>((size_t)nf * 384), *d_l2 = sg.dev<uint8_t>((size_t)nf * 10);
+				int32_t *d_crc = sg.dev<int32_t>((size_t)nf), *d_cv = sg.dev<int32_t>((size_t)nf);
+				if ((r = sg.err())) return r;
 				// 4 x 96 keystream bits per message, one per burst's frame number (gmr1_rx.c:409-412)
-				r = gmr1_hip_a5_batch_dev(st, nf * 4, 1, 96, d_k.as<uint8_t>(), d_fn.as<uint32_t>(), d_ks.as<uint8_t>(), nullptr);
+				r = gmr1_hip_a5_batch_dev(st, nf * 4, 1, 96, d_k, d_fn, d_ks, nullptr);
 				if (r) return r;
 				for (int v = 0; v < 2; v++) {
-					r = gmr1_hip_facch3_decode_batch_dev(st, nf, d_eb.as<int8_t>(), v ? d_ks.as<uint8_t>() : nullptr,
-					                                     d_l2.as<uint8_t>(), nullptr, d_crc.as<int32_t>(), d_cv.as<int32_t>());
+					r = gmr1_hip_facch3_decode_batch_dev(st, nf, d_eb, v ? d_ks : nullptr, d_l2, nullptr, d_crc, d_cv);
 					if (r) return r;
 					f_l2[v].resize((size_t)nf * 10);
 					f_crc[v].resize(nf);
 					f_conv[v].resize(nf);
-					HIP_TRY(hipMemcpyAsync(f_l2[v].data(), d_l2.p, (size_t)nf * 10, hipMemcpyDeviceToHost, st));
-					HIP_TRY(hipMemcpyAsync(f_crc[v].data(), d_crc.p, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
-					HIP_TRY(hipMemcpyAsync(f_conv[v].data(), d_cv.p, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
-					HIP_TRY(hipStreamSynchronize(st));
+					sg.back(f_l2[v].data(), d_l2, (size_t)nf * 10);
+					sg.back(f_crc[v].data(), d_crc, (size_t)nf);
+					sg.back(f_conv[v].data(), d_cv, (size_t)nf);
+					if ((r = sg.fetch())) return r;
 				}
 			}
 
@@ -958,8 +907,7 @@ int RxRun::tch9_pass()
 			// demodulation 682 B per frame, keystreams and decodes at most 662 + 8 + 4 + 658 + 64 B per frame
 			Arena arena;
 			if ((r = arena.init((size_t)n9 * 2300 + 64 * 1024))) return r;
-			g_arena = &arena;
-			struct Reset { ~Reset() { g_arena = nullptr; } } reset;
+			Stage sg(st, &arena);
 			std::vector<uint64_t> off9(n9);
 			std::vector<float> fs9(n9);
 			for (int k = 0; k < n9; k++) {
@@ -968,20 +916,17 @@ int RxRun::tch9_pass()
 				off9[k] = c.base + (uint64_t)((int64_t)x.align + sps * items9[k].tn * 39 - etoa9);
 				fs9[k] = -x.freq_err;
 			}
-			ABuf d_o, d_f, d_eb, d_sid, d_rv;
-			HIP_TRY(d_o.alloc((size_t)n9 * 8)); HIP_TRY(d_f.alloc((size_t)n9 * 4)); HIP_TRY(d_eb.alloc((size_t)n9 * 662));
-			HIP_TRY(d_sid.alloc((size_t)n9 * 4)); HIP_TRY(d_rv.alloc((size_t)n9 * 4));
-			HIP_TRY(hipMemcpyAsync(d_o.p, off9.data(), (size_t)n9 * 8, hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(d_f.p, fs9.data(), (size_t)n9 * 4, hipMemcpyHostToDevice, st));
-			r = demod_dev_energy(st, GMR1_HIP_NT9, n9, sps, in_len9, csd, d_o.as<uint64_t>(), d_f.as<float>(),
-			                     d_eb.as<int8_t>(), 662, d_sid.as<int32_t>(), nullptr, nullptr, d_rv.as<int32_t>());
-			if (r) return r;
 			std::vector<int8_t> h_eb((size_t)n9 * 662);
 			std::vector<int32_t> h_sid(n9), h_rv(n9);
-			HIP_TRY(hipMemcpyAsync(h_eb.data(), d_eb.p, (size_t)n9 * 662, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_sid.data(), d_sid.p, (size_t)n9 * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_rv.data(), d_rv.p, (size_t)n9 * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipStreamSynchronize(st));
+			const uint64_t *d_o = sg.in(off9.data(), (size_t)n9);
+			const float *d_f = sg.in(fs9.data(), (size_t)n9);
+			int8_t *d_eb = sg.out(h_eb.data(), (size_t)n9 * 662);
+			int32_t *d_sid = sg.out(h_sid.data(), (size_t)n9);
+			int32_t *d_rv = sg.out(h_rv.data(), (size_t)n9);
+			if ((r = sg.err())) return r;
+			r = demod_dev_energy(st, GMR1_HIP_NT9, n9, sps, in_len9, csd, d_o, d_f, d_eb, 662, d_sid, nullptr, nullptr, d_rv);
+			if (r) return r;
+			if ((r = sg.fetch())) return r;
 			// classify; TCH9 bursts are laid out run after run (one run per interleaver life)
 			std::vector<int> fj, tj;                 // item indices: FACCH9 jobs, TCH9 jobs (run-major)
 			std::vector<int> run_len;
@@ -1026,48 +971,41 @@ int RxRun::tch9_pass()
 					if (kc) std::memcpy(&keys[(size_t)i * 8], kc + (size_t)c.a * 8, 8);
 					fns[i] = (uint32_t)c.log[items9[k].frame].fn;
 				}
-				ABuf d_e2, d_k, d_fn, d_ks, d_l2f, d_crc, d_cvf, d_l2t, d_cvt;
-				HIP_TRY(d_e2.alloc(eb.size())); HIP_TRY(d_k.alloc(keys.size())); HIP_TRY(d_fn.alloc((size_t)nj * 4));
-				HIP_TRY(d_ks.alloc((size_t)nj * 658));
-				HIP_TRY(d_l2f.alloc((size_t)nf * 38)); HIP_TRY(d_crc.alloc((size_t)nf * 4)); HIP_TRY(d_cvf.alloc((size_t)nf * 4));
-				HIP_TRY(d_l2t.alloc((size_t)nt9 * 60)); HIP_TRY(d_cvt.alloc((size_t)nt9 * 4));
-				HIP_TRY(hipMemcpyAsync(d_e2.p, eb.data(), eb.size(), hipMemcpyHostToDevice, st));
-				HIP_TRY(hipMemcpyAsync(d_k.p, keys.data(), keys.size(), hipMemcpyHostToDevice, st));
-				HIP_TRY(hipMemcpyAsync(d_fn.p, fns.data(), (size_t)nj * 4, hipMemcpyHostToDevice, st));
-				r = gmr1_hip_a5_batch_dev(st, nj, 1, 658, d_k.as<uint8_t>(), d_fn.as<uint32_t>(), d_ks.as<uint8_t>(), nullptr);
-				if (r) return r;
 				std::vector<uint8_t> l2f((size_t)nf * 38), l2t((size_t)nt9 * 60);
 				std::vector<int32_t> crcf(nf), cvf(nf), cvt(nt9);
+				const int8_t *d_e2 = sg.in(eb.data(), eb.size());
+				const uint8_t *d_k = sg.in(keys.data(), keys.size());
+				const uint32_t *d_fn = sg.in(fns.data(), (size_t)nj);
+				uint8_t *d_ks = sg.dev<uint8_t>((size_t)nj * 658);
+				uint8_t *d_l2f = sg.dev<uint8_t>((size_t)nf * 38), *d_l2t = sg.dev<uint8_t>((size_t)nt9 * 60);
+				int32_t *d_crc = sg.dev<int32_t>((size_t)nf), *d_cvf = sg.dev<int32_t>((size_t)nf), *d_cvt = sg.dev<int32_t>((size_t)nt9);
+				if ((r = sg.err())) return r;
+				r = gmr1_hip_a5_batch_dev(st, nj, 1, 658, d_k, d_fn, d_ks, nullptr);
+				if (r) return r;
 				if (nf) {
-					r = gmr1_hip_facch9_decode_batch_dev(st, nf, d_e2.as<int8_t>(), d_ks.as<uint8_t>(), d_l2f.as<uint8_t>(),
-					                                     nullptr, nullptr, d_crc.as<int32_t>(), d_cvf.as<int32_t>());
+					r = gmr1_hip_facch9_decode_batch_dev(st, nf, d_e2, d_ks, d_l2f, nullptr, nullptr, d_crc, d_cvf);
 					if (r) return r;
-					HIP_TRY(hipMemcpyAsync(l2f.data(), d_l2f.p, l2f.size(), hipMemcpyDeviceToHost, st));
-					HIP_TRY(hipMemcpyAsync(crcf.data(), d_crc.p, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
-					HIP_TRY(hipMemcpyAsync(cvf.data(), d_cvf.p, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
+					sg.back(l2f.data(), d_l2f, l2f.size());
+					sg.back(crcf.data(), d_crc, (size_t)nf);
+					sg.back(cvf.data(), d_cvf, (size_t)nf);
+					sg.queue_backs();
 				}
 				std::vector<int32_t> pos((size_t)nt9);       // lives until the synchronisation below
-				{
+				if (nt9) {
 					// all runs in one launch: every burst knows its position in its own run
-					if (nt9) {
-						size_t i = 0;
-						for (int len_run : run_len)
-							for (int q = 0; q < len_run; q++)
-								pos[i++] = q;
-						ABuf d_pos;
-						HIP_TRY(d_pos.alloc((size_t)nt9 * 4));
-						HIP_TRY(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)nt9 * 4, hipMemcpyHostToDevice, st));
-						r = tch9_runs_dev_impl(st, 2 /* GMR1_TCH9_9k6, gmr1_rx.c:333 */, nt9, d_pos.as<int32_t>(),
-						                       d_e2.as<int8_t>() + (size_t)nf * 662, d_ks.as<uint8_t>() + (size_t)nf * 658,
-						                       d_l2t.as<uint8_t>(), d_cvt.as<int32_t>());
-						if (r) return r;
-					}
-					if (nt9) {
-						HIP_TRY(hipMemcpyAsync(l2t.data(), d_l2t.p, l2t.size(), hipMemcpyDeviceToHost, st));
-						HIP_TRY(hipMemcpyAsync(cvt.data(), d_cvt.p, (size_t)nt9 * 4, hipMemcpyDeviceToHost, st));
-					}
+					size_t i = 0;
+					for (int len_run : run_len)
+						for (int q = 0; q < len_run; q++)
+							pos[i++] = q;
+					const int32_t *d_pos = sg.in(pos.data(), (size_t)nt9);
+					if ((r = sg.err())) return r;
+					r = tch9_runs_dev_impl(st, 2 /* GMR1_TCH9_9k6, gmr1_rx.c:333 */, nt9, d_pos, d_e2 + (size_t)nf * 662,
+					                       d_ks + (size_t)nf * 658, d_l2t, d_cvt);
+					if (r) return r;
+					sg.back(l2t.data(), d_l2t, l2t.size());
+					sg.back(cvt.data(), d_cvt, (size_t)nt9);
 				}
-				HIP_TRY(hipStreamSynchronize(st));
+				if ((r = sg.fetch())) return r;
 				// records in frame order per chain: merge the two job lists by item index
 				int a9 = 0, b9 = 0;
 				while (a9 < nf || b9 < nt9) {
@@ -1265,19 +1203,12 @@ int gmr1_hip_rx_run_full(int n_arfcn, int sps, const float *iq, const float *tch
 	for (int i = 0; i < n_arfcn; i++)
 		if (offset[i] + length[i] > iq_len)
 			return fail(-EINVAL, "rx_run: carrier %d runs past the end of iq", i);
-	DBuf d_iq, d_tch, d_csd;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	if (tch) {
-		HIP_TRY(d_tch.alloc(iq_len * 8));
-		HIP_TRY(hipMemcpy(d_tch.p, tch, iq_len * 8, hipMemcpyHostToDevice));
-	}
-	if (csd) {
-		HIP_TRY(d_csd.alloc(iq_len * 8));
-		HIP_TRY(hipMemcpy(d_csd.p, csd, iq_len * 8, hipMemcpyHostToDevice));
-	}
-	return gmr1_hip_rx_run_full_dev(nullptr, n_arfcn, sps, d_iq.as<float>(), tch ? d_tch.as<float>() : nullptr,
-	                                csd ? d_csd.as<float>() : nullptr, offset, length, arfcn, kc, out, max_records,
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const float *d_tch = sg.in(tch, (size_t)iq_len * 2);
+	const float *d_csd = sg.in(csd, (size_t)iq_len * 2);
+	if ((r = sg.err())) return r;
+	return gmr1_hip_rx_run_full_dev(nullptr, n_arfcn, sps, d_iq, d_tch, d_csd, offset, length, arfcn, kc, out, max_records,
 	                                n_records, big_out, max_big, n_big, status, n_chains);
 }
 
@@ -1295,24 +1226,8 @@ int gmr1_hip_rx_run_tch(int n_arfcn, int sps, const float *iq, const float *tch,
                         struct gmr1_hip_rx_record *out, int max_records, int *n_records,
                         int32_t *status, int32_t *n_chains)
 {
-	if (n_records) *n_records = 0;
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if (n_arfcn < 0 || !iq || !offset || !length)
-		return fail(-EINVAL, "rx_run: iq/offset/length are required");
-	for (int i = 0; i < n_arfcn; i++)
-		if (offset[i] + length[i] > iq_len)
-			return fail(-EINVAL, "rx_run: carrier %d runs past the end of iq", i);
-	DBuf d_iq, d_tch;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	if (tch) {
-		HIP_TRY(d_tch.alloc(iq_len * 8));
-		HIP_TRY(hipMemcpy(d_tch.p, tch, iq_len * 8, hipMemcpyHostToDevice));
-	}
-	return gmr1_hip_rx_run_tch_dev(nullptr, n_arfcn, sps, d_iq.as<float>(), tch ? d_tch.as<float>() : nullptr,
-	                               offset, length, arfcn, kc, out, max_records, n_records, status, n_chains);
+	return gmr1_hip_rx_run_full(n_arfcn, sps, iq, tch, nullptr, iq_len, offset, length, arfcn, kc, out, max_records, n_records,
+	                            nullptr, 0, nullptr, status, n_chains);
 }
 
 int gmr1_hip_rx_run(int n_arfcn, int sps, const float *iq, uint64_t iq_len,
@@ -1320,20 +1235,8 @@ int gmr1_hip_rx_run(int n_arfcn, int sps, const float *iq, uint64_t iq_len,
                     struct gmr1_hip_rx_record *out, int max_records, int *n_records,
                     int32_t *status, int32_t *n_chains)
 {
-	if (n_records) *n_records = 0;
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if (n_arfcn < 0 || !iq || !offset || !length)
-		return fail(-EINVAL, "rx_run: iq/offset/length are required");
-	for (int i = 0; i < n_arfcn; i++)
-		if (offset[i] + length[i] > iq_len)
-			return fail(-EINVAL, "rx_run: carrier %d runs past the end of iq", i);
-	DBuf d_iq;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	return gmr1_hip_rx_run_dev(nullptr, n_arfcn, sps, d_iq.as<float>(), offset, length, arfcn,
-	                           out, max_records, n_records, status, n_chains);
+	return gmr1_hip_rx_run_tch(n_arfcn, sps, iq, nullptr, iq_len, offset, length, arfcn, nullptr, out, max_records, n_records,
+	                           status, n_chains);
 }
 
 // What gmr1_gsmtap_makemsg (reference src/gsmtap.c:43-71) puts on the wire for one decoded frame:

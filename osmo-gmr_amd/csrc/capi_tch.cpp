@@ -53,30 +53,19 @@ int gmr1_hip_dkab_demod_batch(int n, int sps, int in_len,
 	if (n <= 0) return 0;
 	if (!iq || !offset || !p || !rv)
 		return fail(-EINVAL, "dkab: iq/offset/p/rv are required");
-	for (int i = 0; i < n; i++)
-		if (offset[i] + (uint64_t)in_len > iq_len)
-			return fail(-EINVAL, "burst %d runs past the end of iq", i);
-	DBuf d_iq, d_off, d_fs, d_p, d_eb, d_toa, d_rv;
-	HIP_TRY(d_iq.alloc(iq_len * 8));
-	HIP_TRY(d_off.alloc((size_t)n * 8));
-	HIP_TRY(d_p.alloc((size_t)n * 4));
-	HIP_TRY(d_eb.alloc((size_t)n * 8));
-	HIP_TRY(d_toa.alloc((size_t)n * 4));
-	HIP_TRY(d_rv.alloc((size_t)n * 4));
-	if (freq_shift) HIP_TRY(d_fs.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_iq.p, iq, iq_len * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_off.p, offset, (size_t)n * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_p.p, p, (size_t)n * 4, hipMemcpyHostToDevice));
-	if (freq_shift) HIP_TRY(hipMemcpy(d_fs.p, freq_shift, (size_t)n * 4, hipMemcpyHostToDevice));
-	r = gmr1_hip_dkab_demod_batch_dev(nullptr, n, sps, in_len, d_iq.as<float>(), d_off.as<uint64_t>(),
-	                                  freq_shift ? d_fs.as<float>() : nullptr, d_p.as<int32_t>(),
-	                                  d_eb.as<int8_t>(), d_toa.as<float>(), d_rv.as<int32_t>());
+	if ((r = bursts_fit(n, offset, in_len, iq_len))) return r;
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const uint64_t *d_off = sg.in(offset, (size_t)n);
+	const int32_t *d_p = sg.in(p, (size_t)n);
+	const float *d_fs = sg.in(freq_shift, (size_t)n);
+	int32_t *d_rv = sg.out(rv, (size_t)n);
+	int8_t *d_eb = sg.out_always(ebits, (size_t)n * 8);
+	float *d_toa = sg.out_always(toa, (size_t)n);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_dkab_demod_batch_dev(nullptr, n, sps, in_len, d_iq, d_off, d_fs, d_p, d_eb, d_toa, d_rv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(rv, d_rv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (ebits) HIP_TRY(hipMemcpy(ebits, d_eb.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-	if (toa) HIP_TRY(hipMemcpy(toa, d_toa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int gmr1_dkab_demod(struct osmo_cxvec *burst_in, int sps, float freq_shift, int p, sbit_t *ebits, float *toa_p)
@@ -119,20 +108,17 @@ int gmr1_hip_a5_batch(int n, int alg, int nbits, const uint8_t *keys, const uint
 	if (n <= 0 || nbits <= 0) return 0;
 	if (alg == 1 && (!keys || !fn))
 		return fail(-EINVAL, "a5: keys / fn are required for A5/1");
-	DBuf d_k, d_fn, d_dl, d_ul;
+	Stage sg;
 	const size_t nb = (size_t)n * nbits;
-	if (keys) { HIP_TRY(d_k.alloc((size_t)n * 8)); HIP_TRY(hipMemcpy(d_k.p, keys, (size_t)n * 8, hipMemcpyHostToDevice)); }
-	if (fn) { HIP_TRY(d_fn.alloc((size_t)n * 4)); HIP_TRY(hipMemcpy(d_fn.p, fn, (size_t)n * 4, hipMemcpyHostToDevice)); }
+	const uint8_t *d_k = sg.in(keys, (size_t)n * 8);
+	const uint32_t *d_fn = sg.in(fn, (size_t)n);
 	// the buffers start out as the caller's, so that "unsupported n" leaves them untouched
-	if (dl) { HIP_TRY(d_dl.alloc(nb)); HIP_TRY(hipMemcpy(d_dl.p, dl, nb, hipMemcpyHostToDevice)); }
-	if (ul) { HIP_TRY(d_ul.alloc(nb)); HIP_TRY(hipMemcpy(d_ul.p, ul, nb, hipMemcpyHostToDevice)); }
-	r = gmr1_hip_a5_batch_dev(nullptr, n, alg, nbits, keys ? d_k.as<uint8_t>() : nullptr, fn ? d_fn.as<uint32_t>() : nullptr,
-	                          dl ? d_dl.as<uint8_t>() : nullptr, ul ? d_ul.as<uint8_t>() : nullptr);
+	uint8_t *d_dl = sg.inout(dl, nb);
+	uint8_t *d_ul = sg.inout(ul, nb);
+	if ((r = sg.err())) return r;
+	r = gmr1_hip_a5_batch_dev(nullptr, n, alg, nbits, d_k, d_fn, d_dl, d_ul);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	if (dl) HIP_TRY(hipMemcpy(dl, d_dl.p, nb, hipMemcpyDeviceToHost));
-	if (ul) HIP_TRY(hipMemcpy(ul, d_ul.p, nb, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 void gmr1_a5(int n, uint8_t *key, uint32_t fn, int nbits, ubit_t *dl, ubit_t *ul)

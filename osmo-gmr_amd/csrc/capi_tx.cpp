@@ -543,23 +543,17 @@ int encode_host(int id, int n, int seq_len, const uint8_t *in0, const uint8_t *i
 	if (r) return r;
 	r = check_args(*hp, n, seq_len, in0, in1, aux0, aux1, ebits, what);
 	if (r) return r;
-	struct Up { const uint8_t *h; size_t per; DBuf d; };
-	Up up[5] = {{in0, (size_t)hp->n_in0, {}}, {in1, (size_t)hp->n_in1, {}}, {aux0, (size_t)hp->n_aux0, {}},
-	            {aux1, (size_t)hp->n_aux1, {}}, {ciph, (size_t)hp->n_ciph, {}}};
-	for (Up &x : up) {
-		if (!x.h || !x.per)
-			continue;
-		HIP_TRY(x.d.alloc(x.per * (size_t)n));
-		HIP_TRY(hipMemcpy(x.d.p, x.h, x.per * (size_t)n, hipMemcpyHostToDevice));
-	}
-	DBuf d_e;
-	HIP_TRY(d_e.alloc((size_t)hp->n_out * (size_t)n));
-	r = encode_dev(nullptr, id, n, seq_len, up[0].d.as<uint8_t>(), up[1].d.as<uint8_t>(), up[2].d.as<uint8_t>(),
-	               up[3].d.as<uint8_t>(), up[4].d.as<uint8_t>(), d_e.as<uint8_t>(), what);
+	Stage sg;
+	const uint8_t *h[5] = {in0, in1, aux0, aux1, ciph};
+	const int per[5] = {hp->n_in0, hp->n_in1, hp->n_aux0, hp->n_aux1, hp->n_ciph};
+	const uint8_t *d[5];
+	for (int i = 0; i < 5; i++)
+		d[i] = per[i] ? sg.in(h[i], (size_t)per[i] * (size_t)n) : nullptr;
+	uint8_t *d_e = sg.out(ebits, (size_t)hp->n_out * (size_t)n);
+	if ((r = sg.err())) return r;
+	r = encode_dev(nullptr, id, n, seq_len, d[0], d[1], d[2], d[3], d[4], d_e, what);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(ebits, d_e.p, (size_t)hp->n_out * (size_t)n, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int tch9_plan(int mode) { return mode == GMR1_TCH9_2k4 ? kPlTch9_2k4 : mode == GMR1_TCH9_4k8 ? kPlTch9_4k8 : mode == GMR1_TCH9_9k6 ? kPlTch9_9k6 : -1; }
@@ -610,14 +604,15 @@ int mod_dev(hipStream_t st, const gmr1_hip_burst_flat &f, int sync_id, int n, co
 		const float ph = f.rotation * (float)i;
 		rot[i] = make_float2(cosf(ph), sinf(ph));
 	}
-	DBuf d_p, d_r;
-	HIP_TRY(d_p.alloc(plan.size() * 2));
-	HIP_TRY(d_r.alloc(rot.size() * 8));
-	HIP_TRY(hipMemcpyAsync(d_p.p, plan.data(), plan.size() * 2, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(d_r.p, rot.data(), rot.size() * 8, hipMemcpyHostToDevice, st));
+	Stage sg(st);
+	int16_t *d_p = sg.dev<int16_t>(plan.size());
+	float2 *d_r = sg.dev<float2>(rot.size());
+	if ((r = sg.err())) return r;
+	HIP_TRY(hipMemcpyAsync(d_p, plan.data(), plan.size() * 2, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_r, rot.data(), rot.size() * 8, hipMemcpyHostToDevice, st));
 	ModArgs a;
 	a.n = n; a.len = f.len; a.nbits = f.nbits; a.n_ebits = f.ebits; a.rotation = f.rotation;
-	a.plan = d_p.as<int16_t>(); a.rot = d_r.as<float2>(); a.ebits = ebits; a.out = reinterpret_cast<float2 *>(out);
+	a.plan = d_p; a.rot = d_r; a.ebits = ebits; a.out = reinterpret_cast<float2 *>(out);
 	HIP_TRY(launch_mod(a, st));
 	HIP_TRY(hipStreamSynchronize(st));         // the plan buffer is released on return
 	return 0;
@@ -632,14 +627,13 @@ int mod_host(const gmr1_hip_burst_flat &f, int sync_id, int n, const uint8_t *eb
 		return fail(-EINVAL, "mod: ebits / out are required");
 	if (n == 0)
 		return 0;
-	DBuf d_e, d_o;
-	HIP_TRY(d_e.alloc((size_t)n * f.ebits));
-	HIP_TRY(d_o.alloc((size_t)n * f.len * 8));
-	HIP_TRY(hipMemcpy(d_e.p, ebits, (size_t)n * f.ebits, hipMemcpyHostToDevice));
-	r = mod_dev(nullptr, f, sync_id, n, d_e.as<uint8_t>(), d_o.as<float>());
+	Stage sg;
+	const uint8_t *d_e = sg.in(ebits, (size_t)n * f.ebits);
+	float *d_o = sg.out(out, (size_t)n * f.len * 2);
+	if ((r = sg.err())) return r;
+	r = mod_dev(nullptr, f, sync_id, n, d_e, d_o);
 	if (r) return r;
-	HIP_TRY(hipMemcpy(out, d_o.p, (size_t)n * f.len * 8, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int builtin_flat(int burst_id, gmr1_hip_burst_flat *f)
@@ -662,27 +656,17 @@ int bitmap_host(int n_in, int n_out, int soft, const void *in, const std::vector
 		return fail(-EINVAL, "%s: bad argument", what);
 	if (n_out == 0)
 		return 0;
-	DBuf d_in, d_out, d_perm, d_mask;
-	HIP_TRY(d_in.alloc((size_t)n_in));
-	HIP_TRY(d_out.alloc((size_t)n_out));
-	HIP_TRY(hipMemcpy(d_in.p, in, (size_t)n_in, hipMemcpyHostToDevice));
+	Stage sg;
 	BitMapArgs a;
 	std::memset(&a, 0, sizeof(a));
-	a.n = n_out; a.soft = soft; a.in = d_in.as<uint8_t>(); a.out = d_out.as<uint8_t>();
-	if (perm) {
-		HIP_TRY(d_perm.alloc((size_t)n_out * 4));
-		HIP_TRY(hipMemcpy(d_perm.p, perm->data(), (size_t)n_out * 4, hipMemcpyHostToDevice));
-		a.perm = d_perm.as<int32_t>();
-	}
-	if (mask) {
-		HIP_TRY(d_mask.alloc((size_t)n_out));
-		HIP_TRY(hipMemcpy(d_mask.p, mask->data(), (size_t)n_out, hipMemcpyHostToDevice));
-		a.mask = d_mask.as<uint8_t>();
-	}
+	a.n = n_out; a.soft = soft;
+	a.in = sg.in(static_cast<const uint8_t *>(in), (size_t)n_in);
+	a.out = sg.out(static_cast<uint8_t *>(out), (size_t)n_out);
+	a.perm = perm ? sg.in(perm->data(), (size_t)n_out) : nullptr;
+	a.mask = mask ? sg.in(mask->data(), (size_t)n_out) : nullptr;
+	if ((r = sg.err())) return r;
 	HIP_TRY(launch_bitmap(a, nullptr));
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n_out, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 std::vector<uint8_t> scramble_mask(int len)         // scramb.c:39-52: 15-bit LFSR, seed 0x4d4b

@@ -49,19 +49,15 @@ int xch_host(int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *con
 	if (n <= 0) return n < 0 ? fail(-EINVAL, "xch_dc12: n < 0") : 0;
 	if (!ebits || !l2 || !crc)
 		return fail(-EINVAL, "xch_dc12: ebits / l2 / crc are required");
-	DBuf d_e, d_l2, d_crc, d_cv;
-	HIP_TRY(d_e.alloc((size_t)n * 432));
-	HIP_TRY(d_l2.alloc((size_t)n * 24));
-	HIP_TRY(d_crc.alloc((size_t)n * 4));
-	HIP_TRY(d_cv.alloc((size_t)n * 4));
-	HIP_TRY(hipMemcpy(d_e.p, ebits, (size_t)n * 432, hipMemcpyHostToDevice));
-	r = xch_dev(nullptr, n, d_e.as<int8_t>(), d_l2.as<uint8_t>(), d_crc.as<int32_t>(), d_cv.as<int32_t>());
+	Stage sg;
+	const int8_t *d_e = sg.in(ebits, (size_t)n * 432);
+	uint8_t *d_l2 = sg.out(l2, (size_t)n * 24);
+	int32_t *d_crc = sg.out(crc, (size_t)n);
+	int32_t *d_cv = sg.out_always(conv, (size_t)n);
+	if ((r = sg.err())) return r;
+	r = xch_dev(nullptr, n, d_e, d_l2, d_crc, d_cv);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(l2, d_l2.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(crc, d_crc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (conv) HIP_TRY(hipMemcpy(conv, d_cv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 int rach_host(int n, const int8_t *ebits, const uint8_t *sb_mask, uint8_t *rach, int32_t *rv, int32_t *conv,
@@ -73,24 +69,17 @@ int rach_host(int n, const int8_t *ebits, const uint8_t *sb_mask, uint8_t *rach,
 	if (n <= 0) return n < 0 ? fail(-EINVAL, "rach: n < 0") : 0;
 	if (!ebits || !sb_mask || !rach || !rv)
 		return fail(-EINVAL, "rach: ebits / sb_mask / rach / rv are required");
-	DBuf d_e, d_m, d_r, d_rv, d_cv, d_crc;
-	HIP_TRY(d_e.alloc((size_t)n * 494));
-	HIP_TRY(d_m.alloc((size_t)n));
-	HIP_TRY(d_r.alloc((size_t)n * 18));
-	HIP_TRY(d_rv.alloc((size_t)n * 4));
-	HIP_TRY(d_cv.alloc((size_t)n * 4));
-	HIP_TRY(d_crc.alloc((size_t)n * 8));
-	HIP_TRY(hipMemcpy(d_e.p, ebits, (size_t)n * 494, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_m.p, sb_mask, (size_t)n, hipMemcpyHostToDevice));
-	r = rach_dev(nullptr, n, d_e.as<int8_t>(), d_m.as<uint8_t>(), d_r.as<uint8_t>(), d_rv.as<int32_t>(),
-	             d_cv.as<int32_t>(), d_crc.as<int32_t>());
+	Stage sg;
+	const int8_t *d_e = sg.in(ebits, (size_t)n * 494);
+	const uint8_t *d_m = sg.in(sb_mask, (size_t)n);
+	uint8_t *d_r = sg.out(rach, (size_t)n * 18);
+	int32_t *d_rv = sg.out(rv, (size_t)n);
+	int32_t *d_cv = sg.out_always(conv, (size_t)n);
+	int32_t *d_crc = sg.out_always(crc, (size_t)n * 2);
+	if ((r = sg.err())) return r;
+	r = rach_dev(nullptr, n, d_e, d_m, d_r, d_rv, d_cv, d_crc);
 	if (r) return r;
-	HIP_TRY(hipStreamSynchronize(nullptr));
-	HIP_TRY(hipMemcpy(rach, d_r.p, (size_t)n * 18, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(rv, d_rv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (conv) HIP_TRY(hipMemcpy(conv, d_cv.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-	if (crc) HIP_TRY(hipMemcpy(crc, d_crc.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-	return 0;
+	return sg.fetch();
 }
 
 }  // namespace
