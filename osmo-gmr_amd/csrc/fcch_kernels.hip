@@ -1166,7 +1166,9 @@ __global__ __launch_bounds__(64 * kFineWaves) void k_fcch_fine(FcchFineArgs a, A
 			const float chirp_rate = (2.0f * c_fcch.freq[tab] * 23400.0f * 23400.0f) / (float)(N * 1000);
 			const float toa_ms = ((pu - pd) / 2.0f) / chirp_rate;
 			const float toa_samples = (toa_ms * 23400.0f * (float)sps) / 1000.0f;
-			const int toa = (int)round((double)toa_samples);
+			// a window without any deviation (all zero, constant) ends in 0 / 0: the reference's (int)round(NaN) is the
+			// x86-64 conversion's "integer indefinite" INT_MIN, and that is what the oracle pins; the GPU's gives 0
+			const int toa = toa_samples != toa_samples ? (int)0x80000000 : (int)round((double)toa_samples);
 			const float fe = (2.0f * kPif * ferr_hz) / 23400.0f;
 			a.toa[b] = toa;
 			if (tl.step == 2)

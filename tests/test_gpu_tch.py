@@ -10,22 +10,22 @@ pytestmark = pytest.mark.gpu
 SPS = 4
 
 
-def _dkab_windows(pkg, n, seed, esn0_db=20.0, win=6, p_max=40):
+def _dkab_windows(pkg, n, seed, esn0_db=20.0, win=6, p_max=40, sps=SPS):
     synth = importlib.import_module(pkg.__name__ + ".synth")
     rng = np.random.default_rng(seed)
-    in_len = 117 * SPS + win
+    in_len = 117 * sps + win
     out = np.zeros((n, in_len), np.complex64)
     ps = rng.integers(0, p_max, n).astype(np.int32)
     bits = rng.integers(0, 2, size=(n, 8), dtype=np.uint8)
     present = rng.random(n) < 0.8
     sigma = np.sqrt(10.0 ** (-esn0_db / 10.0) / 2.0)
     for i in range(n):
-        x = (rng.standard_normal((in_len + 40 * SPS, 2)) * sigma).astype(np.float32).view(np.complex64).reshape(-1)
+        x = (rng.standard_normal((in_len + 40 * sps, 2)) * sigma).astype(np.float32).view(np.complex64).reshape(-1)
         if present[i]:
-            body = synth.shape_bursts(synth.dkab_symbols(bits[i:i + 1], int(ps[i])), SPS, float(rng.random()), 5)[0]
+            body = synth.shape_bursts(synth.dkab_symbols(bits[i:i + 1], int(ps[i])), sps, float(rng.random()), 5)[0]
             x[:body.size] += body * np.exp(1j * rng.uniform(0, 2 * np.pi))
         d = int(rng.integers(0, win + 1))
-        out[i] = x[5 * SPS - d:5 * SPS - d + in_len]
+        out[i] = x[5 * sps - d:5 * sps - d + in_len]
     return out, ps, bits, present
 
 
@@ -68,9 +68,19 @@ def test_a5_keystream_bit_exact(gpu_api, orc, pkg):
     fn = rng.integers(0, 1 << 19, n).astype(np.uint32)
     fn[:4] = [0, 1, 0x7FFFF, 0xFFFFFFFF]
     dl, ul = gpu_api.a5_batch(1, keys, fn, 208, want_ul=True)
-    for i in range(0, n, 7):
+    for i in range(n):
         odl, oul = orc.a5(1, keys[i], int(fn[i]), 208)
         assert np.array_equal(dl[i], odl) and np.array_equal(ul[i], oul), i
+    # a single bit and an odd length: the rows of the batch are nbits apart, whatever nbits is
+    for nbits in (1, 77):
+        dl2, ul2 = gpu_api.a5_batch(1, keys, fn, nbits, want_ul=True)
+        assert dl2.shape == (n, nbits)
+        for i in range(n):
+            odl, oul = orc.a5(1, keys[i], int(fn[i]), nbits)
+            assert np.array_equal(dl2[i], odl) and np.array_equal(ul2[i], oul), (nbits, i)
+        assert np.array_equal(dl2, dl[:, :nbits])       # (the uplink block follows the downlink's nbits: no prefix of ul)
+        d1, u1 = gpu_api.a5(1, keys[5], int(fn[5]), nbits)
+        assert np.array_equal(d1, dl2[5]) and np.array_equal(u1, ul2[5])
     # second, independent implementation (numpy) over the whole batch
     k0 = keys[0]
     assert np.array_equal(gpu_api.a5_batch(1, k0, fn, 96), synth.a5_1(k0, fn.astype(np.int64) & 0xFFFFFFFF, 96))
