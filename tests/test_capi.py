@@ -28,6 +28,61 @@ def _declared_symbols():
     return funcs, data
 
 
+def _declared_prototypes():
+    """name -> (return type, [parameter declarations]) of every function the headers declare"""
+    protos = {}
+    for h in glob.glob(os.path.join(ROOT, "include", "**", "*.h"), recursive=True):
+        txt = open(h).read()
+        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+        txt = re.sub(r"//[^\n]*", "", txt)
+        txt = re.sub(r"(?m)^\s*#.*$", "", txt)
+        for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(gmr1_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+            ret, name, params = (" ".join(x.split()) for x in m.groups())
+            protos[name] = (ret, [] if params == "void" else [q.strip() for q in params.split(",")])
+    return protos
+
+
+# C class of a parameter or return value -> the type its row of api.SIGNATURES must carry.  Beyond the scalar classes:
+# an enum is an int in this ABI, a function returning `const char *` hands back a C string, and void returns nothing.
+_TABLE_TYPE = {"int": C.c_int, "int32_t": C.c_int, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+               "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "void": None}
+
+
+def _table_type(decl, is_return=False):
+    decl = decl.replace("const ", "").strip()
+    if "*" in decl or "[" in decl:
+        return C.c_char_p if is_return and decl.startswith("char") else C.c_void_p
+    if not is_return:
+        decl = re.sub(r"\s*\w+$", "", decl)          # drop the parameter's name
+    return C.c_int if decl.startswith("enum ") else _TABLE_TYPE[decl]
+
+
+def test_signature_table_matches_the_headers(pkg):
+    """Every row of api.SIGNATURES against the declaration it mirrors: as many parameters, each of the type its C class
+    asks for, and the same return type.  (The set of names is test_library_exports_every_declared_symbol's.)"""
+    protos = _declared_prototypes()
+    funcs, _ = _declared_symbols()
+    assert set(protos) == funcs                        # the parser saw every declaration the name search sees
+    wrong = []
+    for name, (ret, params) in sorted(protos.items()):
+        if name in PROGRAM_SUPPLIED:
+            continue
+        want = (_table_type(ret, True), *[_table_type(q) for q in params])
+        if tuple(pkg.api.SIGNATURES[name]) != want:
+            wrong.append((name, ret, params))
+    assert not wrong, wrong
+
+
+def test_typed_prototypes_leave_the_shared_handle_alone(pkg):
+    """api._fn() makes function objects of its own: what load() returns keeps ctypes' defaults for raw callers."""
+    lib = pkg.api.load()
+    f = pkg.api._fn("gmr1_hip_burst_info")
+    assert f is pkg.api._fn("gmr1_hip_burst_info") and f is not lib.gmr1_hip_burst_info
+    assert tuple(f.argtypes) == (C.c_int, C.c_void_p) and f.restype is C.c_int
+    for name in pkg.api.EXPORTED_FUNCTIONS:
+        assert getattr(lib, name).argtypes is None, name
+
+
 def test_library_exports_every_declared_symbol(pkg):
     lib = pkg.api.load()
     funcs, data = _declared_symbols()
@@ -122,6 +177,101 @@ def test_library_covers_what_gmr1_rx_links_against(pkg):
     assert used == set(GMR1_RX_LINKS)
 
 
+_c64 = lambda n: np.zeros(n, np.complex64)
+_u8 = lambda *shape: np.zeros(shape, np.uint8)
+_i8 = lambda *shape: np.zeros(shape, np.int8)
+_NULL_HANDLE = dict(_handle=C.c_void_p(), _n_sel=1)
+
+# what each call gives without a GPU, recorded from api.py as it was before its calls went through typed prototypes
+_NO_GPU_RAISES = {
+    -19: [
+        lambda a: a.init(0),
+        lambda a: a.clock_probe_dev(0),
+        lambda a: a.demod_batch("bcch", _c64(1016), [0], 1016),
+        lambda a: a.demod_batch("bcch", _c64(1016), [0], 1016, freq_shift=[0.0], want_ssyms=False),
+        lambda a: a.demod_taps("bcch", _c64(1016)),
+        lambda a: a.ccch_decode_batch(_i8(1, 432)),
+        lambda a: a.rx_bcch_ccch_batch(_c64(1016), [0], [0], freq_shift=[0.0], want_ebits=False, want_ssyms=False),
+        lambda a: a.fcch_rough_batch(_c64(2048), [0], 2048),
+        lambda a: a.fcch_fine_batch(_c64(2048), [0], freq_shift=[0.0]),
+        lambda a: a.fcch_snr_batch(_c64(2048), [0]),
+        lambda a: a.fcch_rough_multi_batch(_c64(2048), [0], 2048),
+        lambda a: a.facch3_decode_batch(_i8(1, 416)),
+        lambda a: a.facch3_decode_batch(_i8(1, 416), ciph=_u8(1, 384)),
+        lambda a: a.tch3_decode_batch(_i8(1, 212), ciph=_u8(1, 208)),
+        lambda a: a.tch3_rx_batch(_c64(474), [0], 474, freq_shift=[0.0], ciph=_u8(1, 208), want_ebits=False),
+        lambda a: a.detect_batch(["nt3_speech", "nt3_facch"], _c64(474), [0], 474),
+        lambda a: a.detect_batch([4, 5], _c64(474), [0], 474, freq_shift=[0.0], e_toa=1.0),
+        lambda a: a.mod_order_batch(_c64(474), [0], 474),
+        lambda a: a.rx_run(_c64(4096), [0], [4096], max_records=4),
+        lambda a: a.rx_run(_c64(4096), [0], [4096], arfcn=[7], max_records=4),
+        lambda a: a.rx_run_tch(_c64(4096), _c64(4096), [0], [4096], kc=_u8(8), max_records=4),
+        lambda a: a.rx_run_tch(_c64(4096), None, [0], [4096], max_records=4),
+        lambda a: a.rx_run_full(_c64(4096), _c64(4096), None, [0], [4096], kc=_u8(8), max_records=4, max_big=4),
+        lambda a: a.dkab_demod_batch(_c64(474), [0], 474, 0, freq_shift=0.0),
+        lambda a: a.dkab_demod(_c64(474)),
+        lambda a: a.a5_batch(1, _u8(8), 0, 208),
+        lambda a: a.a5_batch(1, _u8(8), 0, 208, want_ul=True),
+        lambda a: a.channelize_plan(2e6, 4, 4096),
+        lambda a: a.channelize(_c64(4096), 2e6, [0]),
+        lambda a: a.ddc_plan(2e6, 4, 4096),
+        lambda a: a.ddc(_c64(4096), 2e6, [0.0]),
+        lambda a: a.facch9_decode_batch(_i8(1, 662), ciph=_u8(1, 658)),
+        lambda a: a.facch9_decode(_i8(662)),
+        lambda a: a.rach_decode(_i8(494), 0),
+        lambda a: a.tch9_decode_batch(_i8(3, 662), 0, 3),
+        lambda a: a.ccch_encode_batch(_u8(1, 24)),
+        lambda a: a.xch_dc12_encode_batch(_u8(1, 24)),
+        lambda a: a.facch3_encode_batch(_u8(1, 10), _u8(1, 32)),
+        lambda a: a.tch3_encode_batch(_u8(1, 2, 10), _u8(1, 4), ciph=_u8(1, 208)),
+        lambda a: a.facch9_encode_batch(_u8(1, 38), _u8(1, 10), _u8(1, 4)),
+        lambda a: a.rach_encode_batch(_u8(1, 18), [0]),
+        lambda a: a.encode_single("xch_dc12", _u8(24)),
+        lambda a: a.codec_decode_batch(_u8(1, 1, 10)),
+        lambda a: a.codec_init_dev(0, 1, 0),
+        lambda a: a.codec_decode_batch_dev(0, 1, 1, 0, 0, 0, 0),
+        lambda a: a.ChanStream(2e6, [0]),
+        lambda a: a.ChanStream.direct(2e6, [0.0]),
+        lambda a: a.RxStream(1),
+        lambda a: a.RxStream(1, arfcn=[7]),
+        lambda a: a.ChanStream(None, None, **_NULL_HANDLE).out_len(16),
+        lambda a: a.ChanStream(None, None, **_NULL_HANDLE).push(_c64(16)),
+        lambda a: a.ChanStream(None, None, **_NULL_HANDLE).push_dev(0, 0, 16, 0, 16),
+    ],
+    # the _dev entries, given null addresses: refused as invalid arguments before anything is touched
+    -22: [
+        lambda a: a.rx_bcch_ccch_batch_dev(0, 1, 4, *[0] * 12),
+        lambda a: a.rx_bcch_ccch_batch_planar_dev(0, 1, 4, 0, 1024, *[None] * 11),
+        lambda a: a.iq_to_planar_dev(0, 4, 1024, 0, 0, 256),
+        lambda a: a.fcch_rough_batch_dev(0, "fcch", 1, 4, 2048, 0, 0, 0, 0, 0),
+        lambda a: a.rx_run_dev(0, 0, [0], [4096], max_records=4),
+        lambda a: a.rx_run_dev(0, 0, [0], [4096], arfcn=[7], out=np.zeros(4, a.RX_RECORD)),
+        lambda a: a.rx_run_dev_prepared(0, 0, [0], [4096], np.zeros(4, a.RX_RECORD))(),
+        lambda a: a.rx_run_dev_raw(0, 0, [0], [4096], 0, 0),
+        lambda a: a.ddc_dev(0, 0, 4096, 2e6, [0.0], 0, 4096),
+        lambda a: a.channelize_dev(0, 0, 4096, 2e6, [0], 0, 4096),
+        lambda a: a.channelize_planar_dev(0, 0, 4096, 2e6, [0], 0, 4096, 1024),
+    ],
+}
+_NO_GPU_RETURNS = {
+    -19: [
+        lambda a: a.pi4cxpsk_demod("bcch", _c64(1016))["rv"],
+        lambda a: a.pi4cxpsk_demod(a.CallerBurst("dc6"), _c64(976))["rv"],
+        lambda a: a.ccch_decode(_i8(432))[1],
+        lambda a: a.fcch_rough(_c64(2048))[0],
+        lambda a: a.fcch_rough_multi(_c64(2048))[0],
+        lambda a: a.facch3_decode(_i8(416))[2],
+        lambda a: a.pi4cxpsk_detect(["nt3_speech", a.CallerBurst("nt3_facch")], 0.0, _c64(474))["rv"],
+        lambda a: a.pi4cxpsk_mod_order(_c64(474)),
+    ],
+    -22: [lambda a: a.fcch_fine(_c64(2048))[0], lambda a: a.fcch_snr(_c64(2048))[0]],
+}
+_NO_GPU_ENCODE_SINGLE = [
+    ("ccch", (_u8(24),)), ("facch3", (_u8(10), _u8(32), None)), ("tch3", (_u8(10), _u8(10), _u8(4), None, 0)),
+    ("facch9", (_u8(38), _u8(10), _u8(4), None)), ("rach", (_u8(18), 0)),
+]
+
+
 def test_no_cpu_fallback(pkg):
     """Without a usable GPU every compute entry point fails loudly (-ENODEV)."""
     import torch
@@ -155,6 +305,41 @@ def test_no_cpu_fallback(pkg):
         pkg.api.encode_single("bcch", np.zeros(24, np.uint8))          # void call: bits_e untouched, error recorded
     rc, _ = pkg.api.pi4cxpsk_mod("bcch", np.zeros(424, np.uint8))
     assert rc == -19
+    # ... and so does every other wrapper and handle class of api.py, at the smallest input its own checks accept: what
+    # comes back is what the library answers (-ENODEV; -EINVAL for the null addresses the _dev entries are given here, which
+    # they refuse before anything else), never a ctypes.ArgumentError or TypeError from the marshalling
+    api = pkg.api
+    for code, calls in _NO_GPU_RAISES.items():
+        for i, call in enumerate(calls):
+            with pytest.raises(api.Gmr1HipError, match=" failed with %d: " % code):
+                call(api)
+                pytest.fail("no error from call %d of _NO_GPU_RAISES[%d]" % (i, code))
+    for code, calls in _NO_GPU_RETURNS.items():
+        assert [call(api) for call in calls] == [code] * len(calls)
+    for chain, args in _NO_GPU_ENCODE_SINGLE:
+        with pytest.raises(api.Gmr1HipError, match="gmr1_%s_encode: no HIP device" % chain):
+            api.encode_single(chain, *args)
+    # the reference's void calls have no code to return: the outputs keep their fill, the error is recorded
+    for out in (*api.a5(1, _u8(8), 0, 8), api.scramble_sbit(_i8(8)), api.scramble_ubit(_u8(8)), api.interleave_intra(_u8(8), 1),
+                api.interleave_intra(_u8(8), 1, inverse=True), api.InterBurstInterleaver().interleave(_u8(648)),
+                api.InterBurstInterleaver().deinterleave(_u8(648))):
+        assert len(set(out.tolist())) == 1 and out[0] in (0xEE, 77)
+    assert [int(v) for v in api.tch3_decode(_i8(212))[3:]] == [0, 0]
+    l2, sa, stt, conv = api.Tch9Channel(0).decode(_i8(662))
+    assert not l2.any() and conv == 0
+    with pytest.raises(api.Gmr1HipError, match="gmr1_tch9_encode: no HIP device"):
+        api.Tch9Encoder(0).encode(_u8(18), _u8(10), _u8(4))
+    assert b"no HIP device" in api.load().gmr1_hip_last_error()
+    assert sorted(api.rx_run_last_timing()) == ["acquisition_ms", "chain_ms", "handback_ms", "host_ms", "traffic_passes_ms"]
+    # the handle classes: the interleaver objects are host memory (made above); the rest refuse at creation
+    for cls in (api.ChanStream, api.RxStream, api.Tch9Channel, api.Tch9Encoder, api.InterBurstInterleaver, api.Codec, api.Shard):
+        assert all(callable(getattr(cls, m)) for m in ("close", "__enter__", "__exit__", "__del__")), cls
+    with api.Tch9Channel(0) as ch:
+        assert ch.il.bits_cpp
+    assert not ch.il.bits_cpp
+    ch.close()                                        # a second close is a no-op
+    with pytest.raises(api.Gmr1HipError, match="gmr1_codec_alloc returned NULL: no HIP device"):
+        api.Codec()
 
 
 def test_product_does_not_reference_oracle():
