@@ -1,6 +1,6 @@
 // capi.cpp -- the C-ABI shim: reference-compatible per-burst calls and the
 // batched entry points of include/gmr1_hip.h.  Host code only; every compute
-// step is a HIP kernel (rx_kernels.hip).  There is no CPU fallback: without a
+// step is a HIP kernel (rx_kernels.hip and the headers it includes).  There is no CPU fallback: without a
 // HIP device every call returns -ENODEV.
 #include <cerrno>
 #include <cmath>

@@ -30,26 +30,20 @@
 #include <cstdlib>
 #include <mutex>
 #include "gmr1_dev.h"
+#include "fast_math.h"
 #include "profile_env.h"
 
 namespace gmr1 {
 
-#define WSYNC()                                                   \
-	do {                                                          \
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");    \
-		__builtin_amdgcn_wave_barrier();                          \
-	} while (0)
-
-static constexpr float kPif = 3.14159265358979323846f;
 static constexpr int kPfbSteps = 64;        // output instants per wavefront (32 new blocks; 128 / 256: 5 / 22 % slower, r06aq)
 static constexpr int kPfbTile = 16;         // instants per LDS transpose tile
 static constexpr int kPfbWb = 4;            // tile reads answered together in k_pfb64's write-out
 // a streamed push is a small grid: its time is one wave's walk, not the machine's throughput -- one tile per wave there
 static constexpr int kPfbStepsStream = 16;
 
-// (every lane of these permutations has a source lane: no "old" value is needed, and none is set up)
+// wave_ops.h's dppf as a plain DPP move: every lane of these permutations has a source lane, so no "old" value is set up
 template <int CTRL>
-__device__ __forceinline__ float dppf(float v)
+__device__ __forceinline__ float dppf_mov(float v)
 {
 	return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
@@ -59,10 +53,10 @@ template <int X>
 __device__ __forceinline__ float lane_xor(float v)
 {
 	if constexpr (X == 32 || X == 16) return __shfl_xor(v, X, 64);
-	else if constexpr (X == 8) return dppf<0x128>(v);               // row_ror:8
-	else if constexpr (X == 4) return dppf<0x1B>(dppf<0x141>(v));   // half mirror, then quad reverse
-	else if constexpr (X == 2) return dppf<0x4E>(v);
-	else return dppf<0xB1>(v);
+	else if constexpr (X == 8) return dppf_mov<0x128>(v);               // row_ror:8
+	else if constexpr (X == 4) return dppf_mov<0x1B>(dppf_mov<0x141>(v));   // half mirror, then quad reverse
+	else if constexpr (X == 2) return dppf_mov<0x4E>(v);
+	else return dppf_mov<0xB1>(v);
 }
 
 // sample s (global index) of a streamed stage's input row: the retained tail below st.x0, the new samples from there, zeros

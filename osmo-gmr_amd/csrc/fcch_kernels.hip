@@ -20,12 +20,11 @@
 // written and read back, a few kB of partials.
 #include <cstring>
 #include "gmr1_dev.h"
+#include "fast_math.h"
 #include "fcch_acq.h"
 #include "profile_env.h"
 
 namespace gmr1 {
-
-static constexpr float kPif = 3.14159265358979323846f;
 
 __constant__ FcchTables c_fcch;
 
@@ -35,14 +34,10 @@ hipError_t upload_fcch_tables(const FcchTables *host, hipStream_t stream)
 }
 
 // ---------------------------------------------------------------------------
-// helpers (same forms as rx_kernels.hip)
+// helpers: dppf, lane_val, sincos_fast and cmul are wave_ops.h's and fast_math.h's; the two sums are this file's own
 // ---------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v)
-{
-	return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row_sum(float v)
+// wave_ops.h's row_sum with the exact lane ^ 4 partner in its third step (two DPP moves where row_sum takes one)
+__device__ __forceinline__ float row_sum_x4(float v)
 {
 	v += dppf<0xB1>(v);                 // xor 1
 	v += dppf<0x4E>(v);                 // xor 2
@@ -50,13 +45,10 @@ __device__ __forceinline__ float row_sum(float v)
 	v += dppf<0x128>(v);                // xor 8
 	return v;
 }
-__device__ __forceinline__ float lane_val(float v, int l)
+// wave_ops.h's wave_sum with the four row sums read out by four readlanes (wave_sum: two row broadcasts and one)
+__device__ __forceinline__ float wave_sum_rl(float v)
 {
-	return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-	v = row_sum(v);
+	v = row_sum_x4(v);
 	return (lane_val(v, 0) + lane_val(v, 16)) + (lane_val(v, 32) + lane_val(v, 48));
 }
 __device__ __forceinline__ double wave_sum_d(double v)
@@ -65,28 +57,6 @@ __device__ __forceinline__ double wave_sum_d(double v)
 	for (int o = 32; o > 0; o >>= 1)
 		v += __shfl_xor(v, o);
 	return v;
-}
-__device__ __forceinline__ void sincos_fast(float x, float &s, float &c)
-{
-	const float k = rintf(x * 0.636619772367581343f);
-	float r = fmaf(-k, 1.57079637050628662109375f, x);
-	r = fmaf(-k, -4.37113900018624283e-8f, r);
-	const float z = r * r;
-	float sp = fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
-	sp = fmaf(sp, z, -1.6666654611e-1f);
-	sp = fmaf(sp * z, r, r);
-	float cp = fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f);
-	cp = fmaf(cp, z, 4.166664568298827e-2f);
-	cp = fmaf(cp * z, z, fmaf(-0.5f, z, 1.0f));
-	const int q = (int)k;
-	const float ss = (q & 1) ? cp : sp;
-	const float cc = (q & 1) ? sp : cp;
-	s = (q & 2) ? -ss : ss;
-	c = ((q + 1) & 2) ? -cc : cc;
-}
-__device__ __forceinline__ float2 cmul(float2 a, float2 b)
-{
-	return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -140,7 +110,7 @@ __global__ __launch_bounds__(256) void k_fcch_stats(FcchRoughArgs a)
 		}
 	}
 	__shared__ float red[3][4];
-	sr = wave_sum(sr); si = wave_sum(si); sq = wave_sum(sq);
+	sr = wave_sum_rl(sr); si = wave_sum_rl(si); sq = wave_sum_rl(sq);
 	const int wv = threadIdx.x >> 6;
 	if ((threadIdx.x & 63) == 0) { red[0][wv] = sr; red[1][wv] = si; red[2][wv] = sq; }
 	__syncthreads();
@@ -476,7 +446,7 @@ __global__ __launch_bounds__(256) void k_fcch_sweep(FcchRoughArgs a)
 		}
 	}
 	__shared__ float red[3][4];
-	sr = wave_sum(sr); si = wave_sum(si); sq = wave_sum(sq);
+	sr = wave_sum_rl(sr); si = wave_sum_rl(si); sq = wave_sum_rl(sq);
 	if (lane == 0) { red[0][wv] = sr; red[1][wv] = si; red[2][wv] = sq; }
 	__syncthreads();
 	if (tid == 0) {
@@ -554,7 +524,7 @@ __global__ __launch_bounds__(256) void k_fcch_sweep(FcchRoughArgs a)
 				rr = fmaf(r1, cs, rr);
 				ri = fmaf(r1, sn, ri);
 			}
-			rr = wave_sum(rr); ri = fs != 0.0f ? wave_sum(ri) : 0.0f;
+			rr = wave_sum_rl(rr); ri = fs != 0.0f ? wave_sum_rl(ri) : 0.0f;
 			if (lane == 0) {
 				const double n = (double)a.len;
 				const double ar = dr / n, ai = di / n;
@@ -803,7 +773,7 @@ __global__ __launch_bounds__(256) void k_fcch_energy(FcchRoughArgs a, int kEnerg
 			rr = fmaf(r, cs, rr);
 			ri = fmaf(r, sn, ri);
 		}
-		rr = wave_sum(rr); ri = fs != 0.0f ? wave_sum(ri) : 0.0f;
+		rr = wave_sum_rl(rr); ri = fs != 0.0f ? wave_sum_rl(ri) : 0.0f;
 		if (lane == 0) {
 			const double n = (double)a.len;
 			const double ar = dr / n, ai = di / n;
@@ -1040,7 +1010,7 @@ __global__ __launch_bounds__(64 * kFineWaves) void k_fcch_fine(FcchFineArgs a, A
 			sr += v.x; si += v.y;
 		}
 	}
-	sr = wave_sum(sr); si = wave_sum(si);
+	sr = wave_sum_rl(sr); si = wave_sum_rl(si);
 	const float avr = sr / (float)nraw, avi = si / (float)nraw;
 	float sq = 0.f;
 	if (in_regs) {
@@ -1057,7 +1027,7 @@ __global__ __launch_bounds__(64 * kFineWaves) void k_fcch_fine(FcchFineArgs a, A
 			sq = fmaf(dx, dx, fmaf(dy, dy, sq));
 		}
 	}
-	float sd = sqrtf(wave_sum(sq) / (float)nraw);
+	float sd = sqrtf(wave_sum_rl(sq) / (float)nraw);
 	if (sd == 0.0f) sd = 1.0f;
 	const float inv = 1.0f / sd;
 
@@ -1212,7 +1182,7 @@ __global__ __launch_bounds__(64 * kFineWaves) void k_fcch_fine(FcchFineArgs a, A
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float block_sum(float v, float *red, int tid)
 {
-	v = wave_sum(v);
+	v = wave_sum_rl(v);
 	__syncthreads();
 	if ((tid & 63) == 0) red[tid >> 6] = v;
 	__syncthreads();

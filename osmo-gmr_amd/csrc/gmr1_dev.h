@@ -75,7 +75,7 @@ struct RxArgs {
 	int32_t *sync_id;
 };
 
-// The receive loop of all chains (rx_kernels.hip), three launches:
+// The receive loop of all chains (rx_loop_kernels.inc), three launches:
 //   k_rx_chain  one wavefront per chain walks the feedback chain -- list a round, demodulate and decode its BCCH burst,
 //               apply the result -- and only LISTS the round's CCCH bursts (nothing feeds back from them);
 //   k_rx4       the listed CCCH bursts of all chains, four per wavefront (the burst kernel at its throughput shape);
@@ -483,7 +483,7 @@ hipError_t launch_facch3(const Facch3Args &a, hipStream_t stream);
 hipError_t launch_tch3(const Tch3Args &a, hipStream_t stream);
 hipError_t launch_rx_tch3(const RxArgs &a, const Tch3Args &t, hipStream_t stream);   // a.impl == 3, NT3 speech
 
-// launchers (rx_kernels.hip)
+// launchers (rx_kernels.hip and the files it includes)
 // descriptors live in __constant__ memory of the current device
 hipError_t upload_types(const DevBurst *host, int first, int count, hipStream_t stream);
 hipError_t launch_rx(const RxArgs &a, bool decode, int max_in_len, hipStream_t stream);

@@ -29,7 +29,7 @@ using namespace t3;
 
 __constant__ ScrBits c_scr = make_scr();
 
-// CRC16 syndromes of a 76-bit message followed by its 16 CRC bits (see rx_kernels.hip)
+// CRC16 syndromes of a 76-bit message followed by its 16 CRC bits (see conv_k5_12.h)
 struct Syn92 { uint16_t s[92]; };
 static constexpr Syn92 make_syn92()
 {
@@ -46,13 +46,14 @@ static constexpr Syn92 make_syn92()
 }
 __constant__ Syn92 c_syn92 = make_syn92();
 
+// wave_ops.h's row_xor on dpp_bc and with the exact lane ^ 4 partner (two DPP moves where row_xor takes one)
 template <int X>
-__device__ __forceinline__ uint32_t row_xor(uint32_t v)
+__device__ __forceinline__ uint32_t row_xor_x4(uint32_t v)
 {
-	if constexpr (X == 8) return dpp<0x128>(v);
-	else if constexpr (X == 4) return dpp<0x1B>(dpp<0x141>(v));
-	else if constexpr (X == 2) return dpp<0x4E>(v);
-	else return dpp<0xB1>(v);
+	if constexpr (X == 8) return dpp_bc<0x128>(v);
+	else if constexpr (X == 4) return dpp_bc<0x1B>(dpp_bc<0x141>(v));
+	else if constexpr (X == 2) return dpp_bc<0x4E>(v);
+	else return dpp_bc<0xB1>(v);
 }
 template <bool ACC = false>
 __device__ __forceinline__ int sbit_cost(int v, int bit)
@@ -74,7 +75,7 @@ static constexpr int kF3Steps = 96;       // 92 bits + 4 flush
 
 // K=5 rate-1/4: g0 = 1+D^3+D^4, g1 = 1+D+D^2+D^4, g2 = 1+D^2+D^4, g3 = 1+D+D^2+D^3+D^4 (conv.c:174-198).
 // Per row location constants of the in-place 16-state butterfly with the masks 8, 7, 2, 1 (one DPP
-// control each; see decode4_k5_12 in rx_kernels.hip for the construction):
+// control each; see decode4_k5_12 in conv_k5_12.h for the construction):
 //   ov[loc] : 4-bit coded word of the own transition per phase (bits 0-15) and of the partner's (16-31)
 //   hi[loc] : bit j set when the lane holds the HIGH predecessor in phase j & 3 (16-step pattern)
 struct K5r4Tab { uint32_t ov[16]; uint32_t hi[16]; };
@@ -119,10 +120,10 @@ __constant__ K5r4Tab c_k5r4 = make_k5r4();
 template <int PH>
 __device__ __forceinline__ uint32_t k5_partner(uint32_t w)
 {
-	if constexpr (PH == 0) return dpp<0x128>(w);            // row_ror:8
-	else if constexpr (PH == 1) return dpp<0x141>(w);       // row_half_mirror: xor 7
-	else if constexpr (PH == 2) return dpp<0x4E>(w);        // quad_perm [2,3,0,1]
-	else return dpp<0xB1>(w);                               // quad_perm [1,0,3,2]
+	if constexpr (PH == 0) return dpp_bc<0x128>(w);            // row_ror:8
+	else if constexpr (PH == 1) return dpp_bc<0x141>(w);       // row_half_mirror: xor 7
+	else if constexpr (PH == 2) return dpp_bc<0x4E>(w);        // quad_perm [2,3,0,1]
+	else return dpp_bc<0xB1>(w);                               // quad_perm [1,0,3,2]
 }
 
 // one rate-1/4 trellis step on the packed word [metric:16 | window decisions:16]; the cost of a coded
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
 	}
 	WSYNC();
 
-	// ---- forward pass on packed words (see decode4_k5_12 in rx_kernels.hip): 4 steps whose decisions
+	// ---- forward pass on packed words (see decode4_k5_12 in conv_k5_12.h): 4 steps whose decisions
 	// are u[-4..-1], five windows of 16 steps (u[16m .. 16m+15]) and a last one of 12 (u[80..91], the
 	// final four being the flush: only b = 0 transitions survive)
 	const uint32_t ovt = c_k5r4.ov[loc], hit = c_k5r4.hi[loc];
@@ -301,10 +302,10 @@ __global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
 			syn ^= bit ? (uint32_t)c_syn92.s[k] : 0u;
 		}
 	}
-	syn ^= row_xor<1>(syn);
-	syn ^= row_xor<2>(syn);
-	syn ^= row_xor<4>(syn);
-	syn ^= row_xor<8>(syn);
+	syn ^= row_xor_x4<1>(syn);
+	syn ^= row_xor_x4<2>(syn);
+	syn ^= row_xor_x4<4>(syn);
+	syn ^= row_xor_x4<8>(syn);
 
 	// ---- outputs: 76 bits LSB first -> 10 bytes, upper nibble of l2[9] = 0 (facch3.c:166-167)
 	const int f = f0 + row;

@@ -5,7 +5,7 @@
 // bits, 4k8 rate 1/3 over 240, 2k4 rate 1/5 over 144, each punctured down to 648 coded bits
 // (gmr1_puncturer_generate, punct.c:48-133).  One kernel, four bursts per wavefront, one per 16-lane DPP
 // row, with the packed [metric:16 | window decisions:16] word and the in-place butterfly (masks 8, 7, 2, 1)
-// of decode4_k5_12 (rx_kernels.hip).  What differs between the four is data:
+// of decode4_k5_12 (conv_k5_12.h).  What differs between the four is data:
 //
 //   * a per-kind MAP (built on the host, capi_nt9.cpp) that says, for every coded bit of every trellis
 //     step, whether it was punctured and otherwise where its soft bit sits in the burst: status / SACCH

@@ -1,5 +1,5 @@
 // Intermediate signals of one burst's demodulation, for parity debugging on someone else's capture.
-// (part of rx_kernels.hip's translation unit, included from rx_loop_kernels.inc inside namespace gmr1)
+// (part of rx_kernels.hip's translation unit, included by it after rx_loop_kernels.inc, inside namespace gmr1)
 //
 // The reference dumps four vectors per gmr1_pi4cxpsk_demod call when it is built with ENABLE_DEBUG_SIGNAL
 // (include/osmocom/gmr1/sdr/defs.h:35-39): "pi4cxpsk_corr" (pi4cxpsk.c:251), "pi4cxpsk_align" (:345),
@@ -115,5 +115,3 @@ hipError_t launch_rx_taps(const RxArgs &a, const RxTapsOut &o, hipStream_t strea
 #undef GMR1_TAPS
 	return hipGetLastError();
 }
-
-#include "rx_server_kernels.inc"

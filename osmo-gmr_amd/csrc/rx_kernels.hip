@@ -1,25 +1,31 @@
-// rx_kernels.hip -- normal-burst receive kernels for gfx950 (MI355X).
+// rx_kernels.hip -- the receive translation unit for gfx950 (MI355X).  This file holds the headline's own text: the fused
+// BCCH / CCCH burst body rx4_body, the kernels around it (k_rx4, k_rx4g, k_rx4g_tch3) and their launchers.  The rest of the
+// translation unit lives in files of its own, included below in the order of their definitions:
 //
-//   k_rx<.., DECODE=false> : pi/4-CxPSK burst demodulation, one burst per wavefront
-//                            (reference src/sdr/pi4cxpsk.c:520-602 gmr1_pi4cxpsk_demod)
-//   k_rx<.., DECODE=true>  : the same, four bursts per wavefront back to back, followed
-//                            by the BCCH/CCCH layer-1 chain for the four bursts at once:
-//                            descramble + de-interleave folded into the branch-metric
-//                            gather, 16-state K=5 rate-1/2 Viterbi with one burst per
-//                            16-lane DPP row, survivor walk, CRC16, LSB-first packing
-//                            (reference src/l1/bcch.c:83-103, src/l1/ccch.c:87-107 and
-//                            libosmocore's generic osmo_conv_decode).
-//   k_rx4                  : the default fused BCCH / CCCH kernel: the same arithmetic with the
-//                            serial phases (timing bisection, sync-symbol terms) done once for
-//                            the four bursts of a wave, one burst per 16-lane row.
-//   k_rx_chain_pipe, k_rx_chain, k_rx_merge, k_rx_pack (rx_loop_kernels.inc, included below): the frame loop of gmr1_rx
-//                            (process_bcch, src/gmr1_rx.c:852-895): the chain kernel walks the BCCH feedback chain of one
-//                            chain per work-group -- rx4_body in its latency shape, cut into pipeline stages (PART) that
-//                            run rounds apart on the work-group's waves -- and lists the CCCH bursts, k_rx4 takes those
-//                            as one batch, k_rx_merge writes the records.
-//   k_rx4g, k_rx4g_tch3    : demodulation only, four bursts per wave; with the TCH3 decoder behind it (tch3_body.h).
-//   k_detect, k_mod_order  : gmr1_pi4cxpsk_detect / _mod_order (pi4cxpsk.c:617-729).
-//   k_l1                   : the layer-1 chain alone on soft bits read from HBM.
+//   wave_ops.h           WSYNC, DPP moves and row / wave reductions, readlane, the LDS flags of the loop's hand-shakes
+//   fast_math.h          sincos_fast, atan2_fast / _turns, cmul, pk_cmac, conj_ref_mul
+//   conv_k5_12.h         the layer-1 chain: constant tables (trellis steps, costs, CRC syndromes, soft-bit tables), branch
+//                        metrics, decode4_k5_12 / decode1_k5_12_lat, survivor walk + CRC16, store_l2
+//                        (reference src/l1/bcch.c:83-103, src/l1/ccch.c:87-107 and libosmocore's osmo_conv_decode)
+//   rx_window.h          the one-burst LDS carve-up; window HBM -> registers -> LDS, statistics, burst energy
+//   rx_one.h             sync_search, demod_one and k_rx: pi/4-CxPSK demodulation, one burst per wavefront; with DECODE four
+//                        bursts back to back and the layer-1 chain behind them
+//                        (reference src/sdr/pi4cxpsk.c:520-602 gmr1_pi4cxpsk_demod)
+//   (here)               c_types, k_coef0; corr_fixed, the Lds4 carve-up, Fmt, LatPre and the loop's helpers;
+//                        rx4_body: the same arithmetic as k_rx with the serial phases (timing bisection, sync-symbol terms)
+//                        done once for the four bursts of a wave, one burst per 16-lane row;
+//                        k_rx4 (the default fused BCCH / CCCH kernel), k_rx4g (demodulation only, four bursts per wave),
+//                        k_rx4g_tch3 (with the TCH3 decoder behind it, tch3_body.h)
+//   rx_small_kernels.h   k_detect, k_mod_order (gmr1_pi4cxpsk_detect / _mod_order, pi4cxpsk.c:617-729), k_l1 / k_l1_acc (the
+//                        layer-1 chain alone on soft bits read from HBM), k_to_planar, with their launchers
+//   (here)               launch_rx, launch_rx_tch3, the profiling build's accessors
+//   rx_loop_kernels.inc  k_rx_chain_pipe, k_rx_chain, k_rx_merge, k_rx_pack: the frame loop of gmr1_rx (process_bcch,
+//                        src/gmr1_rx.c:852-895): the chain kernel walks the BCCH feedback chain of one chain per work-group --
+//                        rx4_body in its latency shape, cut into pipeline stages (PART) that run rounds apart on the
+//                        work-group's waves -- and lists the CCCH bursts, k_rx4 takes those as one batch, k_rx_merge writes
+//                        the records
+//   rx_debug_kernels.inc the intermediate signals of one burst, for parity debugging
+//   rx_server_kernels.inc  k_one_server: rx4_body behind a mailbox in pinned host memory
 //
 // Design notes (DESIGN.md has the long form):
 //   * Work-groups are single 64-lane wavefronts: every hand-off goes through the
@@ -42,1742 +48,21 @@
 
 #include "gmr1_dev.h"
 #include "tch3_body.h"
+#include "wave_ops.h"
+#include "fast_math.h"
+
+namespace gmr1 {
+// the burst formats (upload_types below fills them).  Defined ahead of conv_k5_12.h's tables, where they always stood:
+// the order of the constant objects in the code object stays what it was
+__constant__ DevBurst c_types[kNumTypes];
+}  // namespace gmr1
+
+#include "conv_k5_12.h"
+#include "rx_window.h"
 
 namespace gmr1 {
 
-#define WSYNC()                                                   \
-	do {                                                          \
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");    \
-		__builtin_amdgcn_wave_barrier();                          \
-	} while (0)
-
-static constexpr float kPif = 3.14159265358979323846f;
-typedef float v2f __attribute__((ext_vector_type(2)));   // (re, im) in a register pair: v_pk_add / v_pk_mul / v_pk_fma_f32
-static constexpr int kSteps12 = 212;              // 208 data + 4 flush steps (BCCH/CCCH)
-static constexpr int kEbRow = 448;                // LDS bytes per soft-bit row (>= 432, /16)
-static constexpr int kEbitsLds = 704;             // single-burst soft-bit buffer (>= 662)
-
-// ---------------------------------------------------------------------------
-// constant memory
-// ---------------------------------------------------------------------------
-__constant__ DevBurst c_types[kNumTypes];
-
-
-// Per trellis step of the BCCH / CCCH chain: where the two soft bits of the step
-// sit in the burst's e-bit order and whether the scrambler flips them
-//   bits  0..9  index of c[2k]   bit 10 its scrambling bit
-//   bits 16..25 index of c[2k+1] bit 26 its scrambling bit
-// (interleave.c:73-87 with N=53, scramb.c:39-73; CCCH: 4 leading pad bits, ccch.c:95-96)
-struct StepTable { uint32_t w[2][kSteps12]; };
-static constexpr StepTable make_steps()
-{
-	StepTable t{};
-	for (int chain = 0; chain < 2; chain++) {
-		const int off = chain ? 4 : 0;
-		// scrambling sequence over the e-bit positions
-		bool scr[448] = {};
-		uint16_t r = 0x4d4b;
-		for (int i = 0; i < 448; i++) {
-			uint32_t b = ((r >> 14) ^ r) & 1u;
-			r = (uint16_t)((r << 1) | b);
-			scr[i] = b != 0;
-		}
-		for (int k = 0; k < kSteps12; k++) {
-			uint32_t w = 0;
-			for (int j = 0; j < 2; j++) {
-				const int kc = 2 * k + j;
-				const int ei = 53 * ((5 * kc) & 7) + (kc >> 3) + off;
-				w |= ((uint32_t)ei | (scr[ei] ? 0x400u : 0u)) << (16 * j);
-			}
-			t.w[chain][k] = w;
-		}
-	}
-	return t;
-}
-__constant__ StepTable c_steps = make_steps();
-
-// Viterbi input cost of one soft bit, libosmocore's generic decoder: ((in -+ 127)^2) >> 9, and 0 for
-// an erasure (in == 0).  Index = soft bit as uint8, + 256 when the scrambler flips it (the flipped
-// value is (int8)(-v), so -128 stays -128 exactly as in gmr1_scramble_sbit, scramb.c:63-73).
-// a[]: first coded bit of a step, cost replicated to the bytes of the words ov = 0..3 it belongs
-// to (byte ov holds c0 for ov < 2, c1 otherwise); b[]: second coded bit (c0 for even ov, c1 for odd).
-struct CostTable { uint32_t a[512], b[512]; };
-static constexpr CostTable make_cost()
-{
-	CostTable t{};
-	for (int idx = 0; idx < 512; idx++) {
-		int v = (int)(int8_t)(uint8_t)(idx & 255);
-		if (idx & 256)
-			v = (int)(int8_t)(uint8_t)(-v);
-		const int e0 = v - 127, e1 = v + 127;
-		const uint32_t c0 = v ? (uint32_t)((e0 * e0) >> 9) : 0u;
-		const uint32_t c1 = v ? (uint32_t)((e1 * e1) >> 9) : 0u;
-		t.a[idx] = c0 | (c0 << 8) | (c1 << 16) | (c1 << 24);
-		t.b[idx] = c0 | (c1 << 8) | (c0 << 16) | (c1 << 24);
-	}
-	return t;
-}
-__constant__ CostTable c_cost = make_cost();
-
-// The same for libosmocore's accelerated decoder (osmo_conv_decode_acc, decision D1b: oracle/orc_3p_acc.c).  It MAXIMISES
-// the correlation sum in * (+-1); minimising  sum over the coded bits that contradict the soft bit's sign of |in|  ranks
-// every pair of paths identically ((sum |in| - correlation) / 2, an integer) and is non-negative, so the packed
-// [metric | decisions] words and v_min_u32 serve both decoders.  |in| <= 127 on the fused path (the demodulator's soft
-// bits); two soft bits of -128 in one step would overflow a byte lane -- k_l1 takes 16-bit lanes in this mode.
-static constexpr CostTable make_cost_acc()
-{
-	CostTable t{};
-	for (int idx = 0; idx < 512; idx++) {
-		int v = (int)(int8_t)(uint8_t)(idx & 255);
-		if (idx & 256)
-			v = (int)(int8_t)(uint8_t)(-v);
-		const uint32_t c0 = v < 0 ? (uint32_t)(-v) : 0u;
-		const uint32_t c1 = v > 0 ? (uint32_t)v : 0u;
-		t.a[idx] = c0 | (c0 << 8) | (c1 << 16) | (c1 << 24);
-		t.b[idx] = c0 | (c1 << 8) | (c0 << 16) | (c1 << 24);
-	}
-	return t;
-}
-__constant__ CostTable c_cost_acc = make_cost_acc();
-// what the accelerated decoder gives state 0 as a start: 127 * N * K in correlation units (conv_acc.c reset_decoder),
-// halved like the costs
-constexpr uint32_t kAccLeadK5r2 = 127u * 2u * 5u / 2u;
-
-struct SynTable { uint16_t s[208]; };
-static constexpr SynTable make_syn()
-{
-	// CRC16 (poly 0x1021, init 0; reference src/l1/crc.c:58-63) is linear: the
-	// check word of 192 message bits is the XOR of s[k] over the set bits k.
-	// s[192+i] folds the received CRC bit i (MSB first) in, so that the XOR over
-	// all 208 decoded bits is zero iff the check passes.
-	SynTable t{};
-	for (int k = 0; k < 192; k++) {
-		uint32_t crc = 0x8000u;
-		for (int i = k; i < 192; i++)
-			crc = (crc & 0x8000u) ? (((crc << 1) ^ 0x1021u) & 0xffffu) : ((crc << 1) & 0xffffu);
-		t.s[k] = (uint16_t)crc;
-	}
-	for (int i = 0; i < 16; i++)
-		t.s[192 + i] = (uint16_t)(1u << (15 - i));
-	return t;
-}
-__constant__ SynTable c_syn = make_syn();
-
-// the same table laid out for the decoder's CRC stage: lane `loc` of a row owns decoded bits
-// 13 loc .. 13 loc + 12; w[loc][p] = s[13 loc + 2p] | s[13 loc + 2p + 1] << 16 (two 128-bit loads per lane)
-struct SynRows { uint32_t w[16][8]; };
-static constexpr SynRows make_syn_rows()
-{
-	const SynTable t = make_syn();
-	SynRows r{};
-	for (int loc = 0; loc < 16; loc++)
-		for (int q = 0; q < 13; q++)
-			r.w[loc][q >> 1] |= (uint32_t)t.s[13 * loc + q] << (16 * (q & 1));
-	return r;
-}
-__constant__ __attribute__((aligned(16))) SynRows c_syn_rows = make_syn_rows();
-
-// Soft bits of a pi/4-CQPSK symbol by table (pi4cxpsk.c:452-507): the two soft bits are a function of the symbol's
-// phase quantised to 1/128 symbol (dq = round(|sv - round(sv)| * 128)) -- piecewise constant with every boundary on a
-// multiple of 1/256 symbol.  Cell k of the table covers phases [k, k + 1) / 1024 turns (1 turn = 4 symbols) and holds
-// what the arithmetic gives at the cell's midpoint (no ties there): nearest symbol sp (Gray bits p0 p1), its neighbour
-// on the side of the phase, distance dq; the bit that differs between the two gets 127 - dq, the other 127 - dq/2.
-// Entry = soft bit 0 | soft bit 1 << 8.  The arithmetic form and the table differ only for phases that are exactly a
-// cell boundary in binary floating point.
-struct SbLut { uint16_t v[1024]; };
-static constexpr SbLut make_sb_lut()
-{
-	SbLut t{};
-	for (int k = 0; k < 1024; k++) {
-		int q = 2 * k + 1;                    // cell midpoint in 1/512 symbol; a turn is 2048
-		if (q > 1024)
-			q -= 2048;                        // (-2, 2] symbols
-		const int n = (q + 256 + 2048) / 512 - 4;   // nearest symbol, floor((q + 256) / 512)
-		const int dlq = 512 * n - q;          // round(sv) - sv, odd: never zero
-		const int adl = dlq < 0 ? -dlq : dlq;
-		const int dq = (adl + 2) / 4;         // round(|dl| * 128): adl / 4 = m + 1/4 or m + 3/4
-		const unsigned sp = (unsigned)n & 3u;
-		const unsigned neg = dlq < 0 ? 1u : 0u;
-		const bool f0 = ((sp ^ neg ^ 1u) & 1u) != 0;
-		const int m_near = 127 - dq, m_far = 127 - (dq >> 1);
-		int v0 = f0 ? m_near : m_far;
-		int v1 = f0 ? m_far : m_near;
-		if (sp >> 1)
-			v0 = -v0;
-		if ((sp ^ (sp >> 1)) & 1u)
-			v1 = -v1;
-		t.v[k] = (uint16_t)(((unsigned)v0 & 0xffu) | (((unsigned)v1 & 0xffu) << 8));
-	}
-	return t;
-}
-__device__ __attribute__((aligned(16))) const SbLut g_sb_lut = make_sb_lut();
-constexpr int kSbLutBytes = 2048;
-
-// The same for pi/4-CBPSK (one bit per symbol, a turn is two symbols; pi4cxpsk.c:452-507 with nbits = 1): the symbol's
-// one soft bit is 127 - dq (its neighbour always differs in that bit), negative for symbol 1.  Entry = the soft bit in
-// the low byte; cells and boundaries as above (dq steps at odd multiples of 1/256 symbol, cell edges at multiples of 1/512).
-static constexpr SbLut make_sb_lut1()
-{
-	SbLut t{};
-	for (int k = 0; k < 1024; k++) {
-		int q = 2 * k + 1;                    // cell midpoint in 1/1024 symbol; a turn is 2048
-		if (q > 1024)
-			q -= 2048;                        // (-1, 1] symbols
-		const int n = (q + 512 + 2048) / 1024 - 2;  // nearest symbol, floor((q + 512) / 1024)
-		const int dlq = 1024 * n - q;         // round(sv) - sv, odd: never zero
-		const int adl = dlq < 0 ? -dlq : dlq;
-		const int dq = (adl + 4) / 8;         // round(|dl| * 128): adl / 8 is never half an integer
-		const unsigned sp = (unsigned)n & 1u;
-		const int v0 = sp ? -(127 - dq) : (127 - dq);
-		t.v[k] = (uint16_t)((unsigned)v0 & 0xffu);
-	}
-	return t;
-}
-__device__ __attribute__((aligned(16))) const SbLut g_sb_lut1 = make_sb_lut1();
-
-// ---------------------------------------------------------------------------
-// cross-lane helpers (DPP: no LDS traffic)
-// ---------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t v)
-{
-	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v)
-{
-	return __builtin_bit_cast(float, dpp<CTRL>(__builtin_bit_cast(uint32_t, v)));
-}
-
-// the partner's value in the steps 1, 2, 4, 8 of a reduction over a 16-lane row (every use in this file is such a
-// reduction by a commutative operation, run in that order): lane l ^ X for X in {8, 2, 1}; for X = 4 lane 7 - (l & 7) of
-// the half -- a lane of the half's OTHER quad, whose four lanes all hold that quad's value after steps 1 and 2 -- which is
-// one DPP operand instead of the two moves an exact l ^ 4 takes, with the same result bit for bit
-template <int X>
-__device__ __forceinline__ uint32_t row_xor(uint32_t v)
-{
-	if constexpr (X == 8) return dpp<0x128>(v);                    // row_ror:8
-	else if constexpr (X == 4) return dpp<0x141>(v);               // row_half_mirror
-	else if constexpr (X == 2) return dpp<0x4E>(v);                // quad_perm [2,3,0,1]
-	else return dpp<0xB1>(v);                                      // quad_perm [1,0,3,2]
-}
-template <int X>
-__device__ __forceinline__ float row_xorf(float v)
-{
-	return __builtin_bit_cast(float, row_xor<X>(__builtin_bit_cast(uint32_t, v)));
-}
-
-// every lane gets the sum over its 16-lane row
-__device__ __forceinline__ float row_sum(float v)
-{
-	v += row_xorf<1>(v);
-	v += row_xorf<2>(v);
-	v += row_xorf<4>(v);
-	v += row_xorf<8>(v);
-	return v;
-}
-
-__device__ __forceinline__ float lane_val(float v, int l)
-{
-	return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-
-// (r0 + r16) + (r32 + r48) of the four row sums, wave-uniform.  The two cross-row steps are DPP row broadcasts: lane 15 of
-// every row into the next row (row 1 then holds r16 + r0, row 3 r48 + r32), then lane 31 into rows 2 and 3 (row 3:
-// (r48 + r32) + (r16 + r0)) -- the same three additions, operands swapped, so the same float; one readlane instead of four
-// and no moves back from scalar registers.
-__device__ __forceinline__ float wave_sum(float v)
-{
-	v = row_sum(v);
-	v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xf, 0xf, true));   // row_bcast:15
-	v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xf, 0xf, true));   // row_bcast:31 (rows 0, 1: + 0)
-	return lane_val(v, 63);
-}
-
-// ---------------------------------------------------------------------------
-// math helpers
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float2 cmul(float2 a, float2 b)
-{
-	return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// sin / cos for |x| up to a few thousand radians: two-constant Cody-Waite reduction
-// by pi/2 (exact to ~1e-10 thanks to fma) and the classic single-precision minimax
-// polynomials on [-pi/4, pi/4]; ~1 ulp, so results track libm's to the last bit or two.
-__device__ __forceinline__ void sincos_fast(float x, float &s, float &c)
-{
-	const float k = rintf(x * 0.636619772367581343f);
-	float r = fmaf(-k, 1.57079637050628662109375f, x);
-	r = fmaf(-k, -4.37113900018624283e-8f, r);
-	const float z = r * r;
-	float sp = fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
-	sp = fmaf(sp, z, -1.6666654611e-1f);
-	sp = fmaf(sp * z, r, r);
-	float cp = fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f);
-	cp = fmaf(cp, z, 4.166664568298827e-2f);
-	cp = fmaf(cp * z, z, fmaf(-0.5f, z, 1.0f));
-	const int q = (int)k;
-	const float ss = (q & 1) ? cp : sp;
-	const float cc = (q & 1) ? sp : cp;
-	s = (q & 2) ? -ss : ss;
-	c = ((q + 1) & 2) ? -cc : cc;
-}
-
-// atan2 with ~1.5e-7 absolute error: octant folding + one reciprocal + degree-9 minimax
-__device__ __forceinline__ float atan2_fast(float y, float x)
-{
-	const float ax = fabsf(x), ay = fabsf(y);
-	const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-	const bool big = mn > 0.41421356237f * mx;             // tan(pi/8)
-	const float num = big ? (mn - mx) : mn;
-	const float den = big ? (mn + mx) : mx;
-	const float t = num * __builtin_amdgcn_rcpf(den);
-	const float z = t * t;
-	float p = fmaf(z, 8.05374449538e-2f, -1.38776856032e-1f);
-	p = fmaf(p, z, 1.99777106478e-1f);
-	p = fmaf(p, z, -3.33329491539e-1f);
-	float a = fmaf(p * z, t, t);
-	a += big ? 0.785398163397448309f : 0.0f;
-	a = (ay > ax) ? (1.57079632679489662f - a) : a;
-	a = (x < 0.0f) ? (kPif - a) : a;
-	a = (mx == 0.0f) ? 0.0f : a;
-	return (y < 0.0f) ? -a : a;
-}
-
-// atan2(y, x) / (2 pi), same minimax polynomial as atan2_fast with the coefficients in turns;
-// atan2_turns(0, 0) = 0
-__device__ __forceinline__ float atan2_turns(float y, float x)
-{
-	const float ax = fabsf(x), ay = fabsf(y);
-	const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-	const bool big = mn > 0.41421356237f * mx;             // tan(pi/8)
-	const float num = big ? (mn - mx) : mn;
-	const float den = big ? (mn + mx) : mx;
-	const float t = num * __builtin_amdgcn_rcpf(den);
-	const float z = t * t;
-	float p = fmaf(z, 1.28179325e-2f, -2.20870226e-2f);     // atan2_fast's coefficients / (2 pi)
-	p = fmaf(p, z, 3.17955140e-2f);
-	p = fmaf(p, z, -5.30510363e-2f);
-	p = fmaf(p, z, 1.59154943e-1f);
-	float a = p * t;
-	a += big ? 0.125f : 0.0f;
-	a = (ay > ax) ? (0.25f - a) : a;
-	a = (x < 0.0f) ? (0.5f - a) : a;
-	a = (mx == 0.0f) ? 0.0f : a;
-	return __builtin_copysignf(a, y);
-}
-
-// conj(ref) * v for ref = modulating value of sync symbol `sym` (exact: ref is +-1 / +-j)
-__device__ __forceinline__ float2 conj_ref_mul(int nbits, int sym, float2 v)
-{
-	if (nbits == 2) {
-		// sym0: ( x, y)  sym1: ( y,-x)  sym2: (-x,-y)  sym3: (-y, x)
-		const bool odd = (sym & 1) != 0;
-		const float a = odd ? v.y : v.x, b = odd ? v.x : v.y;
-		return make_float2((sym & 2) ? -a : a, ((sym + 1) & 2) ? -b : b);
-	}
-	return (sym & 1) ? make_float2(-v.x, -v.y) : v;
-}
-
-// K=5 rate-1/2 code (g0 = 1+D^3+D^4, g1 = 1+D+D^2+D^4; reference src/l1/conv.c:123-145)
-__device__ __forceinline__ uint32_t out_k5_12(uint32_t s, uint32_t b)
-{
-	uint32_t reg = (s << 1) | b;
-	return ((uint32_t)(__popc(reg & 0x19u) & 1) << 1) | (uint32_t)(__popc(reg & 0x17u) & 1);
-}
-__device__ __forceinline__ uint32_t rotl4(uint32_t x, int r) { return ((x << r) | (x >> (4 - r))) & 15u; }
-
-// ---------------------------------------------------------------------------
-// LDS carve-up of one wavefront
-//   [x | aux | eb]   aux = corr + coef during the sync search, y afterwards
-//   after the 4 demods of a fused wave, bm and surv overlay x
-// ---------------------------------------------------------------------------
-struct Lds {
-	float2 *x;        // normalised input window           [max_in_len]
-	float *corr;      // accumulated sync correlation      [kMaxWindow]      (aux)
-	float2 *coef;     // rotated sync reference            [kMaxCoef]        (aux + 1 KiB)
-	float2 *y;        // decimated symbols                 [max_len]         (aux)
-	int8_t *eb;       // soft bits: 4 rows (fused) or one buffer
-	uint32_t *bm;     // branch metrics 4 x 212            (overlays x)
-	uint64_t *surv;   // 13 x 64 halfwords of window decisions (overlays x, after bm)
-	uint32_t *ubits;  // decoded bits, 4 rows x 8 words    (overlays x, after surv)
-};
-
-__host__ __device__ inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-__host__ __device__ inline size_t lds_corr_bytes(int max_len, bool decode)
-{
-	if (decode)
-		return align16((size_t)max_len * 4);
-	return align16((size_t)(max_len > kMaxWindow ? max_len : kMaxWindow) * 4);
-}
-
-__host__ __device__ inline size_t lds_layout(int max_in_len, int max_len, bool decode, size_t *off)
-{
-	size_t o = 0;
-	size_t xbytes = align16((size_t)max_in_len * 8);
-	const size_t dec_bytes = 4 * kSteps12 * 4 + kSteps12 * 8 + 4 * 8 * 4;
-	if (decode && xbytes < dec_bytes)
-		xbytes = align16(dec_bytes);
-	off[0] = o; o += xbytes;
-	// aux = correlation accumulator + rotated sync reference.  The fused BCCH / CCCH path knows
-	// its formats (<= max_len lags, 17 sync symbols), which keeps 15 wavefronts per CU resident
-	// (demodulation only: the caller's lag count when it passes the 256 the layout has always had room for)
-	const size_t corr_bytes = lds_corr_bytes(max_len, decode);
-	const size_t coef_bytes = decode ? 32 * 8 : (size_t)kMaxCoef * 8;
-	off[1] = o; o += corr_bytes + coef_bytes;
-	off[2] = o; o += decode ? 4 * kEbRow : kEbitsLds;
-	return align16(o);
-}
-
-__device__ __forceinline__ Lds lds_carve(unsigned char *raw, int max_in_len, int max_len, bool decode)
-{
-	size_t off[3];
-	lds_layout(max_in_len, max_len, decode, off);
-	Lds L;
-	L.x = reinterpret_cast<float2 *>(raw + off[0]);
-	L.corr = reinterpret_cast<float *>(raw + off[1]);
-	L.coef = reinterpret_cast<float2 *>(raw + off[1] + lds_corr_bytes(max_len, decode));
-	L.y = reinterpret_cast<float2 *>(raw + off[1]);
-	L.eb = reinterpret_cast<int8_t *>(raw + off[2]);
-	L.bm = reinterpret_cast<uint32_t *>(raw + off[0]);
-	L.surv = reinterpret_cast<uint64_t *>(raw + off[0] + 4 * kSteps12 * 4);
-	L.ubits = reinterpret_cast<uint32_t *>(raw + off[0] + 4 * kSteps12 * 4 + kSteps12 * 8);
-	return L;
-}
-
-// ---------------------------------------------------------------------------
-// building blocks of the demodulator, one burst per wavefront
-// ---------------------------------------------------------------------------
-
-// window HBM -> registers -> LDS, DC and power normalised
-template <int NPL>
-__device__ __forceinline__ void load_normalise_stats(const float2 *__restrict__ in, int in_len, const Lds &L, int lane,
-                                                     float &avr_o, float &avi_o, float &inv_o)
-{
-	// ---- load + normalise (osmo_cxvec_sig_normalize, decim 1) ------------------
-	// rows k < nfull are whole (no lane test); row nfull is the ragged tail
-	float2 v[NPL];
-	float sr = 0.f, si = 0.f;
-	const int nfull = in_len >> 6;
-	const bool tail = (lane + 64 * nfull) < in_len;
-#pragma unroll
-	for (int k = 0; k < NPL; k++) {
-		if (k < nfull)
-			v[k] = in[lane + 64 * k];
-		else if (k == nfull && tail)
-			v[k] = in[lane + 64 * k];
-		else
-			v[k] = make_float2(0.f, 0.f);
-		sr += v[k].x;
-		si += v[k].y;
-	}
-	sr = wave_sum(sr);
-	si = wave_sum(si);
-	// mean / sigma only fix the DC offset and an overall scale that nothing downstream depends
-	// on, so reciprocals (1 ulp) stand in for the reference's divisions and square root
-	const float inv_n = __builtin_amdgcn_rcpf((float)in_len);
-	// (the mean keeps the true division: a constant window must normalise to exactly zero)
-	const float avr = sr / (float)in_len, avi = si / (float)in_len;
-	float acc = 0.f;
-#pragma unroll
-	for (int k = 0; k < NPL; k++) {
-		if (k < nfull || (k == nfull && tail)) {
-			v[k].x -= avr;
-			v[k].y -= avi;
-			acc = fmaf(v[k].x, v[k].x, fmaf(v[k].y, v[k].y, acc));
-		}
-	}
-	float sigma = wave_sum(acc) * inv_n;
-	float stddev = __builtin_amdgcn_sqrtf(sigma);
-	if (stddev == 0.0f)
-		stddev = 1.0f;
-	const float inv = __builtin_amdgcn_rcpf(stddev);
-#pragma unroll
-	for (int k = 0; k < NPL; k++) {
-		if (k < nfull || (k == nfull && tail))
-			L.x[lane + 64 * k] = make_float2(v[k].x * inv, v[k].y * inv);
-	}
-	avr_o = avr;
-	avi_o = avi;
-	inv_o = inv;
-}
-
-// window statistics only (mean, 1/sigma); the samples stay in registers and are dropped
-// NFULL >= 0: the caller knows in_len >> 6 at compile time (the fused sps = 4 path: 1016 and 976
-// samples both have 15 whole rows), which removes the per-row branches
-// RS = 64: `in` is the window, lane l takes samples l + 64 k.  RS = 16 (polyphase-planar array at 4 samples per symbol,
-// rx4_body's PL): `in` is already this lane's first sample in its plane, sample l + 64 k is 16 k places further on.
-template <int NPL, int NFULL = -1, int RS = 64>
-__device__ __forceinline__ void window_fetch(const float2 *__restrict__ in, int in_len, int lane, float2 (&v)[NPL])
-{
-	const int nfull = NFULL >= 0 ? NFULL : (in_len >> 6);
-	const bool tail = (lane + 64 * nfull) < in_len;
-	const int l0 = RS == 64 ? lane : 0;
-#pragma unroll
-	for (int k = 0; k < NPL; k++) {
-		if (k < nfull)
-			v[k] = in[l0 + RS * k];
-		else if (k == nfull && tail)
-			v[k] = in[l0 + RS * k];
-		else
-			v[k] = make_float2(0.f, 0.f);
-	}
-}
-
-// perm_src >= 0 (rx4_body's PL): this lane holds the samples of ANOTHER lane of the usual assignment (`lane` names that
-// one); the per-lane partial sums -- formed over the same samples in the same order -- are first moved to the lane that
-// usually forms them (every lane fetches from lane perm_src), so the cross-lane sums add the same numbers in the same
-// order and the statistics come out bit-identical.
-template <int NPL, int NFULL = -1>
-__device__ __forceinline__ void window_stats(const float2 (&v)[NPL], int in_len, int lane,
-                                             float &avr_o, float &avi_o, float &inv_o, int perm_src = -1, int odd_src = 1)
-{
-	auto home = [&](float x) {
-		return perm_src < 0 ? x : __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(perm_src << 2, __builtin_bit_cast(int, x)));
-	};
-	// (re, im) pairs through the packed FP32 pipe: one v_pk_add_f32 per sample for the sums, one v_pk_add_f32 and
-	// one v_pk_fma_f32 for the variance (re and im are summed in separate chains, as they are in the mean)
-	v2f s2 = {0.f, 0.f};
-	const int nfull = NFULL >= 0 ? NFULL : (in_len >> 6);
-	const bool tail = (lane + 64 * nfull) < in_len;
-#pragma unroll
-	for (int k = 0; k < NPL; k++)
-		s2 += (v2f){v[k].x, v[k].y};
-	const float sr = wave_sum(home(s2.x));
-	const float si = wave_sum(home(s2.y));
-	const float inv_n = __builtin_amdgcn_rcpf((float)in_len);
-	// true division, see load_normalise -- ONE division sequence for the two wave-uniform sums: lanes with an even `lane`
-	// divide the real sum, those with an odd one (wave lane odd_src is one) the imaginary sum
-	const float quot = ((lane & 1) ? si : sr) / (float)in_len;
-	const float avr = lane_val(quot, 0), avi = lane_val(quot, odd_src);
-	const v2f av = {avr, avi};
-	v2f acc2 = {0.f, 0.f};
-#pragma unroll
-	for (int k = 0; k < NPL; k++) {
-		if (k < nfull || (k == nfull && tail)) {
-			const v2f d = (v2f){v[k].x, v[k].y} - av;
-			acc2 = __builtin_elementwise_fma(d, d, acc2);
-		}
-	}
-	float stddev = __builtin_amdgcn_sqrtf(wave_sum(home(acc2.x + acc2.y)) * inv_n);
-	if (stddev == 0.0f)
-		stddev = 1.0f;
-	avr_o = avr;
-	avi_o = avi;
-	inv_o = __builtin_amdgcn_rcpf(stddev);
-}
-
-template <int NPL, int NFULL = -1>
-__device__ __forceinline__ void load_stats(const float2 *__restrict__ in, int in_len, int lane,
-                                           float &avr_o, float &avi_o, float &inv_o)
-{
-	float2 v[NPL];
-	window_fetch<NPL, NFULL>(in, in_len, lane, v);
-	window_stats<NPL, NFULL>(v, in_len, lane, avr_o, avi_o, inv_o);
-}
-
-// ---- the QUAD layout of a window in registers (rx4_body's QL: the fused batch kernel at 4 samples per symbol) ----
-// Lane l holds window samples 256 b + 4 l + c as v[4 b + c] (b = 0..3, c = 0..3): four CONSECUTIVE samples of each quarter
-// of the window, fetched as two 16-byte loads a quarter (a wave instruction covers 1 KB, every line asked for whole).
-// What it buys: the samples pass 2 keeps -- d, d + 4, d + 8, ... (pi4cxpsk.c:292-295) -- are sub-slot c = d & 3 of EVERY lane
-// of every quarter, one per lane and quarter, in lane order: kept sample i sits in lane (i + (d >> 2)) & 63 of quarter
-// (i + (d >> 2)) >> 6.  A lane ROTATION by d >> 2 (ds_bpermute, no LDS memory) puts kept sample l + 64 r into lane l --
-// pass 2's own assignment -- while the window is still in registers: no second trip to memory for it (rx4_body, QX).
-// With the samples stored polyphase-planar the same assignment is lane l <- place l + 64 b of plane c: a coalesced 512-byte
-// load, and the per-lane partial sums below are formed over the same samples in the same order, so the planar call's
-// statistics equal the interleaved call's bit for bit.
-typedef float v4f_a8 __attribute__((ext_vector_type(4), aligned(8)));
-__device__ __forceinline__ void window_fetch_q(const float2 *__restrict__ in, int in_len, int lane, float2 (&v)[16])
-{
-	const v4f_a8 *__restrict__ p = reinterpret_cast<const v4f_a8 *>(in + 4 * lane);
-#pragma unroll
-	for (int b = 0; b < 4; b++) {
-		const int s0 = 256 * b + 4 * lane;
-#pragma unroll
-		for (int h = 0; h < 2; h++) {
-			float2 lo = make_float2(0.f, 0.f), hi = make_float2(0.f, 0.f);
-			if (b < 3 || s0 + 2 * h + 1 < in_len) {        // (in_len >= 960: the first three quarters are whole)
-				const v4f_a8 u = p[128 * b + h];
-				lo = make_float2(u.x, u.y);
-				hi = make_float2(u.z, u.w);
-			} else if (s0 + 2 * h < in_len) {
-				lo = in[s0 + 2 * h];
-			}
-			v[4 * b + 2 * h] = lo;
-			v[4 * b + 2 * h + 1] = hi;
-		}
-	}
-}
-
-// the same assignment out of a polyphase-planar array: `pl` = the array, o = the window's first sample (flat count)
-__device__ __forceinline__ void window_fetch_q_planar(const float2 *__restrict__ pl, long long plane_stride, uint64_t o, int in_len,
-                                                      int lane, float2 (&v)[16])
-{
-#pragma unroll
-	for (int c = 0; c < 4; c++) {
-		const uint64_t oc = o + (uint64_t)c;
-		const float2 *__restrict__ src = pl + (long long)(oc & 3) * plane_stride + (long long)(oc >> 2) + lane;
-#pragma unroll
-		for (int b = 0; b < 4; b++) {
-			const int sidx = 256 * b + 4 * lane + c;
-			v[4 * b + c] = (b < 3 || sidx < in_len) ? src[64 * b] : make_float2(0.f, 0.f);
-		}
-	}
-}
-
-// mean and 1 / sigma of a window in the quad layout (osmo_cxvec_sig_normalize's statistics), ONE sweep: sum x and sum |x|^2
-// together -- sum |x - m|^2 = sum |x|^2 - n |m|^2, never below zero -- as the small formats' pass 1 has always had it: sigma only
-// sets a scale nothing downstream depends on (every consumer takes an angle, a ratio of energies or the place of a peak), and a
-// second sweep over sixteen register pairs for the variance about the mean is a third of the statistics' instructions.  Packed
-// sums, ONE true division sequence for the two means (a constant window must normalise to exactly zero), reciprocals elsewhere.
-__device__ __forceinline__ void window_stats_q(const float2 (&v)[16], int in_len, int lane, float &avr_o, float &avi_o, float &inv_o)
-{
-	v2f s2 = {0.f, 0.f}, q2 = {0.f, 0.f};
-#pragma unroll
-	for (int k = 0; k < 16; k++) {
-		const v2f x = {v[k].x, v[k].y};                     // (samples beyond the window are zeros)
-		s2 += x;
-		q2 = __builtin_elementwise_fma(x, x, q2);
-	}
-	const float sr = wave_sum(s2.x);
-	const float si = wave_sum(s2.y);
-	const float sq = wave_sum(q2.x + q2.y);
-	const float inv_n = __builtin_amdgcn_rcpf((float)in_len);
-	const float quot = ((lane & 1) ? si : sr) / (float)in_len;
-	const float avr = lane_val(quot, 0), avi = lane_val(quot, 1);
-	const float var = fmaxf(fmaf(-(float)in_len, fmaf(avr, avr, avi * avi), sq), 0.0f) * inv_n;
-	float stddev = __builtin_amdgcn_sqrtf(var);
-	if (stddev == 0.0f)
-		stddev = 1.0f;
-	avr_o = avr;
-	avi_o = avi;
-	inv_o = __builtin_amdgcn_rcpf(stddev);
-}
-
-// burst_energy() of the caller (gmr1_rx.c:172-182): sum |x|^2 over [len>>5, len - len>>5) of the RAW
-// window, divided by len.  Only the receive driver asks for it (RxArgs::energy); the window was
-// read a moment ago, so this second read is served by L1 / L2.
-template <int NPL>
-__device__ __noinline__ float window_energy(const float2 *__restrict__ in, int in_len, int lane)
-{
-	const int bd = in_len >> 5;
-	float e = 0.f;
-#pragma unroll
-	for (int k = 0; k < NPL; k++) {
-		const int idx = lane + 64 * k;
-		if (idx >= bd && idx < in_len - bd) {
-			const float2 v = in[idx];
-			e = fmaf(v.x, v.x, fmaf(v.y, v.y, e));
-		}
-	}
-	return wave_sum(e) / (float)in_len;
-}
-
-// the same sum over a window that is still in registers (window_fetch layout): identical operations in
-// identical order, without the second read
-template <int NPL>
-__device__ __forceinline__ float window_energy_regs(const float2 (&v)[NPL], int in_len, int lane)
-{
-	const int bd = in_len >> 5;
-	float e = 0.f;
-#pragma unroll
-	for (int k = 0; k < NPL; k++) {
-		const int idx = lane + 64 * k;
-		if (idx >= bd && idx < in_len - bd)
-			e = fmaf(v[k].x, v[k].x, fmaf(v[k].y, v[k].y, e));
-	}
-	return wave_sum(e) / (float)in_len;
-}
-
-template <int NPL>
-__device__ __forceinline__ void load_normalise(const float2 *__restrict__ in, int in_len, const Lds &L, int lane)
-{
-	float a, b, c;
-	load_normalise_stats<NPL>(in, in_len, L, lane, a, b, c);
-}
-
-// sync sequence search over the normalised window in L.x with derotation step fs (rad/sample).
-// Returns the winning sequence (-1: none has power), its fractional TOA and power.
-template <int SPS>
-__device__ int sync_search(int type, int in_len, int sps_rt, float fs, const Lds &L, int lane,
-                           int dbg_stop, float &toa_o, float &pwr_o)
-{
-	const DevBurst &bt = c_types[type];
-	const int sps = SPS ? SPS : sps_rt;
-	const int nbits = bt.nbits;
-	const int w = in_len - bt.len * sps + 1;
-	WSYNC();
-	for (int j = lane; j < w; j += 64)
-		L.corr[j] = 0.f;
-
-	// ---- sync search (pi4cxpsk.c:184-268) --------------------------------------
-	float p_toa = 0.f, p_pwr = 0.f;
-	int p_idx = -1;
-	const int win = w < 3 ? w : 3;
-	const int nsync = bt.n_sync;
-
-	for (int sq = 0; sq < nsync; sq++) {
-		const int tl = bt.sync_tl[sq];
-		const int nch = bt.n_chunks[sq];
-
-		// rotated reference: conj(ref_n) * e^{j fs sps n}; the common phase of a lag
-		// drops out under |.|, so the window itself is never derotated here
-		WSYNC();
-		for (int n = lane; n < tl; n += 64) {
-			int ch = 0, base = 0, cum = 0;
-			for (int c = 0; c < nch - 1; c++) {
-				cum += bt.sync[sq][c].len;
-				if (n >= cum) { base = cum; ch = c + 1; }
-			}
-			const int nn = n - base;
-			const int sym = bt.sync[sq][ch].syms[nn];
-			float s, c;
-			sincos_fast(fs * (float)(nn * sps), s, c);
-			L.coef[n] = conj_ref_mul(nbits, sym, make_float2(c, s));
-		}
-		WSYNC();
-
-		for (int j = lane; j < w; j += 64) {
-			float cj = L.corr[j];
-			int base = 0;
-			for (int ch = 0; ch < nch; ch++) {
-				const int pos = bt.sync[sq][ch].pos, len = bt.sync[sq][ch].len;
-				const float2 *xp = L.x + pos * sps + j;
-				const float2 *cp = L.coef + base;
-				float ar = 0.f, ai = 0.f;
-				for (int n = 0; n < len; n++) {
-					const float2 x = xp[n * sps];
-					const float2 cf = cp[n];
-					ar = fmaf(cf.x, x.x, fmaf(-cf.y, x.y, ar));
-					ai = fmaf(cf.x, x.y, fmaf(cf.y, x.x, ai));
-				}
-				base += len;
-				cj += sqrtf(fmaf(ar, ar, ai * ai));
-			}
-			L.corr[j] = cj;
-		}
-		WSYNC();
-		if (dbg_stop == 2) return -100;
-
-		// ---- osmo_cxvec_peak_energy_find(corr, 3, PEAK_EARLY_LATE, &peak) ----------
-		// key = (energy bits << 32) | ~index : max key = highest energy, lowest index on ties
-		unsigned long long key = 0;
-		for (int m = lane; m + win <= w; m += 64) {
-			float e = 0.f;
-			for (int k = 0; k < win; k++) {
-				const float c = L.corr[m + k];
-				e += c * c;
-			}
-			const unsigned long long kk =
-				((unsigned long long)__builtin_bit_cast(uint32_t, e) << 32) | (uint32_t)(~m);
-			key = kk > key ? kk : key;
-		}
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) {
-			const unsigned long long ok = __shfl_xor(key, o);
-			key = ok > key ? ok : key;
-		}
-		int mi = (int)(~(uint32_t)key);
-		if (mi < 0 || mi + win > w)
-			mi = 0;
-		int p = mi;
-		{
-			float pe = -1.f;
-			for (int k = 0; k < win; k++) {
-				const float c = L.corr[mi + k];
-				const float e = c * c;
-				if (e > pe) { pe = e; p = mi + k; }
-			}
-		}
-
-		// sinc-interpolated corr at `pos` (libosmo-dsp interpolate_point, 21 taps):
-		// lanes t = 0..20 of each 32-lane half hold one tap of that half's position.
-		// tap weight sinc(pi (i - pos)) with i - pos = k - f  ->  -(-1)^k sin(pi f) / (pi (k - f))
-		const int t = lane & 31;
-		auto interp_term = [&](float pos) -> float {
-			const float fl = floorf(pos);
-			const int i0 = (int)fl;
-			const float f = pos - fl;
-			int b = i0 - 10, e = i0 + 11;
-			if (b < 0) b = 0;
-			if (e >= w) e = w - 1;
-			const int i = i0 - 10 + t;
-			const bool valid = t < 21 && i >= b && i < e;
-			const float xx = kPif * ((float)i - pos);
-			const float S = __builtin_amdgcn_sinf(0.5f * f);       // sin(pi f), argument in turns
-			const float sg = (t & 1) ? S : -S;                     // k = t - 10 has the parity of t
-			const float wgt = (xx >= 0.01f || xx <= -0.01f) ? sg * __builtin_amdgcn_rcpf(xx) : 1.0f;
-			const float c = L.corr[valid ? i : 0];
-			return valid ? c * wgt : 0.0f;
-		};
-		auto half_total = [&](float v, int half) -> float {
-			v = row_sum(v);
-			return lane_val(v, 32 * half) + lane_val(v, 32 * half + 16);
-		};
-
-		// Early / late bisection (incr = 1/2 ... 1/512), THREE levels per evaluation: each group of 8 lanes
-		// interpolates the correlation at one candidate position and two samples later (same fractional part,
-		// so the same 21 weights; lane sub holds taps k = 3 sub - 10 + {0,1,2}) -- group 0 at the current point,
-		// groups 1 / 2 where the search goes if the early / late side wins, groups 3..6 one level further down.
-		// The candidates are formed by the same float operations the level-by-level walk performs, so it takes
-		// the same decisions; the walk itself is scalar work on two ballots.
-		const int grp = lane >> 3, isub = lane & 7;
-		auto interp_pair = [&](float pos, float &se, float &sl) {
-			const float fl = floorf(pos);
-			const int ib = (int)fl;
-			const float f = pos - fl;
-			const float S = __builtin_amdgcn_sinf(0.5f * f);       // sin(pi f); sin(pi (k - f)) = -(-1)^k sin(pi f)
-			int be = ib - 10, ee = ib + 11, bl = ib - 8, el = ib + 13;
-			if (be < 0) be = 0;
-			if (bl < 0) bl = 0;
-			if (ee >= w) ee = w - 1;
-			if (el >= w) el = w - 1;
-			float ae = 0.f, al = 0.f;
-#pragma unroll
-			for (int tt = 0; tt < 3; tt++) {
-				const int k = 3 * isub - 10 + tt;
-				const float sg = ((isub + tt) & 1) ? S : -S;
-				const float xx = kPif * ((float)k - f);
-				const float wgt = (xx >= 0.01f || xx <= -0.01f) ? sg * __builtin_amdgcn_rcpf(xx) : 1.0f;
-				const int ie = ib + k, il = ib + 2 + k;
-				const bool ve = k <= 10 && ie >= be && ie < ee;
-				const bool vl = k <= 10 && il >= bl && il < el;
-				const float ce = L.corr[ve ? ie : 0], cl = L.corr[vl ? il : 0];
-				ae += ve ? ce * wgt : 0.0f;
-				al += vl ? cl * wgt : 0.0f;
-			}
-			ae += row_xorf<1>(ae);
-			ae += row_xorf<2>(ae);
-			ae += row_xorf<4>(ae);
-			al += row_xorf<1>(al);
-			al += row_xorf<2>(al);
-			al += row_xorf<4>(al);
-			se = ae;
-			sl = al;
-		};
-		float early = (float)p - 1.0f, incr = 0.5f;
-#pragma unroll 1
-		for (int it = 0; it < 3; it++) {
-			const float half = incr * 0.5f, quarter = incr * 0.25f;
-			float pos = early;
-			if (grp == 1) {
-				pos = early - incr;
-			} else if (grp == 2) {
-				pos = early + incr;
-			} else if (grp >= 3 && grp <= 6) {
-				const float a1 = grp < 5 ? early - incr : early + incr;
-				pos = (grp & 1) ? a1 - half : a1 + half;           // 3: - -, 4: - +, 5: + -, 6: + +
-			}
-			float se, sl;
-			interp_pair(pos, se, sl);
-			const float ee = se * se, le = sl * sl;
-			const unsigned long long m_neg = __ballot(ee > le), m_pos = __ballot(ee < le);
-			auto dec = [&](int g) -> int { return ((m_neg >> (8 * g)) & 1ull) ? -1 : (((m_pos >> (8 * g)) & 1ull) ? 1 : 0); };
-			const int d0 = dec(0);
-			if (d0 == 0) break;
-			early = d0 < 0 ? early - incr : early + incr;
-			const int d1 = dec(d0 < 0 ? 1 : 2);
-			if (d1 == 0) break;
-			early = d1 < 0 ? early - half : early + half;
-			const int d2 = dec(3 + (d0 > 0 ? 2 : 0) + (d1 > 0 ? 1 : 0));
-			if (d2 == 0) break;
-			early = d2 < 0 ? early - quarter : early + quarter;
-			incr *= 0.125f;
-		}
-		const float s_toa = early + 1.0f;
-		float pk = half_total(interp_term(s_toa), 0);
-		pk = pk * __builtin_amdgcn_rcpf((float)tl);     // only ranked and tested against 0
-		const float s_pwr = pk * pk;
-		if (s_pwr > p_pwr) {
-			p_pwr = s_pwr;
-			p_toa = s_toa;
-			p_idx = sq;
-		}
-	}
-	toa_o = p_toa;
-	pwr_o = p_pwr;
-	return p_idx;
-}
-
-// ---------------------------------------------------------------------------
-// demodulation of one burst by one wavefront
-// returns the reference's rv (0, or -1 when no sync sequence has power)
-// ---------------------------------------------------------------------------
-template <int NPL, int SPS>
-__device__ int demod_one(int type, const float2 *__restrict__ in, int in_len, int sps_rt,
-                         float freq_shift, const Lds &L, int8_t *__restrict__ eb, int lane,
-                         int dbg_stop, int &sync_id_o, float &toa_o, float &ferr_o,
-                         float *__restrict__ g_ssyms)
-{
-	const DevBurst &bt = c_types[type];
-	const int sps = SPS ? SPS : sps_rt;
-	const int nbits = bt.nbits;
-	const int blen = bt.len;
-
-	load_normalise<NPL>(in, in_len, L, lane);
-	if (dbg_stop == 1) return -100;
-
-	// per-sample derotation step (pi4cxpsk.c:539)
-	const float fs = (freq_shift - bt.rotation) / (float)sps;
-	float p_toa = 0.f, p_pwr = 0.f;
-	const int p_idx = sync_search<SPS>(type, in_len, sps_rt, fs, L, lane, dbg_stop, p_toa, p_pwr);
-	if (p_idx == -100 || dbg_stop == 3) return -100;
-
-	sync_id_o = p_idx;
-	toa_o = p_toa;
-	if (p_idx < 0) {
-		ferr_o = 0.f;
-		return -1;
-	}
-	const int sq = p_idx;
-	const int nch = bt.n_chunks[sq];
-
-	// ---- everything after the sync search works in the PHASE domain ----------------
-	// The reference rotates the decimated burst three times (derotation e^{j fs n},
-	// fine frequency e^{-j f i}, carrier conj(phasor)) and then takes cargf() of each
-	// symbol (pi4cxpsk.c:286-297,574-581,442-460).  arg() of that product is
-	//     arg(x[i sps + d]) + fs (i sps + d) - f i - arg(phasor)      (mod 2 pi)
-	// so only the <= 17 sync symbols are ever rotated as complex numbers; the 234
-	// symbols cost one atan2 and a few adds each.  Soft bits only depend on the phase.
-	const int d = (int)roundf(p_toa);
-	const int row = lane >> 4, col = lane & 15;
-
-	// align (pi4cxpsk.c:280-348): at sps >= 4 symbol i is sample i*sps + d.  Below 4 samples per
-	// symbol the reference first applies a 21-tap sinc fractional delay (osmo_cxvec_convolve,
-	// CONV_NO_DELAY) when |toa - d| > 0.1.  It does so on the DEROTATED burst; with
-	// g[m] = x[m] e^{j fs m} the delayed sample is e^{j fs n} sum_k (p_k e^{j fs (10-k)}) x[n+10-k], so the
-	// rotation moves into 21 complex taps and the common e^{j fs n} stays in the phase domain.
-	const float ofs_frac = p_toa - (float)d;
-	const bool frac_on = (sps < 4) && (fabsf(ofs_frac) > 0.1f);
-	if (frac_on) {
-		WSYNC();
-		if (lane < 21) {
-			const float xx = kPif * ((float)(lane - 10) + ofs_frac);
-			const float pv = (xx >= 0.01f || xx <= -0.01f) ? (sinf(xx) / xx) : 1.0f;
-			float s, c;
-			sincos_fast(fs * (float)(10 - lane), s, c);
-			L.coef[lane] = make_float2(pv * c, pv * s);
-		}
-		WSYNC();
-	}
-	auto pick = [&](int j) -> float2 {
-		if (j < 0 || j >= in_len)
-			return make_float2(0.f, 0.f);
-		if (!frac_on)
-			return L.x[j];
-		float2 acc = make_float2(0.f, 0.f);
-		for (int k = 0; k < 21; k++) {
-			const int m = j + 10 - k;
-			if (m >= 0 && m < in_len) {
-				const float2 q = L.coef[k], x = L.x[m];
-				acc.x = fmaf(q.x, x.x, fmaf(-q.y, x.y, acc.x));
-				acc.y = fmaf(q.x, x.y, fmaf(q.y, x.x, acc.y));
-			}
-		}
-		return acc;
-	};
-
-	auto reduce_2pi = [](float a) -> float {
-		const float k = rintf(a * 0.159154943091895336f);
-		a = fmaf(-k, 6.2831854820251465f, a);
-		return fmaf(-k, -1.7484555e-7f, a);
-	};
-	// conj(ref) * derotated sample of sync symbol j of chunk c (pi4cxpsk.c:386-388)
-	auto sync_term = [&](int c, int j) -> float2 {
-		const int idx = (bt.sync[sq][c].pos + j) * sps + d;
-		float2 x = pick(idx);
-		float s, cc;
-		sincos_fast(fs * (float)idx, s, cc);
-		x = cmul(x, make_float2(cc, s));
-		return conj_ref_mul(nbits, bt.sync[sq][c].syms[j], x);
-	};
-
-	// ---- fine frequency error from the sync chunks (pi4cxpsk.c:360-406) ---------
-	// one chunk per 16-lane row, one sync symbol per lane; chunk sums by DPP
-	float ffe = 0.f;
-	if (nch > 1) {
-		float sumr[kMaxChunks], sumi[kMaxChunks];
-#pragma unroll
-		for (int c0 = 0; c0 < kMaxChunks; c0 += 4) {
-			if (c0 < nch) {
-				const int c = c0 + row;
-				float tr = 0.f, ti = 0.f;
-				if (c < nch) {
-					const int len = bt.sync[sq][c].len;
-					for (int j = col; j < len; j += 16) {
-						const float2 tt = sync_term(c, j);
-						tr += tt.x;
-						ti += tt.y;
-					}
-				}
-				tr = row_sum(tr);
-				ti = row_sum(ti);
-#pragma unroll
-				for (int r = 0; r < 4; r++) {
-					sumr[c0 + r] = lane_val(tr, 16 * r);
-					sumi[c0 + r] = lane_val(ti, 16 * r);
-				}
-			}
-		}
-		float f = 0.f;
-#pragma unroll
-		for (int i = 1; i < kMaxChunks; i++) {
-			if (i < nch) {
-				const float ppos = (float)bt.sync[sq][i - 1].pos + (float)bt.sync[sq][i - 1].len / 2.0f;
-				const float cpos = (float)bt.sync[sq][i].pos + (float)bt.sync[sq][i].len / 2.0f;
-				// corr[i] * conj(corr[i-1])
-				const float re = sumr[i] * sumr[i - 1] - sumi[i] * (-sumi[i - 1]);
-				const float im = sumr[i] * (-sumi[i - 1]) + sumi[i] * sumr[i - 1];
-				f += atan2_fast(im, re) / (cpos - ppos);
-			}
-		}
-		f /= (float)(nch - 1);
-		ffe = f;
-	}
-	ferr_o = ffe;
-	const float rps = -ffe;            // pi4cxpsk.c:574-575
-	if (dbg_stop == 4) return -100;
-
-	// ---- carrier phase from the (frequency-corrected) sync symbols (pi4cxpsk.c:415-433)
-	float tr = 0.f, ti = 0.f;
-#pragma unroll
-	for (int c0 = 0; c0 < kMaxChunks; c0 += 4) {
-		if (c0 < nch) {
-			const int c = c0 + row;
-			if (c < nch) {
-				const int pos = bt.sync[sq][c].pos, len = bt.sync[sq][c].len;
-				for (int j = col; j < len; j += 16) {
-					float2 tt = sync_term(c, j);
-					if (ffe != 0.0f) {
-						float s, cc;
-						sincos_fast(rps * (float)(pos + j), s, cc);
-						tt = cmul(tt, make_float2(cc, s));
-					}
-					tr += tt.x;
-					ti += tt.y;
-				}
-			}
-		}
-	}
-	const float phr = wave_sum(tr), phi = wave_sum(ti);
-	const float psi = atan2_fast(phi, phr);      // arg(phasor); |phasor| never matters
-	if (dbg_stop == 5) return -100;
-
-	// ---- soft symbols + soft bits (pi4cxpsk.c:442-503) ------------------------------
-	constexpr int NSYM = NPL > 16 ? 8 : 4;       // 4 x 64 >= 234, 8 x 64 >= 468
-	const float inv_dd = (float)(1 << nbits) / (2.0f * kPif);
-	const int mask = (1 << nbits) - 1;
-#pragma unroll
-	for (int r = 0; r < NSYM; r++) {
-		const int i = lane + 64 * r;
-		if (i >= blen)
-			continue;
-		const int j = i * sps + d;
-		const float2 x = pick(j);
-		float th = atan2_fast(x.y, x.x) + reduce_2pi(fs * (float)j);
-		th = reduce_2pi(fmaf(rps, (float)i, th) - psi);
-		const float sv = (x.x == 0.0f && x.y == 0.0f) ? 0.0f : th * inv_dd;   // cargf(0) = 0
-		if (g_ssyms)
-			g_ssyms[i] = sv;
-		const int ord = bt.ord_of_sym[i];
-		if (ord >= 0) {
-			const float svr2 = roundf(sv);
-			const int sp = (int)svr2 & mask;
-			const int ss = (svr2 > sv ? (sp - 1) : (sp + 1)) & mask;
-			const int dq = (int)roundf((2.0f * fabsf(svr2 - sv)) * 64.0f);
-			if (nbits == 2) {
-				// symbol -> bits 0:00 1:01 2:11 3:10 (pi4cxpsk.c:95-100)
-				const int p0 = sp >> 1, p1 = (sp ^ (sp >> 1)) & 1;
-				const int s0 = ss >> 1, s1 = (ss ^ (ss >> 1)) & 1;
-				const int v0 = 127 - ((p0 ^ s0) ? dq : (dq >> 1));
-				const int v1 = 127 - ((p1 ^ s1) ? dq : (dq >> 1));
-				const uint32_t pk2 = (uint32_t)(uint8_t)(int8_t)(p0 ? -v0 : v0) |
-				                     ((uint32_t)(uint8_t)(int8_t)(p1 ? -v1 : v1) << 8);
-				*reinterpret_cast<uint16_t *>(eb + 2 * ord) = (uint16_t)pk2;
-			} else {
-				const int p0 = sp & 1, s0 = ss & 1;
-				const int v0 = 127 - ((p0 ^ s0) ? dq : (dq >> 1));
-				eb[ord] = (int8_t)(p0 ? -v0 : v0);
-			}
-		}
-	}
-	WSYNC();
-	return 0;
-}
-
-// ---------------------------------------------------------------------------
-// branch metrics of one burst into bm[0..212): byte ov = cost of coded word ov
-// (descramble + de-interleave folded into the gather via c_steps)
-//   bcch.c:91-92 / ccch.c:95-96, interleave.c:73-87, scramb.c:63-73
-// ---------------------------------------------------------------------------
-template <bool ACC = false>
-__device__ __forceinline__ void branch_metrics_k5_12(const int8_t *__restrict__ eb, int chain,
-                                                     uint32_t *__restrict__ bm, int lane)
-{
-	const CostTable &ct = ACC ? c_cost_acc : c_cost;
-	for (int k = lane; k < kSteps12; k += 64) {
-		const uint32_t st = c_steps.w[chain][k];
-		// the four byte sums c(a) + c(b) of a step come out of one add of two table words
-		const uint32_t ia = (uint32_t)(uint8_t)eb[st & 0x3ffu] | ((st >> 2) & 0x100u);
-		const uint32_t ib = (uint32_t)(uint8_t)eb[(st >> 16) & 0x3ffu] | ((st >> 18) & 0x100u);
-		bm[k] = ct.a[ia] + ct.b[ib];
-	}
-}
-
-// the four bursts of a fused wave at once: every lane owns steps lane + 64 it of each burst, and the
-// three dependent fetches (step descriptor -> soft bits -> cost words) are each issued for all 16
-// (burst, step) pairs before anything waits -- three memory round trips per wave instead of 48
-template <bool ACC = false>
-__device__ __forceinline__ void branch_metrics4_k5_12(const int8_t *__restrict__ eb, int eb_stride, int row_ok,
-                                                      int row_chain, uint32_t *__restrict__ bm, int lane)
-{
-	const CostTable &ct = ACC ? c_cost_acc : c_cost;
-	uint32_t st[2][4];
-#pragma unroll
-	for (int c = 0; c < 2; c++)
-#pragma unroll
-		for (int it = 0; it < 4; it++) {
-			const int k = lane + 64 * it;
-			st[c][it] = k < kSteps12 ? c_steps.w[c][k] : 0u;
-		}
-	uint32_t ia[4][4], ib[4][4];
-#pragma unroll
-	for (int q = 0; q < 4; q++) {
-		const bool ch = ((row_chain >> q) & 1) != 0;
-		const int8_t *e = eb + q * eb_stride;
-#pragma unroll
-		for (int it = 0; it < 4; it++) {
-			const uint32_t s = ch ? st[1][it] : st[0][it];
-			ia[q][it] = (uint32_t)(uint8_t)e[s & 0x3ffu] | ((s >> 2) & 0x100u);
-			ib[q][it] = (uint32_t)(uint8_t)e[(s >> 16) & 0x3ffu] | ((s >> 18) & 0x100u);
-		}
-	}
-	uint32_t va[4][4], vb[4][4];
-#pragma unroll
-	for (int q = 0; q < 4; q++)
-#pragma unroll
-		for (int it = 0; it < 4; it++) {
-			va[q][it] = ct.a[ia[q][it]];
-			vb[q][it] = ct.b[ib[q][it]];
-		}
-#pragma unroll
-	for (int q = 0; q < 4; q++) {
-		const bool ok = ((row_ok >> q) & 1) != 0;
-#pragma unroll
-		for (int it = 0; it < 4; it++) {
-			const int k = lane + 64 * it;
-			if (k < kSteps12)
-				bm[q * kSteps12 + k] = ok ? va[q][it] + vb[q][it] : 0u;
-		}
-	}
-}
-
-// ---------------------------------------------------------------------------
-// 4 x (K=5, rate 1/2, 208 bits + flush) Viterbi, one burst per 16-lane row
-//
-// In-place butterfly: the two predecessors of a state always sit in two lanes of the row that
-// differ by an xor mask, and the two successor states are written back to the same two lanes.
-// The masks of the four phases are 8, 7, 2, 1 -- each ONE DPP control (row_ror:8,
-// row_half_mirror, quad_perm), so the partner's metric arrives folded into the add.  With
-// loc = c0*8 ^ c1*7 ^ c2*2 ^ c3*1, the predecessor state held by a lane in phase ph has bit i =
-// c[(3 - i + ph) & 3]; after 4 steps the layout is back where it started.
-//
-// One 32-bit word per state carries everything the step needs:
-//     [ path metric : 16 | decisions of the current 16-step window : 16 ]
-// The metric never exceeds 212 * 252 = 53 424; unreachable states carry 0xF000 (libosmocore's
-// MAX_AE plays the same role).  Before step j of a window the word of a lane that is the HIGH
-// predecessor ((t >> 1) + 8) of its butterfly has bit j set (tb).  The two candidates of a new
-// state are  own word + (cost << 16)  and  partner word + (cost << 16); v_min_u32 then (a) picks
-// the smaller metric, (b) on equal metrics keeps the LOW predecessor (osmo_conv_decode: strict
-// '>' on ascending states), and (c) leaves the decision in bit j of the winner's history --
-// four VALU instructions per trellis step (add, add with DPP, min, add next tb).  The cost byte
-// is fetched by every lane straight from the branch-metric words in LDS into the HIGH half of a
-// register (ds_read_u8_d16_hi; with SRAM-ECC the low half reads back as zero, which is what the
-// add wants), 8 steps ahead.
-//
-// The decision of step k is the oldest bit of the winning predecessor = input bit u[k-4].
-// Windows start at k = 4 + 16 m, so window m's 16 decisions ARE the decoded bits
-// u[16 m .. 16 m + 15], and its low 4 bits name the survivor's state at the start of the
-// window: the "traceback" is 13 dependent 16-bit LDS reads per burst.
-// ---------------------------------------------------------------------------
-constexpr uint32_t kSentinel = 0xF0000000u;
-
-// per row location: bits 0-7 own cost byte (2 bits per phase), 8-15 partner cost byte, 16-31 the
-// 16-step tb pattern (bit j set when the lane holds a HIGH predecessor in phase j & 3)
-struct DecTable { uint32_t v[16]; };
-static constexpr uint32_t dec_out(uint32_t s, uint32_t b)
-{
-	const uint32_t reg = (s << 1) | b;
-	uint32_t p0 = reg & 0x19u, p1 = reg & 0x17u;
-	p0 ^= p0 >> 4; p0 ^= p0 >> 2; p0 ^= p0 >> 1;
-	p1 ^= p1 >> 4; p1 ^= p1 >> 2; p1 ^= p1 >> 1;
-	return ((p0 & 1u) << 1) | (p1 & 1u);
-}
-static constexpr DecTable make_dec()
-{
-	DecTable t{};
-	for (uint32_t loc = 0; loc < 16; loc++) {
-		// loc in the basis {8, 7, 2, 1}
-		uint32_t c[4] = {0, 0, 0, 0};
-		c[0] = (loc >> 3) & 1u;
-		uint32_t x = loc & 7u;
-		c[1] = (x >> 2) & 1u;
-		x ^= c[1] ? 7u : 0u;
-		c[2] = (x >> 1) & 1u;
-		c[3] = x & 1u;
-		uint32_t e = 0;
-		for (int ph = 0; ph < 4; ph++) {
-			uint32_t sp = 0;
-			for (int i = 0; i < 4; i++)
-				sp |= c[(3 - i + ph) & 3] << i;
-			const uint32_t b = sp >> 3;
-			e |= dec_out(sp, b) << (2 * ph);
-			e |= dec_out(sp ^ 8u, b) << (8 + 2 * ph);
-			for (int j = ph; j < 16; j += 4)
-				e |= b << (16 + j);
-		}
-		t.v[loc] = e;
-	}
-	return t;
-}
-__constant__ DecTable c_dec = make_dec();
-
-#define GMR1_DPP_PH0 "row_ror:8"
-#define GMR1_DPP_PH1 "row_half_mirror"
-#define GMR1_DPP_PH2 "quad_perm:[2,3,0,1]"
-#define GMR1_DPP_PH3 "quad_perm:[1,0,3,2]"
-
-#define ACS_CORE(PH)                                                                               \
-	"s_waitcnt lgkmcnt(%[wt])\n\t"                                                                  \
-	"v_add_u32 %[t1], %[w], %[r]\n\t"                                                               \
-	"v_add_u32_dpp %[t2], %[w], %[q] " GMR1_DPP_PH##PH " row_mask:0xf bank_mask:0xf\n\t"            \
-	"v_min_u32 %[w], %[t1], %[t2]\n\t"
-// step with the operands of position J, prefetching the cost bytes of step J + 8; TN = tb of the next position
-#define ACS_PF(J, PH, WAIT, TN)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             "v_add_u32 %[w], %[w], %[tn]\n\t"                                                  \
-	             "ds_read_u8_d16_hi %[rn], %[ao] offset:%[off]\n\t"                                 \
-	             "ds_read_u8_d16_hi %[qn], %[ap] offset:%[off]\n\t"                                 \
-	             : [w] "+v"(w), [rn] "+v"(R[((J) + 8) & 15]), [qn] "+v"(Q[((J) + 8) & 15]),        \
-	               [t1] "=&v"(t1), [t2] "=&v"(t2)                                                    \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [ao] "v"(ao[PH]), [ap] "v"(ap[PH]), [tn] "v"(TN),   \
-	               [off] "i"(4 * ((J) + 8)), [wt] "i"(WAIT))
-// step without prefetch
-#define ACS_NP(J, PH, WAIT, TN)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             "v_add_u32 %[w], %[w], %[tn]\n\t"                                                  \
-	             : [w] "+v"(w), [t1] "=&v"(t1), [t2] "=&v"(t2)                                       \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [tn] "v"(TN), [wt] "i"(WAIT))
-// last step of a window: the caller clears the decisions and sets the first tb itself
-#define ACS_PF_END(J, PH, WAIT)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             "ds_read_u8_d16_hi %[rn], %[ao] offset:%[off]\n\t"                                 \
-	             "ds_read_u8_d16_hi %[qn], %[ap] offset:%[off]\n\t"                                 \
-	             : [w] "+v"(w), [rn] "+v"(R[((J) + 8) & 15]), [qn] "+v"(Q[((J) + 8) & 15]),        \
-	               [t1] "=&v"(t1), [t2] "=&v"(t2)                                                    \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [ao] "v"(ao[PH]), [ap] "v"(ap[PH]),                 \
-	               [off] "i"(4 * ((J) + 8)), [wt] "i"(WAIT))
-#define ACS_NP_END(J, PH, WAIT)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             : [w] "+v"(w), [t1] "=&v"(t1), [t2] "=&v"(t2)                                       \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [wt] "i"(WAIT))
-// cost bytes of step K (relative to the address registers) into the operands of position J
-#define ACS_LOAD(J, PH, K)                                                                         \
-	asm volatile("ds_read_u8_d16_hi %[rn], %[ao] offset:%[off]\n\t"                                 \
-	             "ds_read_u8_d16_hi %[qn], %[ap] offset:%[off]\n\t"                                 \
-	             : [rn] "+v"(R[J]), [qn] "+v"(Q[J])                                                  \
-	             : [ao] "v"(ao[PH]), [ap] "v"(ap[PH]), [off] "i"(4 * (K)))
-
-struct DecPre;
-__device__ __forceinline__ void k5_12_survivors_crc(uint64_t *__restrict__ surv, uint32_t *__restrict__ ubits, int lane,
-                                                    uint32_t &syn_o, const DecPre *dp = nullptr);
-__device__ __forceinline__ void k5_12_survivors_crc_lat(uint64_t *__restrict__ surv, uint32_t *__restrict__ ubits, int lane,
-                                                        uint32_t &syn_o, const DecPre *dp);
-
-// bm: 4 rows x 212 words; surv: 13 x 64 halfwords of window decisions; ubits: 4 rows x 8 words
-// (decoded bits, LSB first)
-//
-// ACC = libosmocore's accelerated decoder instead of its generic one (decision D1b, oracle/orc_3p_acc.c; costs from
-// c_cost_acc): every start state is allowed, state 0 leading by 127 * N * K; the four flush steps are ordinary
-// butterflies (the survivor walk still starts in state 0); no path metric is returned.  Ties between the two paths into
-// a state fall to the same (lower) predecessor in both decoders.
-struct DecPre {                                    // the decoder's per-lane constants, when the caller keeps them (receive loop)
-	uint32_t dc;
-	uint4 sy0, sy1;
-#ifdef GMR1_HIP_PROFILE
-	unsigned long long *stamp = nullptr;
-#endif
-};
-#ifdef GMR1_HIP_PROFILE
-#define GMR1_DSTAMP(dp, k, lane)                                             \
-	do {                                                                    \
-		if ((dp)->stamp && (lane) == 0)                                     \
-			(dp)->stamp[k] = __builtin_readcyclecounter();                  \
-	} while (0)
-#else
-#define GMR1_DSTAMP(dp, k, lane) do { } while (0)
-#endif
-
-template <bool ACC = false>
-__device__ void decode4_k5_12(const uint32_t *__restrict__ bm, uint64_t *__restrict__ surv,
-                              uint32_t *__restrict__ ubits, int lane, uint32_t &syn_o, uint32_t &final_ae,
-                              const DecPre *dp = nullptr)
-{
-	typedef __attribute__((address_space(3))) const unsigned char lds_cbyte;
-	const int row = lane >> 4;
-	const uint32_t loc = (uint32_t)lane & 15u;
-	// per-location constants (c_dec): cost byte of the own / partner transition per phase, tb pattern
-	const uint32_t dc = dp ? dp->dc : c_dec.v[loc];
-	const uint32_t row_base = (uint32_t)(uintptr_t)(lds_cbyte *)(bm + row * kSteps12);
-	uint32_t ao[4], ap[4];      // LDS byte address of this lane's own / partner cost in step 0 of the phase
-	bool hi[4];
-#pragma unroll
-	for (int ph = 0; ph < 4; ph++) {
-		ao[ph] = row_base + ((dc >> (2 * ph)) & 3u);
-		ap[ph] = row_base + ((dc >> (8 + 2 * ph)) & 3u);
-		hi[ph] = ((dc >> (16 + ph)) & 1u) != 0;
-	}
-	// cost << 16 of the own / partner transition, per window position (low halves stay zero whether
-	// or not the d16 load preserves them)
-	uint32_t R[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, Q[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-	uint32_t T[16];             // tie-break / decision bit of the position: set in HIGH-predecessor lanes
-#pragma unroll
-	for (int j = 0; j < 16; j++)
-		T[j] = (dc >> 16) & (1u << j);
-	uint32_t w = (loc ? (ACC ? kAccLeadK5r2 << 16 : kSentinel) : 0u) | T[0];
-	uint32_t t1, t2;
-	uint16_t *dump = reinterpret_cast<uint16_t *>(surv) + lane;
-
-	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-	// steps 0..3: the decisions are u[-4..-1], dropped
-	ACS_LOAD(0, 0, 0); ACS_LOAD(1, 1, 1); ACS_LOAD(2, 2, 2); ACS_LOAD(3, 3, 3);
-	ACS_NP(0, 0, 6, T[1]); ACS_NP(1, 1, 4, T[2]); ACS_NP(2, 2, 2, T[3]); ACS_NP_END(3, 3, 0);
-	w = (w & 0xffff0000u) | T[0];
-#pragma unroll
-	for (int ph = 0; ph < 4; ph++) {
-		ao[ph] += 16;
-		ap[ph] += 16;
-	}
-	// window pipeline: the costs of 8 steps are always in flight
-	ACS_LOAD(0, 0, 0); ACS_LOAD(1, 1, 1); ACS_LOAD(2, 2, 2); ACS_LOAD(3, 3, 3);
-	ACS_LOAD(4, 0, 4); ACS_LOAD(5, 1, 5); ACS_LOAD(6, 2, 6); ACS_LOAD(7, 3, 7);
-#pragma unroll 1
-	for (int m = 0; m < 12; m++) {
-		ACS_PF(0, 0, 14, T[1]); ACS_PF(1, 1, 14, T[2]); ACS_PF(2, 2, 14, T[3]); ACS_PF(3, 3, 14, T[4]);
-		ACS_PF(4, 0, 14, T[5]); ACS_PF(5, 1, 14, T[6]); ACS_PF(6, 2, 14, T[7]); ACS_PF(7, 3, 14, T[8]);
-		ACS_PF(8, 0, 14, T[9]); ACS_PF(9, 1, 14, T[10]); ACS_PF(10, 2, 14, T[11]); ACS_PF(11, 3, 14, T[12]);
-		ACS_PF(12, 0, 14, T[13]); ACS_PF(13, 1, 14, T[14]); ACS_PF(14, 2, 14, T[15]); ACS_PF_END(15, 3, 14);
-		dump[m * 64] = (uint16_t)w;
-		w = (w & 0xffff0000u) | T[0];
-#pragma unroll
-		for (int ph = 0; ph < 4; ph++) {
-			ao[ph] += 64;
-			ap[ph] += 64;
-		}
-	}
-	// window 12: steps 196..211, the last four are the flush (b = 0 transitions only: the lanes
-	// whose new state ends in 1 become unreachable)
-	ACS_PF(0, 0, 14, T[1]); ACS_PF(1, 1, 14, T[2]); ACS_PF(2, 2, 14, T[3]); ACS_PF(3, 3, 14, T[4]);
-	ACS_PF(4, 0, 14, T[5]); ACS_PF(5, 1, 14, T[6]); ACS_PF(6, 2, 14, T[7]); ACS_PF(7, 3, 14, T[8]);
-	ACS_NP(8, 0, 14, T[9]); ACS_NP(9, 1, 12, T[10]); ACS_NP(10, 2, 10, T[11]); ACS_NP(11, 3, 8, T[12]);
-	if constexpr (ACC) {
-		ACS_NP(12, 0, 6, T[13]); ACS_NP(13, 1, 4, T[14]); ACS_NP(14, 2, 2, T[15]); ACS_NP_END(15, 3, 0);
-		(void)hi;
-	} else {
-		ACS_NP_END(12, 0, 6);
-		w = hi[0] ? kSentinel : (w + T[13]);
-		ACS_NP_END(13, 1, 4);
-		w = hi[1] ? kSentinel : (w + T[14]);
-		ACS_NP_END(14, 2, 2);
-		w = hi[2] ? kSentinel : (w + T[15]);
-		ACS_NP_END(15, 3, 0);
-		w = hi[3] ? kSentinel : w;
-	}
-	dump[12 * 64] = (uint16_t)w;
-	// state 0 ends in location 0 of the row; osmo_conv_decode_acc returns 0, not a metric
-	final_ae = ACC ? 0u : w >> 16;
-	k5_12_survivors_crc(surv, ubits, lane, syn_o, dp);
-}
-
-// The K=5 rate-1/2 decoder shaped for the LATENCY of one burst (the receive loop: a wave alone on its SIMD issues one
-// instruction every four to five cycles whatever the dependences, so a round costs what its instruction count says).
-// The batch decoder above spends 7 instructions per trellis step (wait, add, add-dpp, min, add of the next tie-break bit, two
-// cost-byte reads).  Here a step's operands come ready-made from a table the branch-metric phase expands once per burst:
-// per step and code word two 8-byte entries (this lane the HIGH predecessor or not) -- both generators have the D^0 and D^4
-// taps, so the partner's code word is the own one's complement -- holding  own cost << 16 | tie-break bit if this lane is the
-// HIGH predecessor,  partner's cost << 16 | tie-break bit if the partner is.  One ds_read_b64 and three VALU per step: 5
-// instructions.  212 x 64 B of LDS, which only the loop (one burst per work-group) can afford.  Arithmetic, ties and
-// decisions are the batch decoder's.
-static constexpr bool dec_partner_is_complement()
-{
-	const DecTable t = make_dec();
-	for (int loc = 0; loc < 16; loc++)
-		for (int ph = 0; ph < 4; ph++)
-			if (((t.v[loc] >> (8 + 2 * ph)) & 3u) != (((t.v[loc] >> (2 * ph)) & 3u) ^ 3u))
-				return false;
-	return true;
-}
-static_assert(dec_partner_is_complement(), "the partner transition's code word must be the own one's complement");
-typedef uint32_t lat_u32x2 __attribute__((ext_vector_type(2)));
-constexpr int kLatTabBytes = kSteps12 * 64;
-#define ACSL_CORE(PH)                                                                              \
-	".if %[wt] >= 0\n\t"                                                                            \
-	"s_waitcnt lgkmcnt(%[wt])\n\t"                                                                  \
-	".endif\n\t"                                                                                    \
-	"v_add_u32 %[t1], %[w], %[r]\n\t"                                                               \
-	"v_add_u32_dpp %[t2], %[w], %[q] " GMR1_DPP_PH##PH " row_mask:0xf bank_mask:0xf\n\t"            \
-	"v_min_u32 %[w], %[t1], %[t2]\n\t"
-#define ACSL_PF(J, PH, WAIT)                                                                       \
-	asm volatile(ACSL_CORE(PH)                                                                     \
-	             "ds_read_b64 %[rqn], %[a] offset:%[off]\n\t"                                       \
-	             : [w] "+v"(w), [rqn] "=v"(RQ[((J) + 8) & 15]), [t1] "=&v"(t1), [t2] "=&v"(t2)        \
-	             : [r] "v"(RQ[J].x), [q] "v"(RQ[J].y), [a] "v"(A[PH]), [off] "i"(16 * ((J) + 8)), [wt] "i"(WAIT))
-#define ACSL_NP(J, PH, WAIT)                                                                       \
-	asm volatile(ACSL_CORE(PH)                                                                     \
-	             : [w] "+v"(w), [t1] "=&v"(t1), [t2] "=&v"(t2)                                       \
-	             : [r] "v"(RQ[J].x), [q] "v"(RQ[J].y), [wt] "i"(WAIT))
-#define ACSL_LOAD(J, PH, K)                                                                        \
-	asm volatile("ds_read_b64 %[rqn], %[a] offset:%[off]\n\t" : [rqn] "=v"(RQ[J]) : [a] "v"(A[PH]), [off] "i"(16 * (K)))
-
-// one step's eight entries from its cost word (byte j = cost of code word j): cls = 2 * code word + HIGH
-__device__ __forceinline__ void lat_expand_step(uint32_t *__restrict__ tab, int k, uint32_t word)
-{
-	const uint32_t bit = 1u << (k < 4 ? k : ((k - 4) & 15));
-	const uint32_t c0 = (word << 16) & 0x00ff0000u, c1 = (word << 8) & 0x00ff0000u, c2 = word & 0x00ff0000u,
-	               c3 = (word >> 8) & 0x00ff0000u;
-	// code-word-major ([j][step], 16 bytes each: not HIGH {c_j, c_(3-j) | bit}, HIGH {c_j | bit, c_(3-j)}): lanes own
-	// consecutive steps, so a wave's 16-byte writes are consecutive in LDS (step-major they were 64 bytes apart: eight-way
-	// bank conflicts, 1 400 cycles)
-	uint4 *d = reinterpret_cast<uint4 *>(tab) + k;
-	d[0 * kSteps12] = make_uint4(c0, c3 | bit, c0 | bit, c3);
-	d[1 * kSteps12] = make_uint4(c1, c2 | bit, c1 | bit, c2);
-	d[2 * kSteps12] = make_uint4(c2, c1 | bit, c2 | bit, c1);
-	d[3 * kSteps12] = make_uint4(c3, c0 | bit, c3 | bit, c0);
-}
-
-// TAIL = false: the forward pass alone -- window words to `surv`, the final metric returned; the survivor walk and the CRC
-// (k5_12_survivors_crc_lat) are the caller's, on another wave (k_rx_chain_pipe)
-template <bool ACC = false, bool TAIL = true>
-__device__ void decode1_k5_12_lat(const uint32_t *__restrict__ tab, uint64_t *__restrict__ surv,
-                                  uint32_t *__restrict__ ubits, int lane, uint32_t &syn_o, uint32_t &final_ae,
-                                  const DecPre *dp)
-{
-	typedef __attribute__((address_space(3))) const unsigned char lds_cbyte;
-	const uint32_t loc = (uint32_t)lane & 15u;
-	const uint32_t dc = dp->dc;
-	const uint32_t base = (uint32_t)(uintptr_t)(lds_cbyte *)tab;
-	uint32_t A[4];              // LDS byte address of this lane's entry in step 0 of the phase
-	bool hi[4];
-#pragma unroll
-	for (int ph = 0; ph < 4; ph++) {
-		hi[ph] = ((dc >> (16 + ph)) & 1u) != 0;
-		A[ph] = base + (uint32_t)(kSteps12 * 16) * ((dc >> (2 * ph)) & 3u) + (hi[ph] ? 8u : 0u);
-	}
-	lat_u32x2 RQ[16];
-	uint32_t w = loc ? (ACC ? kAccLeadK5r2 << 16 : kSentinel) : 0u;
-	uint32_t t1, t2;
-	uint16_t *dump = reinterpret_cast<uint16_t *>(surv) + lane;
-
-	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-	// steps 0..3: the decisions are u[-4..-1], dropped
-	ACSL_LOAD(0, 0, 0); ACSL_LOAD(1, 1, 1); ACSL_LOAD(2, 2, 2); ACSL_LOAD(3, 3, 3);
-	ACSL_NP(0, 0, 3); ACSL_NP(1, 1, 2); ACSL_NP(2, 2, 1); ACSL_NP(3, 3, 0);
-	w &= 0xffff0000u;
-#pragma unroll
-	for (int ph = 0; ph < 4; ph++)
-		A[ph] += 4 * 16;
-	// window pipeline: the operands of 8 steps are always in flight
-	ACSL_LOAD(0, 0, 0); ACSL_LOAD(1, 1, 1); ACSL_LOAD(2, 2, 2); ACSL_LOAD(3, 3, 3);
-	ACSL_LOAD(4, 0, 4); ACSL_LOAD(5, 1, 5); ACSL_LOAD(6, 2, 6); ACSL_LOAD(7, 3, 7);
-#pragma unroll 1
-	for (int m = 0; m < 12; m++) {
-		// (one wait per four steps: eight loads are in flight, the four oldest must have landed)
-		ACSL_PF(0, 0, 4); ACSL_PF(1, 1, -1); ACSL_PF(2, 2, -1); ACSL_PF(3, 3, -1);
-		ACSL_PF(4, 0, 4); ACSL_PF(5, 1, -1); ACSL_PF(6, 2, -1); ACSL_PF(7, 3, -1);
-		ACSL_PF(8, 0, 4); ACSL_PF(9, 1, -1); ACSL_PF(10, 2, -1); ACSL_PF(11, 3, -1);
-		ACSL_PF(12, 0, 4); ACSL_PF(13, 1, -1); ACSL_PF(14, 2, -1); ACSL_PF(15, 3, -1);
-		dump[m * 64] = (uint16_t)w;
-		w &= 0xffff0000u;
-#pragma unroll
-		for (int ph = 0; ph < 4; ph++)
-			A[ph] += 16 * 16;
-	}
-	// window 12: steps 196..211, the last four are the flush (generic decoder: b = 0 transitions only -- the lanes whose new
-	// state ends in 1 become unreachable)
-	ACSL_PF(0, 0, 4); ACSL_PF(1, 1, -1); ACSL_PF(2, 2, -1); ACSL_PF(3, 3, -1);
-	ACSL_PF(4, 0, 4); ACSL_PF(5, 1, -1); ACSL_PF(6, 2, -1); ACSL_PF(7, 3, -1);
-	ACSL_NP(8, 0, 4); ACSL_NP(9, 1, -1); ACSL_NP(10, 2, -1); ACSL_NP(11, 3, -1);
-	if constexpr (ACC) {
-		ACSL_NP(12, 0, 0); ACSL_NP(13, 1, -1); ACSL_NP(14, 2, -1); ACSL_NP(15, 3, -1);
-		(void)hi;
-	} else {
-		ACSL_NP(12, 0, 0);
-		w = hi[0] ? kSentinel : w;
-		ACSL_NP(13, 1, -1);
-		w = hi[1] ? kSentinel : w;
-		ACSL_NP(14, 2, -1);
-		w = hi[2] ? kSentinel : w;
-		ACSL_NP(15, 3, -1);
-		w = hi[3] ? kSentinel : w;
-	}
-	dump[12 * 64] = (uint16_t)w;
-	final_ae = ACC ? 0u : w >> 16;
-	GMR1_DSTAMP(dp, 12, lane);
-	if constexpr (TAIL)
-		k5_12_survivors_crc_lat(surv, ubits, lane, syn_o, dp);
-	else
-		syn_o = 0;
-}
-
-// Tail of the decoder shaped for the LATENCY of one burst (the receive loop: one burst per wave, nothing to overlap with):
-// the 13 window words of every location are read at once and the survivor chain is walked with v_readlane on scalars --
-// 13 dependent LDS round trips become one.  Row 0 only; the CRC as in k5_12_survivors_crc.
-__device__ __forceinline__ void k5_12_survivors_crc_lat(uint64_t *__restrict__ surv, uint32_t *__restrict__ ubits, int lane,
-                                                        uint32_t &syn_o, const DecPre *dp)
-{
-	const int row = lane >> 4;
-	const uint32_t loc = (uint32_t)lane & 15u;
-	WSYNC();
-	// survivor chain of row 0: every location's 13 window words at once, then the walk on scalars
-	{
-		constexpr unsigned long long kLocOf =
-			0x0ull | (0x8ull << 4) | (0x7ull << 8) | (0xFull << 12) | (0x2ull << 16) | (0xAull << 20) |
-			(0x5ull << 24) | (0xDull << 28) | (0x1ull << 32) | (0x9ull << 36) | (0x6ull << 40) |
-			(0xEull << 44) | (0x3ull << 48) | (0xBull << 52) | (0x4ull << 56) | (0xCull << 60);
-		const uint16_t *d16 = reinterpret_cast<const uint16_t *>(surv) + loc;      // (rows 1-3 read row 0's words too)
-		uint32_t H[13];
-#pragma unroll
-		for (int m = 0; m < 13; m++)
-			H[m] = d16[m * 64];
-		uint32_t L = 0, hv[13];
-#pragma unroll
-		for (int m = 12; m >= 0; m--) {
-			hv[m] = (uint32_t)__builtin_amdgcn_readlane((int)H[m], (int)L);
-			L = (uint32_t)(kLocOf >> (4 * (hv[m] & 15u))) & 15u;
-		}
-		if (lane == 0) {
-#pragma unroll
-			for (int m = 0; m < 13; m += 2)
-				ubits[m >> 1] = hv[m] | (m == 12 ? 0u : (hv[m + 1] << 16));
-		}
-	}
-	WSYNC();
-	GMR1_DSTAMP(dp, 13, lane);
-	// CRC16 over the 208 decoded bits, 13 bits per lane of the row, XOR-reduced with DPP (as in k5_12_survivors_crc)
-	uint32_t syn = 0;
-	{
-		const uint32_t *ub = ubits + row * 8;
-		const uint32_t k0 = loc * 13u;
-		const uint32_t lo = ub[k0 >> 5], hi2 = ub[(k0 >> 5) + 1];
-		const uint32_t cbits = __builtin_amdgcn_alignbit(hi2, lo, k0 & 31u);
-		const uint32_t sy[7] = {dp->sy0.x, dp->sy0.y, dp->sy0.z, dp->sy0.w, dp->sy1.x, dp->sy1.y, dp->sy1.z};
-		uint32_t acc = 0;
-#pragma unroll
-		for (int pq = 0; pq < 7; pq++) {
-			const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)cbits, 2 * pq, 1);
-			const uint32_t m1 = pq < 6 ? (uint32_t)__builtin_amdgcn_sbfe((int)cbits, 2 * pq + 1, 1) : 0u;
-			acc ^= sy[pq] & ((m0 & 0xffffu) | (m1 & 0xffff0000u));
-		}
-		syn = (acc ^ (acc >> 16)) & 0xffffu;
-		syn ^= row_xor<1>(syn);
-		syn ^= row_xor<2>(syn);
-		syn ^= row_xor<4>(syn);
-		syn ^= row_xor<8>(syn);
-	}
-	syn_o = syn;
-}
-
-// second half of the decoder: survivor chain and CRC16 of the four rows (shared with the 16-bit-lane forward pass below)
-__device__ __forceinline__ void k5_12_survivors_crc(uint64_t *__restrict__ surv, uint32_t *__restrict__ ubits, int lane,
-                                                    uint32_t &syn_o, const DecPre *dp)
-{
-	const int row = lane >> 4;
-	const uint32_t loc = (uint32_t)lane & 15u;
-	// this lane's CRC syndrome words travel while the survivor chain is walked
-	const uint4 sy0 = dp ? dp->sy0 : *reinterpret_cast<const uint4 *>(&c_syn_rows.w[loc][0]);
-	const uint4 sy1 = dp ? dp->sy1 : *reinterpret_cast<const uint4 *>(&c_syn_rows.w[loc][4]);
-	WSYNC();
-
-	// survivor chain, one lane per row: window m's decisions at the survivor's location are the
-	// decoded bits u[16 m ..]; their low nibble (u[16m-4 .. 16m-1] seen from window m) is the state
-	// at the start of the window, bit-reversed: h0 -> state bit 3 -> basis vector 8, h1 -> 7,
-	// h2 -> 2, h3 -> 1  (osmo_conv_decode_get_output, end state 0 after flush)
-	if (loc == 0) {
-		const uint16_t *d16 = reinterpret_cast<const uint16_t *>(surv) + row * 16;
-		// location of the state whose reversed nibble is x, x = 0..15
-		constexpr unsigned long long kLocOf =
-			0x0ull | (0x8ull << 4) | (0x7ull << 8) | (0xFull << 12) | (0x2ull << 16) | (0xAull << 20) |
-			(0x5ull << 24) | (0xDull << 28) | (0x1ull << 32) | (0x9ull << 36) | (0x6ull << 40) |
-			(0xEull << 44) | (0x3ull << 48) | (0xBull << 52) | (0x4ull << 56) | (0xCull << 60);
-		uint32_t L = 0;
-		uint32_t prev = 0;
-#pragma unroll
-		for (int m = 12; m >= 0; m--) {
-			const uint32_t h = d16[m * 64 + L];
-			L = (uint32_t)(kLocOf >> (4 * (h & 15u))) & 15u;
-			if (m & 1)
-				prev = h;
-			else
-				ubits[row * 8 + (m >> 1)] = h | (m == 12 ? 0u : (prev << 16));
-		}
-	}
-	WSYNC();
-
-	// CRC16 over the 208 decoded bits, 13 bits per lane of the row, XOR-reduced with DPP
-	uint32_t syn = 0;
-	{
-		const uint32_t *ub = ubits + row * 8;
-		const uint32_t k0 = loc * 13u;
-		const uint32_t lo = ub[k0 >> 5], hi2 = ub[(k0 >> 5) + 1];      // word 7 of a row is never a data word
-		const uint32_t cbits = __builtin_amdgcn_alignbit(hi2, lo, k0 & 31u);
-		const uint32_t sy[7] = {sy0.x, sy0.y, sy0.z, sy0.w, sy1.x, sy1.y, sy1.z};
-		uint32_t acc = 0;
-#pragma unroll
-		for (int pq = 0; pq < 7; pq++) {
-			const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)cbits, 2 * pq, 1);
-			const uint32_t m1 = pq < 6 ? (uint32_t)__builtin_amdgcn_sbfe((int)cbits, 2 * pq + 1, 1) : 0u;
-			acc ^= sy[pq] & ((m0 & 0xffffu) | (m1 & 0xffff0000u));
-		}
-		syn = (acc ^ (acc >> 16)) & 0xffffu;
-		syn ^= row_xor<1>(syn);
-		syn ^= row_xor<2>(syn);
-		syn ^= row_xor<4>(syn);
-		syn ^= row_xor<8>(syn);
-	}
-	syn_o = syn;
-}
-
-__device__ __forceinline__ void store_l2(uint8_t *l2, const uint32_t *ub)
-{
-	uint32_t *l2w = reinterpret_cast<uint32_t *>(l2);
-#pragma unroll
-	for (int i = 0; i < 6; i++)
-		l2w[i] = ub[i];
-}
-
-// ---------------------------------------------------------------------------
-// kernels
-// ---------------------------------------------------------------------------
-template <int NPL, int SPS, bool DECODE, bool ACC = false>
-__global__ __launch_bounds__(64) void k_rx(RxArgs a, int max_in_len, int max_len)
-{
-	extern __shared__ __align__(16) unsigned char lds_raw[];
-	const int lane = threadIdx.x;
-	const Lds L = lds_carve(lds_raw, max_in_len, max_len, DECODE);
-
-	constexpr int PER = DECODE ? 4 : 1;
-	int g0 = blockIdx.x * PER;
-	int n_end = a.n;
-	if (DECODE && a.seg_count) {
-		// the receive loop's CCCH lists (see k_rx4): segments with unused slots, one time slice of each per launch
-		int sg = g0 / a.seg_stride;
-		int lo = 0;
-		if (a.seg_first) {
-			if (a.seg_groups > 0) {
-				sg = (int)blockIdx.x / a.seg_groups;
-				lo = (a.seg_first[sg] + 3) & ~3;
-				g0 = sg * a.seg_stride + lo + ((int)blockIdx.x % a.seg_groups) * PER;
-			} else {
-				lo = (a.seg_first[sg] + 3) & ~3;
-			}
-		}
-		const int base = sg * a.seg_stride;
-		n_end = min(min(a.n, g0 + PER), base + min(a.seg_count[sg], a.seg_stride));
-		if (g0 >= n_end || g0 < base + lo)
-			return;
-	}
-	int row_ok = 0;       // bit q: burst q of this wave demodulated fine
-	int row_chain = 0;    // bit q: burst q is CCCH
-
-	for (int q = 0; q < PER; q++) {
-		const int g = g0 + q;
-		if (g >= n_end)
-			break;
-		int type, in_len;
-		if (DECODE) {
-			const int kind = a.kind[g] ? 1 : 0;
-			type = kind ? GMR1_HIP_DC6 : GMR1_HIP_BCCH;
-			in_len = a.in_len[kind];
-			row_chain |= kind << q;
-		} else {
-			type = a.fixed_type;
-			in_len = a.in_len[0];
-		}
-		type = __builtin_amdgcn_readfirstlane(type);
-		in_len = __builtin_amdgcn_readfirstlane(in_len);
-		const float fsh = a.freq_shift ? a.freq_shift[g] : 0.0f;
-		int sid = -1;
-		float toa = 0.f, fe = 0.f;
-		float *gss = a.ssyms ? a.ssyms + (size_t)g * a.ssyms_stride : nullptr;
-		int8_t *eb = L.eb + (DECODE ? q * kEbRow : 0);
-
-		WSYNC();
-		const int rv = demod_one<NPL, SPS>(type, a.iq + a.offset[g], in_len, a.sps, fsh, L, eb, lane,
-		                                   a.dbg_stop, sid, toa, fe, gss);
-		if (rv == -100)
-			continue;    // profiling build-out: phase cut-off
-		if (a.energy) {
-			const float e = window_energy<NPL>(a.iq + a.offset[g], in_len, lane);
-			if (lane == 0)
-				a.energy[g] = e;
-		}
-
-		if (lane == 0) {
-			a.rv[g] = rv;
-			if (a.sync_id) a.sync_id[g] = sid;
-			if (a.toa) a.toa[g] = rv ? 0.f : toa;
-			if (a.freq_err) a.freq_err[g] = rv ? 0.f : fe;
-		}
-		if (a.ebits) {
-			const int neb = c_types[type].ebits;
-			int8_t *ge = a.ebits + (size_t)g * a.ebits_stride;
-			for (int i = lane; i < a.ebits_stride; i += 64)
-				ge[i] = (rv == 0 && i < neb) ? eb[i] : (int8_t)0;
-		}
-		if (rv && gss)
-			for (int i = lane; i < c_types[type].len; i += 64)
-				gss[i] = 0.f;
-		if (rv == 0)
-			row_ok |= 1 << q;
-	}
-
-	if (DECODE) {
-		if (a.dbg_stop && a.dbg_stop < 7)
-			return;
-		WSYNC();     // x is dead from here on: bm / surv / ubits overlay it
-		for (int q = 0; q < 4; q++) {
-			if ((row_ok >> q) & 1) {
-				branch_metrics_k5_12<ACC>(L.eb + q * kEbRow, (row_chain >> q) & 1, L.bm + q * kSteps12, lane);
-			} else {
-				for (int k = lane; k < kSteps12; k += 64)
-					L.bm[q * kSteps12 + k] = 0;
-			}
-		}
-		WSYNC();
-		if (a.dbg_stop == 7)
-			return;
-		uint32_t syn, fae;
-		decode4_k5_12<ACC>(L.bm, L.surv, L.ubits, lane, syn, fae);
-		const int row = lane >> 4;
-		const int g = g0 + row;
-		if ((lane & 15) == 0 && g < n_end) {
-			if ((row_ok >> row) & 1) {
-				store_l2(a.l2 + (size_t)g * 24, L.ubits + row * 8);
-				a.crc[g] = syn ? 1 : 0;
-				a.conv[g] = (int32_t)fae;
-			} else {
-				uint32_t *l2w = reinterpret_cast<uint32_t *>(a.l2 + (size_t)g * 24);
-#pragma unroll
-				for (int i = 0; i < 6; i++)
-					l2w[i] = 0;
-				a.crc[g] = -1;
-				a.conv[g] = 0;
-			}
-		}
-	}
-}
+#include "rx_one.h"
 
 // ---------------------------------------------------------------------------
 // k_rx4 -- fused BCCH / CCCH receive, four bursts per wavefront, with the serial phases
@@ -1868,21 +153,7 @@ hipError_t upload_types(const DevBurst *host, int first, int count, hipStream_t 
 // (re, im) per tap -- read straight from the table with scalar loads when no frequency shift was given (`ctab`), else
 // out of lane n of `cfl` (v_readlane) -- and feed the packed FMAs as scalar operands, so a tap costs one LDS read and two
 // v_pk_fma_f32, all reads of a lag issued back to back.  xs: the staged chunk windows, window c = samples
-// [pos_c sps, pos_c sps + T_c sps + w - 1).  corr[j] = sum over chunks of |sum_n c_n x[j + n sps]|.
-//
-// (ar, ai) += c x as two packed FMAs: (-c.im x.im, c.im x.re) first, then c.re (x.re, x.im) -- the order of the scalar
-// chains ar = fma(c.re, x.re, fma(-c.im, x.im, ar)), ai = fma(c.re, x.im, fma(c.im, x.re, ai)).  Written out with the
-// operand selects and the sign on the ONE pair: the compiler builds (-c.im, c.im) and (c.re, c.re) as pairs of their own,
-// four scalar registers a tap, and spills what they displace.  (s_nop: a packed result needs one wait state before its
-// next use, which the compiler's own sequences carry as well.)
-__device__ __forceinline__ void pk_cmac(v2f &acc, unsigned long long c, v2f x)
-{
-	asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\ts_nop 0\n\t"
-	    "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\ts_nop 0"
-	    : "+v"(acc)
-	    : "s"(c), "v"(x));
-}
-
+// [pos_c sps, pos_c sps + T_c sps + w - 1).  corr[j] = sum over chunks of |sum_n c_n x[j + n sps]|.  (pk_cmac: fast_math.h)
 // (lags [j_begin, j_end) of the w there are; j_end < 0: all)
 // (best / best_j, optional: the largest magnitude among this lane's lags and its lag -- rx4_body's QX speculates on it)
 template <int SPS, int T0, int T1, int T2>
@@ -1988,15 +259,6 @@ __host__ __device__ inline int stage_samples_of(const DevBurst &bt, int sps, int
 	return n;
 }
 
-// 64-bit max within each 16-lane row
-template <int X>
-__device__ __forceinline__ unsigned long long row_max_u64(unsigned long long k)
-{
-	const uint32_t lo = row_xor<X>((uint32_t)k), hi = row_xor<X>((uint32_t)(k >> 32));
-	const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-	return o > k ? o : k;
-}
-
 // The body works on bursts g0 .. n_end-1 (at most four) of `a` with one wavefront and its own LDS slice;
 // k_rx4 is the batch kernel around it, k_rx_chain (below) the receive loop's feedback chain that calls it round after round.
 // per-burst arrays of a launch: the batch kernel takes them from its arguments, the receive loop points them
@@ -2081,20 +343,6 @@ struct LoopCo {                    // front wave <-> helper wave, within a tick 
 	float tail[64];                // the correlation of the last partial round of lags (F copies it in: a front that was
 	                               // squashed meanwhile never looks at it)
 };
-// (bounded: a wave that gives up does the work itself -- no hand-shake can hang the work-group)
-__device__ __forceinline__ bool lds_wait_eq(const int *flag, int want)
-{
-	for (int i = 0; i < (1 << 16); i++) {
-		if (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == want)
-			return true;
-		__builtin_amdgcn_s_sleep(1);
-	}
-	return false;
-}
-__device__ __forceinline__ void lds_post(int *flag, int v)
-{
-	__hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 template <int NPL, int SPS>
 struct LatPre {
@@ -2314,6 +562,7 @@ __device__ __forceinline__ void lat_prepare(const RxArgs &a, uint64_t off, int k
 	}
 }
 
+// The burst body's configuration: a type with these members; the kernels name theirs below, Rx4Cfg holds the defaults.
 // LAT: the caller cares about the latency of ONE burst (the receive loop), not about throughput
 // GEN: demodulation only, every burst of the one format a.fixed_type (one training sequence, QPSK, <= 3 sync chunks,
 // <= 18 sync symbols, <= 256 symbols: NT3 speech, DC2, BCCH, DC6) -- the batch form of gmr1_pi4cxpsk_demod for large n
@@ -2336,29 +585,80 @@ __device__ __forceinline__ void lat_prepare(const RxArgs &a, uint64_t off, int k
 // PART (LAT only): 0 the whole burst; 1 its front -- pass 1, timing, sync-symbol terms; rv / toa / freq_err / energy to
 // `io`, the rest of what the middle needs to pre->cut --; 2 its middle -- pass 2 out of pre->win_r, then the decoder's
 // operand table into pre->vtab; the decoder itself is the caller's third stage (see LatPre (3))
-template <int NPL, int SPS, bool LAT = false, bool GEN = false, bool FAC = false, bool ACC = false, bool EN = true, bool PL = false,
-          int EBROW = 432, int PART = 0>
-__device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int stage_samples, int cw, int g0, int n_end,
-                                         unsigned char *__restrict__ lds_raw, int lane, LatPre<NPL, SPS> *pre = nullptr)
-{
-	const int row = lane >> 4, col = lane & 15;
-	const int sps = SPS ? SPS : a.sps;
+struct Rx4Cfg {
+	static constexpr int NPL = 16, SPS = 4;            // window samples per lane / 64; samples per symbol (0: a.sps at run time)
+	static constexpr bool LAT = false, GEN = false, FAC = false, ACC = false, EN = true, PL = false;
+	static constexpr int EBROW = 432, PART = 0;
+};
+// the fused batch kernel (k_rx4; k_one_server runs the same body on one burst)
+template <int NPL_, int SPS_, bool ACC_, bool EN_, bool PL_ = false>
+struct CfgBatch : Rx4Cfg {
+	static constexpr int NPL = NPL_, SPS = SPS_;
+	static constexpr bool ACC = ACC_, EN = EN_, PL = PL_;
+};
+// demodulation only (k_rx4g): generic, small (NPL 8) and two-sequence (FAC) forms
+template <int NPL_, int SPS_, bool FAC_>
+struct CfgDemod : Rx4Cfg {
+	static constexpr int NPL = NPL_, SPS = SPS_;
+	static constexpr bool GEN = true, FAC = FAC_;
+};
+// the small demodulator in front of the TCH3 decoder (k_rx4g_tch3): soft-bit rows packed at 216 bytes
+struct CfgTch3Front : Rx4Cfg {
+	static constexpr int NPL = 8, SPS = 4, EBROW = 216;
+	static constexpr bool GEN = true;
+};
+// the receive loop's BCCH burst: whole (PART 0, k_rx_chain) or one pipeline stage of it (k_rx_chain_pipe)
+template <int NPL_, int SPS_, bool ACC_, int PART_ = 0>
+struct CfgLoop : Rx4Cfg {
+	static constexpr int NPL = NPL_, SPS = SPS_, PART = PART_;
+	static constexpr bool LAT = true, ACC = ACC_;
+};
+
+// what follows from a configuration P
+template <class P>
+struct Rx4Switches : P {
 	// the small generic variant (NPL = 8; the host launches it for formats of <= 128 symbols with one sync chunk of
 	// <= 16 symbols whose window is <= 64 samples: NT3 speech, DC2) drops the unrolled work the long bursts need
-	constexpr bool SMALL = GEN && NPL == 8;
-	static_assert(!FAC || SMALL, "the two-sequence variant builds on the small generic one");
-	static_assert(!PL || (SPS == 4 && !GEN && !LAT && !EN), "the planar layout exists for the fused batch kernel at sps 4");
-	static_assert(PART == 0 || LAT, "only the receive loop's burst is cut in two");
-	const int cwh = FAC ? cw / 2 : cw;                // lags per correlation array
+	static constexpr bool SMALL = P::GEN && P::NPL == 8;
+	static_assert(!P::FAC || SMALL, "the two-sequence variant builds on the small generic one");
+	static_assert(!P::PL || (P::SPS == 4 && !P::GEN && !P::LAT && !P::EN), "the planar layout exists for the fused batch kernel at sps 4");
+	static_assert(P::PART == 0 || P::LAT, "only the receive loop's burst is cut in two");
 	// The next burst's window in flight during this burst's correlation costs 32 registers at the body's peak.  The fused
 	// kernel does without: 78 instead of 87 VGPRs is the step from five to six waves per SIMD, and the sixth wave hides more
 	// latency than the prefetch did (0.288 -> 0.274 ms per 100 k bursts).  The other instantiations keep it.
-	constexpr bool PREFETCH_NEXT = GEN || LAT;
-	constexpr int NSYM = SMALL ? 2 : 4;               // 64-symbol pieces of a burst
-	constexpr int NCHK = SMALL ? 1 : 3;               // sync chunks
-	constexpr int NSH = SMALL ? 1 : 2;                // 16-symbol pieces of the sync sequence
+	static constexpr bool PREFETCH_NEXT = P::GEN || P::LAT;
+	static constexpr int NSYM = SMALL ? 2 : 4;               // 64-symbol pieces of a burst
+	static constexpr int NCHK = SMALL ? 1 : 3;               // sync chunks
+	static constexpr int NSH = SMALL ? 1 : 2;                // 16-symbol pieces of the sync sequence
+	static constexpr bool UB_OVER = !P::LAT && !P::GEN;         // the decoded words go where the branch metrics were (lds4_layout)
+	// QL (the fused batch kernel at 4 samples per symbol, both sample layouts): the window sits in registers in the QUAD layout
+	// (window_fetch_q).  QX (interleaved samples): pass 2's kept samples never make a second trip to memory.  Right behind a
+	// burst's correlation its pick d = round(toa) is SPECULATED as the lag of the largest correlation magnitude (the timing
+	// rows below start their early / late walk on the strongest lag p of the best three-lag window and end within a lag of it,
+	// pi4cxpsk.c:240, so round(toa) is p - 1, p or p + 1, and p is the largest magnitude itself whenever the peak is clean);
+	// the 234 kept samples d + 4 i are then one sub-slot of every lane of the window registers, a lane rotation away from
+	// pass 2's assignment, and what pass 2 takes from a kept sample -- its phase -- is formed on the spot: four registers a
+	// burst instead of a window.  The timing rows then compute the pick as ever; a burst whose pick is NOT the speculated one
+	// (a few per cent: noise decides where toa lies half-way between two samples) takes the old route -- kept samples and sync
+	// symbols re-read from memory, the same operations on the same numbers -- so no output depends on the speculation.
+	static constexpr bool QL = !P::GEN && !P::LAT && !P::EN && P::SPS == 4 && P::NPL == 16;
+	static constexpr bool QX = QL && !P::PL;
+	static_assert(!P::PL || QL, "the planar layout exists for the fused batch kernel");
+};
+
+template <class Cfg>
+__device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int stage_samples, int cw, int g0, int n_end,
+                                         unsigned char *__restrict__ lds_raw, int lane, LatPre<Cfg::NPL, Cfg::SPS> *pre = nullptr)
+{
+	typedef Rx4Switches<Cfg> C;
+	constexpr int NPL = C::NPL, SPS = C::SPS, EBROW = C::EBROW, PART = C::PART;
+	constexpr bool LAT = C::LAT, GEN = C::GEN, FAC = C::FAC, ACC = C::ACC, EN = C::EN, PL = C::PL;
+	constexpr bool SMALL = C::SMALL, QL = C::QL, QX = C::QX, PREFETCH_NEXT = C::PREFETCH_NEXT, UB_OVER = C::UB_OVER;
+	constexpr int NSYM = C::NSYM, NCHK = C::NCHK, NSH = C::NSH;
+	const int row = lane >> 4, col = lane & 15;
+	const int sps = SPS ? SPS : a.sps;
+	const int cwh = FAC ? cw / 2 : cw;                // lags per correlation array
 	size_t off[4];
-	constexpr bool UB_OVER = !LAT && !GEN;
 	lds4_layout(stage_samples, cw, off, GEN, UB_OVER, EBROW);
 	Lds4 L;
 	L.x = reinterpret_cast<float2 *>(lds_raw + off[0]);
@@ -2375,19 +675,6 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 	float avr_r = 0.f, avi_r = 0.f;                    // window mean of this row's burst
 	const float2 *xst_lat = L.x;                       // LAT: where the one burst's sync-chunk windows are staged
 
-	// QL (the fused batch kernel at 4 samples per symbol, both sample layouts): the window sits in registers in the QUAD layout
-	// (window_fetch_q).  QX (interleaved samples): pass 2's kept samples never make a second trip to memory.  Right behind a
-	// burst's correlation its pick d = round(toa) is SPECULATED as the lag of the largest correlation magnitude (the timing
-	// rows below start their early / late walk on the strongest lag p of the best three-lag window and end within a lag of it,
-	// pi4cxpsk.c:240, so round(toa) is p - 1, p or p + 1, and p is the largest magnitude itself whenever the peak is clean);
-	// the 234 kept samples d + 4 i are then one sub-slot of every lane of the window registers, a lane rotation away from
-	// pass 2's assignment, and what pass 2 takes from a kept sample -- its phase -- is formed on the spot: four registers a
-	// burst instead of a window.  The timing rows then compute the pick as ever; a burst whose pick is NOT the speculated one
-	// (a few per cent: noise decides where toa lies half-way between two samples) takes the old route -- kept samples and sync
-	// symbols re-read from memory, the same operations on the same numbers -- so no output depends on the speculation.
-	constexpr bool QL = !GEN && !LAT && !EN && SPS == 4 && NPL == 16;
-	constexpr bool QX = QL && !PL;
-	static_assert(!PL || QL, "the planar layout exists for the fused batch kernel");
 	float th_q[QX ? 4 : 1][4];                         // QX: phase (turns) of kept sample lane + 64 r of burst q
 	uint32_t zm_q = 0xff000000u;                       // bit 4 q + r: that sample counts as 0 + 0j (outside the window, or zero);
 	                                                   // bits 24-31 (row q's lanes): burst q's speculated pick (0 ... 80; 255: none)
@@ -3606,7 +1893,6 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 			io.crc[g_row] = syn ? 1 : 0;
 			io.conv[g_row] = (int32_t)fae;
 		} else {
-
 			uint32_t *l2w = reinterpret_cast<uint32_t *>(io.l2 + (size_t)g_row * 24);
 #pragma unroll
 			for (int i = 0; i < 6; i++)
@@ -3660,7 +1946,7 @@ void k_rx4(RxArgs a, int stage_samples, int cw, int bpw)
 #endif
 	                 a.offset, a.kind, a.freq_shift, a.l2, a.crc, a.conv, a.rv, a.sync_id, a.toa, a.freq_err, a.energy,
 	                 a.ebits, a.ssyms};
-	rx4_body<NPL, SPS, false, false, false, ACC, EN, PL>(a, io, stage_samples, cw, g0, n_end, lds_raw, (int)threadIdx.x);
+	rx4_body<CfgBatch<NPL, SPS, ACC, EN, PL>>(a, io, stage_samples, cw, g0, n_end, lds_raw, (int)threadIdx.x);
 }
 
 // demodulation only, one burst format per launch, four bursts per wavefront (rx4_body<..., GEN>)
@@ -3675,7 +1961,7 @@ __global__ __launch_bounds__(64) void k_rx4g(RxArgs a, int stage_samples, int cw
 #endif
 	                 a.offset, nullptr, a.freq_shift, nullptr, nullptr, nullptr, a.rv, a.sync_id, a.toa, a.freq_err, a.energy,
 	                 a.ebits, a.ssyms};
-	rx4_body<NPL, SPS, false, true, FAC>(a, io, stage_samples, cw, g0, min(a.n, g0 + 4), lds_raw, (int)threadIdx.x);
+	rx4_body<CfgDemod<NPL, SPS, FAC>>(a, io, stage_samples, cw, g0, min(a.n, g0 + 4), lds_raw, (int)threadIdx.x);
 }
 
 // NT3 speech bursts from samples to speech frames in one launch (what rx_tch3 does with a burst, gmr1_rx.c:551-587:
@@ -3701,7 +1987,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRx4gTch3Wav
 	                 a.offset, nullptr, a.freq_shift, nullptr, nullptr, nullptr, a.rv, a.sync_id, a.toa, a.freq_err, a.energy,
 	                 a.ebits, a.ssyms};
 	constexpr int kRow = 216;                    // 212 soft bits + the zero a punctured position reads
-	rx4_body<8, 4, false, true, false, false, true, false, kRow>(a, io, stage_samples, cw, g0, n_end, lds_raw, lane);
+	static_assert(CfgTch3Front::EBROW == kRow, "the body's soft-bit rows are the decoder's");
+	rx4_body<CfgTch3Front>(a, io, stage_samples, cw, g0, n_end, lds_raw, lane);
 	// soft-bit rows of the four bursts at the front of the wave's LDS (kRow bytes apart), the decoder's tables behind them
 	t3::Tch3Lds *S = reinterpret_cast<t3::Tch3Lds *>(lds_raw + 4 * kRow);
 	WSYNC();
@@ -3717,231 +2004,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRx4gTch3Wav
 	}
 }
 
-// ---------------------------------------------------------------------------
-// burst type detection (reference src/sdr/pi4cxpsk.c:617-682 gmr1_pi4cxpsk_detect):
-// normalise once with the rotation of the first candidate type, run the sync search of
-// every candidate, weight the power by 1/|e_toa - toa|, keep the strongest.
-// ---------------------------------------------------------------------------
-template <int NPL, int SPS>
-__global__ __launch_bounds__(64) void k_detect(DetectArgs a, int max_in_len)
-{
-	extern __shared__ __align__(16) unsigned char lds_raw[];
-	const int lane = threadIdx.x;
-	const Lds L = lds_carve(lds_raw, max_in_len, a.max_lags, false);
-	const int g = blockIdx.x;
-	const int sps = SPS ? SPS : a.sps;
-	load_normalise<NPL>(a.iq + a.offset[g], a.in_len, L, lane);
-	const float fsh = a.freq_shift ? a.freq_shift[g] : 0.0f;
-	const float fs = (fsh - a.rot0) / (float)sps;
-	const float e_toa = a.e_toa ? a.e_toa[g] : -1.0f;
-	int p_id = -1, p_sid = -1, rv = 0;
-	float p_toa = 0.f, p_pwr = 0.f;
-	if (a.carry) {
-		// a list of more than four candidates runs as several launches: pick up where the last one stopped
-		rv = a.rv[g];
-		p_id = a.bt_id[g]; p_sid = a.sync_id[g]; p_toa = a.toa[g]; p_pwr = a.best_pwr[g];
-	}
-	for (int id = 0; id < a.n_types && rv == 0; id++) {
-		float toa, pwr;
-		const int sid = sync_search<SPS>(a.types[id], a.in_len, a.sps, fs, L, lane, 0, toa, pwr);
-		if (sid < 0) {
-			rv = sid;
-			break;
-		}
-		if (e_toa >= 0.0f)
-			pwr = (float)((double)pwr / fabs((double)(e_toa - toa)));
-		if (pwr > p_pwr) {
-			p_id = a.first + id; p_sid = sid; p_pwr = pwr; p_toa = toa;
-		}
-	}
-	if (lane == 0) {
-		a.rv[g] = rv;
-		if (a.bt_id) a.bt_id[g] = rv ? -1 : p_id;
-		if (a.sync_id) a.sync_id[g] = rv ? -1 : p_sid;
-		if (a.toa) a.toa[g] = rv ? 0.f : p_toa;
-		if (a.best_pwr) a.best_pwr[g] = p_pwr;
-	}
-}
-
-// ---------------------------------------------------------------------------
-// modulation order estimate (reference src/sdr/pi4cxpsk.c:693-729 gmr1_pi4cxpsk_mod_order):
-// w = v^2 / |v|^2 on the pi/4-derotated window; BPSK if |sum w|^2 >= |sum w^2|^2 / 2, else QPSK
-// ---------------------------------------------------------------------------
-template <int NPL>
-__global__ __launch_bounds__(64) void k_mod_order(ModOrderArgs a, int max_in_len)
-{
-	extern __shared__ __align__(16) unsigned char lds_raw[];
-	const int lane = threadIdx.x;
-	const Lds L = lds_carve(lds_raw, max_in_len, 0, false);
-	const int g = blockIdx.x;
-	load_normalise<NPL>(a.iq + a.offset[g], a.in_len, L, lane);
-	WSYNC();
-	const float fsh = a.freq_shift ? a.freq_shift[g] : 0.0f;
-	const float fs = (fsh - (kPif / 4)) / (float)a.sps;
-	float sbr = 0.f, sbi = 0.f, sqr = 0.f, sqi = 0.f;
-	for (int i = lane; i < a.in_len; i += 64) {
-		float2 v = L.x[i];
-		if (fs != 0.0f) {
-			float s, c;
-			sincos_fast(fs * (float)i, s, c);
-			v = cmul(v, make_float2(c, s));
-		}
-		const float nn = v.x * v.x + v.y * v.y;
-		const float2 vv = cmul(v, v);
-		const float2 w = make_float2(vv.x / nn, vv.y / nn);
-		const float2 ww = cmul(w, w);
-		sbr += w.x; sbi += w.y;
-		sqr += ww.x; sqi += ww.y;
-	}
-	sbr = wave_sum(sbr); sbi = wave_sum(sbi);
-	sqr = wave_sum(sqr); sqi = wave_sum(sqi);
-	if (lane == 0) {
-		const float pb = sbr * sbr + sbi * sbi;
-		const float pq = sqr * sqr + sqi * sqi;
-		a.order[g] = pb < (pq / 2.0f) ? 4 : 2;
-	}
-}
-
-// ---------------------------------------------------------------------------
-// The layer-1 chain under libosmocore's accelerated decoder on soft bits from OUTSIDE (they may hold -128, and two of
-// those in one trellis step cost 256: one more than a byte lane of the branch-metric word takes).  Same packed-word
-// butterfly, same windows, same survivor walk as decode4_k5_12<true>; the four costs of a step are 16-bit lanes of two
-// words, formed here from the soft bits themselves.
-// ---------------------------------------------------------------------------
-template <int PH>
-__device__ __forceinline__ uint32_t k5w_step(uint32_t w, const uint16_t *__restrict__ c4, uint32_t oo, uint32_t op)
-{
-	uint32_t p;
-	if constexpr (PH == 0) p = dpp<0x128>(w);                // row_ror:8
-	else if constexpr (PH == 1) p = dpp<0x141>(w);           // row_half_mirror: xor 7
-	else if constexpr (PH == 2) p = dpp<0x4E>(w);            // quad_perm [2,3,0,1]
-	else p = dpp<0xB1>(w);                                   // quad_perm [1,0,3,2]
-	const uint32_t t1 = ((uint32_t)c4[oo] << 16) + w;
-	const uint32_t t2 = ((uint32_t)c4[op] << 16) + p;
-	return t1 < t2 ? t1 : t2;
-}
-
-__global__ __launch_bounds__(64) void k_l1_acc(L1Args a)
-{
-	__shared__ __align__(16) int8_t s_eb[4 * kEbRow];
-	__shared__ __align__(16) uint2 s_bmw[4 * kSteps12];        // per step: costs of the coded words 00, 01 | 10, 11
-	__shared__ __align__(16) uint64_t s_surv[kSteps12];
-	__shared__ __align__(16) uint32_t s_ub[4 * 8];
-	const int lane = threadIdx.x;
-	const int row = lane >> 4;
-	const uint32_t loc = (uint32_t)lane & 15u;
-	const int g0 = blockIdx.x * 4;
-	const int neb = a.chain == kChainCcch ? 432 : 424;
-	const int chain = a.chain == kChainCcch ? 1 : 0;
-
-	for (int q = 0; q < 4; q++) {
-		const int g = g0 + q;
-		if (g < a.n) {
-			const uint32_t *src = reinterpret_cast<const uint32_t *>(a.ebits + (size_t)g * neb);
-			uint32_t *dst = reinterpret_cast<uint32_t *>(s_eb + q * kEbRow);
-			for (int i = lane; i < neb / 4; i += 64)
-				dst[i] = src[i];
-		}
-	}
-	WSYNC();
-	for (int it = lane; it < 4 * kSteps12; it += 64) {
-		const int q = it / kSteps12, k = it % kSteps12;
-		uint2 v = make_uint2(0u, 0u);
-		if (g0 + q < a.n) {
-			const uint32_t st = c_steps.w[chain][k];
-			int va = s_eb[q * kEbRow + (st & 0x3ffu)], vb = s_eb[q * kEbRow + ((st >> 16) & 0x3ffu)];
-			if (st & 0x400u) va = (int8_t)(-va);                  // gmr1_scramble_sbit: -128 stays -128
-			if (st & 0x4000000u) vb = (int8_t)(-vb);
-			const uint32_t a0 = va < 0 ? (uint32_t)(-va) : 0u, a1 = va > 0 ? (uint32_t)va : 0u;
-			const uint32_t b0 = vb < 0 ? (uint32_t)(-vb) : 0u, b1 = vb > 0 ? (uint32_t)vb : 0u;
-			v = make_uint2((a0 + b0) | ((a0 + b1) << 16), (a1 + b0) | ((a1 + b1) << 16));
-		}
-		s_bmw[it] = v;
-	}
-	WSYNC();
-
-	const uint32_t dc = c_dec.v[loc];
-	uint32_t oo[4], op[4], T[16];
-#pragma unroll
-	for (int ph = 0; ph < 4; ph++) {
-		oo[ph] = (dc >> (2 * ph)) & 3u;
-		op[ph] = (dc >> (8 + 2 * ph)) & 3u;
-	}
-#pragma unroll
-	for (int j = 0; j < 16; j++)
-		T[j] = (dc >> 16) & (1u << j);
-	const uint16_t *c = reinterpret_cast<const uint16_t *>(s_bmw + row * kSteps12);
-	uint16_t *dump = reinterpret_cast<uint16_t *>(s_surv) + lane;
-	uint32_t w = (loc ? kAccLeadK5r2 << 16 : 0u) | T[0];
-	w = k5w_step<0>(w, c + 0, oo[0], op[0]) + T[1];
-	w = k5w_step<1>(w, c + 4, oo[1], op[1]) + T[2];
-	w = k5w_step<2>(w, c + 8, oo[2], op[2]) + T[3];
-	w = k5w_step<3>(w, c + 12, oo[3], op[3]);
-	w = (w & 0xffff0000u) | T[0];
-#pragma unroll 1
-	for (int m = 0; m < 13; m++) {
-		const uint16_t *cm = c + 4 * (4 + 16 * m);
-#pragma unroll
-		for (int j = 0; j < 16; j += 4) {
-			w = k5w_step<0>(w, cm + 4 * (j + 0), oo[0], op[0]) + T[(j + 1) & 15];
-			w = k5w_step<1>(w, cm + 4 * (j + 1), oo[1], op[1]) + T[(j + 2) & 15];
-			w = k5w_step<2>(w, cm + 4 * (j + 2), oo[2], op[2]) + T[(j + 3) & 15];
-			w = k5w_step<3>(w, cm + 4 * (j + 3), oo[3], op[3]) + (j + 4 < 16 ? T[(j + 4) & 15] : 0u);
-		}
-		dump[m * 64] = (uint16_t)w;
-		w = (w & 0xffff0000u) | T[0];
-	}
-	uint32_t syn;
-	k5_12_survivors_crc(s_surv, s_ub, lane, syn);
-	const int g = g0 + row;
-	if (loc == 0 && g < a.n) {
-		store_l2(a.l2 + (size_t)g * 24, s_ub + row * 8);
-		a.crc[g] = syn ? 1 : 0;
-		a.conv[g] = 0;
-	}
-}
-
-__global__ __launch_bounds__(64) void k_l1(L1Args a)
-{
-	__shared__ __align__(16) int8_t s_eb[4 * kEbRow];
-	__shared__ __align__(16) uint32_t s_bm[4 * kSteps12];
-	__shared__ __align__(16) uint64_t s_surv[kSteps12];
-	__shared__ __align__(16) uint32_t s_ub[4 * 8];
-	const int lane = threadIdx.x;
-	const int g0 = blockIdx.x * 4;
-	const int neb = a.chain == kChainCcch ? 432 : 424;
-	const int chain = a.chain == kChainCcch ? 1 : 0;
-
-	// soft bits HBM -> LDS, 4 bytes per lane
-	for (int q = 0; q < 4; q++) {
-		const int g = g0 + q;
-		if (g < a.n) {
-			const uint32_t *src = reinterpret_cast<const uint32_t *>(a.ebits + (size_t)g * neb);
-			uint32_t *dst = reinterpret_cast<uint32_t *>(s_eb + q * kEbRow);
-			for (int i = lane; i < neb / 4; i += 64)
-				dst[i] = src[i];
-		}
-	}
-	WSYNC();
-	for (int q = 0; q < 4; q++) {
-		if (g0 + q < a.n) {
-			branch_metrics_k5_12(s_eb + q * kEbRow, chain, s_bm + q * kSteps12, lane);
-		} else {
-			for (int k = lane; k < kSteps12; k += 64)
-				s_bm[q * kSteps12 + k] = 0;
-		}
-	}
-	WSYNC();
-	uint32_t syn, fae;
-	decode4_k5_12(s_bm, s_surv, s_ub, lane, syn, fae);
-	const int row = lane >> 4;
-	const int g = g0 + row;
-	if ((lane & 15) == 0 && g < a.n) {
-		store_l2(a.l2 + (size_t)g * 24, s_ub + row * 8);
-		a.crc[g] = syn ? 1 : 0;
-		a.conv[g] = (int32_t)fae;
-	}
-}
+#include "rx_small_kernels.h"
 
 // ---------------------------------------------------------------------------
 // launchers
@@ -4049,41 +2112,6 @@ hipError_t launch_rx(const RxArgs &a, bool decode, int max_in_len, hipStream_t s
 	return launch_rx_t<64, 0>(a, decode, max_in_len, max_len, stream);
 }
 
-// Interleaved sample array -> polyphase-planar (what gmr1_hip_rx_bcch_ccch_batch_planar_dev reads): a work-group takes 256 sps
-// consecutive samples; thread t of it reads samples t, t + 256, ... (coalesced) and, through LDS, writes place t of each of
-// the sps planes (coalesced again).  HBM-bound by construction: every sample read once, written once.
-constexpr int kPlanarTile = 256;
-__global__ __launch_bounds__(256) void k_to_planar(const float2 *__restrict__ in, float2 *__restrict__ out, unsigned long long n,
-                                                   int sps, long long plane_stride)
-{
-	extern __shared__ __align__(16) unsigned char lds_raw[];
-	float2 *t = reinterpret_cast<float2 *>(lds_raw);
-	const unsigned long long p0 = (unsigned long long)blockIdx.x * kPlanarTile;     // first place of the tile in every plane
-	const unsigned long long s0 = p0 * (unsigned long long)sps;
-	for (int k = 0; k < sps; k++) {
-		const unsigned long long s = s0 + (unsigned long long)(k * kPlanarTile + (int)threadIdx.x);
-		t[k * kPlanarTile + threadIdx.x] = s < n ? in[s] : make_float2(0.f, 0.f);
-	}
-	__syncthreads();
-	for (int ph = 0; ph < sps; ph++) {
-		const unsigned long long s = s0 + (unsigned long long)((int)threadIdx.x * sps + ph);
-		if (s < n)
-			out[(long long)ph * plane_stride + (long long)(p0 + threadIdx.x)] = t[(int)threadIdx.x * sps + ph];
-	}
-}
-
-hipError_t launch_to_planar(const float2 *in, float2 *out, unsigned long long n, int sps, long long plane_stride, hipStream_t stream)
-{
-	if (n == 0)
-		return hipSuccess;
-	const unsigned long long places = (n + (unsigned long long)sps - 1) / (unsigned long long)sps;
-	const unsigned long long grid = (places + kPlanarTile - 1) / kPlanarTile;
-	if (grid > 0x7fffffffull)
-		return hipErrorInvalidValue;
-	hipLaunchKernelGGL(k_to_planar, dim3((unsigned)grid), dim3(256), (size_t)sps * kPlanarTile * 8, stream, in, out, n, sps, plane_stride);
-	return hipGetLastError();
-}
-
 #ifdef GMR1_HIP_PROFILE
 extern "C" int gmr1_hip_prof_stamps(unsigned long long *out16)
 {
@@ -4113,7 +2141,7 @@ hipError_t launch_rx_tch3(const RxArgs &a, const Tch3Args &t, hipStream_t stream
 		return hipErrorInvalidValue;
 	const int cw = (a.in_len[0] - a.ssyms_stride * 4 + 1 + 15) & ~15;          // lags (ssyms_stride = symbols per burst)
 	size_t off4[4];
-	// the demodulator's phases as rx4_body<8, 4, GEN, ..., EBROW = 216> carves them (pass 1: staged windows, correlation,
+	// the demodulator's phases as rx4_body<CfgTch3Front> carves them (pass 1: staged windows, correlation,
 	// coefficients; pass 2: four 216-byte soft-bit rows and the soft-bit table) -- the same function sizes them here --
 	// and, after them, the rows + the decoder's tables
 	size_t lds = lds4_layout(a.stage_samples, cw, off4, true, false, 216);
@@ -4137,57 +2165,7 @@ hipError_t launch_rx_tch3(const RxArgs &a, const Tch3Args &t, hipStream_t stream
 }
 
 #include "rx_loop_kernels.inc"
-
-hipError_t launch_detect(const DetectArgs &a, hipStream_t stream)
-{
-	if (a.n <= 0)
-		return hipSuccess;
-	if (a.in_len > kMaxInLen)
-		return hipErrorInvalidValue;
-	size_t off[3];
-	const size_t lds = lds_layout(a.in_len, a.max_lags, false, off);
-	if (a.in_len <= 1024) {
-		if (a.sps == 4)
-			hipLaunchKernelGGL((k_detect<16, 4>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-		else
-			hipLaunchKernelGGL((k_detect<16, 0>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-	} else if (a.in_len <= 2048) {
-		if (a.sps == 4)
-			hipLaunchKernelGGL((k_detect<32, 4>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-		else
-			hipLaunchKernelGGL((k_detect<32, 0>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-	} else {
-		hipLaunchKernelGGL((k_detect<64, 0>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-	}
-	return hipGetLastError();
-}
-
-hipError_t launch_mod_order(const ModOrderArgs &a, hipStream_t stream)
-{
-	if (a.n <= 0)
-		return hipSuccess;
-	if (a.in_len > kMaxInLen)
-		return hipErrorInvalidValue;
-	size_t off[3];
-	const size_t lds = lds_layout(a.in_len, 0, false, off);
-	if (a.in_len <= 1024)
-		hipLaunchKernelGGL((k_mod_order<16>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-	else if (a.in_len <= 2048)
-		hipLaunchKernelGGL((k_mod_order<32>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-	else
-		hipLaunchKernelGGL((k_mod_order<64>), dim3(a.n), dim3(64), lds, stream, a, a.in_len);
-	return hipGetLastError();
-}
-
-hipError_t launch_l1(const L1Args &a, hipStream_t stream)
-{
-	if (a.n <= 0)
-		return hipSuccess;
-	if (a.conv_acc)
-		hipLaunchKernelGGL(k_l1_acc, dim3((a.n + 3) / 4), dim3(64), 0, stream, a);
-	else
-		hipLaunchKernelGGL(k_l1, dim3((a.n + 3) / 4), dim3(64), 0, stream, a);
-	return hipGetLastError();
-}
+#include "rx_debug_kernels.inc"
+#include "rx_server_kernels.inc"
 
 }  // namespace gmr1

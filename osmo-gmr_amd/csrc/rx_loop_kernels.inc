@@ -250,7 +250,7 @@ __global__ __launch_bounds__(128) void k_rx_chain(RxArgs a, RxLoopArgs la, int s
 			if constexpr (ONE)
 				rx1_lat_body<NPL, SPS, ACC>(a, io, stage_samples, cw, lds_raw, lane);
 			else
-				rx4_body<NPL, SPS, true, false, false, ACC>(a, io, stage_samples, cw, 0, 1, lds_raw, lane, &pre);
+				rx4_body<CfgLoop<NPL, SPS, ACC>>(a, io, stage_samples, cw, 0, 1, lds_raw, lane, &pre);
 			WSYNC();
 			// the BCCH burst feeds back before the next round is listed (rx_bcch, gmr1_rx.c:782-795)
 			b_frame = frames_at_round + it.frames_before;
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256) void k_rx_chain_pipe(RxArgs a, RxLoopArgs la, 
 				                 reinterpret_cast<unsigned long long *>(((unsigned long long)h.stamp_hi << 32) | h.stamp_lo),
 #endif
 				                 &h.pre.base, b_kind, &h.fsh, nullptr, nullptr, nullptr, b_rv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-				rx4_body<NPL, SPS, true, false, false, ACC, true, false, 432, 2>(a, io, stage_samples, cw, 0, 1, body_p, lane, &pre);
+				rx4_body<CfgLoop<NPL, SPS, ACC, 2>>(a, io, stage_samples, cw, 0, 1, body_p, lane, &pre);
 			}
 			const uint64_t pred = s_pred[t & 1];
 			const int slot = t % 3;
@@ -835,7 +835,7 @@ __global__ __launch_bounds__(256) void k_rx_chain_pipe(RxArgs a, RxLoopArgs la, 
 			                 stamp,
 #endif
 			                 s_off, s_kind, s_fs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-			rx4_body<NPL, SPS, true, false, false, ACC, true, false, 432, 1>(a, io, stage_samples, cw, 0, 1, body_f, lane, &pre);
+			rx4_body<CfgLoop<NPL, SPS, ACC, 1>>(a, io, stage_samples, cw, 0, 1, body_f, lane, &pre);
 			b_frame = frames_at_round + it.frames_before;
 			if (pre.out.found) {
 				// found: the feedback as if the CRC passes and SI1 moves nothing -- the judge (S, three ticks on) will tell (gmr1_rx.c:782-795)
@@ -1280,5 +1280,3 @@ hipError_t launch_rx_loop(const RxArgs &a, const RxLoopArgs &la, int n_chains, h
 		hipLaunchKernelGGL(k_rx_pack, dim3((unsigned)n_chains, kPackParts), dim3(256), 0, stream, la, n_chains);
 	return hipGetLastError();
 }
-
-#include "rx_debug_kernels.inc"

@@ -1,6 +1,6 @@
 // k_one_server -- the fused BCCH / DC6 burst body (rx4_body, exactly what k_rx4 runs for one burst) as a resident one-wave
 // kernel that answers requests from a mailbox in pinned host memory.
-// (part of rx_kernels.hip's translation unit, included from rx_debug_kernels.inc inside namespace gmr1)
+// (part of rx_kernels.hip's translation unit, included by it after rx_debug_kernels.inc, inside namespace gmr1)
 //
 // An unchanged gmr1_rx.c calls gmr1_pi4cxpsk_demod once per burst and waits for the answer: a launch and a stream
 // synchronisation per call cost about twice what the burst itself does (29 us a call; the kernel's share is 10).  With the
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(64) void k_one_server(RxArgs a, OneMail *mb, uint32
 			// what the host wrote before it changed the number: not from this wave's caches
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
 			asm volatile("s_dcache_inv\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-			rx4_body<16, 4, false, false, false, ACC, false, false>(a, io, stage_samples, cw, 0, 1, lds_raw, lane);
+			rx4_body<CfgBatch<16, 4, ACC, false>>(a, io, stage_samples, cw, 0, 1, lds_raw, lane);
 			WSYNC();
 			__threadfence_system();                  // the answer is in host memory before its number is
 			last = r;

@@ -4,14 +4,7 @@
 #pragma once
 
 #include "gmr1_dev.h"
-
-#ifndef WSYNC
-#define WSYNC()                                                   \
-	do {                                                          \
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");    \
-		__builtin_amdgcn_wave_barrier();                          \
-	} while (0)
-#endif
+#include "wave_ops.h"
 
 namespace gmr1 {
 namespace t3 {
@@ -30,10 +23,11 @@ static constexpr ScrBits make_scr()
 	return t;
 }
 
+// wave_ops.h's dpp with bound_ctrl set: every lane of the permutations used here has a source, so nothing is preset
 template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t v)
+__device__ __forceinline__ uint32_t dpp_bc(uint32_t v)
 {
-	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);   // every lane has a source: nothing to preset
+	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
 }
 
 // ---------------------------------------------------------------------------
@@ -197,16 +191,16 @@ template <int PH>
 __device__ __forceinline__ uint32_t k7_partner(uint32_t w)
 {
 	if constexpr (PH == 0) return (uint32_t)__shfl_xor((int)w, 16);
-	else if constexpr (PH == 1) return dpp<0x128>(w);       // row_ror:8
-	else if constexpr (PH == 2) return dpp<0x141>(w);       // row_half_mirror: xor 7
-	else if constexpr (PH == 3) return dpp<0x4E>(w);        // quad_perm [2,3,0,1]
-	else return dpp<0xB1>(w);                               // quad_perm [1,0,3,2]
+	else if constexpr (PH == 1) return dpp_bc<0x128>(w);       // row_ror:8
+	else if constexpr (PH == 2) return dpp_bc<0x141>(w);       // row_half_mirror: xor 7
+	else if constexpr (PH == 3) return dpp_bc<0x4E>(w);        // quad_perm [2,3,0,1]
+	else return dpp_bc<0xB1>(w);                               // quad_perm [1,0,3,2]
 }
 
 typedef __attribute__((address_space(3))) const uint32_t t3_lds_cu32;
 
 // One trellis step at window position J (phase J % 6) on the packed words [metric:16 | decisions of the
-// current 12-step window:16] (see decode4_k5_12 in rx_kernels.hip).  Both generators have the D^0 and D^6
+// current 12-step window:16] (see decode4_k5_12 in conv_k5_12.h).  Both generators have the D^0 and D^6
 // taps, so the two transitions into a state carry complementary code words and their costs add up to a
 // per-step constant K: the words hold 2 * metric - sum K, a candidate is `own + m` / `partner - m` with ONE
 // table value m = (2 cost - K) << 16 (the subtraction takes the DPP operand directly), comparisons and ties
@@ -279,10 +273,10 @@ __device__ __forceinline__ void k7_window_pk(uint32_t &P, const uint32_t (&ad)[6
 __device__ __forceinline__ uint32_t half_min(uint32_t v)
 {
 	uint32_t o;
-	o = dpp<0xB1>(v); v = o < v ? o : v;
-	o = dpp<0x4E>(v); v = o < v ? o : v;
-	o = dpp<0x141>(v); v = o < v ? o : v;
-	o = dpp<0x128>(v); v = o < v ? o : v;
+	o = dpp_bc<0xB1>(v); v = o < v ? o : v;
+	o = dpp_bc<0x4E>(v); v = o < v ? o : v;
+	o = dpp_bc<0x141>(v); v = o < v ? o : v;
+	o = dpp_bc<0x128>(v); v = o < v ? o : v;
 	o = (uint32_t)__shfl_xor((int)v, 16); v = o < v ? o : v;
 	return v;
 }
@@ -402,10 +396,10 @@ __device__ __forceinline__ void tch3_burst(const Tch3Args &a, int g, int lane, c
 	// both sums over the wave at once: rows by DPP, the four row totals through the scalar unit
 	int ksum = 0;
 	if constexpr (!ACC) {
-		ksp += dpp<0xB1>(ksp);
-		ksp += dpp<0x4E>(ksp);
-		ksp += dpp<0x141>(ksp);
-		ksp += dpp<0x140>(ksp);
+		ksp += dpp_bc<0xB1>(ksp);
+		ksp += dpp_bc<0x4E>(ksp);
+		ksp += dpp_bc<0x141>(ksp);
+		ksp += dpp_bc<0x140>(ksp);
 		const uint32_t ks_all = (uint32_t)__builtin_amdgcn_readlane((int)ksp, 0) + (uint32_t)__builtin_amdgcn_readlane((int)ksp, 16) +
 		                        (uint32_t)__builtin_amdgcn_readlane((int)ksp, 32) + (uint32_t)__builtin_amdgcn_readlane((int)ksp, 48);
 		ksum = (int)(fr ? ks_all >> 16 : ks_all & 0xffffu);

@@ -35,7 +35,7 @@ __device__ __forceinline__ float wsum(float v)
 
 __device__ __forceinline__ float arg_fast(float y, float x)
 {
-	// same octant-folded minimax polynomial as the demodulator's atan2 (rx_kernels.hip)
+	// same octant-folded minimax polynomial as the demodulator's atan2 (fast_math.h)
 	const float ax = fabsf(x), ay = fabsf(y);
 	const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
 	const bool big = mn > 0.41421356237f * mx;

@@ -2,7 +2,7 @@
 tests/test_gpu_rx.py and tests/test_gpu_tch.py run them.
 
 The receive loop reaches all three at every sps and with a freq_shift (rx_tch3 hands gmr1_pi4cxpsk_detect and
-gmr1_dkab_demod -freq_err).  launch_detect (rx_kernels.hip) picks k_detect<samples per lane, sps> by in_len and sps; the
+gmr1_dkab_demod -freq_err).  launch_detect (rx_small_kernels.h) picks k_detect<samples per lane, sps> by in_len and sps; the
 cases below, NT3 bursts (117 symbols) in windows of 117 * sps + win samples, reach
 
     sps  win   in_len  k_detect   k_mod_order          sps  win   in_len  k_detect   k_mod_order
