@@ -268,15 +268,22 @@ __device__ __forceinline__ void branch_metrics4_k5_12(const int8_t *__restrict__
 // One 32-bit word per state carries everything the step needs:
 //     [ path metric : 16 | decisions of the current 16-step window : 16 ]
 // The metric never exceeds 212 * 252 = 53 424; unreachable states carry 0xF000 (libosmocore's
-// MAX_AE plays the same role).  Before step j of a window the word of a lane that is the HIGH
-// predecessor ((t >> 1) + 8) of its butterfly has bit j set (tb).  The two candidates of a new
-// state are  own word + (cost << 16)  and  partner word + (cost << 16); v_min_u32 then (a) picks
-// the smaller metric, (b) on equal metrics keeps the LOW predecessor (osmo_conv_decode: strict
-// '>' on ascending states), and (c) leaves the decision in bit j of the winner's history --
-// four VALU instructions per trellis step (add, add with DPP, min, add next tb).  The cost byte
-// is fetched by every lane straight from the branch-metric words in LDS into the HIGH half of a
-// register (ds_read_u8_d16_hi; with SRAM-ECC the low half reads back as zero, which is what the
-// add wants), 8 steps ahead.
+// MAX_AE plays the same role).  In step j of a window a lane that is the HIGH predecessor
+// ((t >> 1) + 8) of its butterfly adds bit j (tb) to what it sends on.  Lanes exchange CANDIDATES,
+// not words: each lane forms  own word + (cost << 16) + tb  twice, once with the cost of its
+// transition into its own successor and once with that into the PARTNER's successor, and the
+// v_min_u32 that takes the partner's candidate through DPP then (a) picks the smaller metric,
+// (b) on equal metrics keeps the LOW predecessor (osmo_conv_decode: strict '>' on ascending
+// states), and (c) leaves the decision in bit j of the winner's history -- three VALU
+// instructions per trellis step (two v_add3_u32, v_min_u32 with DPP); the word carries no tb
+// between steps, and a window ends with a plain clear of the low half.  (Pulling the partner's
+// WORD through DPP instead needs its tb inside the word before it travels: a fourth instruction
+// per step.)  A VGPR written by a VALU instruction must not be read through DPP by the next two
+// instructions: the partner-bound candidate is formed first, and the second add plus the two cost
+// prefetches (or an s_nop) stand between it and the min.  The cost byte is fetched by every lane
+// straight from the branch-metric words in LDS into the HIGH half of a register
+// (ds_read_u8_d16_hi; with SRAM-ECC the low half reads back as zero, which is what the add
+// wants), 8 steps ahead.
 //
 // The decision of step k is the oldest bit of the winning predecessor = input bit u[k-4].
 // Windows start at k = 4 + 16 m, so window m's 16 decisions ARE the decoded bits
@@ -285,8 +292,9 @@ __device__ __forceinline__ void branch_metrics4_k5_12(const int8_t *__restrict__
 // ---------------------------------------------------------------------------
 constexpr uint32_t kSentinel = 0xF0000000u;
 
-// per row location: bits 0-7 own cost byte (2 bits per phase), 8-15 partner cost byte, 16-31 the
-// 16-step tb pattern (bit j set when the lane holds a HIGH predecessor in phase j & 3)
+// per row location: bits 0-7 cost byte of the transition own predecessor -> own successor (2 bits per phase), 8-15 cost
+// byte of own predecessor -> the PARTNER's successor, 16-31 the 16-step tb pattern (bit j set when the lane holds a HIGH
+// predecessor in phase j & 3)
 struct DecTable { uint32_t v[16]; };
 static constexpr uint32_t dec_out(uint32_t s, uint32_t b)
 {
@@ -296,26 +304,32 @@ static constexpr uint32_t dec_out(uint32_t s, uint32_t b)
 	p1 ^= p1 >> 4; p1 ^= p1 >> 2; p1 ^= p1 >> 1;
 	return ((p0 & 1u) << 1) | (p1 & 1u);
 }
+// the predecessor state a row location holds in phase ph (loc in the basis {8, 7, 2, 1})
+static constexpr uint32_t dec_state(uint32_t loc, int ph)
+{
+	uint32_t c[4] = {0, 0, 0, 0};
+	c[0] = (loc >> 3) & 1u;
+	uint32_t x = loc & 7u;
+	c[1] = (x >> 2) & 1u;
+	x ^= c[1] ? 7u : 0u;
+	c[2] = (x >> 1) & 1u;
+	c[3] = x & 1u;
+	uint32_t sp = 0;
+	for (int i = 0; i < 4; i++)
+		sp |= c[(3 - i + ph) & 3] << i;
+	return sp;
+}
 static constexpr DecTable make_dec()
 {
 	DecTable t{};
 	for (uint32_t loc = 0; loc < 16; loc++) {
-		// loc in the basis {8, 7, 2, 1}
-		uint32_t c[4] = {0, 0, 0, 0};
-		c[0] = (loc >> 3) & 1u;
-		uint32_t x = loc & 7u;
-		c[1] = (x >> 2) & 1u;
-		x ^= c[1] ? 7u : 0u;
-		c[2] = (x >> 1) & 1u;
-		c[3] = x & 1u;
 		uint32_t e = 0;
 		for (int ph = 0; ph < 4; ph++) {
-			uint32_t sp = 0;
-			for (int i = 0; i < 4; i++)
-				sp |= c[(3 - i + ph) & 3] << i;
+			// the lane's successor takes input bit b, the partner's (predecessor sp ^ 8) input bit b ^ 1
+			const uint32_t sp = dec_state(loc, ph);
 			const uint32_t b = sp >> 3;
 			e |= dec_out(sp, b) << (2 * ph);
-			e |= dec_out(sp ^ 8u, b) << (8 + 2 * ph);
+			e |= dec_out(sp, b ^ 1u) << (8 + 2 * ph);
 			for (int j = ph; j < 16; j += 4)
 				e |= b << (16 + j);
 		}
@@ -323,6 +337,27 @@ static constexpr DecTable make_dec()
 	}
 	return t;
 }
+// What the partner lane (loc ^ {8, 7, 2, 1}[ph]) sends is what this lane used to add to the partner's word itself: the
+// cost of the partner's predecessor -> this lane's successor.  Both generators have the D^0 and D^4 taps, so that is
+// also the lane's own bits 8-15 (k_l1_acc reads them as the partner's cost into the own successor).
+static constexpr bool dec_exchange_holds()
+{
+	const DecTable t = make_dec();
+	const uint32_t mask[4] = {8u, 7u, 2u, 1u};
+	for (uint32_t loc = 0; loc < 16; loc++)
+		for (int ph = 0; ph < 4; ph++) {
+			const uint32_t sp = dec_state(loc, ph);
+			const uint32_t partner_into_mine = dec_out(sp ^ 8u, sp >> 3);
+			if (dec_state(loc ^ mask[ph], ph) != (sp ^ 8u))
+				return false;
+			if (((t.v[loc ^ mask[ph]] >> (8 + 2 * ph)) & 3u) != partner_into_mine)
+				return false;
+			if (((t.v[loc] >> (8 + 2 * ph)) & 3u) != partner_into_mine)
+				return false;
+		}
+	return true;
+}
+static_assert(dec_exchange_holds(), "the partner lane's bits 8-15 must name the cost of its predecessor into this lane's successor");
 __constant__ DecTable c_dec = make_dec();
 
 #define GMR1_DPP_PH0 "row_ror:8"
@@ -330,45 +365,35 @@ __constant__ DecTable c_dec = make_dec();
 #define GMR1_DPP_PH2 "quad_perm:[2,3,0,1]"
 #define GMR1_DPP_PH3 "quad_perm:[1,0,3,2]"
 
-#define ACS_CORE(PH)                                                                               \
+// both outgoing candidates of the lane: S to the partner's successor, T1 to its own
+#define ACS_CAND                                                                                   \
 	"s_waitcnt lgkmcnt(%[wt])\n\t"                                                                  \
-	"v_add_u32 %[t1], %[w], %[r]\n\t"                                                               \
-	"v_add_u32_dpp %[t2], %[w], %[q] " GMR1_DPP_PH##PH " row_mask:0xf bank_mask:0xf\n\t"            \
-	"v_min_u32 %[w], %[t1], %[t2]\n\t"
-// step with the operands of position J, prefetching the cost bytes of step J + 8; TN = tb of the next position
-#define ACS_PF(J, PH, WAIT, TN)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             "v_add_u32 %[w], %[w], %[tn]\n\t"                                                  \
+	"v_add3_u32 %[s], %[w], %[x], %[t]\n\t"                                                         \
+	"v_add3_u32 %[t1], %[w], %[r], %[t]\n\t"
+#define ACS_MIN(PH)                                                                                \
+	"v_min_u32_dpp %[w], %[s], %[t1] " GMR1_DPP_PH##PH " row_mask:0xf bank_mask:0xf\n\t"
+// step with the operands of position J, prefetching the cost bytes of step J + 8; TB = tb of the position
+#define ACS_PF(J, PH, WAIT, TB)                                                                    \
+	asm volatile(ACS_CAND                                                                          \
 	             "ds_read_u8_d16_hi %[rn], %[ao] offset:%[off]\n\t"                                 \
-	             "ds_read_u8_d16_hi %[qn], %[ap] offset:%[off]\n\t"                                 \
-	             : [w] "+v"(w), [rn] "+v"(R[((J) + 8) & 15]), [qn] "+v"(Q[((J) + 8) & 15]),        \
-	               [t1] "=&v"(t1), [t2] "=&v"(t2)                                                    \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [ao] "v"(ao[PH]), [ap] "v"(ap[PH]), [tn] "v"(TN),   \
+	             "ds_read_u8_d16_hi %[xn], %[ap] offset:%[off]\n\t"                                 \
+	             ACS_MIN(PH)                                                                       \
+	             : [w] "+v"(w), [rn] "+v"(R[((J) + 8) & 15]), [xn] "+v"(X[((J) + 8) & 15]),        \
+	               [t1] "=&v"(t1), [s] "=&v"(s)                                                      \
+	             : [r] "v"(R[J]), [x] "v"(X[J]), [ao] "v"(ao[PH]), [ap] "v"(ap[PH]), [t] "v"(TB),    \
 	               [off] "i"(4 * ((J) + 8)), [wt] "i"(WAIT))
-// step without prefetch
-#define ACS_NP(J, PH, WAIT, TN)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             "v_add_u32 %[w], %[w], %[tn]\n\t"                                                  \
-	             : [w] "+v"(w), [t1] "=&v"(t1), [t2] "=&v"(t2)                                       \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [tn] "v"(TN), [wt] "i"(WAIT))
-// last step of a window: the caller clears the decisions and sets the first tb itself
-#define ACS_PF_END(J, PH, WAIT)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             "ds_read_u8_d16_hi %[rn], %[ao] offset:%[off]\n\t"                                 \
-	             "ds_read_u8_d16_hi %[qn], %[ap] offset:%[off]\n\t"                                 \
-	             : [w] "+v"(w), [rn] "+v"(R[((J) + 8) & 15]), [qn] "+v"(Q[((J) + 8) & 15]),        \
-	               [t1] "=&v"(t1), [t2] "=&v"(t2)                                                    \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [ao] "v"(ao[PH]), [ap] "v"(ap[PH]),                 \
-	               [off] "i"(4 * ((J) + 8)), [wt] "i"(WAIT))
-#define ACS_NP_END(J, PH, WAIT)                                                                    \
-	asm volatile(ACS_CORE(PH)                                                                      \
-	             : [w] "+v"(w), [t1] "=&v"(t1), [t2] "=&v"(t2)                                       \
-	             : [r] "v"(R[J]), [q] "v"(Q[J]), [wt] "i"(WAIT))
+// step without prefetch: the s_nop is the second wait state between the write of S and its read through DPP
+#define ACS_NP(J, PH, WAIT, TB)                                                                    \
+	asm volatile(ACS_CAND                                                                          \
+	             "s_nop 0\n\t"                                                                      \
+	             ACS_MIN(PH)                                                                       \
+	             : [w] "+v"(w), [t1] "=&v"(t1), [s] "=&v"(s)                                         \
+	             : [r] "v"(R[J]), [x] "v"(X[J]), [t] "v"(TB), [wt] "i"(WAIT))
 // cost bytes of step K (relative to the address registers) into the operands of position J
 #define ACS_LOAD(J, PH, K)                                                                         \
 	asm volatile("ds_read_u8_d16_hi %[rn], %[ao] offset:%[off]\n\t"                                 \
-	             "ds_read_u8_d16_hi %[qn], %[ap] offset:%[off]\n\t"                                 \
-	             : [rn] "+v"(R[J]), [qn] "+v"(Q[J])                                                  \
+	             "ds_read_u8_d16_hi %[xn], %[ap] offset:%[off]\n\t"                                 \
+	             : [rn] "+v"(R[J]), [xn] "+v"(X[J])                                                  \
 	             : [ao] "v"(ao[PH]), [ap] "v"(ap[PH]), [off] "i"(4 * (K)))
 
 struct DecPre;
@@ -409,10 +434,10 @@ __device__ void decode4_k5_12(const uint32_t *__restrict__ bm, uint64_t *__restr
 	typedef __attribute__((address_space(3))) const unsigned char lds_cbyte;
 	const int row = lane >> 4;
 	const uint32_t loc = (uint32_t)lane & 15u;
-	// per-location constants (c_dec): cost byte of the own / partner transition per phase, tb pattern
+	// per-location constants (c_dec): cost byte of the transition into the own / the partner's successor per phase, tb pattern
 	const uint32_t dc = dp ? dp->dc : c_dec.v[loc];
 	const uint32_t row_base = (uint32_t)(uintptr_t)(lds_cbyte *)(bm + row * kSteps12);
-	uint32_t ao[4], ap[4];      // LDS byte address of this lane's own / partner cost in step 0 of the phase
+	uint32_t ao[4], ap[4];      // LDS byte address of this lane's cost into its own / the partner's successor in step 0 of the phase
 	bool hi[4];
 #pragma unroll
 	for (int ph = 0; ph < 4; ph++) {
@@ -420,22 +445,22 @@ __device__ void decode4_k5_12(const uint32_t *__restrict__ bm, uint64_t *__restr
 		ap[ph] = row_base + ((dc >> (8 + 2 * ph)) & 3u);
 		hi[ph] = ((dc >> (16 + ph)) & 1u) != 0;
 	}
-	// cost << 16 of the own / partner transition, per window position (low halves stay zero whether
-	// or not the d16 load preserves them)
-	uint32_t R[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, Q[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	// cost << 16 of the transition into the own / the partner's successor, per window position (low halves stay zero
+	// whether or not the d16 load preserves them)
+	uint32_t R[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, X[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	uint32_t T[16];             // tie-break / decision bit of the position: set in HIGH-predecessor lanes
 #pragma unroll
 	for (int j = 0; j < 16; j++)
 		T[j] = (dc >> 16) & (1u << j);
-	uint32_t w = (loc ? (ACC ? kAccLeadK5r2 << 16 : kSentinel) : 0u) | T[0];
-	uint32_t t1, t2;
+	uint32_t w = loc ? (ACC ? kAccLeadK5r2 << 16 : kSentinel) : 0u;
+	uint32_t t1, s;
 	uint16_t *dump = reinterpret_cast<uint16_t *>(surv) + lane;
 
 	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 	// steps 0..3: the decisions are u[-4..-1], dropped
 	ACS_LOAD(0, 0, 0); ACS_LOAD(1, 1, 1); ACS_LOAD(2, 2, 2); ACS_LOAD(3, 3, 3);
-	ACS_NP(0, 0, 6, T[1]); ACS_NP(1, 1, 4, T[2]); ACS_NP(2, 2, 2, T[3]); ACS_NP_END(3, 3, 0);
-	w = (w & 0xffff0000u) | T[0];
+	ACS_NP(0, 0, 6, T[0]); ACS_NP(1, 1, 4, T[1]); ACS_NP(2, 2, 2, T[2]); ACS_NP(3, 3, 0, T[3]);
+	w &= 0xffff0000u;
 #pragma unroll
 	for (int ph = 0; ph < 4; ph++) {
 		ao[ph] += 16;
@@ -446,12 +471,12 @@ __device__ void decode4_k5_12(const uint32_t *__restrict__ bm, uint64_t *__restr
 	ACS_LOAD(4, 0, 4); ACS_LOAD(5, 1, 5); ACS_LOAD(6, 2, 6); ACS_LOAD(7, 3, 7);
 #pragma unroll 1
 	for (int m = 0; m < 12; m++) {
-		ACS_PF(0, 0, 14, T[1]); ACS_PF(1, 1, 14, T[2]); ACS_PF(2, 2, 14, T[3]); ACS_PF(3, 3, 14, T[4]);
-		ACS_PF(4, 0, 14, T[5]); ACS_PF(5, 1, 14, T[6]); ACS_PF(6, 2, 14, T[7]); ACS_PF(7, 3, 14, T[8]);
-		ACS_PF(8, 0, 14, T[9]); ACS_PF(9, 1, 14, T[10]); ACS_PF(10, 2, 14, T[11]); ACS_PF(11, 3, 14, T[12]);
-		ACS_PF(12, 0, 14, T[13]); ACS_PF(13, 1, 14, T[14]); ACS_PF(14, 2, 14, T[15]); ACS_PF_END(15, 3, 14);
+		ACS_PF(0, 0, 14, T[0]); ACS_PF(1, 1, 14, T[1]); ACS_PF(2, 2, 14, T[2]); ACS_PF(3, 3, 14, T[3]);
+		ACS_PF(4, 0, 14, T[4]); ACS_PF(5, 1, 14, T[5]); ACS_PF(6, 2, 14, T[6]); ACS_PF(7, 3, 14, T[7]);
+		ACS_PF(8, 0, 14, T[8]); ACS_PF(9, 1, 14, T[9]); ACS_PF(10, 2, 14, T[10]); ACS_PF(11, 3, 14, T[11]);
+		ACS_PF(12, 0, 14, T[12]); ACS_PF(13, 1, 14, T[13]); ACS_PF(14, 2, 14, T[14]); ACS_PF(15, 3, 14, T[15]);
 		dump[m * 64] = (uint16_t)w;
-		w = (w & 0xffff0000u) | T[0];
+		w &= 0xffff0000u;
 #pragma unroll
 		for (int ph = 0; ph < 4; ph++) {
 			ao[ph] += 64;
@@ -460,20 +485,21 @@ __device__ void decode4_k5_12(const uint32_t *__restrict__ bm, uint64_t *__restr
 	}
 	// window 12: steps 196..211, the last four are the flush (b = 0 transitions only: the lanes
 	// whose new state ends in 1 become unreachable)
-	ACS_PF(0, 0, 14, T[1]); ACS_PF(1, 1, 14, T[2]); ACS_PF(2, 2, 14, T[3]); ACS_PF(3, 3, 14, T[4]);
-	ACS_PF(4, 0, 14, T[5]); ACS_PF(5, 1, 14, T[6]); ACS_PF(6, 2, 14, T[7]); ACS_PF(7, 3, 14, T[8]);
-	ACS_NP(8, 0, 14, T[9]); ACS_NP(9, 1, 12, T[10]); ACS_NP(10, 2, 10, T[11]); ACS_NP(11, 3, 8, T[12]);
+	ACS_PF(0, 0, 14, T[0]); ACS_PF(1, 1, 14, T[1]); ACS_PF(2, 2, 14, T[2]); ACS_PF(3, 3, 14, T[3]);
+	ACS_PF(4, 0, 14, T[4]); ACS_PF(5, 1, 14, T[5]); ACS_PF(6, 2, 14, T[6]); ACS_PF(7, 3, 14, T[7]);
+	ACS_NP(8, 0, 14, T[8]); ACS_NP(9, 1, 12, T[9]); ACS_NP(10, 2, 10, T[10]); ACS_NP(11, 3, 8, T[11]);
 	if constexpr (ACC) {
-		ACS_NP(12, 0, 6, T[13]); ACS_NP(13, 1, 4, T[14]); ACS_NP(14, 2, 2, T[15]); ACS_NP_END(15, 3, 0);
+		ACS_NP(12, 0, 6, T[12]); ACS_NP(13, 1, 4, T[13]); ACS_NP(14, 2, 2, T[14]); ACS_NP(15, 3, 0, T[15]);
 		(void)hi;
 	} else {
-		ACS_NP_END(12, 0, 6);
-		w = hi[0] ? kSentinel : (w + T[13]);
-		ACS_NP_END(13, 1, 4);
-		w = hi[1] ? kSentinel : (w + T[14]);
-		ACS_NP_END(14, 2, 2);
-		w = hi[2] ? kSentinel : (w + T[15]);
-		ACS_NP_END(15, 3, 0);
+		// (a lane just made unreachable sends the bare sentinel on, without a tb)
+		ACS_NP(12, 0, 6, T[12]);
+		w = hi[0] ? kSentinel : w;
+		ACS_NP(13, 1, 4, hi[0] ? 0u : T[13]);
+		w = hi[1] ? kSentinel : w;
+		ACS_NP(14, 2, 2, hi[1] ? 0u : T[14]);
+		w = hi[2] ? kSentinel : w;
+		ACS_NP(15, 3, 0, hi[2] ? 0u : T[15]);
 		w = hi[3] ? kSentinel : w;
 	}
 	dump[12 * 64] = (uint16_t)w;
@@ -484,8 +510,7 @@ __device__ void decode4_k5_12(const uint32_t *__restrict__ bm, uint64_t *__restr
 
 // The K=5 rate-1/2 decoder shaped for the LATENCY of one burst (the receive loop: a wave alone on its SIMD issues one
 // instruction every four to five cycles whatever the dependences, so a round costs what its instruction count says).
-// The batch decoder above spends 7 instructions per trellis step (wait, add, add-dpp, min, add of the next tie-break bit, two
-// cost-byte reads).  Here a step's operands come ready-made from a table the branch-metric phase expands once per burst:
+// The batch decoder above spends 6 instructions per trellis step (wait, two adds, min with DPP, two cost-byte reads).  Here a step's operands come ready-made from a table the branch-metric phase expands once per burst:
 // per step and code word two 8-byte entries (this lane the HIGH predecessor or not) -- both generators have the D^0 and D^4
 // taps, so the partner's code word is the own one's complement -- holding  own cost << 16 | tie-break bit if this lane is the
 // HIGH predecessor,  partner's cost << 16 | tie-break bit if the partner is.  One ds_read_b64 and three VALU per step: 5
@@ -738,11 +763,10 @@ __device__ __forceinline__ void store_l2(uint8_t *l2, const uint32_t *ub)
 		l2w[i] = ub[i];
 }
 
-#undef ACS_CORE
+#undef ACS_CAND
+#undef ACS_MIN
 #undef ACS_PF
 #undef ACS_NP
-#undef ACS_PF_END
-#undef ACS_NP_END
 #undef ACS_LOAD
 #undef ACSL_CORE
 #undef ACSL_PF

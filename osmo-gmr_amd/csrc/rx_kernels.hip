@@ -40,9 +40,11 @@
 //     point: sin(pi (k - f)) = -(-1)^k sin(pi f) for integer tap offsets k.
 //   * The Viterbi butterfly is in place: the two predecessors of a state sit in two lanes
 //     of the row that differ by an xor mask (8, 7, 2, 1 over the four phases: one DPP control
-//     each), so the partner metric arrives folded into the add and no metric ever moves.  A
-//     state's 32-bit word is [metric:16 | decisions of the current 16-step window:16]; v_min_u32
-//     does compare, select, tie-break and decision recording at once (see decode4_k5_12).
+//     each), so the partner's candidate arrives folded into the min and no metric ever moves.  A
+//     state's 32-bit word is [metric:16 | decisions of the current 16-step window:16]; each lane
+//     forms both candidates it sends on (two v_add3_u32: word + cost + tie-break bit) and v_min_u32
+//     with DPP does compare, select, tie-break and decision recording at once -- three VALU per
+//     trellis step (see decode4_k5_12).
 #include <mutex>
 #include <type_traits>
 
