@@ -33,6 +33,7 @@
  *   gmr1_hip_fcch_rough_multi_batch* -> gmr1_fcch_rough_multi include/osmocom/gmr1/sdr/fcch.h:51-53
  *   gmr1_hip_fcch_fine_batch*    -> gmr1_fcch_fine        include/osmocom/gmr1/sdr/fcch.h:55-57
  *   gmr1_hip_fcch_snr_batch*     -> gmr1_fcch_snr         include/osmocom/gmr1/sdr/fcch.h:59-61
+ *   gmr1_hip_fcch_acquire_batch* -> fcch_single_init / fcch_multi_process  src/gmr1_rx.c:605-733 (up to the survivor list)
  */
 #ifndef GMR1_HIP_H
 #define GMR1_HIP_H
@@ -77,7 +78,7 @@ struct gmr1_hip_burst_flat {
 /* ---- library / device ----------------------------------------------------
  * Threads: gmr1_hip_last_error() is per thread; the burst-level _batch / _batch_dev calls keep no state
  * between calls and may run from several threads on different streams.  The calls that use the library's
- * grow-only per-device workspace -- gmr1_hip_fcch_rough*_batch*, gmr1_hip_channelize*, gmr1_hip_ddc*,
+ * grow-only per-device workspace -- gmr1_hip_fcch_rough*_batch*, gmr1_hip_fcch_acquire_batch*, gmr1_hip_channelize*, gmr1_hip_ddc*,
  * gmr1_hip_rx_run*, gmr1_hip_detect_batch* with more than four candidates, and gmr1_hip_tch3_rx_batch* where it
  * runs as two launches without a caller's soft-bit buffer -- may ALSO be called from several threads and streams:
  * they take turns.  The host part of such a call runs under a per-device lock (a second thread waits), and a call
@@ -350,6 +351,39 @@ int gmr1_hip_fcch_snr_batch_dev(void *stream, int fcch_type, int n, int sps,
 int gmr1_hip_fcch_snr_batch(int fcch_type, int n, int sps,
                             const float *iq, uint64_t iq_len, const uint64_t *offset,
                             const float *freq_shift, float *snr);
+/* The whole acquisition gmr1_rx runs on a capture before it follows a carrier (main() -> fcch_single_init and
+ * fcch_multi_process up to its survivor list, gmr1_rx.c:605-733) over n streams at once: rough over 330 ms from start[i],
+ * fine, rough_multi over 650 ms, then fine and snr of every candidate, and the decisions between and behind them -- all on
+ * the device, one record per stream.  It is what gmr1_hip_rx_run* does first; this call stops there and reports what that
+ * one only uses.  Stream i is iq[offset[i] .. offset[i] + length[i]) (complex64; the layout a gmr1_hip_channelize* call
+ * leaves its outputs in), length[i] at most 2^31 - 1; start may be NULL: 8000 everywhere, the samples gmr1_rx discards
+ * (gmr1_rx.c:52).  The window lengths are the reference's whatever the fcch_type, the burst length is the type's.
+ * _dev: iq, offset, length, start and out are device memory; the call enqueues on `stream` and returns -- no copy to the
+ * host, no synchronisation (but for a scratch buffer that has to grow).  The host form copies iq (iq_len complex samples)
+ * and the arrays in and the records out.  n == 0 does nothing.  -EINVAL: fcch_type outside 0..2, sps outside 1..16, n < 0,
+ * a NULL array, iq not aligned to 8 bytes; host form also: a stream that leaves iq or is too long, a negative start (on
+ * the device these two end that stream alone, status -EINVAL). */
+#define GMR1_HIP_ACQ_MAX_CHAINS 16          /* the candidates rough_multi is asked for (mtoa[16], gmr1_rx.c:647) */
+struct gmr1_hip_fcch_acq {
+	int32_t status;        /* 0, or what gmr1_rx's main() would have exited with for this stream: -1 (not enough
+	                          samples, at any of the reference's win_map checks, or a candidate outside the stream),
+	                          rough's rv, rough_multi's negative count.  Not 0: every field below is 0 */
+	int32_t n_chains;      /* survivors of fcch_multi_process: the chains gmr1_hip_rx_run* would follow */
+	int32_t align;         /* start + rough toa + fine toa (fcch_single_init) */
+	int32_t base_align;    /* max(0, align - burst_len*sps): where the 650 ms window begins */
+	float   freq_err;      /* fcch_single_init's, as gmr1_fcch_fine returns it (Hz = 23400 x freq_err / 2 pi) */
+	int32_t n_cand;        /* peaks rough_multi reported */
+	/* the survivors, in candidate order (the first one is the strongest peak); slots at and past n_chains are 0 */
+	int32_t chain_align[GMR1_HIP_ACQ_MAX_CHAINS];     /* base_align + peak + fine toa: first sample of the chain's FCCH */
+	float   chain_freq_err[GMR1_HIP_ACQ_MAX_CHAINS];  /* the candidate's residual (fine with -freq_err applied) */
+	float   chain_snr[GMR1_HIP_ACQ_MAX_CHAINS];       /* gmr1_fcch_snr with -(freq_err + residual) applied, linear */
+};
+int gmr1_hip_fcch_acquire_batch_dev(void *stream, int fcch_type, int n, int sps, const float *iq,
+                                    const uint64_t *offset, const uint64_t *length, const int32_t *start,
+                                    struct gmr1_hip_fcch_acq *out);
+int gmr1_hip_fcch_acquire_batch(int fcch_type, int n, int sps, const float *iq, uint64_t iq_len,
+                                const uint64_t *offset, const uint64_t *length, const int32_t *start,
+                                struct gmr1_hip_fcch_acq *out);
 
 /* Direct mode of the recorder script (utils/gmr1_rx_sdr.py:605-807, DirectOutputParameters / DirectOutputBranch): a few
  * carriers straight from the wideband stream, no filterbank.  Per carrier at freq_hz[i] from the centre:
@@ -529,7 +563,7 @@ struct gmr1_hip_rx_big_record {
 	uint8_t  l2[64];
 };
 /* Measurement aid: wall time, in microseconds, of the phases of the calling thread's last gmr1_hip_rx_run* call --
- * [0] FCCH acquisition (main() -> fcch_single_init / fcch_multi_process, gmr1_rx.c:605-744) incl. its decisions on the host,
+ * [0] FCCH acquisition (main() -> fcch_single_init / fcch_multi_process, gmr1_rx.c:605-744) incl. the chains set up from its result,
  * [1] the frame loop (process_bcch, :852-895) from its first launch until its kernels are through, [2] the records to the
  * caller's buffer, [3] host work around the loop, [4] the traffic-channel passes. */
 int gmr1_hip_rx_run_last_timing(double *us5);

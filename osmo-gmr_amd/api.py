@@ -91,6 +91,8 @@ SIGNATURES = {
     "gmr1_hip_fcch_fine_batch": (I, I, I, I, P, U64, P, P, P, P),
     "gmr1_hip_fcch_snr_batch_dev": (I, P, I, I, I, P, P, P, P),
     "gmr1_hip_fcch_snr_batch": (I, I, I, I, P, U64, P, P, P),
+    "gmr1_hip_fcch_acquire_batch_dev": (I, P, I, I, I, P, P, P, P, P),
+    "gmr1_hip_fcch_acquire_batch": (I, I, I, I, P, U64, P, P, P, P),
     "gmr1_hip_ddc_plan": (I, D, I, U64, P, P, P, P),
     "gmr1_hip_ddc_dev": (I, P, D, I, P, U64, I, P, P, U64, P),
     "gmr1_hip_ddc": (I, D, I, P, U64, I, P, P, U64, P),
@@ -581,6 +583,39 @@ def fcch_snr(iq, sps=4, freq_shift=0.0, fcch_type="fcch"):
 
 def fcch_rough_batch_dev(stream, fcch_type, n, sps, length, iq, offset, freq_shift, toa, rv):
     _call("gmr1_hip_fcch_rough_batch_dev", stream, _fcch_id(fcch_type), n, sps, length, iq, offset, freq_shift, toa, rv)
+
+
+ACQ_MAX_CHAINS = 16
+
+
+class FcchAcq(C.Structure):
+    """struct gmr1_hip_fcch_acq (include/gmr1_hip.h)."""
+    _fields_ = [("status", C.c_int32), ("n_chains", C.c_int32), ("align", C.c_int32), ("base_align", C.c_int32),
+                ("freq_err", C.c_float), ("n_cand", C.c_int32), ("chain_align", C.c_int32 * ACQ_MAX_CHAINS),
+                ("chain_freq_err", C.c_float * ACQ_MAX_CHAINS), ("chain_snr", C.c_float * ACQ_MAX_CHAINS)]
+
+
+# the same layout for arrays of them (FCCH_ACQ.itemsize == ctypes.sizeof(FcchAcq))
+FCCH_ACQ = np.dtype([("status", "<i4"), ("n_chains", "<i4"), ("align", "<i4"), ("base_align", "<i4"), ("freq_err", "<f4"),
+                     ("n_cand", "<i4"), ("chain_align", "<i4", (ACQ_MAX_CHAINS,)), ("chain_freq_err", "<f4", (ACQ_MAX_CHAINS,)),
+                     ("chain_snr", "<f4", (ACQ_MAX_CHAINS,))])
+
+
+def fcch_acquire(iq, offset, length, sps=4, start=None, fcch_type="fcch"):
+    """gmr1_rx's acquisition (fcch_single_init, fcch_multi_process up to its survivor list) of the streams
+    iq[offset[i] : offset[i] + length[i]] -> one FCCH_ACQ record each.  start: where each stream's 330 ms window begins
+    (None: 8000 everywhere)."""
+    iq = _arr(iq, np.complex64, -1)
+    offset, length, start = _arr(offset, np.uint64), _arr(length, np.uint64), _arr(start, np.int32)
+    out = np.zeros(offset.size, FCCH_ACQ)
+    _call("gmr1_hip_fcch_acquire_batch", _fcch_id(fcch_type), offset.size, sps, _p(iq), iq.size, _p(offset), _p(length),
+          _p(start), _p(out))
+    return out
+
+
+def fcch_acquire_dev(stream, n, iq, offset, length, out, sps=4, start=None, fcch_type="fcch"):
+    """The same on device memory (addresses): enqueues on `stream` and returns; out: n records of FCCH_ACQ.itemsize bytes."""
+    _call("gmr1_hip_fcch_acquire_batch_dev", stream, _fcch_id(fcch_type), n, sps, iq, offset, length, start, out)
 
 
 # ---------------------------------------------------------------------------

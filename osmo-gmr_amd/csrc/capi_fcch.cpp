@@ -312,9 +312,238 @@ int fcch_rough_multi_tail(hipStream_t stream, int fcch_type, int n, int sps, int
 	return 0;
 }
 
+namespace {
+struct AcqBuf { void *p = nullptr; size_t n = 0; int dev = -1; };
+
+// (per thread AND per device: a thread that moves on to another GPU must not hand that GPU's kernels this one's memory)
+int acq_buf(AcqBuf &b, size_t bytes, bool *grew)
+{
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	*grew = false;
+	if (b.n >= bytes && b.dev == dev)
+		return 0;
+	if (b.p) {
+		int back = dev;
+		if (b.dev >= 0 && b.dev != dev && hipSetDevice(b.dev) == hipSuccess) {
+			(void)hipFree(b.p);
+			(void)hipSetDevice(back);
+		} else {
+			(void)hipFree(b.p);
+		}
+	}
+	b.p = nullptr;
+	b.n = 0;
+	b.dev = dev;
+	HIP_TRY(hipMalloc(&b.p, bytes + bytes / 4));
+	b.n = bytes + bytes / 4;
+	*grew = true;
+	return 0;
+}
+
+// the spare window of the chain (AcqArgs::spare): n complex samples of noise, written once when the buffer is made
+int acq_spare(size_t n, hipStream_t st, const float2 **out)
+{
+	static thread_local AcqBuf b;
+	bool grew;
+	int r = acq_buf(b, n * sizeof(float2), &grew);
+	if (r) return r;
+	if (grew) {
+		// (later calls may come on other streams: the samples are there before this one returns)
+		HIP_TRY(launch_acq_spare_fill(static_cast<float2 *>(b.p), b.n / sizeof(float2), st));
+		HIP_TRY(hipStreamSynchronize(st));
+	}
+	*out = static_cast<const float2 *>(b.p);
+	return 0;
+}
+
+size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
+
+int acq_check(int tab, int n, int sps, const float *iq, const uint64_t *offset, const uint64_t *length, const void *out)
+{
+	if (tab < 0 || tab >= kFcchTabs)
+		return fail(-EINVAL, "fcch_acquire: unknown burst type");
+	if (n < 0 || !iq || !offset || !length || !out)
+		return fail(-EINVAL, "fcch_acquire: NULL argument");
+	if (sps < 1 || sps > 16)
+		return fail(-EINVAL, "fcch_acquire: sps=%d out of range (1..16)", sps);
+	// (the spare window is addressed as iq + whole samples)
+	if ((uintptr_t)iq & 7)
+		return fail(-EINVAL, "fcch_acquire: iq is not aligned to a complex sample");
+	return 0;
+}
+}  // namespace
+
+int acq_scratch(int slot, size_t bytes, unsigned char **out)
+{
+	static thread_local AcqBuf b[2];
+	bool grew;
+	int r = acq_buf(b[slot & 1], bytes, &grew);
+	if (r) return r;
+	*out = static_cast<unsigned char *>(b[slot & 1].p);
+	return 0;
+}
+
+int fcch_acquire_enqueue(hipStream_t st, int tab, int n, int sps, const float *iq, const uint64_t *offset,
+                         const uint64_t *length, const int32_t *start, const uint64_t *h_length,
+                         struct gmr1_hip_fcch_acq *out)
+{
+	// The five sweeps of fcch_single_init / fcch_multi_process (gmr1_rx.c:605-744) follow each other on the stream
+	// without the host: k_acq_glue's steps (fcch_kernels.hip) do the additions and bound checks between them on the device
+	// and lay out each next sweep's windows; candidate stages run over all kAcqPeaks slots of every carrier (a slot
+	// without a candidate gets a harmless window).  k_acq_begin in front takes the checks on the lengths, k_acq_decide
+	// behind takes the decisions from the sweeps' results and writes the caller's records.
+	int r = acq_check(tab, n, sps, iq, offset, length, out);
+	if (r) return r;
+	if (n == 0) return 0;
+	const int flen = kFcchBuiltin[tab]->len * sps;
+	const int wl1 = (330 * 23400 * sps) / 1000, wl3 = (650 * 23400 * sps) / 1000;
+	const size_t S = (size_t)n * kAcqPeaks;
+	// one block: [per carrier ... | per slot ...]
+	size_t o = 0;
+	auto take = [&](size_t bytes) { const size_t at = o; o += up128(bytes); return at; };
+	const size_t o_base = take(n * 8), o_len = take(n * 8), o_stat = take(n * 4), o_align = take(n * 4), o_ba = take(n * 4),
+	             o_ferr = take(n * 4), o_can3 = take(n * 4), o_off = take(S * 8), o_peaks = take(S * 4), o_toa1 = take(n * 4),
+	             o_rv1 = take(n * 4), o_ftoa = take(n * 4), o_fe = take(n * 4), o_count = take(n * 4), o_ctoa = take(S * 4),
+	             o_cfe = take(S * 4), o_snr = take(S * 4), o_live = take(S * 4), o_fs = take(S * 4);
+	const size_t total = o;
+	unsigned char *d;
+	if ((r = acq_scratch(0, total, &d))) return r;
+	const float2 *spare;
+	if ((r = acq_spare((size_t)wl3, st, &spare))) return r;
+	auto D = [&](size_t at) { return d + at; };
+
+	AcqArgs g;
+	std::memset(&g, 0, sizeof(g));
+	g.n = n; g.sps = sps; g.flen = flen; g.wl3 = wl3;
+	// (both are 8-byte aligned, so the difference is whole samples; windows are iq + offset in 64-bit arithmetic)
+	g.spare = (uint64_t)((uintptr_t)spare - (uintptr_t)iq) / sizeof(float2);
+	g.base = reinterpret_cast<uint64_t *>(D(o_base));
+	g.len = reinterpret_cast<uint64_t *>(D(o_len));
+	g.stat = reinterpret_cast<int32_t *>(D(o_stat));
+	g.align = reinterpret_cast<int32_t *>(D(o_align));
+	g.base_align = reinterpret_cast<int32_t *>(D(o_ba));
+	g.ferr = reinterpret_cast<float *>(D(o_ferr));
+	g.can3 = reinterpret_cast<int32_t *>(D(o_can3));
+	g.toa1 = reinterpret_cast<const int32_t *>(D(o_toa1));
+	g.rv1 = reinterpret_cast<const int32_t *>(D(o_rv1));
+	g.ftoa = reinterpret_cast<const int32_t *>(D(o_ftoa));
+	g.fe = reinterpret_cast<const float *>(D(o_fe));
+	g.peaks = reinterpret_cast<int32_t *>(D(o_peaks));
+	g.count = reinterpret_cast<int32_t *>(D(o_count));
+	g.ctoa = reinterpret_cast<const int32_t *>(D(o_ctoa));
+	g.cfe = reinterpret_cast<const float *>(D(o_cfe));
+	g.off = reinterpret_cast<uint64_t *>(D(o_off));
+	g.fs = reinterpret_cast<float *>(D(o_fs));
+	g.live = reinterpret_cast<int32_t *>(D(o_live));
+	uint64_t *d_off = g.off;
+	float *d_fs = g.fs;
+	AcqIo io;
+	std::memset(&io, 0, sizeof(io));
+	io.offset = offset; io.length = length; io.start = start;
+	io.wl1 = wl1;
+	io.snr = reinterpret_cast<const float *>(D(o_snr));
+	io.out = out;
+	HIP_TRY(launch_acq_begin(g, io, st));
+
+	// What the reference does between two sweeps (k_acq_glue's steps) is done by the producing sweep's last thread
+	// (AcqTail, fcch_acq.h) -- four launches fewer in a chain of small dependent ones; the profiling build keeps the
+	// other form for the comparison (GMR1_HIP_ACQ_UNFUSED).
+	static const bool unfused = profile_env("GMR1_HIP_ACQ_UNFUSED") != nullptr;
+	auto tail = [&](int step, bool skip_dead) {
+		AcqTail t;
+		std::memset(&t, 0, sizeof(t));
+		if (!unfused) {
+			t.step = step;
+			t.skip_dead = skip_dead ? g.live : nullptr;
+			t.g = g;
+		}
+		return t;
+	};
+	// fcch_single_init (gmr1_rx.c:605-639): rough over 330 ms, then fine
+	if ((r = fcch_rough_tail(st, tab, n, sps, wl1, iq, d_off, nullptr, reinterpret_cast<int32_t *>(D(o_toa1)),
+	                         reinterpret_cast<int32_t *>(D(o_rv1)), tail(1, false)))) return r;
+	if (unfused) HIP_TRY(launch_acq_glue(1, g, st));
+	if ((r = fcch_fine_tail(st, tab, 0, n, sps, iq, d_off, nullptr, reinterpret_cast<int32_t *>(D(o_ftoa)),
+	                        reinterpret_cast<float *>(D(o_fe)), nullptr, tail(2, false)))) return r;
+	if (unfused) HIP_TRY(launch_acq_glue(2, g, st));
+	// fcch_multi_process (gmr1_rx.c:643-744); a carrier shorter than 650 ms can only fail here: where the host knows the
+	// lengths the sweep runs over the others (where it does not, over everything: such a carrier's window is the spare one)
+	std::vector<int> k3;
+	for (int k = 0; k < n; k++)
+		if (!h_length || h_length[k] >= (uint64_t)wl3)
+			k3.push_back(k);
+	const bool all3 = (int)k3.size() == n;
+	if (!k3.empty()) {
+		if (all3) {
+			if ((r = fcch_rough_multi_tail(st, tab, n, sps, wl3, iq, d_off, d_fs, reinterpret_cast<int32_t *>(D(o_peaks)),
+			                               kAcqPeaks, reinterpret_cast<int32_t *>(D(o_count)), tail(3, false)))) return r;
+		} else {
+			// mixed lengths: the long-enough carriers one by one at their own slots (rare; captures come in equal lengths)
+			for (int k : k3)
+				if ((r = gmr1_hip_fcch_rough_multi_batch_dev(st, tab, 1, sps, wl3, iq, d_off + k, d_fs + k,
+				                                             reinterpret_cast<int32_t *>(D(o_peaks)) + (size_t)k * kAcqPeaks, kAcqPeaks,
+				                                             reinterpret_cast<int32_t *>(D(o_count)) + k))) return r;
+		}
+	}
+	// (mixed lengths, or no carrier long enough: the step that lays out the candidate slots runs as its own launch)
+	if (unfused || !all3) HIP_TRY(launch_acq_glue(3, g, st));
+	if ((r = fcch_fine_tail(st, tab, 0, (int)S, sps, iq, d_off, d_fs, reinterpret_cast<int32_t *>(D(o_ctoa)),
+	                        reinterpret_cast<float *>(D(o_cfe)), nullptr, tail(4, true)))) return r;
+	if (unfused) HIP_TRY(launch_acq_glue(4, g, st));
+	if ((r = fcch_fine_tail(st, tab, 1, (int)S, sps, iq, d_off, d_fs, nullptr, nullptr, reinterpret_cast<float *>(D(o_snr)),
+	                        tail(0, true)))) return r;
+	HIP_TRY(launch_acq_decide(g, io, st));
+	return 0;
+}
+
 }  // namespace gmr1
 
 extern "C" {
+
+int gmr1_hip_fcch_acquire_batch_dev(void *stream, int fcch_type, int n, int sps, const float *iq,
+                                    const uint64_t *offset, const uint64_t *length, const int32_t *start,
+                                    struct gmr1_hip_fcch_acq *out)
+{
+	int r = acq_check(fcch_type, n, sps, iq, offset, length, out);
+	if (r) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n == 0) return 0;
+	// (the chain's scratch and the sweeps' workspace are this call's until its last launch)
+	WsLease lease;
+	if ((r = lease.acquire(s, (hipStream_t)stream))) return r;
+	return fcch_acquire_enqueue((hipStream_t)stream, fcch_type, n, sps, iq, offset, length, start, nullptr, out);
+}
+
+int gmr1_hip_fcch_acquire_batch(int fcch_type, int n, int sps, const float *iq, uint64_t iq_len,
+                                const uint64_t *offset, const uint64_t *length, const int32_t *start,
+                                struct gmr1_hip_fcch_acq *out)
+{
+	int r = acq_check(fcch_type, n, sps, iq, offset, length, out);
+	if (r) return r;
+	for (int i = 0; i < n; i++) {
+		if (length[i] > 0x7fffffffull || offset[i] > iq_len || length[i] > iq_len - offset[i])
+			return fail(-EINVAL, "fcch_acquire: stream %d is longer than 2^31-1 samples or runs past the end of iq", i);
+		if (start && start[i] < 0)
+			return fail(-EINVAL, "fcch_acquire: start[%d] is negative", i);
+	}
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n == 0) return 0;
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const uint64_t *d_off = sg.in(offset, (size_t)n), *d_len = sg.in(length, (size_t)n);
+	const int32_t *d_start = sg.in(start, (size_t)n);
+	struct gmr1_hip_fcch_acq *d_out = sg.out(out, (size_t)n);
+	if ((r = sg.err())) return r;
+	{
+		WsLease lease;
+		if ((r = lease.acquire(s, nullptr))) return r;
+		if ((r = fcch_acquire_enqueue(nullptr, fcch_type, n, sps, d_iq, d_off, d_len, d_start, length, d_out))) return r;
+	}
+	return sg.fetch();
+}
 
 int gmr1_hip_fcch_rough_multi_batch_dev(void *stream, int fcch_type, int n, int sps, int len,
                                         const float *iq, const uint64_t *offset, const float *freq_shift,

@@ -10,8 +10,8 @@
 // then the BCCH feedback -- and it runs them ON THE GPU: k_rx_chain (rx_kernels.hip) walks every
 // chain's feedback path from the first frame to the end of the capture and lists its CCCH bursts, one
 // k_rx4 batch takes those, k_rx_merge writes the records (the integer control logic is in rx_loop.h);
-// the host only collects them.  FCCH acquisition is three batched sweeps
-// (rough / rough_multi / fine + snr) over all carriers.  The arithmetic of every step runs on the
+// the host only collects them.  FCCH acquisition is one chain of batched sweeps
+// (rough / fine / rough_multi / fine + snr) over all carriers with its decisions taken on the device (capi_fcch.cpp).  The arithmetic of every step runs on the
 // GPU; the host keeps only the per-chain integers the reference keeps in struct chan_desc.
 // There is no CPU fallback.
 //
@@ -36,11 +36,7 @@ using namespace gmr1;
 namespace {
 
 constexpr int kStartDiscard = 8000;   // gmr1_rx.c:52
-constexpr int kSymRate = 23400;
-constexpr int kFcchLen = 117;         // gmr1_fcch_burst.len, fcch.c:50-54
 constexpr int kMaxPeaks = 16;         // gmr1_rx.c:650
-
-float to_hz(float f_rps) { return (kSymRate * f_rps) / (2.0f * 3.14159265358979323846f); }
 
 struct FrameCtx { int align; float freq_err; int fn; };       // what rx_tch3 sees in a frame
 struct AssEvt { int frame; int tn, p; float ref_energy; };     // an IMMEDIATE ASSIGNMENT taken from the CCCH
@@ -142,11 +138,8 @@ struct RxRun {
 	const uint16_t *arfcn;
 	const uint8_t *kc;
 	int A;                                   // carriers
-	int flen;                                // samples of an FCCH burst
 	int r = 0;
 	std::vector<int32_t> stat, nch;          // per carrier: status, chains followed
-	std::vector<int> align, base_align;
-	std::vector<float> ferr;
 	std::vector<RxChain> chains;
 	double t_loop_gpu_us = 0;                // launch to log-on-host
 	double t_chain_us = 0;                   // ... of which: launches until the loop's kernels are through (counters on the host)
@@ -168,167 +161,36 @@ struct RxRun {
 };
 
 
-// grow-only device scratch of the acquisition (its sweeps use the library's shared workspace themselves)
-static int acq_scratch(size_t bytes, unsigned char **out)
-{
-	// (per thread AND per device: a thread that moves on to another GPU must not hand that GPU's kernels this one's memory)
-	struct Buf { void *p = nullptr; size_t n = 0; int dev = -1; };
-	static thread_local Buf b;
-	int dev = 0;
-	HIP_TRY(hipGetDevice(&dev));
-	if (b.n < bytes || b.dev != dev) {
-		if (b.p) {
-			int back = dev;
-			if (b.dev >= 0 && b.dev != dev && hipSetDevice(b.dev) == hipSuccess) {
-				(void)hipFree(b.p);
-				(void)hipSetDevice(back);
-			} else {
-				(void)hipFree(b.p);
-			}
-		}
-		b.p = nullptr;
-		b.n = 0;
-		b.dev = dev;
-		HIP_TRY(hipMalloc(&b.p, bytes + bytes / 4));
-		b.n = bytes + bytes / 4;
-	}
-	*out = static_cast<unsigned char *>(b.p);
-	return 0;
-}
-
 // wall time of the phases of this thread's last gmr1_hip_rx_run* call, microseconds (gmr1_hip_rx_run_last_timing)
 static thread_local double t_last_timing[5] = {0, 0, 0, 0, 0};
 
 int RxRun::acquire()
 {
-	// The five sweeps of fcch_single_init / fcch_multi_process (gmr1_rx.c:605-744) follow each other on the stream
-	// without the host: k_acq_glue (fcch_kernels.hip) does the additions and bound checks between them on the device
-	// and lays out each next sweep's windows; candidate stages run over all kMaxPeaks slots of every carrier (a slot
-	// without a candidate gets a harmless window).  One copy brings every raw sweep result back, and the decisions are
-	// then taken here exactly as before, from those numbers.
-	static_assert(kMaxPeaks == kAcqPeaks, "candidate slots");
+	// The acquisition (fcch_single_init / fcch_multi_process, gmr1_rx.c:605-744) is one chain on the stream, decisions
+	// included (fcch_acquire_enqueue, capi_fcch.cpp -- what gmr1_hip_fcch_acquire_batch_dev runs): the carriers' offsets and
+	// lengths go up in one copy, one struct gmr1_hip_fcch_acq per carrier comes back, and the chains are set up from those.
+	static_assert(kMaxPeaks == kAcqPeaks && kMaxPeaks == GMR1_HIP_ACQ_MAX_CHAINS, "candidate slots");
 	// (profiling build, GMR1_HIP_RX_TIMING: host-side stamps of this call's stages on stderr)
 	static const bool timing = profile_env("GMR1_HIP_RX_TIMING") != nullptr;
 	std::chrono::steady_clock::time_point tp[6];
 	int n_tp = 0;
 	auto stamp = [&] { if (timing && n_tp < 6) tp[n_tp++] = std::chrono::steady_clock::now(); };
 	stamp();
-	const int wl1 = (330 * kSymRate * sps) / 1000, wl3 = (650 * kSymRate * sps) / 1000;
-	std::vector<int> idx;
-	for (int i = 0; i < A; i++) {
-		if ((uint64_t)align[i] + wl1 > length[i]) { stat[i] = -1; continue; }
-		idx.push_back(i);
-	}
-	const int n = (int)idx.size();
-	if (!n)
-		return 0;
-	const size_t S = (size_t)n * kMaxPeaks;
-	// one block, device and pinned host mirror: [per carrier ... | per slot ...]
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t at = o; o += up128(bytes); return at; };
-	// (what the host sends first -- the carriers' parameters, the first sweep's windows and a zeroed peak list -- in front,
-	// so that ONE copy starts the chain; what comes back -- toa1 .. snr -- contiguous behind it)
-	const size_t o_base = take(n * 8), o_len = take(n * 8), o_stat = take(n * 4), o_align = take(n * 4), o_ba = take(n * 4),
-	             o_ferr = take(n * 4), o_can3 = take(n * 4), o_off = take(S * 8), o_peaks = take(S * 4), o_toa1 = take(n * 4),
-	             o_rv1 = take(n * 4), o_ftoa = take(n * 4), o_fe = take(n * 4), o_count = take(n * 4), o_ctoa = take(S * 4),
-	             o_cfe = take(S * 4), o_snr = take(S * 4), o_live = take(S * 4), o_fs = take(S * 4);
-	const size_t total = o;
+	// one block, device and pinned host mirror: [offset | length | results]
+	const size_t o_len = up128((size_t)A * 8), o_res = o_len + up128((size_t)A * 8);
+	const size_t total = o_res + (size_t)A * sizeof(gmr1_hip_fcch_acq);
 	unsigned char *d, *h;
-	if ((r = acq_scratch(total, &d))) return r;
+	if ((r = acq_scratch(1, total, &d))) return r;
 	if ((r = host_log(total, &h))) return r;
-	auto H = [&](size_t at) { return h + at; };
-	auto D = [&](size_t at) { return d + at; };
-	for (int k = 0; k < n; k++) {
-		const int i = idx[k];
-		reinterpret_cast<uint64_t *>(H(o_base))[k] = offset[i];
-		reinterpret_cast<uint64_t *>(H(o_len))[k] = length[i];
-		reinterpret_cast<int32_t *>(H(o_stat))[k] = 0;
-		reinterpret_cast<int32_t *>(H(o_align))[k] = align[i];
-		reinterpret_cast<int32_t *>(H(o_ba))[k] = 0;
-		reinterpret_cast<float *>(H(o_ferr))[k] = 0.f;
-		reinterpret_cast<int32_t *>(H(o_can3))[k] = length[i] >= (uint64_t)wl3 ? 1 : 0;
-		reinterpret_cast<uint64_t *>(H(o_off))[k] = offset[i] + (uint64_t)align[i];
-	}
-	// rough_multi leaves slots past `count` unwritten: the copy back must not carry stale numbers
-	std::memset(H(o_off) + (size_t)n * 8, 0, (o_toa1 - o_off) - (size_t)n * 8);
-	// inputs: everything up to can3, the first sweep's windows, the zeroed peak list -- one copy
-	HIP_TRY(hipMemcpyAsync(d, h, o_toa1, hipMemcpyHostToDevice, st));
+	std::memcpy(h, offset, (size_t)A * 8);
+	std::memcpy(h + o_len, length, (size_t)A * 8);
+	HIP_TRY(hipMemcpyAsync(d, h, o_res, hipMemcpyHostToDevice, st));
 	stamp();
-
-	AcqArgs g;
-	std::memset(&g, 0, sizeof(g));
-	g.n = n; g.sps = sps; g.flen = flen; g.wl3 = wl3;
-	g.base = reinterpret_cast<const uint64_t *>(D(o_base));
-	g.len = reinterpret_cast<const uint64_t *>(D(o_len));
-	g.stat = reinterpret_cast<int32_t *>(D(o_stat));
-	g.align = reinterpret_cast<int32_t *>(D(o_align));
-	g.base_align = reinterpret_cast<int32_t *>(D(o_ba));
-	g.ferr = reinterpret_cast<float *>(D(o_ferr));
-	g.can3 = reinterpret_cast<const int32_t *>(D(o_can3));
-	g.toa1 = reinterpret_cast<const int32_t *>(D(o_toa1));
-	g.rv1 = reinterpret_cast<const int32_t *>(D(o_rv1));
-	g.ftoa = reinterpret_cast<const int32_t *>(D(o_ftoa));
-	g.fe = reinterpret_cast<const float *>(D(o_fe));
-	g.peaks = reinterpret_cast<const int32_t *>(D(o_peaks));
-	g.count = reinterpret_cast<const int32_t *>(D(o_count));
-	g.ctoa = reinterpret_cast<const int32_t *>(D(o_ctoa));
-	g.cfe = reinterpret_cast<const float *>(D(o_cfe));
-	g.off = reinterpret_cast<uint64_t *>(D(o_off));
-	g.fs = reinterpret_cast<float *>(D(o_fs));
-	g.live = reinterpret_cast<int32_t *>(D(o_live));
-	uint64_t *d_off = g.off;
-	float *d_fs = g.fs;
-
-	// What the reference does between two sweeps (k_acq_glue's steps) is done by the producing sweep's last thread
-	// (AcqTail, fcch_acq.h) -- four launches fewer in a chain of small dependent ones; the profiling build keeps the
-	// other form for the comparison (GMR1_HIP_ACQ_UNFUSED).
-	static const bool unfused = profile_env("GMR1_HIP_ACQ_UNFUSED") != nullptr;
-	auto tail = [&](int step, bool skip_dead) {
-		AcqTail t;
-		std::memset(&t, 0, sizeof(t));
-		if (!unfused) {
-			t.step = step;
-			t.skip_dead = skip_dead ? g.live : nullptr;
-			t.g = g;
-		}
-		return t;
-	};
-	// fcch_single_init (gmr1_rx.c:605-639): rough over 330 ms, then fine
-	if ((r = fcch_rough_tail(st, 0, n, sps, wl1, iq, d_off, nullptr, reinterpret_cast<int32_t *>(D(o_toa1)),
-	                         reinterpret_cast<int32_t *>(D(o_rv1)), tail(1, false)))) return r;
-	if (unfused) HIP_TRY(launch_acq_glue(1, g, st));
-	if ((r = fcch_fine_tail(st, 0, 0, n, sps, iq, d_off, nullptr, reinterpret_cast<int32_t *>(D(o_ftoa)),
-	                        reinterpret_cast<float *>(D(o_fe)), nullptr, tail(2, false)))) return r;
-	if (unfused) HIP_TRY(launch_acq_glue(2, g, st));
-	// fcch_multi_process (gmr1_rx.c:643-744); a carrier shorter than 650 ms can only fail here, its dummy window would
-	// not fit either: the sweep runs over the others
-	std::vector<int> k3;
-	for (int k = 0; k < n; k++)
-		if (length[idx[k]] >= (uint64_t)wl3)
-			k3.push_back(k);
-	const bool all3 = (int)k3.size() == n;
-	if (!k3.empty()) {
-		if (all3) {
-			if ((r = fcch_rough_multi_tail(st, 0, n, sps, wl3, iq, d_off, d_fs, reinterpret_cast<int32_t *>(D(o_peaks)),
-			                               kMaxPeaks, reinterpret_cast<int32_t *>(D(o_count)), tail(3, false)))) return r;
-		} else {
-			// mixed lengths: the long-enough carriers one by one at their own slots (rare; captures come in equal lengths)
-			for (int k : k3)
-				if ((r = gmr1_hip_fcch_rough_multi_batch_dev(st, 0, 1, sps, wl3, iq, d_off + k, d_fs + k,
-				                                             reinterpret_cast<int32_t *>(D(o_peaks)) + (size_t)k * kMaxPeaks, kMaxPeaks,
-				                                             reinterpret_cast<int32_t *>(D(o_count)) + k))) return r;
-		}
-	}
-	// (mixed lengths, or no carrier long enough: the step that lays out the candidate slots runs as its own launch)
-	if (unfused || !all3) HIP_TRY(launch_acq_glue(3, g, st));
-	if ((r = fcch_fine_tail(st, 0, 0, (int)S, sps, iq, d_off, d_fs, reinterpret_cast<int32_t *>(D(o_ctoa)),
-	                        reinterpret_cast<float *>(D(o_cfe)), nullptr, tail(4, true)))) return r;
-	if (unfused) HIP_TRY(launch_acq_glue(4, g, st));
-	if ((r = fcch_fine_tail(st, 0, 1, (int)S, sps, iq, d_off, d_fs, nullptr, nullptr, reinterpret_cast<float *>(D(o_snr)),
-	                        tail(0, true)))) return r;
-	// results back: the peak list (in front of toa1) and toa1 .. snr
+	if ((r = fcch_acquire_enqueue(st, 0, A, sps, iq, reinterpret_cast<const uint64_t *>(d),
+	                              reinterpret_cast<const uint64_t *>(d + o_len), nullptr, length,
+	                              reinterpret_cast<gmr1_hip_fcch_acq *>(d + o_res)))) return r;
 	stamp();
-	HIP_TRY(hipMemcpyAsync(H(o_peaks), D(o_peaks), o_live - o_peaks, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(h + o_res, d + o_res, (size_t)A * sizeof(gmr1_hip_fcch_acq), hipMemcpyDeviceToHost, st));
 	stamp();
 	HIP_TRY(hipStreamSynchronize(st));
 	stamp();
@@ -337,65 +199,23 @@ int RxRun::acquire()
 		fprintf(stderr, "acquire: prepare + first copy %.1f us, launches %.1f us, copy back enqueued %.1f us, waited %.1f us\n",
 		        us(tp[0], tp[1]), us(tp[1], tp[2]), us(tp[2], tp[3]), us(tp[3], tp[4]));
 	}
-
-	// ---- the decisions, from the raw sweep results, in the reference's order ------------------------------------
-	const int32_t *toa1 = reinterpret_cast<const int32_t *>(H(o_toa1)), *rv1 = reinterpret_cast<const int32_t *>(H(o_rv1)),
-	              *ftoa = reinterpret_cast<const int32_t *>(H(o_ftoa)), *count = reinterpret_cast<const int32_t *>(H(o_count)),
-	              *peaks = reinterpret_cast<const int32_t *>(H(o_peaks)), *ctoa = reinterpret_cast<const int32_t *>(H(o_ctoa));
-	const float *fe = reinterpret_cast<const float *>(H(o_fe)), *cfe = reinterpret_cast<const float *>(H(o_cfe)),
-	            *snr = reinterpret_cast<const float *>(H(o_snr));
-	for (int k = 0; k < n; k++) {
-		const int i = idx[k];
-		if (rv1[k]) { stat[i] = rv1[k]; continue; }
-		align[i] += toa1[k];
-		if ((uint64_t)align[i] + flen > length[i]) { stat[i] = -1; continue; }
-		align[i] += ftoa[k];
-		ferr[i] = fe[k];
-		base_align[i] = std::max(0, align[i] - flen);
-		if ((uint64_t)base_align[i] + wl3 > length[i]) { stat[i] = -1; continue; }
-		if (count[k] < 0) { stat[i] = count[k]; continue; }
-		// candidates; a carrier with any candidate out of its samples is dropped as a whole (the oracle's early
-		// return, see orc_rx.c), before or after the refinement
-		bool ok = true;
-		for (int q = 0; q < count[k]; q++) {
-			const int64_t p = (int64_t)base_align[i] + peaks[(size_t)k * kMaxPeaks + q];
-			if (p < 0 || p + flen > (int64_t)length[i]) ok = false;
-		}
-		if (!ok) { stat[i] = -1; continue; }
-		for (int q = 0; q < count[k]; q++) {
-			const size_t sl = (size_t)k * kMaxPeaks + q;
-			const int64_t p = (int64_t)base_align[i] + peaks[sl] + ctoa[sl];
-			if (p < 0 || p + flen > (int64_t)length[i]) stat[i] = -1;
-		}
-		if (stat[i]) continue;
-		// survivor selection, candidate order, first one is the reference (gmr1_rx.c:704-733)
-		float ref_snr = 0.f, ref_fe = 0.f;
-		for (int q = 0; q < count[k]; q++) {
-			const size_t sl = (size_t)k * kMaxPeaks + q;
-			if (q == 0) {
-				ref_snr = snr[sl];
-				ref_fe = cfe[sl];
-			} else {
-				if (snr[sl] < 2.0f) continue;
-				if (snr[sl] < ref_snr / 6.0f) continue;
-				if (to_hz(std::fabs(ref_fe - cfe[sl])) > 500.0f) continue;
-			}
+	const gmr1_hip_fcch_acq *res = reinterpret_cast<const gmr1_hip_fcch_acq *>(h + o_res);
+	for (int i = 0; i < A; i++) {
+		if (res[i].status) { stat[i] = res[i].status; continue; }
+		for (int j = 0; j < res[i].n_chains; j++) {
 			RxChain c;
 			c.a = i;
 			c.chain = nch[i]++;
 			c.base = offset[i];
 			c.len = (int)length[i];
-			c.align = base_align[i] + peaks[sl] + ctoa[sl];
-			c.freq_err = ferr[i];
+			c.align = res[i].chain_align[j];
+			c.freq_err = res[i].freq_err;
 			c.fn = 0; c.delay = 0; c.stn = 0;
 			c.bcch_energy = std::nanf("inf");
 			c.done = false;
 			chains.push_back(std::move(c));
 		}
 	}
-	if (timing)
-		fprintf(stderr, "acquire: decisions %.1f us\n",
-		        (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tp[4]).count() / 1e3);
 	return 0;
 }
 
@@ -1076,10 +896,7 @@ int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const
 	run.offset = offset; run.length = length; run.arfcn = arfcn; run.kc = kc;
 	run.A = n_arfcn;
 	run.out = out; run.max_records = max_records;
-	run.flen = kFcchLen * sps;
 	run.stat.assign(n_arfcn, 0); run.nch.assign(n_arfcn, 0);
-	run.align.assign(n_arfcn, kStartDiscard); run.base_align.assign(n_arfcn, 0);
-	run.ferr.assign(n_arfcn, 0.0f);
 	// GMR1_HIP_RX_TIMING=1: wall time of the phases on stderr (profiling only)
 	static const bool timing = profile_env("GMR1_HIP_RX_TIMING") != nullptr;
 	auto now = [] { return std::chrono::steady_clock::now(); };
@@ -1093,7 +910,7 @@ int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const
 	{
 		auto us = [](auto a, auto b) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count() / 1e3; };
 		const double chain = run.t_chain_us > 0 ? run.t_chain_us : run.t_loop_gpu_us;
-		t_last_timing[0] = us(t0, t1);                              // FCCH acquisition incl. its decisions on the host
+		t_last_timing[0] = us(t0, t1);                              // FCCH acquisition incl. the chains set up from its result
 		t_last_timing[1] = chain;                                   // frame loop: launches until its kernels are through
 		t_last_timing[2] = run.t_loop_gpu_us - chain;               // records to the caller's buffer
 		t_last_timing[3] = us(t1, t2) - run.t_loop_gpu_us;          // host work around the loop (chains set up, states read)
@@ -1296,7 +1113,7 @@ int gmr1_hip_gsmtap_pack_big(const struct gmr1_hip_rx_big_record *rec, int with_
 // horizon adds is a stop that the next push may lift (rx_stream_next_done).  A carrier then keeps its samples from
 // rx_stream_keep_from(min chain align): no window of the next walk starts before that (rx_stream_reach_back).
 // ---------------------------------------------------------------------------------------------------------------------
-static_assert(kStartDiscard == kRxStartDiscard, "one start discard");
+static_assert(kStartDiscard == kRxStartDiscard && kStartDiscard == kAcqStart, "one start discard");
 
 struct gmr1_hip_rx_stream {
 	mutable std::mutex mu;               // one push at a time
@@ -1487,7 +1304,6 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 	run.arfcn = h->arfcn.empty() ? nullptr : h->arfcn.data();
 	run.A = A;
 	run.out = out; run.max_records = max_records;
-	run.flen = kFcchLen * sps;
 	run.stat = h->stat; run.nch = h->nch;
 	std::vector<uint64_t> offset((size_t)A), length((size_t)A);
 	for (int i = 0; i < A; i++) {
@@ -1499,8 +1315,6 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 
 	// 2. the acquisition, once every carrier holds what it reads (nothing has been dropped yet: coordinates are absolute)
 	if (!h->acquired && ((long long)h->N >= rx_stream_acq_need(sps) || last)) {
-		run.align.assign(A, kStartDiscard); run.base_align.assign(A, 0);
-		run.ferr.assign(A, 0.0f);
 		if ((r = run.acquire())) return r;
 		h->stat = run.stat; h->nch = run.nch;
 		h->acq_stat = run.stat;

@@ -24,4 +24,14 @@ int fcch_rough_multi_tail(hipStream_t st, int tab, int n, int sps, int len, cons
 int fcch_fine_tail(hipStream_t st, int tab, int mode, int n, int sps, const float *iq, const uint64_t *offset,
                    const float *freq_shift, int32_t *toa, float *freq_err, float *snr, const AcqTail &t);
 
+// The whole chain, enqueued on `st` (both the public entry and the receive loop's RxRun::acquire): k_acq_begin, the five
+// sweeps with their tails, k_acq_decide -- one struct gmr1_hip_fcch_acq per stream at `out`.  Every pointer is device memory
+// but h_length: the lengths once more on the host where the caller has them there (null: it has not), which only chooses
+// how rough_multi is launched when some streams are shorter than its window.  The caller holds a WsLease.
+int fcch_acquire_enqueue(hipStream_t st, int tab, int n, int sps, const float *iq, const uint64_t *offset,
+                         const uint64_t *length, const int32_t *start, const uint64_t *h_length,
+                         struct gmr1_hip_fcch_acq *out);
+// grow-only device scratch of the calling thread on the current device: slot 0 the chain's own, slot 1 its caller's staging
+int acq_scratch(int slot, size_t bytes, unsigned char **out);
+
 }  // namespace gmr1

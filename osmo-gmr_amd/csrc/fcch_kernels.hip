@@ -15,9 +15,12 @@
 //   k_fcch_stats, k_fcch_corr : the two-pass form of the rough sweep (round 4; profiling build, GMR1_HIP_FCCH_TWO_PASS)
 //   acq_step1..4, k_acq_glue  : what gmr1_rx does between two sweeps of its acquisition (gmr1_rx.c:605-702), run by the
 //                   producing sweep's last thread (AcqTail, fcch_acq.h) or as a launch of its own
+//   k_acq_begin, k_acq_decide : the two ends of that chain: the checks on the carriers' lengths in front of the first sweep,
+//                   the survivor decisions behind the last one, one struct gmr1_hip_fcch_acq per carrier
 //
 // HBM traffic per 1-s stream (93 600 samples): 748.8 kB read once (x 1.065: the tiles' overlap), 187 kB of raw correlation
 // written and read back, a few kB of partials.
+#include <cerrno>
 #include <cstring>
 #include "gmr1_dev.h"
 #include "fast_math.h"
@@ -680,7 +683,8 @@ __device__ inline void acq_step2(const AcqArgs &a, int k, int ftoa, float fe)
 		fs = -fe;
 	}
 	a.stat[k] = stat;
-	a.off[k] = a.base[k] + (uint64_t)((stat || !a.can3[k]) ? 0 : a.base_align[k]);
+	// (a carrier shorter than the 650 ms window: the library's spare one, should the sweep run over this slot at all)
+	a.off[k] = a.can3[k] ? a.base[k] + (uint64_t)(stat ? 0 : a.base_align[k]) : a.spare;
 	a.fs[k] = fs;
 }
 
@@ -1544,6 +1548,131 @@ hipError_t launch_acq_glue(int step, const AcqArgs &a, hipStream_t st)
 		return hipSuccess;
 	const int n = (step <= 2) ? a.n : a.n * kAcqPeaks;
 	hipLaunchKernelGGL(k_acq_glue, dim3((n + 255) / 256), dim3(256), 0, st, step, a);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_acq_begin -- in front of the chain: what gmr1_rx checks before its first sweep (the 330 ms window has to lie within the
+// carrier, fcch_single_init gmr1_rx.c:612-616), from lengths that live on the device; the chain's per-carrier entries and
+// the first sweep's windows.  A carrier that fails here is swept over the library's spare window: it may hold no sample.
+// A length above 2^31 - 1 or a negative start ends the carrier with -EINVAL.
+// ---------------------------------------------------------------------------
+__global__ void k_acq_begin(AcqArgs a, AcqIo io)
+{
+	const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= a.n)
+		return;
+	const uint64_t len = io.length[k];
+	const int32_t start = io.start ? io.start[k] : kAcqStart;
+	int stat = 0;
+	if (len > 0x7fffffffull || start < 0)
+		stat = -EINVAL;
+	else if ((uint64_t)start + (uint64_t)io.wl1 > len)
+		stat = -1;
+	a.base[k] = stat ? a.spare : io.offset[k];
+	a.len[k] = stat ? 0 : len;
+	a.stat[k] = stat;
+	a.align[k] = stat ? 0 : start;
+	a.base_align[k] = 0;
+	a.ferr[k] = 0.f;
+	a.can3[k] = (!stat && len >= (uint64_t)a.wl3) ? 1 : 0;
+	a.off[k] = a.base[k] + (uint64_t)a.align[k];
+	// rough_multi leaves slots past its count unwritten, and does not run at all over a carrier it cannot take
+	a.count[k] = 0;
+	for (int j = 0; j < kAcqPeaks; j++)
+		a.peaks[(size_t)k * kAcqPeaks + j] = 0;
+}
+
+hipError_t launch_acq_begin(const AcqArgs &a, const AcqIo &io, hipStream_t st)
+{
+	if (a.n <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_acq_begin, dim3((a.n + 63) / 64), dim3(64), 0, st, a, io);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_acq_decide -- behind the chain: what fcch_multi_process decides once every candidate has its refined position, residual
+// frequency and SNR (gmr1_rx.c:699-733), one thread per carrier, into the caller's struct gmr1_hip_fcch_acq.  The checks up to
+// the candidate windows are the chain's own (acq_step1..3 left their verdict in `stat`); here: a refined candidate out of the
+// carrier's samples drops the carrier, then the survivors in candidate order with candidate 0 as the reference.  The float
+// comparisons are written as gmr1_rx writes them, in single precision.
+// ---------------------------------------------------------------------------
+__device__ inline float acq_to_hz(float f_rps) { return (23400 * f_rps) / (2.0f * 3.14159265358979323846f); }
+
+__global__ void k_acq_decide(AcqArgs a, AcqIo io)
+{
+	const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= a.n)
+		return;
+	struct gmr1_hip_fcch_acq *o = io.out + k;
+	const size_t s0 = (size_t)k * kAcqPeaks;
+	const int64_t len = (int64_t)a.len[k];
+	const int ba = a.base_align[k];
+	int stat = a.stat[k];
+	const int cnt = stat ? 0 : min(a.count[k], kAcqPeaks);
+	for (int q = 0; q < cnt; q++) {
+		const int64_t p = (int64_t)ba + a.peaks[s0 + q] + a.ctoa[s0 + q];
+		if (p < 0 || p + a.flen > len)
+			stat = -1;
+	}
+	int nc = 0;
+	if (!stat) {
+		float ref_snr = 0.f, ref_fe = 0.f;
+		for (int q = 0; q < cnt; q++) {
+			const float snr = io.snr[s0 + q], cfe = a.cfe[s0 + q];
+			if (q == 0) {
+				ref_snr = snr;
+				ref_fe = cfe;
+			} else {
+				if (snr < 2.0f) continue;
+				if (snr < ref_snr / 6.0f) continue;
+				if (acq_to_hz(fabsf(ref_fe - cfe)) > 500.0f) continue;
+			}
+			o->chain_align[nc] = ba + a.peaks[s0 + q] + a.ctoa[s0 + q];
+			o->chain_freq_err[nc] = cfe;
+			o->chain_snr[nc] = snr;
+			nc++;
+		}
+	}
+	// the unused slots hold nothing of an earlier call
+	for (int j = nc; j < GMR1_HIP_ACQ_MAX_CHAINS; j++) {
+		o->chain_align[j] = 0;
+		o->chain_freq_err[j] = 0.f;
+		o->chain_snr[j] = 0.f;
+	}
+	o->status = stat;
+	o->n_chains = nc;
+	o->align = stat ? 0 : a.align[k];
+	o->base_align = stat ? 0 : ba;
+	o->freq_err = stat ? 0.f : a.ferr[k];
+	o->n_cand = cnt;
+}
+
+hipError_t launch_acq_decide(const AcqArgs &a, const AcqIo &io, hipStream_t st)
+{
+	if (a.n <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_acq_decide, dim3((a.n + 63) / 64), dim3(64), 0, st, a, io);
+	return hipGetLastError();
+}
+
+// the spare window's samples: noise of about unit power, what a carrier without a signal looks like to the sweeps
+__global__ void k_acq_spare_fill(float2 *p, size_t n)
+{
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n)
+		return;
+	uint32_t h = (uint32_t)i * 2654435761u + 0x9e3779b9u;
+	h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+	p[i] = make_float2((float)(h & 0xffffu) * (1.0f / 32768.0f) - 1.0f, (float)(h >> 16) * (1.0f / 32768.0f) - 1.0f);
+}
+
+hipError_t launch_acq_spare_fill(float2 *p, size_t n, hipStream_t st)
+{
+	if (!n)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_acq_spare_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n);
 	return hipGetLastError();
 }
 

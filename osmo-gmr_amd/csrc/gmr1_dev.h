@@ -213,27 +213,46 @@ hipError_t launch_fcch_fine(const FcchFineArgs &a, int nsym, hipStream_t stream)
 // between two sweeps (add the found offset, check the bounds, lay out the next sweep's windows) runs in k_acq_glue, so
 // the five sweeps need no host round trip between them.  Entries are per carrier of the sweep list (`k`), candidate
 // slots per carrier are kAcqPeaks wide; a slot that is not live gets the carrier's first sample as a harmless window.
+// k_acq_begin in front of the chain takes the checks gmr1_rx makes before its first sweep and fills the per-carrier
+// entries from what the caller handed in; k_acq_decide behind it takes the decisions of fcch_multi_process and writes
+// one struct gmr1_hip_fcch_acq per carrier (AcqIo).
 constexpr int kAcqPeaks = 16;
+constexpr int kAcqStart = 8000;      // samples gmr1_rx discards at the start of a capture (gmr1_rx.c:52)
 struct AcqArgs {
 	int n;                       // carriers in the list
 	int sps, flen;               // samples of an FCCH burst
 	int wl3;                     // samples of the 650 ms sweep
-	const uint64_t *base;        // n: first sample of the carrier
-	const uint64_t *len;         // n: samples of the carrier
+	// A carrier that fails before its first sweep has no window of its own to sweep over (it may hold no sample at all),
+	// and one shorter than 650 ms has none for rough_multi: their sweeps read these wl3 samples of the library's instead,
+	// given as an offset from iq like every other window (modulo 2^64; the results are never looked at).
+	uint64_t spare;
+	uint64_t *base;              // n: first sample of the carrier (k_acq_begin: `spare` when the carrier failed there)
+	uint64_t *len;               // n: samples of the carrier
 	int32_t *stat;               // n: 0 alive, else the status the carrier ends with
 	int32_t *align, *base_align; // n
 	float *ferr;                 // n
-	const int32_t *can3;         // n: the carrier is long enough for the 650 ms sweep at all
+	int32_t *can3;               // n: the carrier is long enough for the 650 ms sweep at all
 	// sweep outputs the glue reads
 	const int32_t *toa1, *rv1;   // rough
 	const int32_t *ftoa; const float *fe;           // fine
-	const int32_t *peaks, *count;                   // rough_multi: n x kAcqPeaks, n
+	int32_t *peaks, *count;                         // rough_multi: n x kAcqPeaks, n (zeroed by k_acq_begin)
 	const int32_t *ctoa; const float *cfe;          // fine over the candidate slots
 	// next sweep's inputs the glue writes
 	uint64_t *off;               // n or n x kAcqPeaks
 	float *fs;
 	int32_t *live;               // n x kAcqPeaks: the slot holds a candidate
 };
+// the two ends of the chain: what the caller hands in and what it gets back (all device memory)
+struct AcqIo {
+	const uint64_t *offset, *length;   // n: the carriers, samples from iq
+	const int32_t *start;              // n: where the 330 ms window begins; null: kAcqStart
+	int wl1;                           // samples of the 330 ms sweep
+	const float *snr;                  // n x kAcqPeaks: the SNR stage's result
+	struct gmr1_hip_fcch_acq *out;     // n
+};
+hipError_t launch_acq_begin(const AcqArgs &a, const AcqIo &io, hipStream_t stream);
+hipError_t launch_acq_decide(const AcqArgs &a, const AcqIo &io, hipStream_t stream);
+hipError_t launch_acq_spare_fill(float2 *p, size_t n, hipStream_t stream);
 hipError_t launch_acq_glue(int step, const AcqArgs &a, hipStream_t stream);
 
 // ---- traffic-channel layer 1 (l1_kernels.hip) -------------------------------
