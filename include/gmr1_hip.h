@@ -34,6 +34,7 @@
  *   gmr1_hip_fcch_fine_batch*    -> gmr1_fcch_fine        include/osmocom/gmr1/sdr/fcch.h:55-57
  *   gmr1_hip_fcch_snr_batch*     -> gmr1_fcch_snr         include/osmocom/gmr1/sdr/fcch.h:59-61
  *   gmr1_hip_fcch_acquire_batch* -> fcch_single_init / fcch_multi_process  src/gmr1_rx.c:605-733 (up to the survivor list)
+ *   gmr1_hip_tch3_follow_batch*  -> rx_tch3, src/gmr1_rx.c:355-600
  */
 #ifndef GMR1_HIP_H
 #define GMR1_HIP_H
@@ -79,7 +80,7 @@ struct gmr1_hip_burst_flat {
  * Threads: gmr1_hip_last_error() is per thread; the burst-level _batch / _batch_dev calls keep no state
  * between calls and may run from several threads on different streams.  The calls that use the library's
  * grow-only per-device workspace -- gmr1_hip_fcch_rough*_batch*, gmr1_hip_fcch_acquire_batch*, gmr1_hip_channelize*, gmr1_hip_ddc*,
- * gmr1_hip_rx_run*, gmr1_hip_detect_batch* with more than four candidates, and gmr1_hip_tch3_rx_batch* where it
+ * gmr1_hip_rx_run*, gmr1_hip_tch3_follow_batch*, gmr1_hip_detect_batch* with more than four candidates, and gmr1_hip_tch3_rx_batch* where it
  * runs as two launches without a caller's soft-bit buffer -- may ALSO be called from several threads and streams:
  * they take turns.  The host part of such a call runs under a per-device lock (a second thread waits), and a call
  * on another stream first makes its stream wait, on the device, for the previous user's kernels; nothing is
@@ -546,6 +547,74 @@ int gmr1_hip_rx_run_tch(int n_arfcn, int sps, const float *iq, const float *tch,
                         const uint64_t *offset, const uint64_t *length, const uint16_t *arfcn, const uint8_t *kc,
                         struct gmr1_hip_rx_record *out, int max_records, int *n_records,
                         int32_t *status, int32_t *n_chains);
+
+/* ---- following a voice call: rx_tch3 over many calls at once (gmr1_rx.c:355-600) ------------------------
+ * What gmr1_rx does per frame once an IMMEDIATE ASSIGNMENT has named a timeslot -- burst energy against the running
+ * DKAB / burst averages, DKAB search or burst type detection, FACCH3 bursts grouped by sync sequence and decoded every
+ * four bursts or at a sync change, speech bursts decoded, A5/1 deciphering switched on by the first message that only
+ * decodes ciphered -- for n_calls calls in one invocation, every decision taken on the device.  The state of a call is
+ * the caller's: struct gmr1_hip_tch3_state goes in and comes back, so a call is continued by the next invocation with
+ * the frames that follow (as the speech decoder's state is, gmr1_hip_codec_*).  The caller finds the call: timeslot,
+ * DKAB position and key come from its own control plane (or from a type-2 record of gmr1_hip_rx_run*), and it cuts
+ * the windows as burst_map does (gmr1_rx.c:149-170).
+ *
+ * Call c owns frames first[c] .. first[c+1]-1 in time order; first[0] = 0, first[n_calls] = n_frames, non-decreasing.
+ * Frame k's window is iq[offset[k] .. offset[k] + in_len) (complex64), offset = carrier start + align + sps*tn*39 - e_toa
+ * with in_len = 117*sps + sps + sps/2 and e_toa = (in_len - 117*sps) >> 1 (gmr1_rx.c:549-551; the entry derives e_toa from
+ * in_len the same way); a frame whose window does not fit is not handed in (burst_map fails: rx_tch3 returns before it
+ * touches anything).  freq_shift[k] = -freq_err of the frame (rad/symbol), fn[k] its frame number.
+ * One record per frame handed in comes back at out[k]; a frame yields at most one payload (a speech burst: its two
+ * frames; a FACCH3 burst: at most one flush -- at a sync change or as the fourth burst, never both).  In both Viterbi
+ * decoder modes (gmr1_hip_set_conv_decoder) payloads and conv follow the selected mode.
+ *
+ * _dev: every pointer is device memory; the call enqueues on `stream` and returns -- no copy to the host and no
+ * synchronisation (but for the workspace that has to grow).  The host form copies iq (iq_len complex samples) and the
+ * arrays in, state and out back.  n_calls == 0 or n_frames == 0 does nothing; a call without frames keeps its state
+ * untouched.  -EINVAL: sps outside 1..16, in_len below 117*sps or above GMR1_HIP_MAX_IN_LEN, a negative count, a NULL
+ * array, iq not aligned to 8 bytes; host form also: first not as described, a window that leaves iq (on the device the
+ * entries of first are clamped to 0..n_frames).  -ENODEV without a device.  Nothing is written on either. */
+struct gmr1_hip_tch3_state {        /* struct tch3_state of gmr1_rx.c:59-78 plus the key; all-zero = no call */
+	int32_t  active;            /* 0: every frame is GMR1_HIP_TCH3_OFF and nothing changes */
+	int32_t  p;                 /* DKAB position (IMMEDIATE ASSIGNMENT) */
+	int32_t  ciph;              /* A5/1 deciphering is on (set by the first FACCH3 message that only decodes ciphered) */
+	int32_t  weak_cnt;          /* consecutive frames without DKAB or burst; the tenth ends the call */
+	int32_t  sync_id;           /* sync sequence of the FACCH3 message being collected */
+	int32_t  burst_cnt;         /* its bursts so far */
+	float    energy_dkab, energy_burst;   /* running averages; threshold = (energy_dkab + energy_burst) / 4 */
+	uint32_t bi_fn[4];          /* frame number of each stored burst (A5/1 runs per burst), 0xffffffff: none */
+	int8_t   ebits[4 * 104];    /* the stored bursts' soft bits, burst fn & 3 at 104 * (fn & 3) */
+	uint8_t  kc[8];             /* the call's key */
+};                                  /* 472 bytes */
+
+enum { GMR1_HIP_TCH3_OFF = 0, GMR1_HIP_TCH3_DKAB, GMR1_HIP_TCH3_DKAB_MISSING, GMR1_HIP_TCH3_FACCH,
+       GMR1_HIP_TCH3_SPEECH, GMR1_HIP_TCH3_ERR };
+
+struct gmr1_hip_tch3_frame {        /* one per frame handed in, in the order handed in; 40 bytes */
+	uint8_t  cls;       /* what rx_tch3 did with the frame (enum above); OFF: the call was not active; ERR: the DKAB
+	                       search, the detector or the demodulator refused the window (rx_tch3 returns rv < 0) */
+	uint8_t  type;      /* 0 nothing to report | 0x10 two speech frames | 0x12 a FACCH3 message whose CRC passed */
+	uint8_t  len;       /* 0 | 20 | 10 */
+	uint8_t  ciph;      /* the payload was deciphered */
+	uint32_t fn;        /* speech: the frame's fn; FACCH3: fn of the flush - 3 (gmr1_rx.c:432-436) */
+	int32_t  conv;      /* as gmr1_hip_rx_run_tch reports it (speech: conv0 & 0xffff | conv1 << 16) */
+	float    energy;    /* burst_energy of the window (of every frame handed in, whatever its class) */
+	uint8_t  l2[20];    /* type 0 / len 10: the rest is 0 */
+	uint8_t  pad[4];    /* 0 */
+};
+
+/* rx_tch3_init (gmr1_rx.c:358-378) on a caller-held state: host arithmetic, needs no device.  Sets active, p, the two
+ * energies from ref_energy (gmr1_rx takes burst_energy of the CCCH burst that carried the assignment), weak_cnt, sync_id,
+ * clears ebits -- and, like the reference, leaves ciph, burst_cnt, bi_fn (and kc) as they are.  -EINVAL: s is NULL. */
+int gmr1_hip_tch3_state_assign(struct gmr1_hip_tch3_state *s, int p, float ref_energy);
+
+int gmr1_hip_tch3_follow_batch_dev(void *stream, int n_calls, int sps, int in_len, const float *iq,
+                                   const int32_t *first /* n_calls + 1 */, int n_frames,
+                                   const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                                   struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
+int gmr1_hip_tch3_follow_batch(int n_calls, int sps, int in_len, const float *iq, uint64_t iq_len,
+                               const int32_t *first, int n_frames,
+                               const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                               struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
 
 /* The whole application: gmr1_rx with all its optional arguments (tch.cfile, key, tch_csd.cfile; gmr1_rx.c:897-975).
  * csd holds, per carrier, the carrier of the TCH9 (circuit switched data) channel an ASSIGNMENT COMMAND 1

@@ -117,6 +117,9 @@ SIGNATURES = {
     "gmr1_hip_rx_run_tch_dev": (I, P, I, I, P, P, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_tch": (I, I, I, P, P, U64, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_last_timing": (I, P),
+    "gmr1_hip_tch3_state_assign": (I, P, I, F),
+    "gmr1_hip_tch3_follow_batch_dev": (I, P, I, I, I, P, P, I, P, P, P, P, P),
+    "gmr1_hip_tch3_follow_batch": (I, I, I, I, P, U64, P, I, P, P, P, P, P),
     "gmr1_hip_rx_run_full_dev": (I, P, I, I, P, P, P, P, P, P, P, P, I, P, P, I, P, P, P),
     "gmr1_hip_rx_run_full": (I, I, I, P, P, P, U64, P, P, P, P, P, I, P, P, I, P, P, P),
     "gmr1_hip_codec_state_bytes": (SZ,),
@@ -616,6 +619,66 @@ def fcch_acquire(iq, offset, length, sps=4, start=None, fcch_type="fcch"):
 def fcch_acquire_dev(stream, n, iq, offset, length, out, sps=4, start=None, fcch_type="fcch"):
     """The same on device memory (addresses): enqueues on `stream` and returns; out: n records of FCCH_ACQ.itemsize bytes."""
     _call("gmr1_hip_fcch_acquire_batch_dev", stream, _fcch_id(fcch_type), n, sps, iq, offset, length, start, out)
+
+
+# ---------------------------------------------------------------------------
+# following a voice call (rx_tch3)
+# ---------------------------------------------------------------------------
+TCH3_OFF, TCH3_DKAB, TCH3_DKAB_MISSING, TCH3_FACCH, TCH3_SPEECH, TCH3_ERR = range(6)
+
+
+class Tch3State(C.Structure):
+    """struct gmr1_hip_tch3_state (include/gmr1_hip.h)."""
+    _fields_ = [("active", C.c_int32), ("p", C.c_int32), ("ciph", C.c_int32), ("weak_cnt", C.c_int32),
+                ("sync_id", C.c_int32), ("burst_cnt", C.c_int32), ("energy_dkab", C.c_float), ("energy_burst", C.c_float),
+                ("bi_fn", C.c_uint32 * 4), ("ebits", C.c_int8 * 416), ("kc", C.c_uint8 * 8)]
+
+
+class Tch3Frame(C.Structure):
+    """struct gmr1_hip_tch3_frame (include/gmr1_hip.h)."""
+    _fields_ = [("cls", C.c_uint8), ("type", C.c_uint8), ("len", C.c_uint8), ("ciph", C.c_uint8), ("fn", C.c_uint32),
+                ("conv", C.c_int32), ("energy", C.c_float), ("l2", C.c_uint8 * 20), ("pad", C.c_uint8 * 4)]
+
+
+# the same layouts for arrays of them
+TCH3_STATE = np.dtype([("active", "<i4"), ("p", "<i4"), ("ciph", "<i4"), ("weak_cnt", "<i4"), ("sync_id", "<i4"),
+                       ("burst_cnt", "<i4"), ("energy_dkab", "<f4"), ("energy_burst", "<f4"), ("bi_fn", "<u4", (4,)),
+                       ("ebits", "i1", (416,)), ("kc", "u1", (8,))])
+TCH3_FRAME = np.dtype([("cls", "u1"), ("type", "u1"), ("len", "u1"), ("ciph", "u1"), ("fn", "<u4"), ("conv", "<i4"),
+                       ("energy", "<f4"), ("l2", "u1", (20,)), ("pad", "u1", (4,))])
+
+
+def tch3_in_len(sps):
+    """The window rx_tch3 cuts for a frame (gmr1_rx.c:549-551): an NT3 burst and sps + sps/2 samples of search room."""
+    return 117 * sps + sps + sps // 2
+
+
+def tch3_state_assign(state, p, ref_energy, index=0):
+    """rx_tch3_init on state[index] of a TCH3_STATE array (in place; host arithmetic, needs no device) -> state."""
+    assert state.dtype == TCH3_STATE and state.flags.c_contiguous and state.flags.writeable
+    _call("gmr1_hip_tch3_state_assign", state.ctypes.data + index * TCH3_STATE.itemsize, p, ref_energy)
+    return state
+
+
+def tch3_follow(iq, first, offset, freq_shift, fn, state, sps=4, in_len=None):
+    """rx_tch3 over the frames of len(first) - 1 calls: call c owns frames first[c] .. first[c+1], frame k's window is
+    iq[offset[k] : offset[k] + in_len].  -> (TCH3_FRAME record per frame, the calls' TCH3_STATE after them); `state` itself
+    is left as it is."""
+    iq = _arr(iq, np.complex64, -1)
+    first, offset = _arr(first, np.int32), _arr(offset, np.uint64)
+    freq_shift, fn = _arr(freq_shift, np.float32), _arr(fn, np.uint32)
+    state = np.array(state, TCH3_STATE, ndmin=1)
+    out = np.zeros(offset.size, TCH3_FRAME)
+    _call("gmr1_hip_tch3_follow_batch", first.size - 1, sps, tch3_in_len(sps) if in_len is None else in_len, _p(iq), iq.size,
+          _p(first), offset.size, _p(offset), _p(freq_shift), _p(fn), _p(state), _p(out))
+    return out, state
+
+
+def tch3_follow_dev(stream, n_calls, n_frames, iq, first, offset, freq_shift, fn, state, out, sps=4, in_len=None):
+    """The same on device memory (addresses): enqueues on `stream` and returns; state: n_calls x TCH3_STATE.itemsize bytes,
+    updated in place; out: n_frames x TCH3_FRAME.itemsize bytes."""
+    _call("gmr1_hip_tch3_follow_batch_dev", stream, n_calls, sps, tch3_in_len(sps) if in_len is None else in_len, iq, first,
+          n_frames, offset, freq_shift, fn, state, out)
 
 
 # ---------------------------------------------------------------------------

@@ -1,0 +1,181 @@
+// capi_tch3_follow.cpp -- C ABI of the batched TCH3 call follower (reference src/gmr1_rx.c:355-600: rx_tch3_init, rx_tch3
+// and its helpers).  The state of a call is the caller's; every decision between the frames is taken on the device
+// (tch3_follow_kernels.hip, tch3_follow.h).
+#include "capi_common.h"
+
+#include "../../include/gmr1_hip.h"
+
+using namespace gmr1;
+
+namespace {
+
+int follow_check(int n_calls, int sps, int in_len, const float *iq, const int32_t *first, int n_frames,
+                 const uint64_t *offset, const float *freq_shift, const uint32_t *fn, const void *state, const void *out)
+{
+	if (n_calls < 0 || n_frames < 0)
+		return fail(-EINVAL, "tch3_follow: negative count");
+	if (!iq || !first || !offset || !freq_shift || !fn || !state || !out)
+		return fail(-EINVAL, "tch3_follow: NULL argument");
+	if (sps < 1 || sps > 16)
+		return fail(-EINVAL, "tch3_follow: sps=%d out of range (1..16)", sps);
+	if (in_len < 117 * sps || in_len > kMaxInLen)
+		return fail(-EINVAL, "tch3_follow: window of %d samples (%d..%d at sps=%d)", in_len, 117 * sps, kMaxInLen, sps);
+	if ((uintptr_t)iq & 7)
+		return fail(-EINVAL, "tch3_follow: iq is not aligned to a complex sample");
+	return 0;
+}
+
+size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
+
+// The whole chain, enqueued on `st`; every pointer is device memory.  The caller has checked the arguments and holds a
+// WsLease: the per-frame results, job slots, keystreams and decodes lie in the device's workspace.
+int follow_enqueue(hipStream_t st, DevState *ds, int n_calls, int sps, int in_len, const float *iq, const int32_t *first,
+                   int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                   struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out)
+{
+	const size_t n = (size_t)n_frames;
+	size_t o = 0;
+	auto take = [&](size_t bytes) { const size_t at = o; o += up128(bytes); return at; };
+	const size_t o_call = take(n * 4), o_p = take(n * 4), o_et = take(n * 4), o_en = take(n * 4), o_krv = take(n * 4),
+	             o_drv = take(n * 4), o_bt = take(n * 4), o_dsid = take(n * 4), o_dtoa = take(n * 4), o_frv = take(n * 4),
+	             o_fsid = take(n * 4), o_ftoa = take(n * 4), o_srv = take(n * 4), o_feb = take(n * 104), o_seb = take(n * 212),
+	             o_cls = take(n), o_need = take(n), o_jeb = take(n * 416), o_jfn = take(n * 16), o_kss = take(n * 208),
+	             o_ksf = take(n * 384), o_sfr0 = take(n * 20), o_sfr1 = take(n * 20), o_scv0 = take(n * 8), o_scv1 = take(n * 8),
+	             o_fl0 = take(n * 10), o_fl1 = take(n * 10), o_fcrc0 = take(n * 4), o_fcrc1 = take(n * 4), o_fcv0 = take(n * 4),
+	             o_fcv1 = take(n * 4);
+	void *ws;
+	int r = dev_workspace(ds, o + 128, &ws);
+	if (r) return r;
+	unsigned char *d = reinterpret_cast<unsigned char *>(((uintptr_t)ws + 127) & ~(uintptr_t)127);
+	auto I32 = [&](size_t at) { return reinterpret_cast<int32_t *>(d + at); };
+	auto F32 = [&](size_t at) { return reinterpret_cast<float *>(d + at); };
+	auto U8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(d + at); };
+	auto I8 = [&](size_t at) { return reinterpret_cast<int8_t *>(d + at); };
+
+	Tch3FollowArgs a;
+	std::memset(&a, 0, sizeof(a));
+	a.n_calls = n_calls; a.n_frames = n_frames;
+	a.e_toa = (in_len - 117 * sps) >> 1;           // burst_map's e_toa for a window of 117 sps + win (gmr1_rx.c:157-167)
+	a.first = first; a.fn = fn; a.state = state; a.out = out;
+	a.call_of = I32(o_call); a.p = I32(o_p); a.et = F32(o_et);
+	a.energy = F32(o_en); a.dkab_rv = I32(o_krv); a.det_rv = I32(o_drv); a.btid = I32(o_bt);
+	a.facch_rv = I32(o_frv); a.facch_sid = I32(o_fsid); a.speech_rv = I32(o_srv);
+	a.facch_eb = I8(o_feb);
+	a.cls = U8(o_cls); a.need = U8(o_need); a.job_eb = I8(o_jeb); a.job_fn = reinterpret_cast<uint32_t *>(d + o_jfn);
+	a.ks_speech = U8(o_kss); a.ks_facch = U8(o_ksf);
+	a.sp_frames[0] = U8(o_sfr0); a.sp_frames[1] = U8(o_sfr1);
+	a.sp_conv[0] = I32(o_scv0); a.sp_conv[1] = I32(o_scv1);
+	a.fa_l2[0] = U8(o_fl0); a.fa_l2[1] = U8(o_fl1);
+	a.fa_crc[0] = I32(o_fcrc0); a.fa_crc[1] = I32(o_fcrc1);
+	a.fa_conv[0] = I32(o_fcv0); a.fa_conv[1] = I32(o_fcv1);
+
+	HIP_TRY(launch_tch3f_prep(a, st));
+
+	// A. speculative per-frame work (what RxRun::tch3_pass runs, capi_rx.cpp): the state machine picks from it
+	r = demod_dev_energy(st, GMR1_HIP_NT3_FACCH, n_frames, sps, in_len, iq, offset, freq_shift, I8(o_feb), 104, I32(o_fsid),
+	                     F32(o_ftoa), F32(o_en), I32(o_frv));
+	if (r) return r;
+	r = demod_dev_energy(st, GMR1_HIP_NT3_SPEECH, n_frames, sps, in_len, iq, offset, freq_shift, I8(o_seb), 212, nullptr, nullptr,
+	                     nullptr, I32(o_srv));
+	if (r) return r;
+	{
+		const int ids[2] = {GMR1_HIP_NT3_FACCH, GMR1_HIP_NT3_SPEECH};     // gmr1_rx.c:534-538
+		r = gmr1_hip_detect_batch_dev(st, 2, ids, n_frames, sps, in_len, iq, offset, freq_shift, a.et, I32(o_bt), I32(o_dsid),
+		                              F32(o_dtoa), I32(o_drv));
+		if (r) return r;
+	}
+	r = gmr1_hip_dkab_demod_batch_dev(st, n_frames, sps, in_len, iq, offset, freq_shift, a.p, nullptr, nullptr, I32(o_krv));
+	if (r) return r;
+
+	// B. the state machine, call by call
+	HIP_TRY(launch_tch3f_walk(a, st));
+
+	// C. keystreams and decodes, plain and deciphered, over the frames that ask for one
+	HIP_TRY(launch_a5_tch3f(a, st));
+	for (int v = 0; v < 2; v++) {
+		Tch3Args t;
+		t.n = n_frames; t.m = 0; t.conv_acc = conv_acc();
+		t.ebits = I8(o_seb); t.ciph = v ? a.ks_speech : nullptr;
+		t.frames = U8(v ? o_sfr1 : o_sfr0); t.bits_s = nullptr; t.conv = I32(v ? o_scv1 : o_scv0);
+		HIP_TRY(launch_tch3_jobs(t, a.need, st));
+		Facch3Args f;
+		f.n = n_frames; f.conv_acc = conv_acc();
+		f.ebits = a.job_eb; f.ciph = v ? a.ks_facch : nullptr;
+		f.l2 = U8(v ? o_fl1 : o_fl0); f.bits_s = nullptr; f.crc = I32(v ? o_fcrc1 : o_fcrc0); f.conv = I32(v ? o_fcv1 : o_fcv0);
+		HIP_TRY(launch_facch3_jobs(f, a.need, st));
+	}
+
+	// D. ciphering state and records, in frame order
+	HIP_TRY(launch_tch3f_emit(a, st));
+	return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmr1_hip_tch3_state_assign(struct gmr1_hip_tch3_state *s, int p, float ref_energy)
+{
+	if (!s)
+		return fail(-EINVAL, "tch3_state_assign: NULL state");
+	// rx_tch3_init, gmr1_rx.c:358-376: ciph, burst_cnt and bi_fn keep what they hold
+	s->active = 1;
+	s->p = p;
+	s->energy_burst = ref_energy * 0.75f;
+	s->energy_dkab = s->energy_burst / 8.0f;
+	s->weak_cnt = 0;
+	s->sync_id = 0;
+	std::memset(s->ebits, 0, sizeof(s->ebits));
+	return 0;
+}
+
+int gmr1_hip_tch3_follow_batch_dev(void *stream, int n_calls, int sps, int in_len, const float *iq,
+                                   const int32_t *first, int n_frames,
+                                   const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                                   struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out)
+{
+	int r = follow_check(n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	if (r) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	WsLease lease;
+	if ((r = lease.acquire(s, (hipStream_t)stream))) return r;
+	return follow_enqueue((hipStream_t)stream, s, n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state, out);
+}
+
+int gmr1_hip_tch3_follow_batch(int n_calls, int sps, int in_len, const float *iq, uint64_t iq_len,
+                               const int32_t *first, int n_frames,
+                               const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                               struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out)
+{
+	int r = follow_check(n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	if (r) return r;
+	if (first[0] != 0 || first[n_calls] != n_frames)
+		return fail(-EINVAL, "tch3_follow: first[] must run from 0 to n_frames");
+	for (int c = 0; c < n_calls; c++)
+		if (first[c + 1] < first[c])
+			return fail(-EINVAL, "tch3_follow: first[%d] decreases", c + 1);
+	if ((r = bursts_fit(n_frames, offset, in_len, iq_len))) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const int32_t *d_first = sg.in(first, (size_t)n_calls + 1);
+	const uint64_t *d_off = sg.in(offset, (size_t)n_frames);
+	const float *d_fs = sg.in(freq_shift, (size_t)n_frames);
+	const uint32_t *d_fn = sg.in(fn, (size_t)n_frames);
+	struct gmr1_hip_tch3_state *d_state = sg.inout(state, (size_t)n_calls);
+	struct gmr1_hip_tch3_frame *d_out = sg.out(out, (size_t)n_frames);
+	if ((r = sg.err())) return r;
+	{
+		WsLease lease;
+		if ((r = lease.acquire(s, nullptr))) return r;
+		if ((r = follow_enqueue(nullptr, s, n_calls, sps, in_len, d_iq, d_first, n_frames, d_off, d_fs, d_fn, d_state, d_out)))
+			return r;
+	}
+	return sg.fetch();
+}
+
+}  // extern "C"

@@ -402,6 +402,39 @@ hipError_t launch_rx_stage(const RxStageArgs &a, hipStream_t stream);
 
 hipError_t launch_dkab(const DkabArgs &a, hipStream_t stream);
 hipError_t launch_a5(const A5Args &a, hipStream_t stream);
+
+// The batched TCH3 call follower (gmr1_hip_tch3_follow_batch*: capi_tch3_follow.cpp, tch3_follow_kernels.hip, tch3_follow.h).
+// Everything is device memory.  Arrays "per frame" have n_frames slots in the order the frames were handed in; what a
+// kernel leaves unwritten in one (a frame that asks for no decode) nobody reads.
+struct Tch3FollowArgs {
+	int n_calls, n_frames;
+	int e_toa;                         // (in_len - 117 sps) >> 1: what burst_map returns, for the detector
+	const int32_t *first;              // n_calls + 1
+	const uint32_t *fn;                // per frame
+	struct gmr1_hip_tch3_state *state; // n_calls
+	struct gmr1_hip_tch3_frame *out;   // per frame
+	// k_tch3f_prep: the call a frame belongs to, its DKAB position, the detector's expected time of arrival
+	int32_t *call_of, *p;
+	float *et;
+	// the speculative per-frame results (step A)
+	const float *energy;
+	const int32_t *dkab_rv, *det_rv, *btid, *facch_rv, *facch_sid, *speech_rv;
+	const int8_t *facch_eb;            // x 104
+	// k_tch3f_walk: class, decode asked for (tch3_follow.h), and at a flush the four stored bursts and their frame numbers
+	uint8_t *cls, *need;
+	int8_t *job_eb;                    // x 416
+	uint32_t *job_fn;                  // x 4
+	// keystreams and decodes, [0] plain and [1] deciphered
+	uint8_t *ks_speech, *ks_facch;     // x 208, x 384
+	const uint8_t *sp_frames[2];       // x 20
+	const int32_t *sp_conv[2];         // x 2
+	const uint8_t *fa_l2[2];           // x 10
+	const int32_t *fa_crc[2], *fa_conv[2];
+};
+hipError_t launch_tch3f_prep(const Tch3FollowArgs &a, hipStream_t stream);
+hipError_t launch_tch3f_walk(const Tch3FollowArgs &a, hipStream_t stream);
+hipError_t launch_a5_tch3f(const Tch3FollowArgs &a, hipStream_t stream);
+hipError_t launch_tch3f_emit(const Tch3FollowArgs &a, hipStream_t stream);
 // NT9 bursts: FACCH9 and the three TCH9 modes share one decoder kernel (nt9_kernels.hip)
 struct Nt9Args {
 	int n;                     // bursts
@@ -500,6 +533,9 @@ hipError_t launch_bitmap(const BitMapArgs &a, hipStream_t stream);
 hipError_t launch_rx_loop(const RxArgs &a, const RxLoopArgs &la, int n_chains, hipStream_t stream);
 hipError_t launch_facch3(const Facch3Args &a, hipStream_t stream);
 hipError_t launch_tch3(const Tch3Args &a, hipStream_t stream);
+// the same two over one slot per frame of a TCH3 follower call: only where need[i] is 2 (FACCH3 flush) / 1 (speech burst)
+hipError_t launch_facch3_jobs(const Facch3Args &a, const uint8_t *need, hipStream_t stream);
+hipError_t launch_tch3_jobs(const Tch3Args &a, const uint8_t *need, hipStream_t stream);
 hipError_t launch_rx_tch3(const RxArgs &a, const Tch3Args &t, hipStream_t stream);   // a.impl == 3, NT3 speech
 
 // launchers (rx_kernels.hip and the files it includes)

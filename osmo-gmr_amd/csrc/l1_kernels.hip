@@ -140,8 +140,9 @@ __device__ __forceinline__ uint32_t k5r4_step(uint32_t w, const CT *__restrict__
 }
 
 // ACC: two soft bits of -128 in one table entry cost 256 -- 16-bit table entries in that mode
+// need (k_facch3_jobs): frame f is decoded only where need[f] == 2, the others count as absent; null: all a.n frames
 template <bool ACC>
-__global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
+__device__ __forceinline__ void facch3_block(const Facch3Args &a, const uint8_t *__restrict__ need)
 {
 	typedef typename std::conditional<ACC, uint16_t, uint8_t>::type CT;
 	typedef typename std::conditional<ACC, uint4, uint2>::type CW;
@@ -153,12 +154,15 @@ __global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
 	const int row = lane >> 4;
 	const uint32_t loc = (uint32_t)lane & 15u;
 	const int f0 = blockIdx.x * 4;
+	auto live = [&](int f) { return f < a.n && (!need || need[f] == 2); };
+	if (need && !(live(f0) || live(f0 + 1) || live(f0 + 2) || live(f0 + 3)))
+		return;
 
 	// ---- soft bits of the 4 frames (4 x 104 each) HBM -> LDS
 	for (int q = 0; q < 4; q++) {
 		const int f = f0 + q;
 		uint32_t *dst = reinterpret_cast<uint32_t *>(&s_eb[q][0]);
-		if (f < a.n) {
+		if (live(f)) {
 			const uint32_t *src = reinterpret_cast<const uint32_t *>(a.ebits + (size_t)f * 416);
 			for (int i = lane; i < 104; i += 64)
 				dst[i] = src[i];
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
 	if (a.bits_s) {
 		for (int q = 0; q < 4; q++) {
 			const int f = f0 + q;
-			if (f < a.n && lane < 32)
+			if (live(f) && lane < 32)
 				a.bits_s[(size_t)f * 32 + lane] = s_eb[q][104 * (lane >> 3) + 22 + (lane & 7)] < 0;
 		}
 	}
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
 			const int e = p < 22 ? p : p + 8;
 			int v = s_eb[q][104 * burst + e];
 			bool flip = (c_scr.w[p >> 5] >> (p & 31)) & 1u;
-			if (a.ciph && (f0 + q) < a.n)
+			if (a.ciph && live(f0 + q))
 				flip ^= a.ciph[(size_t)(f0 + q) * 384 + 96 * burst + p] != 0;
 			if (flip)
 				v = (int8_t)(-v);
@@ -309,7 +313,7 @@ __global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
 
 	// ---- outputs: 76 bits LSB first -> 10 bytes, upper nibble of l2[9] = 0 (facch3.c:166-167)
 	const int f = f0 + row;
-	if (f < a.n) {
+	if (live(f)) {
 		if (loc < 5) {
 			const uint32_t w = s_ub[row][loc >> 1] >> (16 * (loc & 1));
 			uint32_t h = w & 0xffffu;
@@ -324,16 +328,28 @@ __global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
 	}
 }
 
+template <bool ACC>
+__global__ __launch_bounds__(64) void k_facch3(Facch3Args a)
+{
+	facch3_block<ACC>(a, nullptr);
+}
+
+// the TCH3 follower's flushes (tch3_follow_kernels.hip): one slot per frame handed in, a message only where the walk left one
+template <bool ACC>
+__global__ __launch_bounds__(64) void k_facch3_jobs(Facch3Args a, const uint8_t *__restrict__ need)
+{
+	facch3_block<ACC>(a, need);
+}
+
 // ---------------------------------------------------------------------------
 // TCH3 speech (the decoder itself: tch3_body.h)
 // ---------------------------------------------------------------------------
 template <bool ACC>
-__global__ __launch_bounds__(64) void k_tch3(Tch3Args a)
+__device__ __forceinline__ void tch3_block(const Tch3Args &a, int g)
 {
 	__shared__ __align__(16) int8_t s_e[216];
 	__shared__ __align__(16) Tch3Lds s_t3;
 	const int lane = threadIdx.x;
-	const int g = blockIdx.x;
 	tch3_fill_locof(&s_t3, lane);
 	{
 		const uint32_t *src = reinterpret_cast<const uint32_t *>(a.ebits + (size_t)g * 212);
@@ -347,6 +363,21 @@ __global__ __launch_bounds__(64) void k_tch3(Tch3Args a)
 	tch3_lane(lc, &s_t3, lane);
 	WSYNC();
 	tch3_burst<ACC>(a, g, lane, s_e, &s_t3, lc);
+}
+
+template <bool ACC>
+__global__ __launch_bounds__(64) void k_tch3(Tch3Args a)
+{
+	tch3_block<ACC>(a, blockIdx.x);
+}
+
+// the TCH3 follower's speech bursts: one slot per frame handed in, a burst only where need[g] == 1
+template <bool ACC>
+__global__ __launch_bounds__(64) void k_tch3_jobs(Tch3Args a, const uint8_t *__restrict__ need)
+{
+	if (need[blockIdx.x] != 1)
+		return;
+	tch3_block<ACC>(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -371,6 +402,28 @@ hipError_t launch_tch3(const Tch3Args &a, hipStream_t st)
 		hipLaunchKernelGGL(k_tch3<true>, dim3(a.n), dim3(64), 0, st, a);
 	else
 		hipLaunchKernelGGL(k_tch3<false>, dim3(a.n), dim3(64), 0, st, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_facch3_jobs(const Facch3Args &a, const uint8_t *need, hipStream_t st)
+{
+	if (a.n <= 0)
+		return hipSuccess;
+	if (a.conv_acc)
+		hipLaunchKernelGGL(k_facch3_jobs<true>, dim3((a.n + 3) / 4), dim3(64), 0, st, a, need);
+	else
+		hipLaunchKernelGGL(k_facch3_jobs<false>, dim3((a.n + 3) / 4), dim3(64), 0, st, a, need);
+	return hipGetLastError();
+}
+
+hipError_t launch_tch3_jobs(const Tch3Args &a, const uint8_t *need, hipStream_t st)
+{
+	if (a.n <= 0)
+		return hipSuccess;
+	if (a.conv_acc)
+		hipLaunchKernelGGL(k_tch3_jobs<true>, dim3(a.n), dim3(64), 0, st, a, need);
+	else
+		hipLaunchKernelGGL(k_tch3_jobs<false>, dim3(a.n), dim3(64), 0, st, a, need);
 	return hipGetLastError();
 }
 

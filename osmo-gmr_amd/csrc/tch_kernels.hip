@@ -203,24 +203,9 @@ __device__ __forceinline__ uint32_t a5_out(const A5State &s)    // a5.c:191-216
 	return m0 ^ m1 ^ m2;
 }
 
-__global__ __launch_bounds__(64) void k_a5(A5Args a)
+// A5/1 of one (key, frame number): nbits of downlink keystream to dl, then as many of uplink to ul (either may be null)
+__device__ __forceinline__ void a5_1_stream(const uint8_t *__restrict__ key, uint32_t fn, int nbits, uint8_t *dl, uint8_t *ul)
 {
-	const int g = blockIdx.x * 64 + threadIdx.x;
-	if (g >= a.n)
-		return;
-	uint8_t *dl = a.dl ? a.dl + (size_t)g * a.nbits : nullptr;
-	uint8_t *ul = a.ul ? a.ul + (size_t)g * a.nbits : nullptr;
-	if (a.alg == 0) {                    // a5.c:60-66
-		for (int i = 0; i < a.nbits; i++) {
-			if (dl) dl[i] = 0;
-			if (ul) ul[i] = 0;
-		}
-		return;
-	}
-	if (a.alg != 1)                      // a5.c:72-75: A5/2..7 leave the buffers alone
-		return;
-	const uint8_t *key = a.keys + (size_t)g * 8;
-	const uint32_t fn = a.fn[g];
 	uint32_t lkey[8];
 #pragma unroll
 	for (int i = 0; i < 8; i++)
@@ -244,16 +229,54 @@ __global__ __launch_bounds__(64) void k_a5(A5Args a)
 	s.r0 |= 1; s.r1 |= 1; s.r2 |= 1; s.r3 |= 1;
 	for (int i = 0; i < 250; i++)
 		a5_step(s);
-	for (int i = 0; i < a.nbits; i++) {
+	for (int i = 0; i < nbits; i++) {
 		a5_step(s);
 		if (dl) dl[i] = (uint8_t)a5_out(s);
 	}
 	if (!ul)
 		return;
-	for (int i = 0; i < a.nbits; i++) {
+	for (int i = 0; i < nbits; i++) {
 		a5_step(s);
 		ul[i] = (uint8_t)a5_out(s);
 	}
+}
+
+__global__ __launch_bounds__(64) void k_a5(A5Args a)
+{
+	const int g = blockIdx.x * 64 + threadIdx.x;
+	if (g >= a.n)
+		return;
+	uint8_t *dl = a.dl ? a.dl + (size_t)g * a.nbits : nullptr;
+	uint8_t *ul = a.ul ? a.ul + (size_t)g * a.nbits : nullptr;
+	if (a.alg == 0) {                    // a5.c:60-66
+		for (int i = 0; i < a.nbits; i++) {
+			if (dl) dl[i] = 0;
+			if (ul) ul[i] = 0;
+		}
+		return;
+	}
+	if (a.alg != 1)                      // a5.c:72-75: A5/2..7 leave the buffers alone
+		return;
+	a5_1_stream(a.keys + (size_t)g * 8, a.fn[g], a.nbits, dl, ul);
+}
+
+// The TCH3 follower's keystreams (tch3_follow_kernels.hip), five lanes per frame handed in: lane 0 the 208 bits of a speech
+// burst (need == 1), lanes 1..4 the 96 bits of each stored burst of a FACCH3 flush (need == 2; gmr1_rx.c:405-408, 518),
+// all from the key of the frame's call.  A lane with nothing to do returns at once.
+__global__ __launch_bounds__(64) void k_a5_tch3f(Tch3FollowArgs a)
+{
+	const int g = blockIdx.x * 64 + threadIdx.x;
+	if (g >= 5 * a.n_frames)
+		return;
+	const int k = g / 5, sub = g - 5 * k;
+	const int need = a.need[k];
+	if (need != (sub ? 2 : 1))
+		return;
+	const uint8_t *key = a.state[a.call_of[k]].kc;
+	if (sub == 0)
+		a5_1_stream(key, a.fn[k], 208, a.ks_speech + (size_t)k * 208, nullptr);
+	else
+		a5_1_stream(key, a.job_fn[(size_t)k * 4 + sub - 1], 96, a.ks_facch + (size_t)k * 384 + 96 * (sub - 1), nullptr);
 }
 
 hipError_t launch_a5(const A5Args &a, hipStream_t stream)
@@ -261,6 +284,14 @@ hipError_t launch_a5(const A5Args &a, hipStream_t stream)
 	if (a.n <= 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_a5, dim3((a.n + 63) / 64), dim3(64), 0, stream, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_a5_tch3f(const Tch3FollowArgs &a, hipStream_t stream)
+{
+	if (a.n_frames <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_a5_tch3f, dim3((5 * a.n_frames + 63) / 64), dim3(64), 0, stream, a);
 	return hipGetLastError();
 }
 
