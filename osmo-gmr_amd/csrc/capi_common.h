@@ -97,6 +97,13 @@ int demod_dev_energy(hipStream_t st, int burst_id, int n, int sps, int in_len, c
                      const uint64_t *offset, const float *freq_shift, int8_t *ebits, int ebits_stride,
                      int32_t *sync_id, float *toa, float *energy, int32_t *rv);
 
+// gmr1_hip_tch3_follow_batch_dev on scratch of the caller's (capi_tch3_follow.cpp): tch3_follow_scratch_bytes(n_frames) of
+// device memory on a 128-byte boundary.  The arguments are not checked; the caller holds a WsLease.
+size_t tch3_follow_scratch_bytes(int n_frames);
+int tch3_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, const float *iq, const int32_t *first,
+                        int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                        struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
+
 // Device scratch of a traffic pass: one carve-up of the grow-only device workspace (none of the kernels the
 // passes launch uses it) instead of dozens of hipMalloc / hipFree pairs per call.
 struct Arena {

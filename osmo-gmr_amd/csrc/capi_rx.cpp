@@ -16,7 +16,9 @@
 // There is no CPU fallback.
 //
 // The traffic channels never feed back into that loop, so their follow-ups run after it as batched
-// passes of their own (RxRun::tch3_pass, RxRun::tch9_pass).  GSMTAP transport and per-burst stderr
+// passes of their own: RxRun::tch3_pass hands every chain with an IMMEDIATE ASSIGNMENT to the batched call follower
+// (capi_tch3_follow.cpp), whose state machine runs on the device, one invocation per assignment a chain sees;
+// RxRun::tch9_pass demodulates, classifies on the host and decodes.  GSMTAP transport and per-burst stderr
 // logging are out of scope; what GSMTAP would have carried comes back as records.
 
 #include "capi_common.h"
@@ -78,33 +80,11 @@ void emit(RxChain &c, uint16_t arfcn, int type, int fn, int tn, const uint8_t *l
 	c.rec_frame.push_back(frame);
 }
 
-// TCH3 state of a chain (struct tch3_state, gmr1_rx.c:59-78)
-struct Tch3State {
-	int active = 0;
-	int tn = 0, p = 0, ciph = 0;
-	float energy_dkab = 0.f, energy_burst = 0.f;
-	int weak_cnt = 0;
-	int8_t ebits[104 * 4] = {};
-	uint32_t bi_fn[4] = {0, 0, 0, 0};
-	int sync_id = 0, burst_cnt = 0;
-};
-
 struct TchItem {          // one frame of a chain in which rx_tch3 maps a burst
 	int chain_idx, frame;
-	int tn, p, e_toa;
+	int tn, ev;           // the assignment it belongs to: its timeslot, its index in the chain's events
 };
 
-struct TchJob {           // a decode the walk asks for: a speech burst or a FACCH3 flush
-	int chain_idx, frame;
-	int is_flush;
-	int fn;               // cd->fn when it happens
-	int tn;
-	int item;             // speech: index of the TchItem whose soft bits are decoded
-	int8_t ebits[104 * 4];    // flush: the four stored bursts
-	uint32_t bi_fn[4];
-};
-
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
 
 // grow-only pinned host buffer of the calling thread: the burst log of the receive loop comes back through it
@@ -409,289 +389,123 @@ int RxRun::frame_loop()
 int RxRun::tch3_pass()
 {
 	// ---- TCH3 follow-up (rx_tch3, gmr1_rx.c:355-600) ----------------------------------------------
-	// Nothing the traffic channel does feeds back into the BCCH / CCCH loop, so it runs afterwards,
-	// for all chains at once, in four steps:
-	//   A. for every frame from a chain's first assignment on, speculatively: burst energy, FACCH3
-	//      and speech demodulation, burst type detection, DKAB search         (4 batched launches)
-	//   B. host: the per-frame state machine (energy thresholds, DKAB / weak count, FACCH3 burst
-	//      grouping by sync sequence) over those results, producing the list of decodes it calls for
-	//   C. A5/1 keystreams and the TCH3 / FACCH3 decodes, each with and without deciphering
-	//   D. host: the ciphering state (a FACCH3 that only decodes ciphered switches it on) picks
-	//      the variant, records are emitted in frame order.
-	if (tch) {
-		std::vector<TchItem> titems;
-		const int twin = sps + (sps / 2);            // gmr1_rx.c:551
-		const int t_in_len = 117 * sps + twin;
-		const int t_etoa = twin >> 1;
-		for (size_t ci = 0; ci < chains.size(); ci++) {
-			RxChain &c = chains[ci];
-			if (c.events.empty())
+	// Nothing the traffic channel does feeds back into the BCCH / CCCH loop, so it runs afterwards, for all chains at
+	// once, through the batched call follower (tch3_follow_enqueue, capi_tch3_follow.cpp -- what
+	// gmr1_hip_tch3_follow_batch_dev runs): every chain with an assignment is one call.  This pass knows which frames of
+	// which chain belong to which assignment and where the records go; the per-frame work, the state machine, the
+	// decodes and the ciphering state are the follower's, on the device.  rx_tch3_init runs on the host between two
+	// invocations, so invocation g takes, of every call, the frames from its assignment g up to the next one: a chain
+	// that is assigned once -- the usual case -- costs one invocation and one synchronisation.
+	if (!tch)
+		return 0;
+	std::vector<TchItem> titems;
+	std::vector<int> calls;                      // the chains with an assignment
+	std::vector<size_t> next;                    // per call: its first item no invocation has taken yet
+	const int twin = sps + (sps / 2);            // gmr1_rx.c:551
+	const int t_in_len = 117 * sps + twin;
+	const int t_etoa = twin >> 1;
+	size_t n_gen = 0;
+	for (size_t ci = 0; ci < chains.size(); ci++) {
+		RxChain &c = chains[ci];
+		if (c.events.empty())
+			continue;
+		calls.push_back((int)ci);
+		next.push_back(titems.size());
+		n_gen = std::max(n_gen, c.events.size());
+		size_t ev = 0;
+		for (int f = c.events[0].frame; f < (int)c.log.size(); f++) {
+			while (ev + 1 < c.events.size() && c.events[ev + 1].frame <= f)
+				ev++;
+			const int tn = c.events[ev].tn;
+			const int64_t begin = (int64_t)c.log[f].align + sps * tn * 39 - t_etoa;
+			if (begin < 0 || begin + t_in_len > c.len)
+				continue;                         // burst_map fails: rx_tch3 returns before touching anything
+			titems.push_back({(int)ci, f, tn, (int)ev});
+		}
+	}
+	const int nt = (int)titems.size(), n_calls = (int)calls.size();
+	if (!nt)
+		return 0;
+	// the calls' states: no call, not ciphered, the carrier's key (ciphering outlives a re-assignment, gmr1_rx.c:358-376)
+	std::vector<gmr1_hip_tch3_state> state((size_t)n_calls);
+	std::memset(state.data(), 0, state.size() * sizeof(state[0]));
+	if (kc)
+		for (int q = 0; q < n_calls; q++)
+			std::memcpy(state[q].kc, kc + (size_t)chains[calls[q]].a * 8, 8);
+	// per frame 56 B staged here and the follower's scratch, six staged arrays; no invocation has more than nt frames
+	Arena arena;
+	if ((r = arena.init((size_t)n_calls * sizeof(state[0]) + ((size_t)n_calls + 1) * 4 + (size_t)nt * 56 + 6 * 128 +
+	                    tch3_follow_scratch_bytes(nt)))) return r;
+	std::vector<int32_t> first((size_t)n_calls + 1);
+	std::vector<int> item;                       // of each frame handed in
+	std::vector<uint64_t> t_off;
+	std::vector<float> t_fs;
+	std::vector<uint32_t> t_fn;
+	std::vector<gmr1_hip_tch3_frame> got;
+	for (size_t g = 0; g < n_gen; g++) {
+		item.clear(); t_off.clear(); t_fs.clear(); t_fn.clear();
+		for (int q = 0; q < n_calls; q++) {
+			const RxChain &c = chains[calls[q]];
+			first[q] = (int32_t)item.size();
+			if (g >= c.events.size())
 				continue;
-			size_t ev = 0;
-			for (int f = c.events[0].frame; f < (int)c.log.size(); f++) {
-				while (ev + 1 < c.events.size() && c.events[ev + 1].frame <= f)
-					ev++;
-				const int tn = c.events[ev].tn;
-				const int64_t begin = (int64_t)c.log[f].align + sps * tn * 39 - t_etoa;
-				if (begin < 0 || begin + t_in_len > c.len)
-					continue;                         // burst_map fails: rx_tch3 returns before touching anything
-				titems.push_back({(int)ci, f, tn, c.events[ev].p, t_etoa});
+			// rx_tch3_init.  An assignment none of whose frames fits hands no frame in, and the next one's follows it on
+			// the same state: every assignment is applied, in the order the reference applies them
+			gmr1_hip_tch3_state_assign(&state[q], c.events[g].p, c.events[g].ref_energy);
+			for (size_t &k = next[q]; k < titems.size() && titems[k].chain_idx == calls[q] && titems[k].ev == (int)g; k++) {
+				const FrameCtx &x = c.log[titems[k].frame];
+				item.push_back((int)k);
+				t_off.push_back(c.base + (uint64_t)((int64_t)x.align + sps * titems[k].tn * 39 - t_etoa));
+				t_fs.push_back(-x.freq_err);
+				t_fn.push_back((uint32_t)x.fn);
 			}
 		}
-		const int nt = (int)titems.size();
-		if (nt) {
-			// step A needs 376 B per frame, the decodes of step C at most 866 B per frame
-			Arena arena;
-			if ((r = arena.init((size_t)nt * 1300 + 64 * 1024))) return r;
-			Stage sg(st, &arena);
-			std::vector<uint64_t> t_off(nt);
-			std::vector<float> t_fs(nt), t_et(nt);
-			std::vector<int32_t> t_p(nt);
-			for (int k = 0; k < nt; k++) {
-				const RxChain &c = chains[titems[k].chain_idx];
-				const FrameCtx &x = c.log[titems[k].frame];
-				t_off[k] = c.base + (uint64_t)((int64_t)x.align + sps * titems[k].tn * 39 - t_etoa);
-				t_fs[k] = -x.freq_err;
-				t_et[k] = (float)t_etoa;
-				t_p[k] = titems[k].p;
-			}
-			std::vector<int8_t> h_feb((size_t)nt * 104), h_seb((size_t)nt * 212);
-			std::vector<int32_t> h_fsid(nt), h_frv(nt), h_srv(nt), h_bt(nt), h_drv(nt), h_krv(nt);
-			std::vector<float> h_en(nt);
-			const uint64_t *d_off2 = sg.in(t_off.data(), (size_t)nt);
-			const float *d_fs2 = sg.in(t_fs.data(), (size_t)nt);
-			const float *d_et = sg.in(t_et.data(), (size_t)nt);
-			const int32_t *d_pp = sg.in(t_p.data(), (size_t)nt);
-			int8_t *d_feb = sg.out(h_feb.data(), (size_t)nt * 104);
-			int8_t *d_seb = sg.out(h_seb.data(), (size_t)nt * 212);
-			int32_t *d_fsid = sg.out(h_fsid.data(), (size_t)nt);
-			int32_t *d_frv = sg.out(h_frv.data(), (size_t)nt);
-			int32_t *d_srv = sg.out(h_srv.data(), (size_t)nt);
-			int32_t *d_bt = sg.out(h_bt.data(), (size_t)nt);
-			int32_t *d_drv = sg.out(h_drv.data(), (size_t)nt);
-			int32_t *d_krv = sg.out(h_krv.data(), (size_t)nt);
-			float *d_en = sg.out(h_en.data(), (size_t)nt);
-			int32_t *d_dsid = sg.dev<int32_t>((size_t)nt);
-			float *d_dtoa = sg.dev<float>((size_t)nt), *d_ftoa = sg.dev<float>((size_t)nt);
-			if ((r = sg.err())) return r;
+		const int n = (int)item.size();
+		first[n_calls] = n;
+		if (!n)
+			continue;
+		got.resize((size_t)n);
+		arena.off = 0;                            // the invocation before is through (fetch)
+		Stage sg(st, &arena);
+		const int32_t *d_first = sg.in(first.data(), first.size());
+		const uint64_t *d_off = sg.in(t_off.data(), (size_t)n);
+		const float *d_fs = sg.in(t_fs.data(), (size_t)n);
+		const uint32_t *d_fn = sg.in(t_fn.data(), (size_t)n);
+		gmr1_hip_tch3_state *d_state = sg.inout(state.data(), state.size());
+		gmr1_hip_tch3_frame *d_got = sg.out(got.data(), (size_t)n);
+		unsigned char *scratch = sg.dev<unsigned char>(tch3_follow_scratch_bytes(n));
+		if ((r = sg.err())) return r;
+		r = tch3_follow_enqueue(st, scratch, n_calls, sps, t_in_len, tch, d_first, n, d_off, d_fs, d_fn, d_state, d_got);
+		if (r) return r;
+		if ((r = sg.fetch())) return r;
 
-			// A. speculative per-frame work
-			r = demod_dev_energy(st, GMR1_HIP_NT3_FACCH, nt, sps, t_in_len, tch, d_off2, d_fs2, d_feb, 104, d_fsid, d_ftoa, d_en,
-			                     d_frv);
-			if (r) return r;
-			r = demod_dev_energy(st, GMR1_HIP_NT3_SPEECH, nt, sps, t_in_len, tch, d_off2, d_fs2, d_seb, 212, nullptr, nullptr,
-			                     nullptr, d_srv);
-			if (r) return r;
-			{
-				const int ids[2] = {GMR1_HIP_NT3_FACCH, GMR1_HIP_NT3_SPEECH};     // gmr1_rx.c:534-538
-				r = gmr1_hip_detect_batch_dev(st, 2, ids, nt, sps, t_in_len, tch, d_off2, d_fs2, d_et, d_bt, d_dsid, d_dtoa, d_drv);
-				if (r) return r;
-			}
-			r = gmr1_hip_dkab_demod_batch_dev(st, nt, sps, t_in_len, tch, d_off2, d_fs2, d_pp, nullptr, nullptr, d_krv);
-			if (r) return r;
-			if ((r = sg.fetch())) return r;
-
-
-			// B. the state machine of rx_tch3 (gmr1_rx.c:531-600) and its helpers, chain by chain
-			std::vector<TchJob> jobs;
-			{
-				int k = 0;
-				while (k < nt) {
-					const int ci = titems[k].chain_idx;
-					RxChain &c = chains[ci];
-					Tch3State ts;
-					size_t ev = 0;
-					auto flush = [&](int frame, int fn) {       // _rx_tch3_facch_flush, gmr1_rx.c:397-450 (decode deferred)
-						TchJob j;
-						j.chain_idx = ci; j.frame = frame; j.is_flush = 1; j.fn = fn; j.tn = ts.tn; j.item = -1;
-						std::memcpy(j.ebits, ts.ebits, sizeof(j.ebits));
-						std::memcpy(j.bi_fn, ts.bi_fn, sizeof(j.bi_fn));
-						jobs.push_back(j);
-						ts.sync_id ^= 1;
-						ts.burst_cnt = 0;
-						std::memset(ts.bi_fn, 0xff, sizeof(ts.bi_fn));
-						std::memset(ts.ebits, 0, sizeof(ts.ebits));
-					};
-					for (; k < nt && titems[k].chain_idx == ci; k++) {
-						const TchItem &ti = titems[k];
-						// assignments taken in this frame or in skipped ones (rx_tch3_init, gmr1_rx.c:358-378)
-						while (ev < c.events.size() && c.events[ev].frame <= ti.frame) {
-							const AssEvt &e = c.events[ev++];
-							ts.active = 1;
-							ts.tn = e.tn; ts.p = e.p;
-							ts.energy_burst = e.ref_energy * 0.75f;
-							ts.energy_dkab = ts.energy_burst / 8.0f;
-							ts.weak_cnt = 0;
-							ts.sync_id = 0;
-							std::memset(ts.ebits, 0, sizeof(ts.ebits));
-						}
-						if (!ts.active)
-							continue;
-						const int fn = c.log[ti.frame].fn;
-						const float be = h_en[k];
-						const float det = (ts.energy_dkab + ts.energy_burst) / 4.0f;
-						if (be < det) {
-							const int drv = h_krv[k];
-							if (drv < 0)
-								continue;
-							if (drv == 1) {
-								if (ts.weak_cnt++ > 8)
-									ts.active = 0;
-							} else
-								ts.energy_dkab = (0.1f * be) + (0.9f * ts.energy_dkab);
-							continue;
-						}
-						ts.weak_cnt = 0;
-						ts.energy_burst = (0.1f * be) + (0.9f * ts.energy_burst);
-						if (h_drv[k] < 0)
-							continue;
-						if (h_bt[k] == 0) {
-							// _rx_tch3_facch, gmr1_rx.c:452-493
-							if (h_frv[k] < 0)
-								continue;
-							const int bi = fn & 3;
-							if (h_fsid[k] != ts.sync_id)
-								flush(ti.frame, fn);
-							std::memcpy(&ts.ebits[104 * bi], &h_feb[(size_t)k * 104], 104);
-							ts.sync_id = h_fsid[k];
-							ts.bi_fn[bi] = (uint32_t)fn;
-							ts.burst_cnt += 1;
-							if (ts.burst_cnt == 4)
-								flush(ti.frame, fn);
-						} else {
-							// _rx_tch3_speech, gmr1_rx.c:495-529
-							if (h_srv[k] < 0)
-								continue;
-							TchJob j;
-							j.chain_idx = ci; j.frame = ti.frame; j.is_flush = 0; j.fn = fn; j.tn = ts.tn; j.item = k;
-							jobs.push_back(j);
-						}
-					}
-				}
-			}
-
-			// C. keystreams and decodes, plain and deciphered
-			std::vector<int> sj, fj;
-			for (size_t j = 0; j < jobs.size(); j++)
-				(jobs[j].is_flush ? fj : sj).push_back((int)j);
-			const int ns = (int)sj.size(), nf = (int)fj.size();
-			std::vector<uint8_t> s_fr[2], f_l2[2];
-			std::vector<int32_t> s_conv[2], f_crc[2], f_conv[2];
-			if (ns) {
-				std::vector<int8_t> eb((size_t)ns * 212);
-				std::vector<uint8_t> keys((size_t)ns * 8, 0);
-				std::vector<uint32_t> fns(ns);
-				for (int i = 0; i < ns; i++) {
-					const TchJob &j = jobs[sj[i]];
-					std::memcpy(&eb[(size_t)i * 212], &h_seb[(size_t)j.item * 212], 212);
-					if (kc) std::memcpy(&keys[(size_t)i * 8], kc + (size_t)chains[j.chain_idx].a * 8, 8);
-					fns[i] = (uint32_t)j.fn;
-				}
-				const int8_t *d_eb = sg.in(eb.data(), eb.size());
-				const uint8_t *d_k = sg.in(keys.data(), keys.size());
-				const uint32_t *d_fn = sg.in(fns.data(), (size_t)ns);
-				uint8_t *d_ks = sg.dev<uint8_t>((size_t)ns * 208), *d_fr = sg.dev<uint8_t>((size_t)ns * 20);
-				int32_t *d_cv = sg.dev<int32_t>((size_t)ns * 2);
-				if ((r = sg.err())) return r;
-				r = gmr1_hip_a5_batch_dev(st, ns, 1, 208, d_k, d_fn, d_ks, nullptr);
-				if (r) return r;
-				for (int v = 0; v < 2; v++) {
-					r = gmr1_hip_tch3_decode_batch_dev(st, ns, 0, d_eb, v ? d_ks : nullptr, d_fr, nullptr, d_cv);
-					if (r) return r;
-					s_fr[v].resize((size_t)ns * 20);
-					s_conv[v].resize((size_t)ns * 2);
-					sg.back(s_fr[v].data(), d_fr, (size_t)ns * 20);
-					sg.back(s_conv[v].data(), d_cv, (size_t)ns * 2);
-					if ((r = sg.fetch())) return r;
-				}
-			}
-			if (nf) {
-				std::vector<int8_t> eb((size_t)nf * 416);
-				std::vector<uint8_t> keys((size_t)nf * 4 * 8, 0);
-				std::vector<uint32_t> fns((size_t)nf * 4);
-				for (int i = 0; i < nf; i++) {
-					const TchJob &j = jobs[fj[i]];
-					std::memcpy(&eb[(size_t)i * 416], j.ebits, 416);
-					for (int b = 0; b < 4; b++) {
-						if (kc) std::memcpy(&keys[((size_t)i * 4 + b) * 8], kc + (size_t)chains[j.chain_idx].a * 8, 8);
-						fns[(size_t)i * 4 + b] = j.bi_fn[b];
-					}
-				}
-				const int8_t *d_eb = sg.in(eb.data(), eb.size());
-				const uint8_t *d_k = sg.in(keys.data(), keys.size());
-				const uint32_t *d_fn = sg.in(fns.data(), (size_t)nf * 4);
-				uint8_t *d_ks = sg.dev<uint8_t>((size_t)nf * 384), *d_l2 = sg.dev<uint8_t>((size_t)nf * 10);
-				int32_t *d_crc = sg.dev<int32_t>((size_t)nf), *d_cv = sg.dev<int32_t>((size_t)nf);
-				if ((r = sg.err())) return r;
-				// 4 x 96 keystream bits per message, one per burst's frame number (gmr1_rx.c:409-412)
-				r = gmr1_hip_a5_batch_dev(st, nf * 4, 1, 96, d_k, d_fn, d_ks, nullptr);
-				if (r) return r;
-				for (int v = 0; v < 2; v++) {
-					r = gmr1_hip_facch3_decode_batch_dev(st, nf, d_eb, v ? d_ks : nullptr, d_l2, nullptr, d_crc, d_cv);
-					if (r) return r;
-					f_l2[v].resize((size_t)nf * 10);
-					f_crc[v].resize(nf);
-					f_conv[v].resize(nf);
-					sg.back(f_l2[v].data(), d_l2, (size_t)nf * 10);
-					sg.back(f_crc[v].data(), d_crc, (size_t)nf);
-					sg.back(f_conv[v].data(), d_cv, (size_t)nf);
-					if ((r = sg.fetch())) return r;
-				}
-			}
-
-
-			// D. ciphering state and records, in the order things happened
-			{
-				std::vector<int> ciph(chains.size(), 0);
-				int is = 0, iff = 0;
-				for (size_t jj = 0; jj < jobs.size(); jj++) {
-					const TchJob &j = jobs[jj];
-					RxChain &c = chains[j.chain_idx];
-					const uint16_t an = arfcn ? arfcn[c.a] : (uint16_t)c.a;
-					int &cf = ciph[j.chain_idx];
-					if (!j.is_flush) {
-						const int v = cf ? 1 : 0;
-						const int32_t *cv = &s_conv[v][(size_t)is * 2];
-						emit(c, an, 0x10 /* GSMTAP_GMR1_TCH3 */, j.fn, j.tn, &s_fr[v][(size_t)is * 20],
-						     (cv[0] & 0xffff) | (cv[1] << 16), j.frame, 20);
-						is++;
-					} else {
-						int v = cf ? 1 : 0;
-						int crc = f_crc[v][iff];
-						if (!cf && crc) {                 // retry with ciphering (gmr1_rx.c:420-432)
-							v = 1;
-							crc = f_crc[1][iff];
-							if (!crc)
-								cf = 1;
-						}
-						if (!crc) {
-							const uint8_t *m = &f_l2[v][(size_t)iff * 10];
-							emit(c, an, 0x12 /* GSMTAP_GMR1_TCH3 | GSMTAP_GMR1_FACCH */, j.fn - 3, j.tn, m,
-							     f_conv[v][iff], j.frame, 10);
-							// ASSIGNMENT COMMAND 1 starts the TCH9 follow-up (gmr1_rx.c:248-258, 436-442)
-							if (csd && m[3] == 0x06 && m[4] == 0x2e)
-								c.events9.push_back({j.frame, ((m[5] & 0x03) << 3) | (m[6] >> 5), 0, 0.f});
-						}
-						iff++;
-					}
-				}
-			}
-
-			// frame order within each chain: BCCH / CCCH of a frame come before its TCH records
-			for (RxChain &c : chains) {
-				if (c.events.empty())
-					continue;
-				std::vector<size_t> order(c.rec.size());
-				for (size_t i = 0; i < order.size(); i++) order[i] = i;
-				std::stable_sort(order.begin(), order.end(),
-				                 [&](size_t x, size_t y) { return c.rec_frame[x] < c.rec_frame[y]; });
-				std::vector<gmr1_hip_rx_record> sorted(c.rec.size());
-				for (size_t i = 0; i < order.size(); i++) sorted[i] = c.rec[order[i]];
-				c.rec.swap(sorted);
-			}
+		// records, chain by chain in frame order
+		for (int k = 0; k < n; k++) {
+			const gmr1_hip_tch3_frame &fr = got[k];
+			if (!fr.type)
+				continue;
+			const TchItem &ti = titems[item[k]];
+			RxChain &c = chains[ti.chain_idx];
+			emit(c, arfcn ? arfcn[c.a] : (uint16_t)c.a, fr.type, (int)fr.fn, ti.tn, fr.l2, fr.conv, ti.frame, fr.len);
+			// ASSIGNMENT COMMAND 1 on the FACCH3 starts the TCH9 follow-up (gmr1_rx.c:248-258, 436-442)
+			const uint8_t *m = fr.l2;
+			if (csd && fr.type == 0x12 /* GSMTAP_GMR1_TCH3 | GSMTAP_GMR1_FACCH */ && m[3] == 0x06 && m[4] == 0x2e)
+				c.events9.push_back({ti.frame, ((m[5] & 0x03) << 3) | (m[6] >> 5), 0, 0.f});
 		}
 	}
 
+	// frame order within each chain: BCCH / CCCH of a frame come before its TCH records
+	for (RxChain &c : chains) {
+		if (c.events.empty())
+			continue;
+		std::vector<size_t> order(c.rec.size());
+		for (size_t i = 0; i < order.size(); i++) order[i] = i;
+		std::stable_sort(order.begin(), order.end(),
+		                 [&](size_t x, size_t y) { return c.rec_frame[x] < c.rec_frame[y]; });
+		std::vector<gmr1_hip_rx_record> sorted(c.rec.size());
+		for (size_t i = 0; i < order.size(); i++) sorted[i] = c.rec[order[i]];
+		c.rec.swap(sorted);
+	}
 	return 0;
 }
 

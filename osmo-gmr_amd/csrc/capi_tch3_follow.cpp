@@ -27,26 +27,42 @@ int follow_check(int n_calls, int sps, int in_len, const float *iq, const int32_
 
 size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
 
+// where the follower's scratch of n frames lies, from a 128-byte boundary: per-frame results, job slots, keystreams, decodes
+struct FollowScratch {
+	size_t call, p, et, en, krv, drv, bt, dsid, dtoa, frv, fsid, ftoa, srv, feb, seb, cls, need, jeb, jfn, kss, ksf, sfr[2],
+	       scv[2], fl[2], fcrc[2], fcv[2], bytes;
+	explicit FollowScratch(size_t n)
+	{
+		size_t o = 0;
+		auto take = [&](size_t b) { const size_t at = o; o += up128(b); return at; };
+		call = take(n * 4); p = take(n * 4); et = take(n * 4); en = take(n * 4); krv = take(n * 4); drv = take(n * 4);
+		bt = take(n * 4); dsid = take(n * 4); dtoa = take(n * 4); frv = take(n * 4); fsid = take(n * 4); ftoa = take(n * 4);
+		srv = take(n * 4); feb = take(n * 104); seb = take(n * 212); cls = take(n); need = take(n); jeb = take(n * 416);
+		jfn = take(n * 16); kss = take(n * 208); ksf = take(n * 384);
+		for (int v = 0; v < 2; v++) sfr[v] = take(n * 20);
+		for (int v = 0; v < 2; v++) scv[v] = take(n * 8);
+		for (int v = 0; v < 2; v++) fl[v] = take(n * 10);
+		for (int v = 0; v < 2; v++) fcrc[v] = take(n * 4);
+		for (int v = 0; v < 2; v++) fcv[v] = take(n * 4);
+		bytes = o;
+	}
+};
+
+}  // namespace
+
+namespace gmr1 {
+
+size_t tch3_follow_scratch_bytes(int n_frames) { return FollowScratch((size_t)n_frames).bytes; }
+
 // The whole chain, enqueued on `st`; every pointer is device memory.  The caller has checked the arguments and holds a
-// WsLease: the per-frame results, job slots, keystreams and decodes lie in the device's workspace.
-int follow_enqueue(hipStream_t st, DevState *ds, int n_calls, int sps, int in_len, const float *iq, const int32_t *first,
-                   int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
-                   struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out)
+// WsLease; `scratch` is tch3_follow_scratch_bytes(n_frames) of device memory on a 128-byte boundary that is the chain's
+// alone until its last kernel is through.
+int tch3_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, const float *iq, const int32_t *first,
+                        int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                        struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out)
 {
-	const size_t n = (size_t)n_frames;
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t at = o; o += up128(bytes); return at; };
-	const size_t o_call = take(n * 4), o_p = take(n * 4), o_et = take(n * 4), o_en = take(n * 4), o_krv = take(n * 4),
-	             o_drv = take(n * 4), o_bt = take(n * 4), o_dsid = take(n * 4), o_dtoa = take(n * 4), o_frv = take(n * 4),
-	             o_fsid = take(n * 4), o_ftoa = take(n * 4), o_srv = take(n * 4), o_feb = take(n * 104), o_seb = take(n * 212),
-	             o_cls = take(n), o_need = take(n), o_jeb = take(n * 416), o_jfn = take(n * 16), o_kss = take(n * 208),
-	             o_ksf = take(n * 384), o_sfr0 = take(n * 20), o_sfr1 = take(n * 20), o_scv0 = take(n * 8), o_scv1 = take(n * 8),
-	             o_fl0 = take(n * 10), o_fl1 = take(n * 10), o_fcrc0 = take(n * 4), o_fcrc1 = take(n * 4), o_fcv0 = take(n * 4),
-	             o_fcv1 = take(n * 4);
-	void *ws;
-	int r = dev_workspace(ds, o + 128, &ws);
-	if (r) return r;
-	unsigned char *d = reinterpret_cast<unsigned char *>(((uintptr_t)ws + 127) & ~(uintptr_t)127);
+	const FollowScratch o((size_t)n_frames);
+	unsigned char *d = static_cast<unsigned char *>(scratch);
 	auto I32 = [&](size_t at) { return reinterpret_cast<int32_t *>(d + at); };
 	auto F32 = [&](size_t at) { return reinterpret_cast<float *>(d + at); };
 	auto U8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(d + at); };
@@ -57,34 +73,34 @@ int follow_enqueue(hipStream_t st, DevState *ds, int n_calls, int sps, int in_le
 	a.n_calls = n_calls; a.n_frames = n_frames;
 	a.e_toa = (in_len - 117 * sps) >> 1;           // burst_map's e_toa for a window of 117 sps + win (gmr1_rx.c:157-167)
 	a.first = first; a.fn = fn; a.state = state; a.out = out;
-	a.call_of = I32(o_call); a.p = I32(o_p); a.et = F32(o_et);
-	a.energy = F32(o_en); a.dkab_rv = I32(o_krv); a.det_rv = I32(o_drv); a.btid = I32(o_bt);
-	a.facch_rv = I32(o_frv); a.facch_sid = I32(o_fsid); a.speech_rv = I32(o_srv);
-	a.facch_eb = I8(o_feb);
-	a.cls = U8(o_cls); a.need = U8(o_need); a.job_eb = I8(o_jeb); a.job_fn = reinterpret_cast<uint32_t *>(d + o_jfn);
-	a.ks_speech = U8(o_kss); a.ks_facch = U8(o_ksf);
-	a.sp_frames[0] = U8(o_sfr0); a.sp_frames[1] = U8(o_sfr1);
-	a.sp_conv[0] = I32(o_scv0); a.sp_conv[1] = I32(o_scv1);
-	a.fa_l2[0] = U8(o_fl0); a.fa_l2[1] = U8(o_fl1);
-	a.fa_crc[0] = I32(o_fcrc0); a.fa_crc[1] = I32(o_fcrc1);
-	a.fa_conv[0] = I32(o_fcv0); a.fa_conv[1] = I32(o_fcv1);
+	a.call_of = I32(o.call); a.p = I32(o.p); a.et = F32(o.et);
+	a.energy = F32(o.en); a.dkab_rv = I32(o.krv); a.det_rv = I32(o.drv); a.btid = I32(o.bt);
+	a.facch_rv = I32(o.frv); a.facch_sid = I32(o.fsid); a.speech_rv = I32(o.srv);
+	a.facch_eb = I8(o.feb);
+	a.cls = U8(o.cls); a.need = U8(o.need); a.job_eb = I8(o.jeb); a.job_fn = reinterpret_cast<uint32_t *>(d + o.jfn);
+	a.ks_speech = U8(o.kss); a.ks_facch = U8(o.ksf);
+	a.sp_frames[0] = U8(o.sfr[0]); a.sp_frames[1] = U8(o.sfr[1]);
+	a.sp_conv[0] = I32(o.scv[0]); a.sp_conv[1] = I32(o.scv[1]);
+	a.fa_l2[0] = U8(o.fl[0]); a.fa_l2[1] = U8(o.fl[1]);
+	a.fa_crc[0] = I32(o.fcrc[0]); a.fa_crc[1] = I32(o.fcrc[1]);
+	a.fa_conv[0] = I32(o.fcv[0]); a.fa_conv[1] = I32(o.fcv[1]);
 
 	HIP_TRY(launch_tch3f_prep(a, st));
 
-	// A. speculative per-frame work (what RxRun::tch3_pass runs, capi_rx.cpp): the state machine picks from it
-	r = demod_dev_energy(st, GMR1_HIP_NT3_FACCH, n_frames, sps, in_len, iq, offset, freq_shift, I8(o_feb), 104, I32(o_fsid),
-	                     F32(o_ftoa), F32(o_en), I32(o_frv));
+	// A. speculative per-frame work: the state machine picks from it
+	int r = demod_dev_energy(st, GMR1_HIP_NT3_FACCH, n_frames, sps, in_len, iq, offset, freq_shift, I8(o.feb), 104, I32(o.fsid),
+	                         F32(o.ftoa), F32(o.en), I32(o.frv));
 	if (r) return r;
-	r = demod_dev_energy(st, GMR1_HIP_NT3_SPEECH, n_frames, sps, in_len, iq, offset, freq_shift, I8(o_seb), 212, nullptr, nullptr,
-	                     nullptr, I32(o_srv));
+	r = demod_dev_energy(st, GMR1_HIP_NT3_SPEECH, n_frames, sps, in_len, iq, offset, freq_shift, I8(o.seb), 212, nullptr, nullptr,
+	                     nullptr, I32(o.srv));
 	if (r) return r;
 	{
 		const int ids[2] = {GMR1_HIP_NT3_FACCH, GMR1_HIP_NT3_SPEECH};     // gmr1_rx.c:534-538
-		r = gmr1_hip_detect_batch_dev(st, 2, ids, n_frames, sps, in_len, iq, offset, freq_shift, a.et, I32(o_bt), I32(o_dsid),
-		                              F32(o_dtoa), I32(o_drv));
+		r = gmr1_hip_detect_batch_dev(st, 2, ids, n_frames, sps, in_len, iq, offset, freq_shift, a.et, I32(o.bt), I32(o.dsid),
+		                              F32(o.dtoa), I32(o.drv));
 		if (r) return r;
 	}
-	r = gmr1_hip_dkab_demod_batch_dev(st, n_frames, sps, in_len, iq, offset, freq_shift, a.p, nullptr, nullptr, I32(o_krv));
+	r = gmr1_hip_dkab_demod_batch_dev(st, n_frames, sps, in_len, iq, offset, freq_shift, a.p, nullptr, nullptr, I32(o.krv));
 	if (r) return r;
 
 	// B. the state machine, call by call
@@ -95,13 +111,13 @@ int follow_enqueue(hipStream_t st, DevState *ds, int n_calls, int sps, int in_le
 	for (int v = 0; v < 2; v++) {
 		Tch3Args t;
 		t.n = n_frames; t.m = 0; t.conv_acc = conv_acc();
-		t.ebits = I8(o_seb); t.ciph = v ? a.ks_speech : nullptr;
-		t.frames = U8(v ? o_sfr1 : o_sfr0); t.bits_s = nullptr; t.conv = I32(v ? o_scv1 : o_scv0);
+		t.ebits = I8(o.seb); t.ciph = v ? a.ks_speech : nullptr;
+		t.frames = U8(o.sfr[v]); t.bits_s = nullptr; t.conv = I32(o.scv[v]);
 		HIP_TRY(launch_tch3_jobs(t, a.need, st));
 		Facch3Args f;
 		f.n = n_frames; f.conv_acc = conv_acc();
 		f.ebits = a.job_eb; f.ciph = v ? a.ks_facch : nullptr;
-		f.l2 = U8(v ? o_fl1 : o_fl0); f.bits_s = nullptr; f.crc = I32(v ? o_fcrc1 : o_fcrc0); f.conv = I32(v ? o_fcv1 : o_fcv0);
+		f.l2 = U8(o.fl[v]); f.bits_s = nullptr; f.crc = I32(o.fcrc[v]); f.conv = I32(o.fcv[v]);
 		HIP_TRY(launch_facch3_jobs(f, a.need, st));
 	}
 
@@ -110,7 +126,7 @@ int follow_enqueue(hipStream_t st, DevState *ds, int n_calls, int sps, int in_le
 	return 0;
 }
 
-}  // namespace
+}  // namespace gmr1
 
 extern "C" {
 
@@ -141,7 +157,10 @@ int gmr1_hip_tch3_follow_batch_dev(void *stream, int n_calls, int sps, int in_le
 	if (n_calls == 0 || n_frames == 0) return 0;
 	WsLease lease;
 	if ((r = lease.acquire(s, (hipStream_t)stream))) return r;
-	return follow_enqueue((hipStream_t)stream, s, n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	Arena ws;                                      // the start of the device's workspace
+	if ((r = ws.init(tch3_follow_scratch_bytes(n_frames)))) return r;
+	return tch3_follow_enqueue((hipStream_t)stream, ws.base, n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state,
+	                           out);
 }
 
 int gmr1_hip_tch3_follow_batch(int n_calls, int sps, int in_len, const float *iq, uint64_t iq_len,
@@ -172,7 +191,10 @@ int gmr1_hip_tch3_follow_batch(int n_calls, int sps, int in_len, const float *iq
 	{
 		WsLease lease;
 		if ((r = lease.acquire(s, nullptr))) return r;
-		if ((r = follow_enqueue(nullptr, s, n_calls, sps, in_len, d_iq, d_first, n_frames, d_off, d_fs, d_fn, d_state, d_out)))
+		Arena ws;
+		if ((r = ws.init(tch3_follow_scratch_bytes(n_frames)))) return r;
+		if ((r = tch3_follow_enqueue(nullptr, ws.base, n_calls, sps, in_len, d_iq, d_first, n_frames, d_off, d_fs, d_fn, d_state,
+		                             d_out)))
 			return r;
 	}
 	return sg.fetch();

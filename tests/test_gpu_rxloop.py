@@ -1,5 +1,7 @@
 """GPU parity of the batched receive loop (gmr1_hip_rx_run*, reference src/gmr1_rx.c:605-895)
 against the oracle's restatement of the same loop, carrier by carrier."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -259,6 +261,44 @@ def test_rx_loop_tch3_follow_up_matches_oracle(gpu_api, orc, pkg, decoder):
         assert sp <= got
     assert n_tch > 100
     # without the traffic carriers: exactly the BCCH / CCCH records
+    rec0, _, _, _ = gpu_api.rx_run(np.concatenate(bc), offset, length, sps=SPS)
+    assert _key_n(rec0) == _key_n(rec[rec["type"] < 0x10])
+
+
+REASSIGNED = [(31, [(15, 11, 20), (55, 4, 7)]), (32, [(12, 20, 33), (40, 9, 12), (70, 11, 20)])]
+
+
+@functools.lru_cache(maxsize=1)
+def _reassigned_capture(pkg):
+    """Two carriers whose calls are re-assigned once and twice; ciphered from 20 frames after the first assignment.
+    Built once for both decoder modes."""
+    kc = np.arange(1, 9, dtype=np.uint8)
+    return [workloads.bcch_tch_reassigned(pkg, seed, ia, seconds=5.0, sps=SPS, kc=kc, cipher_after=20)
+            for seed, ia in REASSIGNED], kc
+
+
+def test_rx_loop_tch3_several_assignments_on_one_chain(gpu_api, orc, pkg, decoder):
+    """Several IMMEDIATE ASSIGNMENTs on one chain (rx_tch3_init again, gmr1_rx.c:358-378: timeslot, DKAB position and
+    energies start over, the ciphering state and the FACCH3 burst count stay): the traffic pass hands the follower one
+    invocation per assignment, here two for one carrier and three for the other in the same call.  Records are the
+    oracle's, carrier by carrier, and every assignment is followed."""
+    caps, kc = _reassigned_capture(pkg)
+    bc, tc = [c[0] for c in caps], [c[1] for c in caps]
+    length = np.array([x.size for x in bc], np.uint64)
+    offset = np.concatenate([[0], np.cumsum(length)[:-1]]).astype(np.uint64)
+    rec, status, chains, found = gpu_api.rx_run_tch(np.concatenate(bc), np.concatenate(tc), offset, length, sps=SPS,
+                                                    kc=np.stack([kc, kc]))
+    assert found == len(rec) and not status.any()
+    for i, (_, ia) in enumerate(REASSIGNED):
+        orv, orec, och = orc.rx_run_tch(bc[i], tc[i], sps=SPS, arfcn=i, kc=kc)
+        assert orv == 0 and chains[i] == och
+        # the oracle saw every assignment and followed each of them
+        n_ia = sum(1 for r in orec if r["type"] == 2 and r["l2"][1] == 0x06 and r["l2"][2] == 0x3f)
+        per_tn = [int(np.sum((orec["type"] >= 0x10) & (orec["tn"] == tn))) for _, tn, _ in ia]
+        print("carrier", i, "IMM.ASS", n_ia, "traffic records per assignment", per_tn)
+        assert n_ia == len(ia)
+        assert min(per_tn) >= 10, per_tn
+        assert _key_n(rec[rec["arfcn"] == i]) == _key_n(orec), f"carrier {i}: records differ from the oracle's"
     rec0, _, _, _ = gpu_api.rx_run(np.concatenate(bc), offset, length, sps=SPS)
     assert _key_n(rec0) == _key_n(rec[rec["type"] < 0x10])
 

@@ -184,6 +184,34 @@ def bcch_tch_pair(pkg, seed, seconds=4.0, sps=4, stn=3, delay=2, tn=11, p=20, k_
     return bcch, tch, sent, sent_t
 
 
+def bcch_tch_reassigned(pkg, seed, imm_ass, seconds=5.0, sps=4, stn=3, delay=2, kc=None, cipher_after=None,
+                        esn0_db=28.0, cfo_hz=60.0):
+    """A BCCH carrier whose CCCH carries several IMMEDIATE ASSIGNMENTs, imm_ass = [(k, tn, p), ...] with rising k, and the
+    traffic carrier they point to: the sum of one TCH3 carrier per assignment, each from the frame its assignment was
+    sent in up to the next one's.  cipher_after: frames after the FIRST assignment from which the TCH is A5/1-ciphered
+    with kc.  Returns (bcch, tch, sent, the assignments as (k sent, tn, p))."""
+    from importlib import import_module
+    synth = import_module(pkg.__name__ + ".synth")
+    rng = np.random.default_rng(seed)
+    n = int(seconds * 23400 * sps)
+    t0 = int(rng.integers(0, 24 * 39 * sps))
+    fn0 = int(rng.integers(0, 1 << 18))
+    fb, fd = pkg.api.burst_format("bcch"), pkg.api.burst_format("dc6")
+    fs, ff = pkg.api.burst_format("nt3_speech"), pkg.api.burst_format("nt3_facch")
+    bcch, sent = synth.synth_bcch_carrier(fb, fd, n, sps, rng, stn=stn, delay=delay, fn0=fn0, t0=t0,
+                                          esn0_db=esn0_db, cfo_hz=cfo_hz, imm_ass=list(imm_ass))
+    ks = [s["k"] for s in sent if s["type"] == "ccch" and s.get("imm_ass")]
+    assert len(ks) == len(imm_ass) and ks == sorted(set(ks)), "every assignment needs a CCCH frame of its own"
+    tch = np.zeros(n, np.complex64)
+    for i, (_, tn, p) in enumerate(imm_ass):
+        part, _ = synth.synth_tch3_carrier(fs, ff, n, sps, rng, t0=t0, fn0=fn0, k_start=ks[i],
+                                           k_stop=ks[i + 1] if i + 1 < len(ks) else None, tn=tn, p=p, kc=kc,
+                                           cipher_from=None if cipher_after is None else ks[0] + cipher_after,
+                                           esn0_db=esn0_db, cfo_hz=cfo_hz)
+        tch += part
+    return bcch, tch, sent, [(k, tn, p) for k, (_, tn, p) in zip(ks, imm_ass)]
+
+
 def wideband_capture(pkg, seed, seconds=2.5, samp_rate=2.0e6, carriers=((3, {}), (17, {}), (60, {})), sps=4):
     """A wideband capture (wideband container): each (channel, kwargs) is a BCCH
     carrier sent with root-raised-cosine pulses on ARFCN raster position `channel` (k x 31.25 kHz from the
