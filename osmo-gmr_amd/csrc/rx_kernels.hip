@@ -591,12 +591,13 @@ struct Rx4Cfg {
 	static constexpr int NPL = 16, SPS = 4;            // window samples per lane / 64; samples per symbol (0: a.sps at run time)
 	static constexpr bool LAT = false, GEN = false, FAC = false, ACC = false, EN = true, PL = false;
 	static constexpr int EBROW = 432, PART = 0;
+	static constexpr bool EARLY = false;               // the batch kernel asks early for what its bursts need (Rx4Switches)
 };
 // the fused batch kernel (k_rx4; k_one_server runs the same body on one burst)
-template <int NPL_, int SPS_, bool ACC_, bool EN_, bool PL_ = false>
+template <int NPL_, int SPS_, bool ACC_, bool EN_, bool PL_ = false, bool EARLY_ = false>
 struct CfgBatch : Rx4Cfg {
 	static constexpr int NPL = NPL_, SPS = SPS_;
-	static constexpr bool ACC = ACC_, EN = EN_, PL = PL_;
+	static constexpr bool ACC = ACC_, EN = EN_, PL = PL_, EARLY = EARLY_;
 };
 // demodulation only (k_rx4g): generic, small (NPL 8) and two-sequence (FAC) forms
 template <int NPL_, int SPS_, bool FAC_>
@@ -615,6 +616,13 @@ struct CfgLoop : Rx4Cfg {
 	static constexpr int NPL = NPL_, SPS = SPS_, PART = PART_;
 	static constexpr bool LAT = true, ACC = ACC_;
 };
+
+// experiment on the headline instantiation (build.py --variant): GMR1_EXP_RX4_TOUCH 1 / 2 -- a wave touches its next burst's
+// window (window_touch_q) right behind this burst's requests / behind its statistics.  Measured: 4 % and 3 % SLOWER than
+// without (profiles/r07a_ab_rx4_waits.txt), so the product is built without (0).
+#ifndef GMR1_EXP_RX4_TOUCH
+#define GMR1_EXP_RX4_TOUCH 0
+#endif
 
 // what follows from a configuration P
 template <class P>
@@ -646,6 +654,12 @@ struct Rx4Switches : P {
 	static constexpr bool QL = !P::GEN && !P::LAT && !P::EN && P::SPS == 4 && P::NPL == 16;
 	static constexpr bool QX = QL && !P::PL;
 	static_assert(!P::PL || QL, "the planar layout exists for the fused batch kernel");
+	// EARLY (the batch kernel, interleaved samples): what a wave's bursts need from memory before their windows can be asked
+	// for is asked for once, ahead of the first window (AHEAD); the rows behind pass 1 take their burst's kind / offset /
+	// frequency shift from those scalars (H_ROW); and a window's ragged last quarter no longer holds its loads back (ONE_LOAD)
+	static constexpr bool AHEAD = P::EARLY && QX;
+	static constexpr int TOUCH = AHEAD ? GMR1_EXP_RX4_TOUCH : 0;
+	static constexpr bool H_ROW = AHEAD, ONE_LOAD = AHEAD;
 };
 
 template <class Cfg>
@@ -657,6 +671,8 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 	constexpr bool LAT = C::LAT, GEN = C::GEN, FAC = C::FAC, ACC = C::ACC, EN = C::EN, PL = C::PL;
 	constexpr bool SMALL = C::SMALL, QL = C::QL, QX = C::QX, PREFETCH_NEXT = C::PREFETCH_NEXT, UB_OVER = C::UB_OVER;
 	constexpr int NSYM = C::NSYM, NCHK = C::NCHK, NSH = C::NSH;
+	constexpr int TOUCH = C::TOUCH;
+	constexpr bool AHEAD = C::AHEAD, H_ROW = C::H_ROW;
 	const int row = lane >> 4, col = lane & 15;
 	const int sps = SPS ? SPS : a.sps;
 	const int cwh = FAC ? cw / 2 : cw;                // lags per correlation array
@@ -692,6 +708,32 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 	auto op_off = [&](int g) -> uint64_t {
 		if constexpr (LAT && PART != 0) return pre->b_off; else return io.offset[g];
 	};
+	// AHEAD: the four bursts' kind, offset and frequency shift, asked for together before the first window (one trip to
+	// the L2 a wave instead of three in a row a burst) and kept in scalars; a burst the wave does not have shadows its first
+	int kind_s[4] = {0, 0, 0, 0};
+	uint64_t off_s[4] = {0, 0, 0, 0};
+	float fsh_s[4] = {0.f, 0.f, 0.f, 0.f};
+	if constexpr (AHEAD) {
+		if (g0 < n_end) {
+			int kv[4];
+			uint64_t ov[4];
+			float fv[4];
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				const int gq = g0 + q < n_end ? g0 + q : g0;
+				kv[q] = op_kind(gq);
+				ov[q] = op_off(gq);
+				fv[q] = op_fsh(gq);
+			}
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				kind_s[q] = __builtin_amdgcn_readfirstlane(kv[q]);
+				off_s[q] = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ov[q]) |
+				           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ov[q] >> 32)) << 32);
+				fsh_s[q] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fv[q])));
+			}
+		}
+	}
 	float2 wv_own[NPL];
 	bool co_on = false;                                // (LAT, PART 1) the helper wave shares this burst's front (LatPre (4))
 	int co_p = 0;
@@ -848,16 +890,32 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 			asm volatile("" : "+v"(lane_l));
 		const int lane = lane_l;
 		const int row = lane >> 4, col = lane & 15;
-		const int kind = GEN ? 0 : __builtin_amdgcn_readfirstlane(op_kind(g));
+		const bool has_nx = TOUCH != 0 && window_touch_wanted(q, g, n_end);
+		int kind_l;
+		if constexpr (AHEAD)
+			kind_l = kind_s[q];
+		else
+			kind_l = GEN ? 0 : __builtin_amdgcn_readfirstlane(op_kind(g));
+		const int kind = kind_l;
 		const int type = GEN ? a.fixed_type : (kind ? GMR1_HIP_DC6 : GMR1_HIP_BCCH);
 		const int in_len = __builtin_amdgcn_readfirstlane(a.in_len[kind]);
 		const DevBurst &bt = c_types[type];
 		typedef Fmt<GEN> F;
 		const int w = in_len - F::len(bt) * sps + 1;
-		const float fsh = op_fsh(g);
+		float fsh_l;
+		if constexpr (AHEAD)
+			fsh_l = fsh_s[q];
+		else
+			fsh_l = op_fsh(g);
+		const float fsh = fsh_l;
 		const float fs = (fsh - F::rotation(bt)) / (float)sps;
 
-		const float2 *__restrict__ in = a.iq + op_off(g);
+		const float2 *__restrict__ in = a.iq + (AHEAD ? off_s[q] : op_off(g));
+		Touched touched = {0, 0};
+		auto touch_next = [&]() {
+			if (has_nx)
+				touched = window_touch_q(a.iq + off_s[(q + 1) & 3], __builtin_amdgcn_readfirstlane(a.in_len[kind_s[(q + 1) & 3]]), lane);
+		};
 		const int sl = lane;
 		const int tl = F::tl(bt, kind);
 		const int nch = F::nch(bt);
@@ -900,7 +958,7 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 				window_fetch_q_planar(a.iq, a.plane_stride, io.offset[g], in_len, lane, wv);
 			} else {
 			if constexpr (QL)
-				window_fetch_q(in, in_len, lane, wv);
+				window_fetch_q<C::ONE_LOAD>(in, in_len, lane, wv);
 			else if (q == 0 || !PREFETCH_NEXT)
 				window_fetch<NPL, NFULL>(in, in_len, lane, wv);
 #pragma unroll
@@ -913,6 +971,11 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 					sv[c][h] = sidx < wl ? src[sidx] : make_float2(0.f, 0.f);
 				}
 			}
+			// (the youngest load: the wait for this burst's data leaves it in flight)
+			if constexpr (TOUCH == 1)
+				touch_next();
+			if constexpr (C::ONE_LOAD)
+				window_fix_q(in_len, lane, wv);
 			}
 		}
 		// rotated reference of the (single) sync sequence: without a caller-supplied frequency shift it only depends on
@@ -974,6 +1037,8 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 		}
 		GMR1_STAMP(1);
 		if (row == q) { avr_r = avr; avi_r = avi; inv_r = inv; }
+		if constexpr (TOUCH == 2)
+			touch_next();
 		if (PREFETCH_NEXT && !LAT && q + 1 < 4 && g + 1 < n_end) {
 			// the next burst's window travels during this burst's correlation
 			const int kind1 = GEN ? 0 : __builtin_amdgcn_readfirstlane(io.kind[g + 1] ? 1 : 0);
@@ -1026,6 +1091,9 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 				wb += wl;
 			}
 		}
+		// (TOUCH 1: the touch was asked for right behind the samples staged above, so it is here by now)
+		if constexpr (TOUCH == 1)
+			window_touch_done(touched);
 		WSYNC();
 		float *corr = L.corr + q * cw;
 		if constexpr (!GEN) {
@@ -1146,6 +1214,8 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 			}
 			corr[j] = cj;
 		}
+		if constexpr (TOUCH == 2)
+			window_touch_done(touched);
 	}
 	}
 	WSYNC();
@@ -1153,16 +1223,44 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 	if (a.dbg_stop == 2) return;
 	}
 
+
 	// per-row (lane-resident) burst parameters: looked up here, not before pass 1, which has no register to spare for them
-	const int kind_r = (!GEN && row_live) ? op_kind(g_row) : 0;
+	// (H_ROW: out of the scalars pass 1 read them into -- no trip to memory)
+	int kind_row = 0;
+	uint64_t off_row = 0;
+	float fsh_row = 0.f;
+	if constexpr (H_ROW) {
+		// (the row number is made opaque here, so that the selects below are not formed burst by burst inside pass 1)
+		int row_o = row;
+		asm volatile("" : "+v"(row_o));
+		kind_row = row_o == 0 ? kind_s[0] : (row_o == 1 ? kind_s[1] : (row_o == 2 ? kind_s[2] : kind_s[3]));
+		off_row = row_o == 0 ? off_s[0] : (row_o == 1 ? off_s[1] : (row_o == 2 ? off_s[2] : off_s[3]));
+		fsh_row = row_o == 0 ? fsh_s[0] : (row_o == 1 ? fsh_s[1] : (row_o == 2 ? fsh_s[2] : fsh_s[3]));
+		if (!row_live) {
+			kind_row = 0;
+			off_row = 0;
+			fsh_row = 0.f;
+		}
+	}
+	int kind_r_l;
+	if constexpr (H_ROW)
+		kind_r_l = kind_row;
+	else
+		kind_r_l = (!GEN && row_live) ? op_kind(g_row) : 0;
+	const int kind_r = kind_r_l;
 	const int type_r = GEN ? a.fixed_type : (kind_r ? GMR1_HIP_DC6 : GMR1_HIP_BCCH);
 	typedef Fmt<GEN> F;
 	const int in_len_r = kind_r ? a.in_len[1] : a.in_len[0];
-	const float fsh_r = row_live ? op_fsh(g_row) : 0.0f;
+	float fsh_r_l;
+	if constexpr (H_ROW)
+		fsh_r_l = fsh_row;
+	else
+		fsh_r_l = row_live ? op_fsh(g_row) : 0.0f;
+	const float fsh_r = fsh_r_l;
 	const DevBurst &bt_r = c_types[type_r];
 	const float fs_r = (fsh_r - F::rotation(bt_r)) / (float)sps;     // pi4cxpsk.c:539
 	const int w_r = in_len_r - F::len(bt_r) * sps + 1;
-	const float2 *__restrict__ in_r = a.iq + (row_live ? op_off(g_row) : 0);
+	const float2 *__restrict__ in_r = a.iq + (H_ROW ? off_row : (row_live ? op_off(g_row) : 0));
 
 	// =========================== rows: peak + early/late timing ===========================
 	// osmo_cxvec_peak_energy_find(corr, 3, PEAK_EARLY_LATE, &peak), pi4cxpsk.c:240
@@ -1730,6 +1828,7 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 		reinterpret_cast<uint4 *>(lutw)[lane + 64] = lut_b;
 		WSYNC();
 	}
+
 	int row_ok = 0, row_chain = 0;
 	Sym4 nxt1, nxt2;
 	if constexpr (!QX) { nxt1 = first; nxt2 = second; }
@@ -1948,7 +2047,7 @@ void k_rx4(RxArgs a, int stage_samples, int cw, int bpw)
 #endif
 	                 a.offset, a.kind, a.freq_shift, a.l2, a.crc, a.conv, a.rv, a.sync_id, a.toa, a.freq_err, a.energy,
 	                 a.ebits, a.ssyms};
-	rx4_body<CfgBatch<NPL, SPS, ACC, EN, PL>>(a, io, stage_samples, cw, g0, n_end, lds_raw, (int)threadIdx.x);
+	rx4_body<CfgBatch<NPL, SPS, ACC, EN, PL, true>>(a, io, stage_samples, cw, g0, n_end, lds_raw, (int)threadIdx.x);
 }
 
 // demodulation only, one burst format per launch, four bursts per wavefront (rx4_body<..., GEN>)

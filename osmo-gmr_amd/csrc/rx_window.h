@@ -2,6 +2,7 @@
 // statistics, burst energy.
 #pragma once
 #include "conv_k5_12.h"
+#include "rx_touch.h"
 
 namespace gmr1 {
 
@@ -209,6 +210,14 @@ __device__ __forceinline__ void load_stats(const float2 *__restrict__ in, int in
 // load, and the per-lane partial sums below are formed over the same samples in the same order, so the planar call's
 // statistics equal the interleaved call's bit for bit.
 typedef float v4f_a8 __attribute__((ext_vector_type(4), aligned(8)));
+// ONE: every register pair of the ragged last quarter is the destination of ONE load.  With the two alternative loads of the
+// plain form (sixteen bytes where both samples lie inside the window, eight where only the first does) the second is held
+// back until the first has arrived -- the same registers -- and with it everything asked for behind it: a burst's window
+// came in three round trips in a row instead of one.  A lane whose second sample lies outside takes its sixteen bytes one
+// sample EARLIER (inside the window: the last quarter starts at sample 768) and keeps the upper half: the same values.
+// That lane's registers are put right by window_fix_q, which the caller runs once everything else has been asked for (a
+// select on the spot would wait for the load on the spot).
+template <bool ONE = false>
 __device__ __forceinline__ void window_fetch_q(const float2 *__restrict__ in, int in_len, int lane, float2 (&v)[16])
 {
 	const v4f_a8 *__restrict__ p = reinterpret_cast<const v4f_a8 *>(in + 4 * lane);
@@ -218,6 +227,14 @@ __device__ __forceinline__ void window_fetch_q(const float2 *__restrict__ in, in
 #pragma unroll
 		for (int h = 0; h < 2; h++) {
 			float2 lo = make_float2(0.f, 0.f), hi = make_float2(0.f, 0.f);
+			if (ONE && b == 3) {
+				const bool full = s0 + 2 * h + 1 < in_len, part = !full && s0 + 2 * h < in_len;
+				if (full || part) {
+					const v4f_a8 u = *reinterpret_cast<const v4f_a8 *>(in + s0 + 2 * h - (part ? 1 : 0));
+					lo = make_float2(u.x, u.y);
+					hi = make_float2(u.z, u.w);
+				}
+			} else
 			if (b < 3 || s0 + 2 * h + 1 < in_len) {        // (in_len >= 960: the first three quarters are whole)
 				const v4f_a8 u = p[128 * b + h];
 				lo = make_float2(u.x, u.y);
@@ -229,6 +246,42 @@ __device__ __forceinline__ void window_fetch_q(const float2 *__restrict__ in, in
 			v[4 * b + 2 * h + 1] = hi;
 		}
 	}
+}
+
+__device__ __forceinline__ void window_fix_q(int in_len, int lane, float2 (&v)[16])
+{
+	const int s0 = 256 * 3 + 4 * lane;
+#pragma unroll
+	for (int h = 0; h < 2; h++) {
+		const bool part = s0 + 2 * h + 1 >= in_len && s0 + 2 * h < in_len;
+		v[12 + 2 * h] = part ? v[12 + 2 * h + 1] : v[12 + 2 * h];
+		v[12 + 2 * h + 1] = part ? make_float2(0.f, 0.f) : v[12 + 2 * h + 1];
+	}
+}
+
+// The wave's look-ahead as lines in the XCD's L2: every 128-byte line the NEXT burst's window overlaps is asked for with one
+// dword load a lane (a second window in registers costs the sixth wave, see Rx4Switches::PREFETCH_NEXT).  The addresses
+// are window_touch_offset's (rx_touch.h), all inside the window's own bytes.  Plain loads: a volatile one is a flat load
+// at system scope with a full wait right behind it.  What keeps them alive is the caller handing the returned word to
+// window_touch_done() -- an empty asm that names the register -- at a point where waiting costs nothing; the wait counts
+// stay the compiler's own.
+struct Touched { uint32_t a, b; };
+__device__ __forceinline__ Touched window_touch_q(const float2 *__restrict__ next, int in_len, int lane)
+{
+	const char *base = reinterpret_cast<const char *>(next);
+	const unsigned mis = (unsigned)(reinterpret_cast<uintptr_t>(next) & (uintptr_t)(kTouchLine - 1));
+	const int o = window_touch_offset(mis, in_len, lane);
+	Touched t = {0, 0};                                         // (two words, never combined: combining them would wait for both)
+	if (o >= 0)
+		t.a = *reinterpret_cast<const uint32_t *>(base + o);
+	const int o64 = window_touch_offset(mis, in_len, 64);       // (wave-uniform: the 65th line of a window that starts inside a line)
+	if (o64 >= 0 && lane == 0)
+		t.b = *reinterpret_cast<const uint32_t *>(base + o64);
+	return t;
+}
+__device__ __forceinline__ void window_touch_done(const Touched &t)
+{
+	asm volatile("" : : "v"(t.a), "v"(t.b));
 }
 
 // the same assignment out of a polyphase-planar array: `pl` = the array, o = the window's first sample (flat count)
