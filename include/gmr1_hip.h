@@ -517,7 +517,8 @@ int gmr1_hip_rx_run(int n_arfcn, int sps, const float *iq, uint64_t iq_len,
  *    one is refused (-EINVAL).
  *  - A chain whose walk outgrows the loop's buffers stops for good and its carrier's status becomes -EIO, as in
  *    gmr1_hip_rx_run; the carrier's other chains go on.
- *  - TCH3 / TCH9 follow-ups are not performed.  Without a GPU every entry point returns -ENODEV. */
+ *  - A handle made by _create follows no traffic channel; one made by _create_tch (below) follows TCH3 calls.  TCH9
+ *    follow-ups are not performed by either.  Without a GPU every entry point returns -ENODEV. */
 struct gmr1_hip_rx_stream;
 int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struct gmr1_hip_rx_stream **h);
 int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_records);
@@ -528,6 +529,32 @@ int gmr1_hip_rx_stream_push(struct gmr1_hip_rx_stream *h, const float *iq, uint6
 int gmr1_hip_rx_stream_status(const struct gmr1_hip_rx_stream *h, int32_t *status, int32_t *n_chains,
                               uint64_t *retained);
 int gmr1_hip_rx_stream_destroy(struct gmr1_hip_rx_stream *h);
+
+/* The streaming loop with the TCH3 follow-up: gmr1_hip_rx_run_tch over a capture pushed piece by piece.  kc = n_arfcn x 8
+ * key bytes (NULL: the all-zero key).  `tch` has the layout, stride and timing of `iq`: carrier i's traffic samples of a
+ * push are tch[2*(i*iq_stride + k)], k < n (a channelizer-stream push with twice the channels feeds both).
+ *  - A handle made by _create_tch takes only _push_tch*, one made by _create only _push*: the wrong pairing is refused
+ *    (-EINVAL) and leaves the handle as it was, as does tch == NULL with n > 0.  _max_records, _status and _destroy serve
+ *    both kinds; for a tch handle _max_records adds one record per frame a chain's walk can log (a frame gives at most
+ *    one TCH3 record).
+ *  - The records of any sequence of pushes ending with `last`, stable-sorted by (carrier, chain), are byte-identical to
+ *    one gmr1_hip_rx_run_tch call on the whole capture with the same kc: every field, conv included, in both Viterbi
+ *    decoder modes, for any push sizes (0 included).  Within a push they come by carrier, chain, frame; a frame's BCCH /
+ *    CCCH records before its TCH3 record.  An IMMEDIATE ASSIGNMENT is followed from its own frame on, so the call's
+ *    records start in the push that returns the assignment.
+ *  - The traffic samples are retained exactly as the BCCH carrier's are (_status's `retained` holds for both); every
+ *    chain's struct gmr1_hip_tch3_state stays in device memory between pushes.
+ *  - `out` is host memory.  Everything else is as for gmr1_hip_rx_stream_push*.
+ *  - -EIO (the handle takes no further pushes) also when a frame the walk admitted does not hold its traffic window: an
+ *    SI1 that moves a chain's timeslot label down by more than 13 slots inside the newest frame of a push that is not
+ *    the last.  gmr1_hip_rx_run_tch has no such limit. */
+int gmr1_hip_rx_stream_create_tch(int n_arfcn, int sps, const uint16_t *arfcn,
+                                  const uint8_t *kc /* n_arfcn x 8, or NULL */, struct gmr1_hip_rx_stream **h);
+int gmr1_hip_rx_stream_push_tch_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch,
+                                    uint64_t iq_stride, uint64_t n, int last, struct gmr1_hip_rx_record *out,
+                                    int max_records, int *n_records);
+int gmr1_hip_rx_stream_push_tch(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride,
+                                uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records);
 
 /* The same with the TCH3 follow-up (gmr1_rx's optional tch.cfile and key arguments, gmr1_rx.c:355-600,
  * 897-975): tch holds, for every carrier, the traffic carrier an IMMEDIATE ASSIGNMENT on its CCCH points
@@ -606,6 +633,12 @@ struct gmr1_hip_tch3_frame {        /* one per frame handed in, in the order han
  * energies from ref_energy (gmr1_rx takes burst_energy of the CCCH burst that carried the assignment), weak_cnt, sync_id,
  * clears ebits -- and, like the reference, leaves ciph, burst_cnt, bi_fn (and kc) as they are.  -EINVAL: s is NULL. */
 int gmr1_hip_tch3_state_assign(struct gmr1_hip_tch3_state *s, int p, float ref_energy);
+/* The same on states in device memory, between two invocations of gmr1_hip_tch3_follow_batch_dev, so that a call's state
+ * never visits the host: for j < n what gmr1_hip_tch3_state_assign(&state[call[j]], p[j], ref_energy[j]) does, in the order
+ * of j (a call named twice gets both; call[j] < 0 is skipped).  call, p, ref_energy and state are device memory; the entry
+ * enqueues on `stream` and returns.  -EINVAL: n < 0 or a NULL array; -ENODEV without a device. */
+int gmr1_hip_tch3_state_assign_batch_dev(void *stream, int n, const int32_t *call, const int32_t *p,
+                                         const float *ref_energy, struct gmr1_hip_tch3_state *state);
 
 int gmr1_hip_tch3_follow_batch_dev(void *stream, int n_calls, int sps, int in_len, const float *iq,
                                    const int32_t *first /* n_calls + 1 */, int n_frames,

@@ -114,10 +114,14 @@ SIGNATURES = {
     "gmr1_hip_rx_stream_push": (I, P, P, U64, U64, I, P, I, P),
     "gmr1_hip_rx_stream_status": (I, P, P, P, P),
     "gmr1_hip_rx_stream_destroy": (I, P),
+    "gmr1_hip_rx_stream_create_tch": (I, I, I, P, P, P),
+    "gmr1_hip_rx_stream_push_tch_dev": (I, P, P, P, P, U64, U64, I, P, I, P),
+    "gmr1_hip_rx_stream_push_tch": (I, P, P, P, U64, U64, I, P, I, P),
     "gmr1_hip_rx_run_tch_dev": (I, P, I, I, P, P, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_tch": (I, I, I, P, P, U64, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_last_timing": (I, P),
     "gmr1_hip_tch3_state_assign": (I, P, I, F),
+    "gmr1_hip_tch3_state_assign_batch_dev": (I, P, I, P, P, P, P),
     "gmr1_hip_tch3_follow_batch_dev": (I, P, I, I, I, P, P, I, P, P, P, P, P),
     "gmr1_hip_tch3_follow_batch": (I, I, I, I, P, U64, P, I, P, P, P, P, P),
     "gmr1_hip_rx_run_full_dev": (I, P, I, I, P, P, P, P, P, P, P, P, I, P, P, I, P, P, P),
@@ -660,6 +664,12 @@ def tch3_state_assign(state, p, ref_energy, index=0):
     return state
 
 
+def tch3_state_assign_batch_dev(stream, n, call, p, ref_energy, state):
+    """rx_tch3_init on device-resident states (addresses): entry j < n assigns state[call[j]] with p[j], ref_energy[j], in
+    the order of j; enqueues on `stream` and returns."""
+    _call("gmr1_hip_tch3_state_assign_batch_dev", stream, n, call, p, ref_energy, state)
+
+
 def tch3_follow(iq, first, offset, freq_shift, fn, state, sps=4, in_len=None):
     """rx_tch3 over the frames of len(first) - 1 calls: call c owns frames first[c] .. first[c+1], frame k's window is
     iq[offset[k] : offset[k] + in_len].  -> (TCH3_FRAME record per frame, the calls' TCH3_STATE after them); `state` itself
@@ -1035,6 +1045,15 @@ def rx_run_tch(iq, tch, offset, length, sps=4, arfcn=None, kc=None, max_records=
     return out[:min(n_rec.value, cap)].copy(), status, chains, n_rec.value
 
 
+def rx_run_tch_dev(stream, iq_ptr, tch_ptr, offset, length, sps=4, arfcn=None, kc=None, max_records=1 << 16):
+    """gmr1_hip_rx_run_tch_dev: rx_run_tch with both captures already in HBM (device addresses, same layout)."""
+    out, cap = _records(None, max_records)
+    run, n_rec, status, chains = _rx_loop("gmr1_hip_rx_run_tch_dev", (stream, len(offset), sps, iq_ptr, tch_ptr), offset,
+                                          length, arfcn, _p(out), cap, kc=kc)
+    _check(run(), "gmr1_hip_rx_run_tch_dev")
+    return out[:min(n_rec.value, cap)].copy(), status, chains, n_rec.value
+
+
 # ---------------------------------------------------------------------------
 # wideband -> per-ARFCN channelizer (reference utils/gmr1_rx_sdr.py:391-602)
 # ---------------------------------------------------------------------------
@@ -1159,14 +1178,22 @@ class ChanStream(_LibHandle):
 class RxStream(_LibHandle):
     """gmr1_hip_rx_stream_*: the receive loop (rx_run) over a capture pushed piece by piece.  Each push returns the records
     that became final in it; all pushes' records up to the `last` one, stable-sorted by (carrier, chain), are identical to
-    one rx_run() call on the whole capture."""
+    one rx_run() call on the whole capture.  tch=True: the loop also follows TCH3 calls (rx_run_tch with the same kc) --
+    every push then takes the traffic carriers' samples as well."""
     _destroy_fn = "gmr1_hip_rx_stream_destroy"
 
-    def __init__(self, n_arfcn, sps=4, arfcn=None):
+    def __init__(self, n_arfcn, sps=4, arfcn=None, tch=False, kc=None):
         self._h = C.c_void_p()
         self.n = int(n_arfcn)
+        self.tch = bool(tch)
         self._arfcn = _arr(arfcn, np.uint16)
-        _call("gmr1_hip_rx_stream_create", self.n, sps, _p(self._arfcn), C.byref(self._h))
+        if self.tch:
+            kc = _arr(kc, np.uint8, (self.n, 8))
+            _call("gmr1_hip_rx_stream_create_tch", self.n, sps, _p(self._arfcn), _p(kc), C.byref(self._h))
+        else:
+            if kc is not None:
+                raise ValueError("kc belongs to a handle that follows TCH3 calls (tch=True)")
+            _call("gmr1_hip_rx_stream_create", self.n, sps, _p(self._arfcn), C.byref(self._h))
 
     def max_records(self, n):
         """the most records the next push of n samples per carrier can return"""
@@ -1177,27 +1204,46 @@ class RxStream(_LibHandle):
     def _out(self, n, out):
         return _records(out, self.max_records(n))[0]
 
-    def push(self, iq, last=False, out=None):
-        """host (n_arfcn, n) complex64 -> the records that became final (RX_RECORD[])"""
+    def _kind(self, tch):
+        if self.tch and tch is None:
+            raise ValueError("a handle that follows TCH3 calls takes the traffic carriers' samples with every push (tch=)")
+        if not self.tch and tch is not None:
+            raise ValueError("tch= belongs to a handle made with tch=True")
+
+    def push(self, iq, last=False, out=None, tch=None):
+        """host (n_arfcn, n) complex64 (and, on a tch handle, tch of the same shape) -> the records that became final
+        (RX_RECORD[])"""
+        self._kind(tch)
         iq = _arr(iq, np.complex64, (self.n, -1))
         n = iq.shape[1]
         out = self._out(n, out)
         got = C.c_int()
-        _call("gmr1_hip_rx_stream_push", self._h, _p(iq), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
+        if self.tch:
+            tch = _arr(tch, np.complex64, (self.n, n))
+            _call("gmr1_hip_rx_stream_push_tch", self._h, _p(iq), _p(tch), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
+        else:
+            _call("gmr1_hip_rx_stream_push", self._h, _p(iq), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
         return out[:got.value]
 
-    def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None):
-        """device samples (carrier i at iq_ptr + 8 * i * iq_stride), read on `stream` -> the records (synchronous).
+    def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None, tch_ptr=None):
+        """device samples (carrier i at iq_ptr + 8 * i * iq_stride; on a tch handle its traffic samples at tch_ptr + 8 * i *
+        iq_stride), read on `stream` -> the records (synchronous).
         out: a host RX_RECORD array, or None; out_ptr (device / pinned) goes through push_dev_raw."""
         out = self._out(n, out)
-        got = self.push_dev_raw(stream, iq_ptr, iq_stride, n, last, out.ctypes.data, out.size)
+        got = self.push_dev_raw(stream, iq_ptr, iq_stride, n, last, out.ctypes.data, out.size, tch_ptr)
         return out[:got]
 
-    def push_dev_raw(self, stream, iq_ptr, iq_stride, n, last, out_ptr, max_records):
-        """gmr1_hip_rx_stream_push_dev with a caller's record buffer (any memory rx_run_dev takes) -> records written"""
+    def push_dev_raw(self, stream, iq_ptr, iq_stride, n, last, out_ptr, max_records, tch_ptr=None):
+        """gmr1_hip_rx_stream_push_dev with a caller's record buffer (any memory rx_run_dev takes) -> records written; on a
+        tch handle gmr1_hip_rx_stream_push_tch_dev, whose record buffer is host memory"""
+        self._kind(tch_ptr)
         got = C.c_int()
-        _call("gmr1_hip_rx_stream_push_dev", stream, self._h, iq_ptr, iq_stride, n, 1 if last else 0, out_ptr,
-              max_records, C.byref(got))
+        if self.tch:
+            _call("gmr1_hip_rx_stream_push_tch_dev", stream, self._h, iq_ptr, tch_ptr, iq_stride, n, 1 if last else 0, out_ptr,
+                  max_records, C.byref(got))
+        else:
+            _call("gmr1_hip_rx_stream_push_dev", stream, self._h, iq_ptr, iq_stride, n, 1 if last else 0, out_ptr,
+                  max_records, C.byref(got))
         return got.value
 
     def status(self):

@@ -17,7 +17,8 @@
 //
 // The traffic channels never feed back into that loop, so their follow-ups run after it as batched
 // passes of their own: RxRun::tch3_pass hands every chain with an IMMEDIATE ASSIGNMENT to the batched call follower
-// (capi_tch3_follow.cpp), whose state machine runs on the device, one invocation per assignment a chain sees;
+// (capi_tch3_follow.cpp), whose state machine runs on the device, one invocation per assignment a chain sees
+// (tch3_follow_chains, which a push of the streaming loop runs over its own frames too);
 // RxRun::tch9_pass demodulates, classifies on the host and decodes.  GSMTAP transport and per-burst stderr
 // logging are out of scope; what GSMTAP would have carried comes back as records.
 
@@ -79,11 +80,6 @@ void emit(RxChain &c, uint16_t arfcn, int type, int fn, int tn, const uint8_t *l
 	c.rec.push_back(r);
 	c.rec_frame.push_back(frame);
 }
-
-struct TchItem {          // one frame of a chain in which rx_tch3 maps a burst
-	int chain_idx, frame;
-	int tn, ev;           // the assignment it belongs to: its timeslot, its index in the chain's events
-};
 
 size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
 
@@ -340,6 +336,8 @@ int RxRun::frame_loop()
 		direct_total = n_total;
 	} else {
 		HIP_TRY(hipMemcpyAsync(h, d, total, hipMemcpyDeviceToHost, st));
+		if (loop_state)
+			HIP_TRY(hipMemcpyAsync(h + o_st, loop_state, (size_t)nc * sizeof(RxLoopState), hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
 	}
 	t_loop_gpu_us = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_start).count() / 1e3;
@@ -386,57 +384,81 @@ int RxRun::frame_loop()
 	return 0;
 }
 
-int RxRun::tch3_pass()
+// What a chain's TCH3 follow-up carries from one run of tch3_follow_chains to the next: a push of the streaming loop
+// continues the call the pushes before it found (the one-shot pass starts from nothing)
+struct TchCarry {
+	int tn = 0;               // the timeslot of the last assignment
+	bool assigned = false;    // there was one
+};
+
+// ---- TCH3 follow-up (rx_tch3, gmr1_rx.c:355-600) ----------------------------------------------
+// Nothing the traffic channel does feeds back into the BCCH / CCCH loop, so it runs afterwards, for all chains at once,
+// through the batched call follower (tch3_follow_enqueue, capi_tch3_follow.cpp -- what gmr1_hip_tch3_follow_batch_dev
+// runs): chain calls[q] is call q, its state is slot q of a device array.  This function knows which frames of which
+// chain belong to which assignment, which window each reads and where the records go -- for the one-shot pass (the whole
+// capture's log; the states start from h_state0 and die with the call) and for a push of the streaming loop (this push's
+// log; the states are the handle's d_state, the timeslots the handle's `carry`); the per-frame work, the state machine,
+// the decodes and the ciphering state are the follower's, on the device.  rx_tch3_init runs between two invocations
+// (k_tch3f_assign, on the states where they lie), so invocation g takes, of every call, the frames from its g-th
+// assignment of this log up to the next one, and invocation 0 the frames before the first, which belong to the call
+// carried in: a chain that is assigned once -- the usual case -- costs one invocation and one synchronisation.
+// horizon: the log was walked against samples that more will follow (a push that is not the last): every logged frame
+// was admitted by align + 2 * frame_len <= len, which its TCH3 window fits, so a window that does not
+// is an error (-EIO) instead of a frame dropped that the one-shot call reads.
+int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t *arfcn, bool want9, bool horizon,
+                       std::vector<RxChain> &chains, const std::vector<int> &calls, const gmr1_hip_tch3_state *h_state0,
+                       gmr1_hip_tch3_state *d_state, TchCarry *carry)
 {
-	// ---- TCH3 follow-up (rx_tch3, gmr1_rx.c:355-600) ----------------------------------------------
-	// Nothing the traffic channel does feeds back into the BCCH / CCCH loop, so it runs afterwards, for all chains at
-	// once, through the batched call follower (tch3_follow_enqueue, capi_tch3_follow.cpp -- what
-	// gmr1_hip_tch3_follow_batch_dev runs): every chain with an assignment is one call.  This pass knows which frames of
-	// which chain belong to which assignment and where the records go; the per-frame work, the state machine, the
-	// decodes and the ciphering state are the follower's, on the device.  rx_tch3_init runs on the host between two
-	// invocations, so invocation g takes, of every call, the frames from its assignment g up to the next one: a chain
-	// that is assigned once -- the usual case -- costs one invocation and one synchronisation.
-	if (!tch)
-		return 0;
+	struct TchItem {          // one frame of a call in which rx_tch3 maps a burst
+		int call, frame;
+		int tn, gen;          // the assignment it belongs to: its timeslot; 1 + its index in the log's events, 0: carried in
+	};
+	int r = 0;
 	std::vector<TchItem> titems;
-	std::vector<int> calls;                      // the chains with an assignment
-	std::vector<size_t> next;                    // per call: its first item no invocation has taken yet
-	const int twin = sps + (sps / 2);            // gmr1_rx.c:551
-	const int t_in_len = 117 * sps + twin;
-	const int t_etoa = twin >> 1;
-	size_t n_gen = 0;
-	for (size_t ci = 0; ci < chains.size(); ci++) {
-		RxChain &c = chains[ci];
-		if (c.events.empty())
+	const int n_calls = (int)calls.size();
+	std::vector<size_t> next((size_t)n_calls);   // per call: its first item no invocation has taken yet
+	std::vector<char> touched((size_t)n_calls, 0);
+	const int t_in_len = rx_tch3_in_len(sps);
+	size_t n_gen = 0;                            // invocations: one per assignment any call sees, and one before them
+	bool any_event = false;
+	for (int q = 0; q < n_calls; q++) {
+		const RxChain &c = chains[calls[q]];
+		next[q] = titems.size();
+		any_event |= !c.events.empty();
+		bool have = carry && carry[q].assigned;
+		int tn = have ? carry[q].tn : 0;
+		if (!have && c.events.empty())
 			continue;
-		calls.push_back((int)ci);
-		next.push_back(titems.size());
-		n_gen = std::max(n_gen, c.events.size());
+		n_gen = std::max(n_gen, c.events.size() + 1);
 		size_t ev = 0;
-		for (int f = c.events[0].frame; f < (int)c.log.size(); f++) {
-			while (ev + 1 < c.events.size() && c.events[ev + 1].frame <= f)
-				ev++;
-			const int tn = c.events[ev].tn;
-			const int64_t begin = (int64_t)c.log[f].align + sps * tn * 39 - t_etoa;
+		// IMM.ASS on the CCCH starts the follow-up in that very frame (gmr1_rx.c:235-246, 836-841)
+		for (int f = have ? 0 : c.events[0].frame; f < (int)c.log.size(); f++) {
+			while (ev < c.events.size() && c.events[ev].frame <= f)
+				tn = c.events[ev++].tn;
+			const long long begin = rx_tch3_begin(c.log[f].align, sps, tn);
+			if (begin + t_in_len > c.len && horizon)
+				return fail(-EIO, "tch3 follow-up: a frame the walk admitted does not hold its traffic window");
 			if (begin < 0 || begin + t_in_len > c.len)
 				continue;                         // burst_map fails: rx_tch3 returns before touching anything
-			titems.push_back({(int)ci, f, tn, (int)ev});
+			titems.push_back({q, f, tn, (int)ev});
 		}
 	}
-	const int nt = (int)titems.size(), n_calls = (int)calls.size();
-	if (!nt)
+	const int nt = (int)titems.size();
+	if (!nt && (h_state0 || !any_event))
 		return 0;
-	// the calls' states: no call, not ciphered, the carrier's key (ciphering outlives a re-assignment, gmr1_rx.c:358-376)
-	std::vector<gmr1_hip_tch3_state> state((size_t)n_calls);
-	std::memset(state.data(), 0, state.size() * sizeof(state[0]));
-	if (kc)
-		for (int q = 0; q < n_calls; q++)
-			std::memcpy(state[q].kc, kc + (size_t)chains[calls[q]].a * 8, 8);
-	// per frame 56 B staged here and the follower's scratch, six staged arrays; no invocation has more than nt frames
+	// the states if they start here, first[] and an assignment per call, per frame 56 B staged and the follower's scratch;
+	// no invocation has more than nt frames
 	Arena arena;
-	if ((r = arena.init((size_t)n_calls * sizeof(state[0]) + ((size_t)n_calls + 1) * 4 + (size_t)nt * 56 + 6 * 128 +
-	                    tch3_follow_scratch_bytes(nt)))) return r;
-	std::vector<int32_t> first((size_t)n_calls + 1);
+	if ((r = arena.init((h_state0 ? (size_t)n_calls * sizeof(gmr1_hip_tch3_state) + 128 : 0) + ((size_t)n_calls + 1) * 4 +
+	                    (size_t)n_calls * 12 + (size_t)nt * 56 + 10 * 128 + tch3_follow_scratch_bytes(nt)))) return r;
+	if (h_state0) {
+		Stage s0(st, &arena);
+		d_state = const_cast<gmr1_hip_tch3_state *>(s0.in(h_state0, (size_t)n_calls));
+		if ((r = s0.err())) return r;
+	}
+	const size_t arena_kept = arena.off;
+	std::vector<int32_t> first((size_t)n_calls + 1), a_call, a_p;
+	std::vector<float> a_en;
 	std::vector<int> item;                       // of each frame handed in
 	std::vector<uint64_t> t_off;
 	std::vector<float> t_fs;
@@ -444,40 +466,52 @@ int RxRun::tch3_pass()
 	std::vector<gmr1_hip_tch3_frame> got;
 	for (size_t g = 0; g < n_gen; g++) {
 		item.clear(); t_off.clear(); t_fs.clear(); t_fn.clear();
+		a_call.clear(); a_p.clear(); a_en.clear();
 		for (int q = 0; q < n_calls; q++) {
 			const RxChain &c = chains[calls[q]];
 			first[q] = (int32_t)item.size();
-			if (g >= c.events.size())
+			if (g > c.events.size())
 				continue;
 			// rx_tch3_init.  An assignment none of whose frames fits hands no frame in, and the next one's follows it on
 			// the same state: every assignment is applied, in the order the reference applies them
-			gmr1_hip_tch3_state_assign(&state[q], c.events[g].p, c.events[g].ref_energy);
-			for (size_t &k = next[q]; k < titems.size() && titems[k].chain_idx == calls[q] && titems[k].ev == (int)g; k++) {
+			if (g > 0) {
+				a_call.push_back(q);
+				a_p.push_back(c.events[g - 1].p);
+				a_en.push_back(c.events[g - 1].ref_energy);
+			}
+			for (size_t &k = next[q]; k < titems.size() && titems[k].call == q && titems[k].gen == (int)g; k++) {
 				const FrameCtx &x = c.log[titems[k].frame];
 				item.push_back((int)k);
-				t_off.push_back(c.base + (uint64_t)((int64_t)x.align + sps * titems[k].tn * 39 - t_etoa));
+				t_off.push_back(c.base + (uint64_t)rx_tch3_begin(x.align, sps, titems[k].tn));
 				t_fs.push_back(-x.freq_err);
 				t_fn.push_back((uint32_t)x.fn);
 			}
 		}
-		const int n = (int)item.size();
+		const int n = (int)item.size(), n_assign = (int)a_call.size();
 		first[n_calls] = n;
-		if (!n)
+		if (!n && !n_assign)
 			continue;
 		got.resize((size_t)n);
-		arena.off = 0;                            // the invocation before is through (fetch)
+		arena.off = arena_kept;                   // the invocation before is through (fetch)
 		Stage sg(st, &arena);
-		const int32_t *d_first = sg.in(first.data(), first.size());
-		const uint64_t *d_off = sg.in(t_off.data(), (size_t)n);
-		const float *d_fs = sg.in(t_fs.data(), (size_t)n);
-		const uint32_t *d_fn = sg.in(t_fn.data(), (size_t)n);
-		gmr1_hip_tch3_state *d_state = sg.inout(state.data(), state.size());
-		gmr1_hip_tch3_frame *d_got = sg.out(got.data(), (size_t)n);
-		unsigned char *scratch = sg.dev<unsigned char>(tch3_follow_scratch_bytes(n));
-		if ((r = sg.err())) return r;
-		r = tch3_follow_enqueue(st, scratch, n_calls, sps, t_in_len, tch, d_first, n, d_off, d_fs, d_fn, d_state, d_got);
-		if (r) return r;
-		if ((r = sg.fetch())) return r;
+		if (n_assign) {
+			const int32_t *d_call = sg.in(a_call.data(), (size_t)n_assign), *d_p = sg.in(a_p.data(), (size_t)n_assign);
+			const float *d_en = sg.in(a_en.data(), (size_t)n_assign);
+			if ((r = sg.err())) return r;
+			if ((r = gmr1_hip_tch3_state_assign_batch_dev(st, n_assign, d_call, d_p, d_en, d_state))) return r;
+		}
+		if (n) {
+			const int32_t *d_first = sg.in(first.data(), first.size());
+			const uint64_t *d_off = sg.in(t_off.data(), (size_t)n);
+			const float *d_fs = sg.in(t_fs.data(), (size_t)n);
+			const uint32_t *d_fn = sg.in(t_fn.data(), (size_t)n);
+			gmr1_hip_tch3_frame *d_got = sg.out(got.data(), (size_t)n);
+			unsigned char *scratch = sg.dev<unsigned char>(tch3_follow_scratch_bytes(n));
+			if ((r = sg.err())) return r;
+			r = tch3_follow_enqueue(st, scratch, n_calls, sps, t_in_len, tch, d_first, n, d_off, d_fs, d_fn, d_state, d_got);
+			if (r) return r;
+		}
+		if ((r = sg.fetch())) return r;           // (also ahead of the next invocation's staging: the vectors are reused)
 
 		// records, chain by chain in frame order
 		for (int k = 0; k < n; k++) {
@@ -485,19 +519,23 @@ int RxRun::tch3_pass()
 			if (!fr.type)
 				continue;
 			const TchItem &ti = titems[item[k]];
-			RxChain &c = chains[ti.chain_idx];
+			RxChain &c = chains[calls[ti.call]];
+			touched[ti.call] = 1;
 			emit(c, arfcn ? arfcn[c.a] : (uint16_t)c.a, fr.type, (int)fr.fn, ti.tn, fr.l2, fr.conv, ti.frame, fr.len);
 			// ASSIGNMENT COMMAND 1 on the FACCH3 starts the TCH9 follow-up (gmr1_rx.c:248-258, 436-442)
 			const uint8_t *m = fr.l2;
-			if (csd && fr.type == 0x12 /* GSMTAP_GMR1_TCH3 | GSMTAP_GMR1_FACCH */ && m[3] == 0x06 && m[4] == 0x2e)
+			if (want9 && fr.type == 0x12 /* GSMTAP_GMR1_TCH3 | GSMTAP_GMR1_FACCH */ && m[3] == 0x06 && m[4] == 0x2e)
 				c.events9.push_back({ti.frame, ((m[5] & 0x03) << 3) | (m[6] >> 5), 0, 0.f});
 		}
 	}
 
-	// frame order within each chain: BCCH / CCCH of a frame come before its TCH records
-	for (RxChain &c : chains) {
-		if (c.events.empty())
+	for (int q = 0; q < n_calls; q++) {
+		RxChain &c = chains[calls[q]];
+		if (carry && !c.events.empty())
+			carry[q] = {c.events.back().tn, true};
+		if (!touched[q])
 			continue;
+		// frame order within each chain: BCCH / CCCH of a frame come before its TCH records
 		std::vector<size_t> order(c.rec.size());
 		for (size_t i = 0; i < order.size(); i++) order[i] = i;
 		std::stable_sort(order.begin(), order.end(),
@@ -507,6 +545,26 @@ int RxRun::tch3_pass()
 		c.rec.swap(sorted);
 	}
 	return 0;
+}
+
+int RxRun::tch3_pass()
+{
+	// every chain with an IMMEDIATE ASSIGNMENT is one call of tch3_follow_chains
+	if (!tch)
+		return 0;
+	std::vector<int> calls;
+	for (size_t ci = 0; ci < chains.size(); ci++)
+		if (!chains[ci].events.empty())
+			calls.push_back((int)ci);
+	if (calls.empty())
+		return 0;
+	// the calls' states: no call, not ciphered, the carrier's key (ciphering outlives a re-assignment, gmr1_rx.c:358-376)
+	std::vector<gmr1_hip_tch3_state> state(calls.size());
+	std::memset(state.data(), 0, state.size() * sizeof(state[0]));
+	if (kc)
+		for (size_t q = 0; q < calls.size(); q++)
+			std::memcpy(state[q].kc, kc + (size_t)chains[calls[q]].a * 8, 8);
+	return r = tch3_follow_chains(st, sps, tch, arfcn, csd != nullptr, false, chains, calls, state.data(), nullptr, nullptr);
 }
 
 int RxRun::tch9_pass()
@@ -926,6 +984,13 @@ int gmr1_hip_gsmtap_pack_big(const struct gmr1_hip_rx_big_record *rec, int with_
 // align + 2 * frame_len, so a walk to H samples does exactly what the one-shot walk does up to there; the only thing the
 // horizon adds is a stop that the next push may lift (rx_stream_next_done).  A carrier then keeps its samples from
 // rx_stream_keep_from(min chain align): no window of the next walk starts before that (rx_stream_reach_back).
+//
+// A handle made by gmr1_hip_rx_stream_create_tch also follows TCH3 calls (gmr1_hip_rx_run_tch over pushes).  It holds the
+// traffic carrier's samples in a second ping-pong pair with the first one's stride, held and keep (k_rx_stage_copy), one
+// struct gmr1_hip_tch3_state per chain in device memory and, on the host, each chain's assigned timeslot.  A push walks the
+// chains with the frame log on, then hands this push's frames to tch3_follow_chains -- the one-shot pass's own rule for
+// frames, assignments and windows -- on those states: the call a push leaves is the call the next one continues.  The
+// traffic windows of admitted frames fit the samples held for the same reason the walk's own do.
 // ---------------------------------------------------------------------------------------------------------------------
 static_assert(kStartDiscard == kRxStartDiscard && kStartDiscard == kAcqStart, "one start discard");
 
@@ -955,10 +1020,19 @@ struct gmr1_hip_rx_stream {
 	size_t h_in_bytes = 0;
 	float *d_in = nullptr;
 	size_t d_in_bytes = 0;
+	// a handle that follows TCH3 calls (gmr1_hip_rx_stream_create_tch)
+	bool tch = false;
+	std::vector<uint8_t> kc;             // A x 8 (empty: the all-zero key)
+	float2 *tbuf[2] = {nullptr, nullptr};          // the traffic carrier's samples: buf's layout, stride, held and keep
+	gmr1_hip_tch3_state *d_tstate = nullptr;       // one per chain, parallel to d_state
+	std::vector<TchCarry> carry;         // per chain
 	~gmr1_hip_rx_stream()
 	{
 		for (float2 *p : buf)
 			if (p) (void)hipFree(p);
+		for (float2 *p : tbuf)
+			if (p) (void)hipFree(p);
+		if (d_tstate) (void)hipFree(d_tstate);
 		if (d_state) (void)hipFree(d_state);
 		if (d_car) (void)hipFree(d_car);
 		if (d_err) (void)hipFree(d_err);
@@ -1004,14 +1078,22 @@ long long rx_stream_bound(const gmr1_hip_rx_stream *h, uint64_t n)
 		chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
 		len = std::max(len, rx_stream_next_held(h, i, n));
 	}
-	return chains ? chains * rx_stream_rec_per_chain(len, h->sps) : 0;
+	if (!chains)
+		return 0;
+	return chains * (h->tch ? rx_stream_tch_rec_per_chain(len, h->sps) : rx_stream_rec_per_chain(len, h->sps));
 }
 
-int rx_stream_check(const gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n, int last,
-                    const gmr1_hip_rx_record *out, int max_records, const int *n_records)
+// with_tch: the call is one of gmr1_hip_rx_stream_push_tch*
+int rx_stream_check(const gmr1_hip_rx_stream *h, bool with_tch, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
+                    int last, const gmr1_hip_rx_record *out, int max_records, const int *n_records)
 {
 	if (!h || !n_records || max_records < 0 || (max_records > 0 && !out) || (n > 0 && !iq))
 		return fail(-EINVAL, "rx_stream_push: handle / n_records (and iq when n > 0, out when max_records > 0) are required");
+	if (h->tch != with_tch)
+		return fail(-EINVAL, h->tch ? "rx_stream_push: a handle of gmr1_hip_rx_stream_create_tch takes gmr1_hip_rx_stream_push_tch*"
+		                            : "rx_stream_push_tch: the handle was not made by gmr1_hip_rx_stream_create_tch");
+	if (with_tch && n > 0 && !tch)
+		return fail(-EINVAL, "rx_stream_push_tch: tch is required when n > 0");
 	int dev = 0;
 	HIP_TRY(hipGetDevice(&dev));
 	if (dev != h->device)
@@ -1035,8 +1117,9 @@ int rx_stream_check(const gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_st
 }
 
 // the device part of a push; the caller holds h->mu and the workspace lease, and has validated everything
-int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, uint64_t iq_stride, uint64_t n, int last,
-                        gmr1_hip_rx_record *out, int max_records, int *n_records)
+// (tch: the traffic carrier's chunk, laid out as iq, for a handle that follows TCH3 calls)
+int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, const float2 *tch, uint64_t iq_stride, uint64_t n,
+                        int last, gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
 	const int A = h->A, sps = h->sps;
 	// 1. staging: [kept tail | chunk] -> the other buffer, states rebased
@@ -1047,22 +1130,28 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 		need = std::max(need, next[i]);
 	}
 	need = (need + kRxKeepAlign - 1) / kRxKeepAlign * kRxKeepAlign;
-	float2 *src = h->buf[h->cur];
+	float2 *src = h->buf[h->cur], *tsrc = h->tbuf[h->cur];
 	const long long src_stride = h->stride;
-	float2 *fresh = nullptr;
-	if (need > h->stride) {
-		// grow-only: a new pair; the old current buffer is the source of this one staging and then goes
-		HIP_TRY(hipMalloc(&fresh, (size_t)A * (size_t)need * sizeof(float2)));
-		if (h->buf[1 - h->cur]) {
-			(void)hipFree(h->buf[1 - h->cur]);
-			h->buf[1 - h->cur] = nullptr;
+	const bool grow = need > h->stride;
+	// the destination of this staging in a pair (the traffic pair follows the first one's decision)
+	auto other = [&](float2 **pair) -> int {
+		float2 *&o = pair[1 - h->cur];
+		if (grow) {
+			// grow-only: a new pair; the old current buffer is the source of this one staging and then goes
+			float2 *fresh = nullptr;
+			HIP_TRY(hipMalloc(&fresh, (size_t)A * (size_t)need * sizeof(float2)));
+			if (o) (void)hipFree(o);
+			o = fresh;
+		} else if (!o && need > 0) {
+			HIP_TRY(hipMalloc(&o, (size_t)A * (size_t)h->stride * sizeof(float2)));
 		}
-		h->buf[1 - h->cur] = fresh;
-		h->stride = need;
-	} else if (!h->buf[1 - h->cur] && need > 0) {
-		HIP_TRY(hipMalloc(&h->buf[1 - h->cur], (size_t)A * (size_t)h->stride * sizeof(float2)));
-	}
-	float2 *dst = h->buf[1 - h->cur];
+		return 0;
+	};
+	int r = other(h->buf);
+	if (!r && h->tch) r = other(h->tbuf);
+	if (r) return r;
+	if (grow) h->stride = need;
+	float2 *dst = h->buf[1 - h->cur], *tdst = h->tbuf[1 - h->cur];
 	for (int i = 0; i < A; i++) {
 		RxStageCarrier &c = h->h_car[i];
 		const bool dead = rx_stream_dead(h, i);
@@ -1093,11 +1182,21 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 		sa.state = h->d_state;
 		sa.err = h->d_err;
 		HIP_TRY(launch_rx_stage(sa, st));
+		if (tdst) {
+			sa.src = tsrc ? tsrc : tdst;
+			sa.dst = tdst;
+			sa.iq = tch ? tch : tdst;
+			sa.state = nullptr;
+			sa.err = nullptr;
+			HIP_TRY(launch_rx_stage_copy(sa, st));
+		}
 	}
-	if (fresh && src) {
-		HIP_TRY(hipStreamSynchronize(st));     // the staging has read the old buffer
-		(void)hipFree(src);
+	if (grow && (src || tsrc)) {
+		HIP_TRY(hipStreamSynchronize(st));     // the staging has read the old buffers
+		if (src) (void)hipFree(src);
+		if (tsrc) (void)hipFree(tsrc);
 		h->buf[h->cur] = nullptr;
+		h->tbuf[h->cur] = nullptr;
 	}
 	h->cur = 1 - h->cur;
 	for (int i = 0; i < A; i++) {
@@ -1114,7 +1213,9 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 
 	RxRun run;
 	run.st = st; run.sps = sps; run.iq = reinterpret_cast<const float *>(h->buf[h->cur]);
-	run.tch = nullptr; run.csd = nullptr; run.kc = nullptr;
+	// (a traffic carrier makes the walk log its frames and hand its records back chain by chain, as in gmr1_hip_rx_run_tch)
+	run.tch = h->tch ? reinterpret_cast<const float *>(h->tbuf[h->cur]) : nullptr;
+	run.csd = nullptr; run.kc = nullptr;
 	run.arfcn = h->arfcn.empty() ? nullptr : h->arfcn.data();
 	run.A = A;
 	run.out = out; run.max_records = max_records;
@@ -1125,7 +1226,7 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 		length[i] = (uint64_t)h->held[i];
 	}
 	run.offset = offset.data(); run.length = length.data();
-	int r = 0;
+	std::vector<gmr1_hip_tch3_state> t0;     // the calls' first states: lives until this push's synchronisation
 
 	// 2. the acquisition, once every carrier holds what it reads (nothing has been dropped yet: coordinates are absolute)
 	if (!h->acquired && ((long long)h->N >= rx_stream_acq_need(sps) || last)) {
@@ -1150,6 +1251,17 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 				s0[k].done = rx_stream_next_done(kRxDoneUnstarted, c.align, c.len, sps, last);
 			}
 			HIP_TRY(hipMemcpyAsync(h->d_state, s0.data(), (size_t)nc * sizeof(RxLoopState), hipMemcpyHostToDevice, st));
+			if (h->tch) {
+				// the chains' calls: none yet, not ciphered, the carrier's key (RxRun::tch3_pass)
+				t0.resize((size_t)nc);
+				std::memset(t0.data(), 0, t0.size() * sizeof(t0[0]));
+				if (!h->kc.empty())
+					for (int k = 0; k < nc; k++)
+						std::memcpy(t0[k].kc, &h->kc[(size_t)h->chains[k].a * 8], 8);
+				HIP_TRY(hipMalloc(&h->d_tstate, (size_t)nc * sizeof(gmr1_hip_tch3_state)));
+				HIP_TRY(hipMemcpyAsync(h->d_tstate, t0.data(), (size_t)nc * sizeof(gmr1_hip_tch3_state), hipMemcpyHostToDevice, st));
+				h->carry.assign((size_t)nc, TchCarry());
+			}
 		}
 		h->acquired = true;
 	}
@@ -1181,6 +1293,25 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 	}
 	*n_records = run.direct ? run.direct_total : 0;
 
+	// 3b. the TCH3 follow-up over this push's frames, and the records chain by chain in frame order
+	if (h->tch && h->acquired && !h->chains.empty()) {
+		std::vector<int> calls(h->chains.size());
+		for (size_t k = 0; k < calls.size(); k++)
+			calls[k] = (int)k;
+		if ((r = tch3_follow_chains(st, sps, run.tch, run.arfcn, false, !last, h->chains, calls, nullptr, h->d_tstate,
+		                            h->carry.data()))) return r;
+		int total = 0;
+		for (RxChain &c : h->chains) {
+			const int cnt = (int)c.rec.size();
+			const int fit = std::max(0, std::min(cnt, max_records - total));
+			if (fit)
+				std::memcpy(out + total, c.rec.data(), (size_t)fit * sizeof(gmr1_hip_rx_record));
+			total += cnt;
+			c.rec.clear(); c.rec_frame.clear(); c.log.clear(); c.events.clear();     // the next push's walk starts them over
+		}
+		*n_records = total;
+	}
+
 	// 4. what each carrier keeps for the next push
 	for (int i = 0; i < A; i++) {
 		if (h->ended || rx_stream_dead(h, i)) {
@@ -1200,28 +1331,93 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 	return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struct gmr1_hip_rx_stream **out)
+// gmr1_hip_rx_stream_push_dev and _push_tch_dev (tch_entry)
+int rx_stream_push_dev_any(void *stream, gmr1_hip_rx_stream *h, bool tch_entry, const float *iq, const float *tch, uint64_t iq_stride,
+                           uint64_t n, int last, gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
 	DevState *ds;
 	int r = dev_state(&ds);
 	if (r) return r;
+	if (n_records) *n_records = 0;
+	std::unique_lock<std::mutex> lk;
+	if (h)
+		lk = std::unique_lock<std::mutex>(h->mu);
+	if ((r = rx_stream_check(h, tch_entry, iq, tch, iq_stride, n, last, out, max_records, n_records)))
+		return r;
+	hipStream_t st = (hipStream_t)stream;
+	// the loop holds the device's workspace, side stream and events: pushes of other handles wait their turn
+	WsLease lease;
+	if ((r = lease.acquire(ds, st))) return r;
+	r = rx_stream_push_impl(st, h, reinterpret_cast<const float2 *>(iq), reinterpret_cast<const float2 *>(tch), iq_stride, n, last,
+	                        out, max_records, n_records);
+	if (r) h->broken = true;
+	return r;
+}
+
+// gmr1_hip_rx_stream_push and _push_tch (tch_entry)
+int rx_stream_push_host_any(gmr1_hip_rx_stream *h, bool tch_entry, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
+                            int last, gmr1_hip_rx_record *out, int max_records, int *n_records)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (n_records) *n_records = 0;
+	std::unique_lock<std::mutex> lk;
+	if (h)
+		lk = std::unique_lock<std::mutex>(h->mu);
+	if ((r = rx_stream_check(h, tch_entry, iq, tch, iq_stride, n, last, out, max_records, n_records)))
+		return r;
+	// the chunk goes up packed (stride n) through the handle's pinned block, the traffic carrier's behind it
+	const size_t half = (size_t)h->A * (size_t)n * sizeof(float2), bytes = tch_entry ? 2 * half : half;
+	if (bytes > h->h_in_bytes) {
+		if (h->h_in) (void)hipHostFree(h->h_in);
+		if (h->d_in) (void)hipFree(h->d_in);
+		h->h_in = nullptr; h->d_in = nullptr; h->h_in_bytes = h->d_in_bytes = 0;
+		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_in), bytes, hipHostMallocDefault));
+		h->h_in_bytes = bytes;
+		HIP_TRY(hipMalloc(&h->d_in, bytes));
+		h->d_in_bytes = bytes;
+	}
+	for (int i = 0; i < h->A && n > 0; i++) {
+		std::memcpy(h->h_in + (size_t)i * n * 2, iq + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
+		if (tch_entry)
+			std::memcpy(h->h_in + half / 4 + (size_t)i * n * 2, tch + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
+	}
+	WsLease lease;
+	if ((r = lease.acquire(ds, nullptr))) return r;
+	if (bytes)
+		HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, bytes, hipMemcpyHostToDevice, nullptr));
+	r = rx_stream_push_impl(nullptr, h, reinterpret_cast<const float2 *>(h->d_in),
+	                        tch_entry ? reinterpret_cast<const float2 *>(h->d_in + half / 4) : nullptr, n, n, last, out, max_records,
+	                        n_records);
+	if (r) h->broken = true;
+	return r;
+}
+
+int rx_stream_create_check(const char *who, int n_arfcn, int sps, struct gmr1_hip_rx_stream **out)
+{
 	if (!out)
-		return fail(-EINVAL, "rx_stream_create: h is required");
+		return fail(-EINVAL, "%s: h is required", who);
 	*out = nullptr;
 	if (n_arfcn < 1 || n_arfcn > 65535)
-		return fail(-EINVAL, "rx_stream_create: n_arfcn=%d (1..65535)", n_arfcn);
+		return fail(-EINVAL, "%s: n_arfcn=%d (1..65535)", who, n_arfcn);
 	if (sps < 1 || sps > 16)                  // gmr1_rx.c:919-922
-		return fail(-EINVAL, "rx_stream_create: sps=%d unsupported (1..16)", sps);
+		return fail(-EINVAL, "%s: sps=%d unsupported (1..16)", who, sps);
+	return 0;
+}
+
+// kc: the handle follows TCH3 calls (tch); n_arfcn x 8 key bytes, or NULL for the all-zero key
+int rx_stream_make(int n_arfcn, int sps, const uint16_t *arfcn, bool tch, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
+{
 	std::unique_ptr<gmr1_hip_rx_stream> h(new gmr1_hip_rx_stream);
 	HIP_TRY(hipGetDevice(&h->device));
 	h->A = n_arfcn;
 	h->sps = sps;
+	h->tch = tch;
 	if (arfcn)
 		h->arfcn.assign(arfcn, arfcn + n_arfcn);
+	if (kc)
+		h->kc.assign(kc, kc + (size_t)n_arfcn * 8);
 	h->stat.assign(n_arfcn, 0);
 	h->nch.assign(n_arfcn, 0);
 	h->held.assign(n_arfcn, 0);
@@ -1233,6 +1429,28 @@ int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struc
 	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_err), 4, hipHostMallocDefault));
 	*out = h.release();
 	return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struct gmr1_hip_rx_stream **out)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if ((r = rx_stream_create_check("rx_stream_create", n_arfcn, sps, out))) return r;
+	return rx_stream_make(n_arfcn, sps, arfcn, false, nullptr, out);
+}
+
+int gmr1_hip_rx_stream_create_tch(int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
+{
+	int r = rx_stream_create_check("rx_stream_create_tch", n_arfcn, sps, out);
+	if (r) return r;
+	DevState *ds;
+	if ((r = dev_state(&ds))) return r;
+	return rx_stream_make(n_arfcn, sps, arfcn, true, kc, out);
 }
 
 int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_records)
@@ -1253,56 +1471,26 @@ int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t 
 int gmr1_hip_rx_stream_push_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n,
                                 int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if (n_records) *n_records = 0;
-	std::unique_lock<std::mutex> lk;
-	if (h)
-		lk = std::unique_lock<std::mutex>(h->mu);
-	if ((r = rx_stream_check(h, iq, iq_stride, n, last, out, max_records, n_records)))
-		return r;
-	hipStream_t st = (hipStream_t)stream;
-	// the loop holds the device's workspace, side stream and events: pushes of other handles wait their turn
-	WsLease lease;
-	if ((r = lease.acquire(ds, st))) return r;
-	r = rx_stream_push_impl(st, h, reinterpret_cast<const float2 *>(iq), iq_stride, n, last, out, max_records, n_records);
-	if (r) h->broken = true;
-	return r;
+	return rx_stream_push_dev_any(stream, h, false, iq, nullptr, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push(struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n, int last,
                             struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if (n_records) *n_records = 0;
-	std::unique_lock<std::mutex> lk;
-	if (h)
-		lk = std::unique_lock<std::mutex>(h->mu);
-	if ((r = rx_stream_check(h, iq, iq_stride, n, last, out, max_records, n_records)))
-		return r;
-	// the chunk goes up packed (stride n) through the handle's pinned block
-	const size_t bytes = (size_t)h->A * (size_t)n * sizeof(float2);
-	if (bytes > h->h_in_bytes) {
-		if (h->h_in) (void)hipHostFree(h->h_in);
-		if (h->d_in) (void)hipFree(h->d_in);
-		h->h_in = nullptr; h->d_in = nullptr; h->h_in_bytes = h->d_in_bytes = 0;
-		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_in), bytes, hipHostMallocDefault));
-		h->h_in_bytes = bytes;
-		HIP_TRY(hipMalloc(&h->d_in, bytes));
-		h->d_in_bytes = bytes;
-	}
-	for (int i = 0; i < h->A && n > 0; i++)
-		std::memcpy(h->h_in + (size_t)i * n * 2, iq + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
-	WsLease lease;
-	if ((r = lease.acquire(ds, nullptr))) return r;
-	if (bytes)
-		HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, bytes, hipMemcpyHostToDevice, nullptr));
-	r = rx_stream_push_impl(nullptr, h, reinterpret_cast<const float2 *>(h->d_in), n, n, last, out, max_records, n_records);
-	if (r) h->broken = true;
-	return r;
+	return rx_stream_push_host_any(h, false, iq, nullptr, iq_stride, n, last, out, max_records, n_records);
+}
+
+int gmr1_hip_rx_stream_push_tch_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch,
+                                    uint64_t iq_stride, uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records,
+                                    int *n_records)
+{
+	return rx_stream_push_dev_any(stream, h, true, iq, tch, iq_stride, n, last, out, max_records, n_records);
+}
+
+int gmr1_hip_rx_stream_push_tch(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
+                                int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records)
+{
+	return rx_stream_push_host_any(h, true, iq, tch, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_status(const struct gmr1_hip_rx_stream *h, int32_t *status, int32_t *n_chains, uint64_t *retained)

@@ -2,6 +2,9 @@
 // and its helpers).  The state of a call is the caller's; every decision between the frames is taken on the device
 // (tch3_follow_kernels.hip, tch3_follow.h).
 #include "capi_common.h"
+#include "tch3_follow.h"
+
+#include <cstddef>
 
 #include "../../include/gmr1_hip.h"
 
@@ -134,14 +137,28 @@ int gmr1_hip_tch3_state_assign(struct gmr1_hip_tch3_state *s, int p, float ref_e
 {
 	if (!s)
 		return fail(-EINVAL, "tch3_state_assign: NULL state");
-	// rx_tch3_init, gmr1_rx.c:358-376: ciph, burst_cnt and bi_fn keep what they hold
-	s->active = 1;
-	s->p = p;
-	s->energy_burst = ref_energy * 0.75f;
-	s->energy_dkab = s->energy_burst / 8.0f;
-	s->weak_cnt = 0;
-	s->sync_id = 0;
+	// rx_tch3_init, gmr1_rx.c:358-376: ciph, burst_cnt and bi_fn keep what they hold (tch3_follow_assign, which
+	// k_tch3f_assign runs on device-resident states)
+	static_assert(offsetof(gmr1_hip_tch3_state, ebits) == sizeof(Tch3Walk), "Tch3Walk is the state up to its soft bits");
+	Tch3Walk w;
+	std::memcpy(&w, s, sizeof(w));
+	tch3_follow_assign(w, p, ref_energy);
+	std::memcpy(s, &w, sizeof(w));
 	std::memset(s->ebits, 0, sizeof(s->ebits));
+	return 0;
+}
+
+int gmr1_hip_tch3_state_assign_batch_dev(void *stream, int n, const int32_t *call, const int32_t *p, const float *ref_energy,
+                                         struct gmr1_hip_tch3_state *state)
+{
+	if (n < 0)
+		return fail(-EINVAL, "tch3_state_assign_batch: negative count");
+	if (!call || !p || !ref_energy || !state)
+		return fail(-EINVAL, "tch3_state_assign_batch: NULL argument");
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	HIP_TRY(launch_tch3f_assign(n, call, p, ref_energy, state, (hipStream_t)stream));
 	return 0;
 }
 

@@ -399,6 +399,8 @@ struct RxStageArgs {
 	int32_t *err;                  // set to 1 when a chain about to walk could reach before its carrier's kept samples
 };
 hipError_t launch_rx_stage(const RxStageArgs &a, hipStream_t stream);
+// the same copy for the traffic carrier's buffer pair (k_rx_stage_copy): no states, no error word
+hipError_t launch_rx_stage_copy(const RxStageArgs &a, hipStream_t stream);
 
 hipError_t launch_dkab(const DkabArgs &a, hipStream_t stream);
 hipError_t launch_a5(const A5Args &a, hipStream_t stream);
@@ -435,6 +437,9 @@ hipError_t launch_tch3f_prep(const Tch3FollowArgs &a, hipStream_t stream);
 hipError_t launch_tch3f_walk(const Tch3FollowArgs &a, hipStream_t stream);
 hipError_t launch_a5_tch3f(const Tch3FollowArgs &a, hipStream_t stream);
 hipError_t launch_tch3f_emit(const Tch3FollowArgs &a, hipStream_t stream);
+// rx_tch3_init on device-resident states (k_tch3f_assign): entry j < n assigns state[call[j]], entries of one call in order
+hipError_t launch_tch3f_assign(int n, const int32_t *call, const int32_t *p, const float *ref_energy,
+                               struct gmr1_hip_tch3_state *state, hipStream_t stream);
 // NT9 bursts: FACCH9 and the three TCH9 modes share one decoder kernel (nt9_kernels.hip)
 struct Nt9Args {
 	int n;                     // bursts

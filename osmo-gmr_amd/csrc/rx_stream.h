@@ -56,11 +56,25 @@ GMR1_HD int rx_stream_next_done(int done, int align, int len, int sps, int last)
 	return done;
 }
 
+// Frames a walk over `len` samples can log per chain: the per-chain frame log of RxRun::frame_loop
+GMR1_HD long long rx_stream_frames_per_chain(long long len, int sps) { return len / rx_stream_frame_len(sps) + 2; }
+
 // Records a walk over `len` samples can hand back per chain: the per-chain record buffer of RxRun::frame_loop
 GMR1_HD long long rx_stream_rec_per_chain(long long len, int sps)
 {
-	const long long max_frames = len / rx_stream_frame_len(sps) + 2;
-	return (max_frames / 7 + 8) * kLoopPerRound;
+	return (rx_stream_frames_per_chain(len, sps) / 7 + 8) * kLoopPerRound;
+}
+
+// The window rx_tch3 cuts on the traffic carrier for a frame at `align` (burst_map of an NT3 burst with sps + sps / 2
+// samples of search room, gmr1_rx.c:149-170, 549-551): [begin, begin + in_len).  rx_tch3 returns before it touches
+// anything when begin < 0 or begin + in_len > len.  One rule for the one-shot pass and the streaming push.
+GMR1_HD int rx_tch3_in_len(int sps) { return 117 * sps + sps + sps / 2; }
+GMR1_HD long long rx_tch3_begin(int align, int sps, int tn) { return (long long)align + sps * tn * 39 - ((sps + sps / 2) >> 1); }
+
+// A tch handle hands back, on top of the BCCH / CCCH records, at most one TCH3 record per frame a chain's walk logs
+GMR1_HD long long rx_stream_tch_rec_per_chain(long long len, int sps)
+{
+	return rx_stream_rec_per_chain(len, sps) + rx_stream_frames_per_chain(len, sps);
 }
 
 }  // namespace gmr1

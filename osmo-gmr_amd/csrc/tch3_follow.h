@@ -42,6 +42,18 @@ struct Tch3Act {
 	uint32_t job_fn[4];                    // bi_fn as the flush finds it
 };
 
+// rx_tch3_init (gmr1_rx.c:358-376) on the state's scalars: ciph, burst_cnt and bi_fn keep what they hold.  The caller clears
+// the 416 soft bits (the host entry with a memset, k_tch3f_assign with all lanes).
+GMR1_HD void tch3_follow_assign(Tch3Walk &s, int p, float ref_energy)
+{
+	s.active = 1;
+	s.p = p;
+	s.energy_burst = ref_energy * 0.75f;
+	s.energy_dkab = s.energy_burst / 8.0f;
+	s.weak_cnt = 0;
+	s.sync_id = 0;
+}
+
 GMR1_HD void tch3_follow_flush(Tch3Walk &s, Tch3Act &a, int when)
 {
 	a.need = kT3NeedFlush;

@@ -8,6 +8,7 @@
 //   k_a5_tch3f     (tch_kernels.hip) keystreams of the frames that ask for a decode
 //   k_tch3_jobs, k_facch3_jobs   (l1_kernels.hip) the decodes, plain and deciphered
 //   k_tch3f_emit   one lane per call: the ciphering state picks the variant, the caller's records are written
+// and, between two invocations, k_tch3f_assign (gmr1_hip_tch3_state_assign_batch_dev): rx_tch3_init on the states where they lie.
 //
 // k_tch3f_walk is a latency chain.  The per-frame results of 64 frames are fetched by the 64 lanes at once and handed to
 // the step one frame at a time by readlane, so the chain never waits for a load that depends on the step before; the
@@ -198,6 +199,60 @@ __global__ __launch_bounds__(64) void k_tch3f_emit(Tch3FollowArgs a)
 		a.out[k] = r;
 	}
 	a.state[c].ciph = ciph;
+}
+
+// rx_tch3_init on device-resident states: entry j assigns state[call[j]].  One wavefront per entry; the wave of the FIRST
+// entry that names a call takes all of that call's entries, in order, so a call named twice gets both and no two waves
+// write one state.  The scalars are wave-uniform and written by one lane, the 416 soft bits are cleared by all lanes.
+__global__ __launch_bounds__(64 * kWalkWaves) void k_tch3f_assign(int n, const int32_t *__restrict__ call, const int32_t *__restrict__ p,
+                                                                  const float *__restrict__ ref_energy, gmr1_hip_tch3_state *state)
+{
+	const int lane = threadIdx.x & 63;
+	const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWalkWaves + (threadIdx.x >> 6)));
+	if (w >= n)
+		return;
+	const int c = call[w];
+	if (c < 0)
+		return;
+	for (int j0 = 0; j0 < w; j0 += 64) {           // an earlier entry names this call: its wave applies this one too
+		const int j = j0 + lane;
+		if (__ballot(j < w && call[j] == c))
+			return;
+	}
+	gmr1_hip_tch3_state *st = state + c;
+	Tch3Walk s;
+	s.active = st->active; s.p = st->p; s.ciph = st->ciph; s.weak_cnt = st->weak_cnt;
+	s.sync_id = st->sync_id; s.burst_cnt = st->burst_cnt;
+	s.energy_dkab = st->energy_dkab; s.energy_burst = st->energy_burst;
+#pragma unroll
+	for (int i = 0; i < 4; i++)
+		s.bi_fn[i] = st->bi_fn[i];
+	for (int j0 = w; j0 < n; j0 += 64) {
+		const int j = j0 + lane;
+		unsigned long long m = __ballot(j < n && call[j] == c);
+		while (m) {
+			const int k = j0 + __builtin_ctzll(m);
+			m &= m - 1;
+			tch3_follow_assign(s, p[k], ref_energy[k]);
+		}
+	}
+	uint32_t *st_eb = reinterpret_cast<uint32_t *>(st->ebits);
+	for (int i = lane; i < 104; i += 64)
+		st_eb[i] = 0;
+	if (lane == 0) {
+		st->active = s.active; st->p = s.p; st->weak_cnt = s.weak_cnt; st->sync_id = s.sync_id;
+		st->energy_dkab = s.energy_dkab; st->energy_burst = s.energy_burst;
+	}
+}
+
+hipError_t launch_tch3f_assign(int n, const int32_t *call, const int32_t *p, const float *ref_energy,
+                               struct gmr1_hip_tch3_state *state, hipStream_t stream)
+{
+	if (n <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_tch3f_assign, dim3((n + kWalkWaves - 1) / kWalkWaves), dim3(64 * kWalkWaves), 0, stream, n, call, p,
+	                   ref_energy, state);
+	return hipGetLastError();
 }
 
 hipError_t launch_tch3f_prep(const Tch3FollowArgs &a, hipStream_t stream)

@@ -6,8 +6,11 @@ after the call: from its first device operation to its last, gaps where the stre
 included); median and p99 over the last three quarters of the pushes, the maximum over all; then the total of a pass against the one-shot call, and the
 real-time factor (capture seconds per second of the pass).  Then the chained pipeline: a wideband capture through
 ChanStream.push_dev -> RxStream.push_dev on one stream, against channelize + rx_run.  Checks the records are identical.
+--tch: every carrier has a traffic carrier with one call on it (an IMMEDIATE ASSIGNMENT around frame 40, some ciphered),
+the handle follows TCH3 calls (push_tch_dev) and the one-shot call is gmr1_hip_rx_run_tch_dev; the chained pipeline is
+left out.
 
-    python tools/time_rx_stream.py [--seconds 60] [--pushes 0.01,0.1,1] [--out result.json]
+    python tools/time_rx_stream.py [--seconds 60] [--pushes 0.01,0.1,1] [--tch] [--wide-seconds 0] [--out result.json]
 """
 import argparse
 import json
@@ -28,11 +31,20 @@ def _sorted(rec, arfcn):
     return rec[np.argsort(key, kind="stable")] if len(rec) else rec
 
 
+def finish(res, out):
+    print(json.dumps(res))
+    if out:
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--pushes", default="0.01,0.1,1", help="push lengths in seconds")
-    ap.add_argument("--wide-seconds", type=float, default=10.0, help="length of the chained pipeline's wideband capture")
+    ap.add_argument("--wide-seconds", type=float, default=10.0,
+                    help="length of the chained pipeline's wideband capture (0: leave the pipeline out)")
+    ap.add_argument("--tch", action="store_true", help="follow TCH3 calls: one call per carrier")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -44,28 +56,45 @@ def main():
     api.load()
     api.init(0)
     sps, A, rate = 4, 64, 23400 * 4
-    base = [workloads.bcch_carrier(pkg, 900 + k, seconds=args.seconds, sps=sps, stn=(7 * k) % 32, delay=k % 8,
-                                   cfo_hz=40.0 * k - 150.0, esn0_db=10.0 + k)[0] for k in range(8)]
+    kc = dt = None
+    if args.tch:
+        keys = [np.arange(8, dtype=np.uint8) + k if k % 2 else None for k in range(8)]
+        pairs = [workloads.bcch_tch_pair(pkg, 900 + k, seconds=args.seconds, sps=sps, stn=(7 * k) % 32, delay=k % 8, tn=(5 * k + 3) % 32,
+                                         p=(7 * k) % 40, k_ass=40, kc=keys[k], cipher_after=None if keys[k] is None else 25,
+                                         cfo_hz=40.0 * k - 150.0)[:2] for k in range(8)]
+        base = [b for b, _ in pairs]
+        kc = np.stack([keys[i % 8] if keys[i % 8] is not None else np.zeros(8, np.uint8) for i in range(A)])
+    else:
+        base = [workloads.bcch_carrier(pkg, 900 + k, seconds=args.seconds, sps=sps, stn=(7 * k) % 32, delay=k % 8,
+                                       cfo_hz=40.0 * k - 150.0, esn0_db=10.0 + k)[0] for k in range(8)]
     n = min(x.size for x in base)
     x = np.stack([base[i % 8][:n] for i in range(A)]).astype(np.complex64)
     arfcn = np.arange(A, dtype=np.uint16) + 100
     d = torch.from_numpy(x.view(np.float32).reshape(A, -1)).cuda()
+    if args.tch:
+        dt = torch.from_numpy(np.stack([pairs[i % 8][1][:n] for i in range(A)]).astype(np.complex64).view(np.float32).reshape(A, -1)).cuda()
     stream = torch.cuda.current_stream()
     st = stream.cuda_stream
     offset = np.arange(A, dtype=np.uint64) * np.uint64(n)
     length = np.full(A, n, np.uint64)
-    res = {"carriers": A, "capture_s": n / rate, "sps": sps}
+    res = {"carriers": A, "capture_s": n / rate, "sps": sps, "tch": bool(args.tch)}
     out = np.empty(1 << 21, api.RX_RECORD)
-    api.rx_run_dev(st, d.data_ptr(), offset, length, sps=sps, arfcn=arfcn, out=out)      # warm-up
+    if args.tch:
+        one_shot = lambda: api.rx_run_tch_dev(st, d.data_ptr(), dt.data_ptr(), offset, length, sps=sps, arfcn=arfcn, kc=kc,
+                                              max_records=1 << 21)
+    else:
+        one_shot = lambda: api.rx_run_dev(st, d.data_ptr(), offset, length, sps=sps, arfcn=arfcn, out=out)
+    one_shot()      # warm-up
     t = []
     for _ in range(3):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ref, rst, rch, _ = api.rx_run_dev(st, d.data_ptr(), offset, length, sps=sps, arfcn=arfcn, out=out)
+        ref, rst, rch, _ = one_shot()
         t.append(time.perf_counter() - t0)
     ref = ref.copy()
     res["one_shot_ms"] = 1e3 * min(t)
     res["records"] = int(len(ref))
+    res["tch_records"] = int(np.sum(ref["type"] >= 0x10))
     for p_s in [float(v) for v in args.pushes.split(",")]:
         p = int(round(p_s * rate))
         best = None
@@ -73,7 +102,7 @@ def main():
             per, got, evs = [], [], []
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            with api.RxStream(A, sps=sps, arfcn=arfcn) as s:
+            with api.RxStream(A, sps=sps, arfcn=arfcn, tch=args.tch, kc=kc) as s:
                 at = 0
                 buf = np.empty(max(s.max_records(p), 1), api.RX_RECORD)
                 while at < n:
@@ -83,7 +112,8 @@ def main():
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(stream)
                     q0 = time.perf_counter()
-                    r = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf)
+                    r = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf,
+                                   tch_ptr=dt.data_ptr() + 8 * at if args.tch else None)
                     per.append(time.perf_counter() - q0)
                     e1.record(stream)
                     evs.append((e0, e1))
@@ -108,6 +138,8 @@ def main():
                                  "push_dev_ms_max": float(dev_ms.max()), "identical": bool(same)}
         print(json.dumps({("push_%gs" % p_s): res["push_%gs" % p_s]}), flush=True)
     # the chained pipeline
+    if args.tch or args.wide_seconds <= 0:
+        return finish(res, args.out)
     fs = 2.0e6
     carriers = tuple((c, dict(stn=(3 * c) % 32, delay=c % 8, cfo_hz=float(c))) for c in (3, 17, 33, 60))
     wide, _ = workloads.wideband_capture(pkg, 5, seconds=args.wide_seconds, carriers=carriers)
@@ -145,10 +177,7 @@ def main():
         res["core_mhz"] = core
     except Exception:       # noqa: BLE001
         pass
-    print(json.dumps(res))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    finish(res, args.out)
 
 
 if __name__ == "__main__":
