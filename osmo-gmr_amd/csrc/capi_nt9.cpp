@@ -145,7 +145,7 @@ int nt9_dev(hipStream_t st, int kind, int n, int seq_len, const int8_t *ebits, c
 
 namespace gmr1 {
 // TCH9 bursts of several interleaver runs of unequal length, run after run, in one launch: seq_pos[i] (device)
-// = position of burst i in its run (the receive loop's TCH9 follow-up, capi_rx.cpp)
+// = position of burst i in its run (the receive loop's TCH9 follow-up, capi_rx_follow.cpp)
 int tch9_runs_dev_impl(hipStream_t st, int mode, int n, const int32_t *seq_pos, const int8_t *ebits, const uint8_t *ciph,
                        uint8_t *l2, int32_t *conv)
 {

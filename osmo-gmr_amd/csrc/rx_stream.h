@@ -1,4 +1,4 @@
-// rx_stream.h -- the integer arithmetic of the streaming receive loop (gmr1_hip_rx_stream_*, capi_rx.cpp): when the
+// rx_stream.h -- the integer arithmetic of the streaming receive loop (gmr1_hip_rx_stream_*, capi_rx_stream.cpp): when the
 // acquisition may run, what a carrier keeps between pushes, how the chain states move with it.  Host-callable (tests,
 // sizing) and used by the staging kernel (rx_stream_kernels.hip).  No signal arithmetic here.
 #pragma once

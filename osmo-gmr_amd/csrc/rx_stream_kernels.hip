@@ -1,4 +1,4 @@
-// rx_stream_kernels.hip -- the staging step of the streaming receive loop (gmr1_hip_rx_stream_push*, capi_rx.cpp).
+// rx_stream_kernels.hip -- the staging step of the streaming receive loop (gmr1_hip_rx_stream_push*, capi_rx_stream.cpp).
 //
 // k_rx_stage, one launch per push: per carrier (blockIdx.y) the samples it keeps from the handle's current buffer and the
 // caller's strided chunk go, back to back, into the other buffer of the handle's ping-pong pair, two complex samples per
