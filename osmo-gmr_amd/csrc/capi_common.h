@@ -69,17 +69,16 @@ int dev_state(DevState **out);
 // grow-only device scratch of the current device; the caller holds a WsLease from here to its last launch
 int dev_workspace(DevState *s, size_t bytes, void **out);
 
-// fused BCCH / CCCH receive with the optional burst_energy() output (capi.cpp)
-// the fused BCCH / DC6 launch arguments without the per-call pointers (rx_base_args, capi.cpp): for the one-burst server
-int rx_fused_base_args(int sps, const float *iq, RxArgs *out);
-int rx_bcch_ccch_dev_impl(hipStream_t stream, int n, int sps,
-                          const float *iq, const uint64_t *offset, const uint8_t *kind,
-                          const float *freq_shift,
-                          uint8_t *l2, int32_t *crc, int32_t *conv,
-                          float *toa, float *freq_err, float *energy,
-                          int8_t *ebits, float *ssyms, int32_t *rv, long long plane_stride = 0);
+// What every burst of the fused BCCH / DC6 path shares (window lengths, strides, staging size, decoder), written into `a`,
+// which the caller has zeroed and given its pointers (capi_rx_fused.cpp).  -EINVAL below min_sps samples per symbol, or
+// if the burst tables are not what the fused kernels are built for.
+int rx_fused_base_args(int sps, RxArgs *a, int min_sps = 4);
+// The fused BCCH / CCCH receive of a.n bursts (capi_rx_fused.cpp).  `a`: zeroed, then n, sps, plane_stride, iq and the
+// per-burst pointers (offset, kind, l2, crc, conv, rv required; energy: the optional burst_energy() output); the rest is
+// filled in here.
+int rx_fused_launch(hipStream_t stream, RxArgs a);
 
-// process_bcch of n_chains chains in one launch (capi.cpp / launch_rx_loop); every pointer in `la` is device memory
+// process_bcch of n_chains chains in one launch (capi_rx_fused.cpp / launch_rx_loop); every pointer in `la` is device memory
 int rx_loop_dev_impl(hipStream_t stream, int n_chains, int sps, const float *iq, const RxLoopArgs &la);
 
 // gmr1_hip_rx_run_dev that also reports how many records each carrier contributed (capi_rx.cpp; the sharded entry keeps
@@ -92,10 +91,29 @@ int rx_run_dev_counted(void *stream, int n_arfcn, int sps, const float *iq, cons
 int tch9_runs_dev_impl(hipStream_t st, int mode, int n, const int32_t *seq_pos, const int8_t *ebits, const uint8_t *ciph,
                        uint8_t *l2, int32_t *conv);
 
-// gmr1_hip_demod_batch_dev of a built-in burst type, plus burst_energy() of each window (capi.cpp)
+// gmr1_hip_demod_batch_dev of a built-in burst type, plus burst_energy() of each window (capi_demod.cpp)
 int demod_dev_energy(hipStream_t st, int burst_id, int n, int sps, int in_len, const float *iq,
                      const uint64_t *offset, const float *freq_shift, int8_t *ebits, int ebits_stride,
                      int32_t *sync_id, float *toa, float *energy, int32_t *rv);
+
+// One demodulation launch of n bursts of one format (capi_demod.cpp): `type` is the descriptor-table slot `ht` is uploaded
+// in.  demod_dev_impl: device pointers.  demod_host_impl: host pointers staged through HBM, blocking; `custom` is a
+// caller-defined description to upload into its slot first (NULL for a built-in type).
+int demod_dev_impl(hipStream_t st, int type, const DevBurst &ht,
+                   int n, int sps, int in_len, const float *iq, const uint64_t *offset,
+                   const float *freq_shift, int8_t *ebits, int ebits_stride, int32_t *sync_id,
+                   float *toa, float *freq_err, float *ssyms, int32_t *rv, float *energy = nullptr);
+int demod_host_impl(int type, const DevBurst &ht, const DevBurst *custom,
+                    int n, int sps, int in_len, const float *iq, uint64_t iq_len,
+                    const uint64_t *offset, const float *freq_shift,
+                    int8_t *ebits, int ebits_stride, int32_t *sync_id,
+                    float *toa, float *freq_err, float *ssyms, int32_t *rv);
+// the profiling switch GMR1_HIP_DBG_STOP (RxArgs::dbg_stop; 0 in the product build), read once (capi_demod.cpp)
+int dbg_stop_env();
+
+// BCCH / CCCH batch decode, chain = kChainBcch / kChainCcch (capi_l1.cpp): device pointers; host pointers, blocking
+int l1_dev(hipStream_t st, int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv);
+int l1_host(int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv);
 
 // gmr1_hip_tch3_follow_batch_dev on scratch of the caller's (capi_tch3_follow.cpp): tch3_follow_scratch_bytes(n_frames) of
 // device memory on a 128-byte boundary.  The arguments are not checked; the caller holds a WsLease.

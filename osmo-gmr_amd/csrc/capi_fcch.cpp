@@ -99,7 +99,7 @@ int rough_dev(hipStream_t st, int tab, int n, int sps, int len, const float *iq,
 			a.epoch = fb.epoch;
 			// (a poll is three coherent 8-byte loads and a short sleep, a microsecond or two: the bound is some tens of milliseconds.
 			// Profiling build: GMR1_HIP_FCCH_FOLD_POLLS=0 makes every tile give up at once -- the fallback path, for the tests)
-			static const int polls = [] { const char *e = profile_env("GMR1_HIP_FCCH_FOLD_POLLS"); return e ? atoi(e) : 1 << 14; }();
+			static const int polls = profile_env_int("GMR1_HIP_FCCH_FOLD_POLLS", 1 << 14);
 			a.fold_polls = polls;
 			// (profiling build: GMR1_HIP_FCCH_FOLD_GIVEUP=k,r makes the tiles with tile % k == r give up as if their wait had run
 			// out, the others fold -- a stream whose tiles did not start together; a negative r counts from the stream's end)
@@ -115,7 +115,7 @@ int rough_dev(hipStream_t st, int tab, int n, int sps, int len, const float *iq,
 	}
 	// (profiling build: GMR1_HIP_FCCH_POISON=1 fills the lag / sample scratch with 0x4f bytes, about 3.5e9 a float, first: a lag
 	// that no tile wrote then decides the pick, whatever earlier calls left there)
-	static const bool poison = [] { const char *e = profile_env("GMR1_HIP_FCCH_POISON"); return e && atoi(e) != 0; }();
+	static const bool poison = profile_env_int("GMR1_HIP_FCCH_POISON", 0) != 0;
 	if (poison)
 		HIP_TRY(hipMemsetAsync(a.dec, 0x4f, b_dec, st));
 	HIP_TRY(launch_fcch_rough_tail(a, ntaps, tl, st));

@@ -1,12 +1,69 @@
-// capi_l1.cpp -- C-ABI entry points of the traffic-channel layer-1 decoders (FACCH3, TCH3).
+// capi_l1.cpp -- C-ABI entry points of the layer-1 decoders: BCCH and CCCH (l1_dev / l1_host, which the reference's
+// one-burst decode calls in capi_one.cpp go through as well), FACCH3, TCH3.
 #include "capi_common.h"
 
 #include <osmocom/gmr1/l1/facch3.h>
 #include <osmocom/gmr1/l1/tch3.h>
 
+namespace gmr1 {
+
+// BCCH / CCCH batch decode (chain: kChainBcch / kChainCcch); device pointers, then host pointers staged through HBM
+int l1_dev(hipStream_t st, int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv)
+{
+	if (n < 0 || !ebits || !l2 || !crc || !conv)
+		return fail(-EINVAL, "l1 decode: NULL argument");
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	L1Args a;
+	a.n = n; a.chain = chain; a.conv_acc = conv_acc(); a.ebits = ebits; a.l2 = l2; a.crc = crc; a.conv = conv;
+	HIP_TRY(launch_l1(a, st));
+	return 0;
+}
+
+int l1_host(int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv)
+{
+	const int neb = chain == kChainCcch ? 432 : 424;
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	if (n <= 0) return 0;
+	Stage sg;
+	const int8_t *d_eb = sg.in(ebits, (size_t)n * neb);
+	uint8_t *d_l2 = sg.out(l2, (size_t)n * 24);
+	int32_t *d_crc = sg.out(crc, (size_t)n);
+	int32_t *d_conv = sg.out(conv, (size_t)n);
+	if ((r = sg.err())) return r;
+	r = l1_dev(nullptr, chain, n, d_eb, d_l2, d_crc, d_conv);
+	if (r) return r;
+	return sg.fetch();
+}
+
+}  // namespace gmr1
+
 using namespace gmr1;
 
 extern "C" {
+
+int gmr1_hip_bcch_decode_batch_dev(void *stream, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv)
+{
+	return l1_dev((hipStream_t)stream, kChainBcch, n, ebits, l2, crc, conv);
+}
+
+int gmr1_hip_ccch_decode_batch_dev(void *stream, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv)
+{
+	return l1_dev((hipStream_t)stream, kChainCcch, n, ebits, l2, crc, conv);
+}
+
+int gmr1_hip_bcch_decode_batch(int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv)
+{
+	return l1_host(kChainBcch, n, ebits, l2, crc, conv);
+}
+
+int gmr1_hip_ccch_decode_batch(int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv)
+{
+	return l1_host(kChainCcch, n, ebits, l2, crc, conv);
+}
 
 int gmr1_hip_facch3_decode_batch_dev(void *stream, int n, const int8_t *ebits, const uint8_t *ciph,
                                      uint8_t *l2, uint8_t *bits_s, int32_t *crc, int32_t *conv)

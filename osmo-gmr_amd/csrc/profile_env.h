@@ -18,4 +18,12 @@ inline const char *profile_env(const char *name)
 #endif
 }
 
+// an integer switch: atoi of the variable, dflt where it is unset (always, in the product build).  Read it once, as
+// `static const int v = profile_env_int(...)`: the language makes that initialisation safe between threads.
+inline int profile_env_int(const char *name, int dflt)
+{
+	const char *e = profile_env(name);
+	return e ? atoi(e) : dflt;
+}
+
 }  // namespace gmr1

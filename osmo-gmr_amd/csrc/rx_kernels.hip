@@ -298,7 +298,7 @@ struct RxIo {
 // DC6 path: the two formats' numbers themselves (nb.c:36-62, 94-120) -- one sync chunk of 11 / 7 symbols at 28, two of 3
 // at 119 and 197, 234 pi/4-CQPSK symbols --, so that no phase waits for a table entry (a per-row descriptor lookup is a
 // vector load from constant memory: three dependent ones sat in front of the sync-symbol terms); the host refuses to start
-// the fused kernels unless the tables say exactly this (fused_formats_match, capi.cpp).
+// the fused kernels unless the tables say exactly this (fused_formats_match, rx_select.h).
 constexpr unsigned long long kFusedSymsBcch =      // [0 2 2 0 0 0 2 0 2 2 2 | 2 2 0 | 2 2 0], two bits each, first symbol lowest
 	0ull | 2ull << 2 | 2ull << 4 | 0ull << 6 | 0ull << 8 | 0ull << 10 | 2ull << 12 | 0ull << 14 | 2ull << 16 | 2ull << 18 | 2ull << 20 |
 	2ull << 22 | 2ull << 24 | 0ull << 26 | 2ull << 28 | 2ull << 30 | 0ull << 32;

@@ -1,5 +1,5 @@
 // The reference's one-burst calls without a launch per call: a one-wave "server" kernel that stays on the device between
-// calls and takes its requests from a mailbox in pinned host memory (rx_server_kernels.inc, capi.cpp: OneBurst).
+// calls and takes its requests from a mailbox in pinned host memory (rx_server_kernels.inc, capi_one.cpp: OneBurst).
 #pragma once
 #include "gmr1_dev.h"
 

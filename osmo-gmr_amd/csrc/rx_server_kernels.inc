@@ -12,7 +12,7 @@
 //   * It ends by itself: after idle_us without a request, after life_us in any case, or when the host has started a newer
 //     generation -- nothing here can spin for ever, and a process that dies leaves nothing behind for longer than idle_us.
 //     It leaves its generation number in `ended`; the host starts the next generation when the current one has ended
-//     (capi.cpp), on the servers' one stream, so a new one starts when the last has gone.
+//     (capi_one.cpp), on the servers' one stream, so a new one starts when the last has gone.
 
 }  // namespace gmr1 (left for the header, which opens it itself)
 #include "rx_server.h"
