@@ -71,18 +71,7 @@ __global__ __launch_bounds__(64) void k_rx_taps(RxArgs a, RxTapsOut o, int max_i
 		const int j = i * sps + d;
 		float2 x = make_float2(0.f, 0.f);
 		if (j >= 0 && j < in_len) {
-			if (!frac_on) {
-				x = L.x[j];
-			} else {
-				for (int k = 0; k < 21; k++) {
-					const int m = j + 10 - k;
-					if (m >= 0 && m < in_len) {
-						const float2 q = L.coef[k], v = L.x[m];
-						x.x = fmaf(q.x, v.x, fmaf(-q.y, v.y, x.x));
-						x.y = fmaf(q.x, v.y, fmaf(q.y, v.x, x.y));
-					}
-				}
-			}
+			x = frac_on ? delayed_sample(L, fs, j, in_len) : L.x[j];
 		}
 		const float2 al = rot(x, j);
 		o.align[i] = al;

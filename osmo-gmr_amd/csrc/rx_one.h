@@ -204,6 +204,30 @@ __device__ int sync_search(int type, int in_len, int sps_rt, float fs, const Lds
 	return p_idx;
 }
 
+// One sample of the burst behind the reference's 21-tap fractional delay (pi4cxpsk.c:310-327), less the common rotation
+// e^{j fl(fs j)}, which the callers add in the phase domain.  L.coef holds the taps with the rotation between neighbours in
+// them, p_k e^{j fs (10 - k)} (see demod_one).  The reference de-rotates sample m by the fp32 PRODUCT fs * m before it delays
+// (osmo_cxvec_sig_normalize), and hundreds of radians into a burst that product is rounded by up to 3e-5 rad, for each of the
+// 21 samples under the pulse in its own way.  In a sample tens of times weaker than its neighbours that is more than 1e-4 of
+// a soft-symbol step, so the roundings taken here are the reference's: eps = (fl(fs m) - fl(fs j)) - fs (m - j), a few 1e-5
+// at most, enters as the factor 1 + j eps.
+__device__ __forceinline__ float2 delayed_sample(const Lds &L, float fs, int j, int in_len)
+{
+	const float pj = fs * (float)j;
+	float2 acc = make_float2(0.f, 0.f);
+	for (int k = 0; k < 21; k++) {
+		const int m = j + 10 - k;
+		if (m >= 0 && m < in_len) {
+			const float2 q = L.coef[k], x = L.x[m];
+			const float eps = fmaf(-fs, (float)(10 - k), fs * (float)m - pj);
+			const float tr = fmaf(q.x, x.x, -q.y * x.y), ti = fmaf(q.x, x.y, q.y * x.x);
+			acc.x += fmaf(-eps, ti, tr);
+			acc.y += fmaf(eps, tr, ti);
+		}
+	}
+	return acc;
+}
+
 // ---------------------------------------------------------------------------
 // demodulation of one burst by one wavefront
 // returns the reference's rv (0, or -1 when no sync sequence has power)
@@ -251,7 +275,8 @@ __device__ int demod_one(int type, const float2 *__restrict__ in, int in_len, in
 	// symbol the reference first applies a 21-tap sinc fractional delay (osmo_cxvec_convolve,
 	// CONV_NO_DELAY) when |toa - d| > 0.1.  It does so on the DEROTATED burst; with
 	// g[m] = x[m] e^{j fs m} the delayed sample is e^{j fs n} sum_k (p_k e^{j fs (10-k)}) x[n+10-k], so the
-	// rotation moves into 21 complex taps and the common e^{j fs n} stays in the phase domain.
+	// rotation moves into 21 complex taps and the common e^{j fs n} stays in the phase domain (delayed_sample, which also
+	// takes over how the reference rounds fs m).
 	const float ofs_frac = p_toa - (float)d;
 	const bool frac_on = (sps < 4) && (fabsf(ofs_frac) > 0.1f);
 	if (frac_on) {
@@ -270,16 +295,7 @@ __device__ int demod_one(int type, const float2 *__restrict__ in, int in_len, in
 			return make_float2(0.f, 0.f);
 		if (!frac_on)
 			return L.x[j];
-		float2 acc = make_float2(0.f, 0.f);
-		for (int k = 0; k < 21; k++) {
-			const int m = j + 10 - k;
-			if (m >= 0 && m < in_len) {
-				const float2 q = L.coef[k], x = L.x[m];
-				acc.x = fmaf(q.x, x.x, fmaf(-q.y, x.y, acc.x));
-				acc.y = fmaf(q.x, x.y, fmaf(q.y, x.x, acc.y));
-			}
-		}
-		return acc;
+		return delayed_sample(L, fs, j, in_len);
 	};
 
 	auto reduce_2pi = [](float a) -> float {
@@ -369,11 +385,17 @@ __device__ int demod_one(int type, const float2 *__restrict__ in, int in_len, in
 	if (dbg_stop == 5) return -100;
 
 	// ---- soft symbols + soft bits (pi4cxpsk.c:442-503) ------------------------------
-	constexpr int NSYM = NPL > 16 ? 8 : 4;       // 4 x 64 >= 234, 8 x 64 >= 468
+	// one symbol per lane and piece, pieces for the longest format whatever the window: a burst of more than 256 symbols fits a
+	// window of 1024 samples or fewer at 1 and 2 samples per symbol (NT9 and RACH, 351 symbols, DC12, 468); a piece beyond the
+	// burst's length costs its test
+	constexpr int NSYM = (kMaxLen + 63) / 64;
+	static_assert(NSYM * 64 >= kMaxLen, "the soft-symbol loop covers every format's length");
 	const float inv_dd = (float)(1 << nbits) / (2.0f * kPif);
 	const int mask = (1 << nbits) - 1;
 #pragma unroll
 	for (int r = 0; r < NSYM; r++) {
+		if (64 * r >= blen)
+			break;                                   // (wave-uniform: the pieces beyond the burst are jumped over)
 		const int i = lane + 64 * r;
 		if (i >= blen)
 			continue;
