@@ -392,7 +392,9 @@ int gmr1_hip_fcch_acquire_batch(int fcch_type, int n, int sps, const float *iq, 
  * low_pass(1, 1, .45 / decim2, .1 / decim2)), pfb.arb_resampler_ccf(resamp, root_raised_cosine(32, ..., 0.35), 32) -- the
  * split chosen as the script's _select_decim does (2.0 Msps: 7, 6, 1.9656).  out: n_sel streams of *n_out complex64 at
  * 23400 x sps, out_stride complex samples apart.  -EINVAL for rates the reference itself cannot run (an exact multiple
- * of 23400 x sps) or whose resampler is longer than the kernel holds (e.g. 1.0 Msps: rate 0.468). */
+ * of 23400 x sps), whose resampler has more than 96 taps per phase, or whose 64 output phases of a wave span more input
+ * than the kernel's window for that bank holds (1.0 and 1.5 Msps at sps 1: 636 and 602 samples against 512) -- from the
+ * plan, the one-shot calls and gmr1_hip_ddc_stream_create alike, before anything is launched. */
 int gmr1_hip_ddc_plan(double samp_rate, int sps, uint64_t n_in, int32_t *decim1, int32_t *decim2, double *resamp,
                       uint64_t *n_out);
 int gmr1_hip_ddc_dev(void *stream, double samp_rate, int sps, const float *wide, uint64_t n_in, int n_sel,

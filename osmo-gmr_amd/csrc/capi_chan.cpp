@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/gmr1_hip.h"
+#include "chan_select.h"
 
 using namespace gmr1;
 
@@ -336,6 +337,13 @@ int get_ddc_plan(double samp_rate, int sps, const DdcPlan **out)
 		return fail(-EINVAL, "ddc: the sample rate must be a whole number of Hz");
 	const long long g = gcdll(num, den);
 	p.num = num / g; p.den = den / g;
+	// the 64 output phases of a wave must fit the window its tap bank gets (chan_select.h: the launchers' own rule, so that
+	// plan, one-shot call and stream refuse the same plans, here and not at the first launch): 1.0 and 1.5 Msps at sps 1
+	int span = 0;
+	if (!resamp_plan_runs(p.num, p.den, kNfilt, kBankTaps, &span))
+		return fail(-EINVAL, "ddc: %.1f samples/s at sps %d: the resampler (rate %.4f, %d taps per phase) spans %d input samples "
+		                     "per wave, the kernel's window holds %d", samp_rate, sps, resamp, p.tpf, span,
+		            kBankTaps == kRsTapsLong ? kRsWinLong : kRsWinShort);
 	std::vector<float2> bank((size_t)kNfilt * kBankTaps, make_float2(0.f, 0.f));
 	for (int j = 0; j < kNfilt; j++)
 		for (int k = 0; k < p.tpf; k++) {

@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <mutex>
 #include "gmr1_dev.h"
+#include "chan_select.h"
 #include "fast_math.h"
 #include "profile_env.h"
 
@@ -413,13 +414,8 @@ hipError_t launch_pfb(const PfbArgs &a, hipStream_t stream)
 // which the wave stages with coalesced loads one period ahead.  Single-wavefront work-groups, no
 // s_barrier; outputs of a wave are 64 consecutive samples = one 512-byte store.
 // ---------------------------------------------------------------------------
-// taps per filter: 30 for the 941-tap / 32-phase bank of every plan that raises the rate; the direct mode at 1.0 Msps
-// resamples DOWN (rate 0.468) and its root-raised cosine is 95 taps per phase long -- a second instantiation
-static constexpr int kRsTapsShort = 30, kRsTapsLong = 96;
-static constexpr int kRsPeriods = 32;        // periods one wave walks
-static constexpr int kRsPeriodsStream = 4;   // ... in a streamed push (a small grid: the walk is the push's time)
+// (tap banks, windows and periods per wave: chan_select.h, with the rule that picks among the forms below)
 static constexpr int kRsRing = 8;            // k_resamp2: ring slots of one period's window each (seven periods in flight)
-static constexpr int kRsWinTight = 128, kRsWinShort = 256, kRsWinLong = 512;     // LDS window (samples) per wave, >= span
 
 // acc += e (s.re, s.im) for the real tap e that sits in the LOW (HI = false) or HIGH half of the register pair `ee`: one
 // v_pk_fma_f32 with the half picked by the operand selects.  The compiler's own code for the two scalar chains
@@ -841,7 +837,6 @@ void k_resamp2(ResampArgs a, long long P, long long Q, int span)
 //   * Every wave issues exactly one DMA per period (the vmcnt arithmetic of k_resamp2): waves without a chunk fetch into
 //     a dump slot.  Waves beyond the period's last output group still fetch and count as producers; they skip the rest.
 // ---------------------------------------------------------------------------
-static constexpr int kRsWg = 8;              // waves of a k_resamp2w work-group
 static constexpr int kRsAhead = 4;           // periods its chunks are asked for ahead of their use
 
 __device__ __forceinline__ unsigned rsw_peek(unsigned addr)
@@ -1189,124 +1184,96 @@ hipError_t launch_ddc_fir(const DdcFirArgs &a, hipStream_t stream)
 	return hipGetLastError();
 }
 
-static hipError_t launch_resamp_stream(const ResampArgs &a, hipStream_t stream);
+// the rule's inputs of a launch (chan_select.h); the profiling build's switches are read here
+static ResampQuery resamp_query(const ResampArgs &a)
+{
+	static const bool one_only = []{ const char *e = profile_env("GMR1_HIP_RESAMP_R"); return e && atoi(e) == 1; }();
+	static const bool shared_ring = profile_env("GMR1_HIP_RESAMP_WG") != nullptr;
+	static const bool wg1 = profile_env("GMR1_HIP_RESAMP_WG1") != nullptr;
+	ResampQuery q;
+	q.num = a.num; q.den = a.den; q.nfilt = a.nfilt; q.tpf = a.tpf; q.T = a.T; q.n_out = a.n_out; q.n_slots = a.n_slots;
+	q.planar = a.planar_sps > 0;
+	q.stream = a.st.xt != nullptr;
+	q.ext = a.rotation != 0.0f || (!q.stream && q.planar);
+	q.o0 = a.st.o0;
+	q.one_only = one_only; q.shared_ring = shared_ring; q.wg1 = wg1;
+	return q;
+}
+
+static hipError_t launch_resamp_stream(const ResampArgs &a, const ResampChoice &c, hipStream_t stream);
 
 hipError_t launch_resamp(const ResampArgs &a, hipStream_t stream)
 {
-	if (a.st.xt)
-		return launch_resamp_stream(a, stream);
-	if (a.n_out <= 0 || a.n_slots <= 0)
+	const ResampChoice c = resamp_choice(resamp_query(a));
+	if (c.form == kRsFormNone)
 		return hipSuccess;
-	const bool lng = a.tpf == kRsTapsLong;
-	if (a.tpf != kRsTapsShort && !lng)
+	if (c.form == kRsFormRefused)
 		return hipErrorInvalidValue;
-	const int taps = lng ? kRsTapsLong : kRsTapsShort, win = lng ? kRsWinLong : kRsWinShort;
-	long long g = a.num, b = a.den * a.nfilt;
-	while (b) { const long long t = g % b; g = b; b = t; }
-	const long long P = a.den * a.nfilt / g, Q = a.num / g;
-	// inputs the 64 phases of a wave can touch
-	const int span = (int)((63 * a.num) / (a.den * a.nfilt)) + taps + 2;
-	if (span > win)
-		return hipErrorInvalidValue;
-	const long long periods = (a.n_out + P - 1) / P;
-	const unsigned gx = (unsigned)((P + 63) / 64), gz = (unsigned)((periods + kRsPeriods - 1) / kRsPeriods);
+	if (a.st.xt)
+		return launch_resamp_stream(a, c, stream);
+	const long long P = c.P, Q = c.Q;
+	const dim3 grid(c.gx, c.gy, c.gz);
 	const bool ext = a.rotation != 0.0f || a.planar_sps > 0;
-	// two consecutive outputs per lane where the rate goes up (their windows then start at most one sample apart) and the
-	// 128 phases of a wave still fit the tight window (profiling build: GMR1_HIP_RESAMP_R=1 keeps one output per lane)
-	static const bool one_only = []{ const char *e = profile_env("GMR1_HIP_RESAMP_R"); return e && atoi(e) == 1; }();
-	const int span_r = (int)((127 * a.num) / (a.den * a.nfilt)) + taps + 2;
-	const int multi_r = (!lng && !ext && !one_only && a.num < a.den * a.nfilt && span_r <= kRsWinTight && P >= 2 && a.T >= 2) ? 2 : 1;
-	if (lng && ext)
-		return hipErrorInvalidValue;             // (the long bank is the direct mode's: neither option reaches it)
-	if (lng)
-		hipLaunchKernelGGL((k_resamp<kRsTapsLong, kRsWinLong>), dim3(gx, (unsigned)a.n_slots, gz), dim3(64), 0, stream, a, P, Q, span);
-	else if (ext && span <= kRsWinTight)
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, true>), dim3(gx, (unsigned)a.n_slots, gz), dim3(64), 0, stream, a, P, Q, span);
-	else if (ext)
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, true>), dim3(gx, (unsigned)a.n_slots, gz), dim3(64), 0, stream, a, P, Q, span);
-	else if (multi_r > 1) {
-		// one window ring per work-group of kRsWg waves where the union of their windows is fewer chunks than they are and
-		// the period has at least that many output groups (k_resamp2w); else a ring per wave
-		const long long gx2 = (P + 127) / 128;
-		const int span_w = (int)(((long long)(kRsWg * 128 - 1) * a.num) / (a.den * a.nfilt)) + taps + 2;
-		const int nch = (span_w + 127) / 128;
-		// (measured slower than a ring per wave -- 0.47-0.50 against 0.42 ms with 0.78 against 1.43 GB fetched: DESIGN 4.7 --, so
-		// only the profiling build runs it, on request)
-		static const bool shared_ring = profile_env("GMR1_HIP_RESAMP_WG") != nullptr;
-		if (shared_ring && nch < kRsWg && gx2 >= kRsWg) {
-			const size_t lds_w = ((size_t)kRsRing * (nch * 128 + 4) + 128) * sizeof(float2);
-			static std::mutex mu;
-			static bool told[64] = {};
-			int dev = 0;
-			if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-				return hipErrorInvalidDevice;
-			{
-				std::lock_guard<std::mutex> lk(mu);
-				if (!told[dev]) {
-					const hipError_t e = hipFuncSetAttribute((const void *)k_resamp2w<kRsRing>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)kRsRing * (kRsWg * 128 + 4) + 128) * sizeof(float2)));
-					if (e != hipSuccess)
-						return e;
-					told[dev] = true;
-				}
+	if (c.form == kRsFormTwoShared) {
+		// one window ring per work-group of kRsWg waves (k_resamp2w): measured slower than a ring per wave -- 0.47-0.50 against
+		// 0.42 ms with 0.78 against 1.43 GB fetched: DESIGN 4.7 --, so only the profiling build runs it, on request
+		const size_t lds_w = ((size_t)kRsRing * (c.nch * 128 + 4) + 128) * sizeof(float2);
+		static std::mutex mu;
+		static bool told[64] = {};
+		int dev = 0;
+		if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+			return hipErrorInvalidDevice;
+		{
+			std::lock_guard<std::mutex> lk(mu);
+			if (!told[dev]) {
+				const hipError_t e = hipFuncSetAttribute((const void *)k_resamp2w<kRsRing>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)kRsRing * (kRsWg * 128 + 4) + 128) * sizeof(float2)));
+				if (e != hipSuccess)
+					return e;
+				told[dev] = true;
 			}
-			hipLaunchKernelGGL((k_resamp2w<kRsRing>), dim3((unsigned)((gx2 + kRsWg - 1) / kRsWg), (unsigned)a.n_slots, gz), dim3(64 * kRsWg), lds_w, stream, a, P, Q, nch);
-		} else {
-			// eight consecutive output groups per work-group (each wave its own ring, nothing synchronised): the same time as a
-			// wave per work-group, 750 MB fetched instead of 1 426 MB (profiles/r06aq; the profiling build keeps the other form:
-			// GMR1_HIP_RESAMP_WG1=1)
-			// (the largest of 8, 4, 2 groups that divides the period's groups: a work-group's LDS is its waves' rings whether or
-			// not they have an output group, so a part-filled one would cost residency)
-			static const bool wg1 = profile_env("GMR1_HIP_RESAMP_WG1") != nullptr;
-			const int wgw = wg1 ? 1 : (gx2 % 8 == 0 ? 8 : (gx2 % 4 == 0 ? 4 : (gx2 % 2 == 0 ? 2 : 1)));
-			const dim3 grid2((unsigned)(gx2 / wgw), (unsigned)a.n_slots, gz);
-			if (wgw == 8)
-				hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing, 8>), grid2, dim3(64 * 8), 0, stream, a, P, Q, span_r);
-			else if (wgw == 4)
-				hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing, 4>), grid2, dim3(64 * 4), 0, stream, a, P, Q, span_r);
-			else if (wgw == 2)
-				hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing, 2>), grid2, dim3(64 * 2), 0, stream, a, P, Q, span_r);
-			else
-				hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing>), grid2, dim3(64), 0, stream, a, P, Q, span_r);
 		}
-	}
-
-	else if (span <= kRsWinTight)
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight>), dim3(gx, (unsigned)a.n_slots, gz), dim3(64), 0, stream, a, P, Q, span);
+		hipLaunchKernelGGL((k_resamp2w<kRsRing>), grid, dim3(64 * kRsWg), lds_w, stream, a, P, Q, c.nch);
+	} else if (c.form == kRsFormTwo) {
+		// eight consecutive output groups per work-group (each wave its own ring, nothing synchronised): the same time as a
+		// wave per work-group, 750 MB fetched instead of 1 426 MB (profiles/r06aq; the profiling build keeps the other form:
+		// GMR1_HIP_RESAMP_WG1=1)
+		if (c.wg == 8)
+			hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing, 8>), grid, dim3(64 * 8), 0, stream, a, P, Q, c.span_r);
+		else if (c.wg == 4)
+			hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing, 4>), grid, dim3(64 * 4), 0, stream, a, P, Q, c.span_r);
+		else if (c.wg == 2)
+			hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing, 2>), grid, dim3(64 * 2), 0, stream, a, P, Q, c.span_r);
+		else
+			hipLaunchKernelGGL((k_resamp2<kRsWinTight, kRsRing>), grid, dim3(64), 0, stream, a, P, Q, c.span_r);
+	} else if (c.taps == kRsTapsLong)
+		hipLaunchKernelGGL((k_resamp<kRsTapsLong, kRsWinLong>), grid, dim3(64), 0, stream, a, P, Q, c.span);
+	else if (ext && c.win == kRsWinTight)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, true>), grid, dim3(64), 0, stream, a, P, Q, c.span);
+	else if (ext)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, true>), grid, dim3(64), 0, stream, a, P, Q, c.span);
+	else if (c.win == kRsWinTight)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight>), grid, dim3(64), 0, stream, a, P, Q, c.span);
 	else
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort>), dim3(gx, (unsigned)a.n_slots, gz), dim3(64), 0, stream, a, P, Q, span);
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort>), grid, dim3(64), 0, stream, a, P, Q, c.span);
 	return hipGetLastError();
 }
 
 // the outputs [st.o0, n_out) of a streamed run: k_resamp's STREAM instantiations, periods from the one st.o0 falls in
-static hipError_t launch_resamp_stream(const ResampArgs &a, hipStream_t stream)
+static hipError_t launch_resamp_stream(const ResampArgs &a, const ResampChoice &c, hipStream_t stream)
 {
-	if (a.n_out <= a.st.o0 || a.n_slots <= 0)
-		return hipSuccess;
-	const bool lng = a.tpf == kRsTapsLong;
-	if ((a.tpf != kRsTapsShort && !lng) || a.st.o0 < 0 || a.planar_sps > 0)
-		return hipErrorInvalidValue;
-	const int taps = lng ? kRsTapsLong : kRsTapsShort, win = lng ? kRsWinLong : kRsWinShort;
-	long long g = a.num, b = a.den * a.nfilt;
-	while (b) { const long long t = g % b; g = b; b = t; }
-	const long long P = a.den * a.nfilt / g, Q = a.num / g;
-	const int span = (int)((63 * a.num) / (a.den * a.nfilt)) + taps + 2;
-	if (span > win)
-		return hipErrorInvalidValue;
-	const long long periods = (a.n_out + P - 1) / P - a.st.o0 / P;
-	const dim3 grid((unsigned)((P + 63) / 64), (unsigned)a.n_slots, (unsigned)((periods + kRsPeriodsStream - 1) / kRsPeriodsStream));
+	const long long P = c.P, Q = c.Q;
+	const dim3 grid(c.gx, c.gy, c.gz);
 	const bool rot = a.rotation != 0.0f;
-	if (lng && rot)
-		return hipErrorInvalidValue;
-	if (lng)
-		hipLaunchKernelGGL((k_resamp<kRsTapsLong, kRsWinLong, false, true>), grid, dim3(64), 0, stream, a, P, Q, span);
-	else if (rot && span <= kRsWinTight)
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, true, true>), grid, dim3(64), 0, stream, a, P, Q, span);
+	if (c.taps == kRsTapsLong)
+		hipLaunchKernelGGL((k_resamp<kRsTapsLong, kRsWinLong, false, true>), grid, dim3(64), 0, stream, a, P, Q, c.span);
+	else if (rot && c.win == kRsWinTight)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, true, true>), grid, dim3(64), 0, stream, a, P, Q, c.span);
 	else if (rot)
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, true, true>), grid, dim3(64), 0, stream, a, P, Q, span);
-	else if (span <= kRsWinTight)
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, false, true>), grid, dim3(64), 0, stream, a, P, Q, span);
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, true, true>), grid, dim3(64), 0, stream, a, P, Q, c.span);
+	else if (c.win == kRsWinTight)
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinTight, false, true>), grid, dim3(64), 0, stream, a, P, Q, c.span);
 	else
-		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, false, true>), grid, dim3(64), 0, stream, a, P, Q, span);
+		hipLaunchKernelGGL((k_resamp<kRsTapsShort, kRsWinShort, false, true>), grid, dim3(64), 0, stream, a, P, Q, c.span);
 	return hipGetLastError();
 }
 

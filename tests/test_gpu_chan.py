@@ -193,6 +193,20 @@ def test_direct_mode_refusals(gpu_api):
     # phase and the kernel's long instantiation holds 96)
     d1, d2, rs, _ = gpu_api.ddc_plan(1.5e6, 4, 100000)
     assert (d1, d2) == (8, 1) and abs(rs - 0.4992) < 1e-9
+    # ... but a plan is refused where the 64 output phases of a wave span more input than the window its tap bank gets
+    # (csrc/chan_select.h): at sps 1 the 96-tap plans step 8.5 (1.0 Msps) and 8.0 (1.5 Msps) inputs per output, 636 and 602
+    # samples against 512 -- by the plan, by the one-shot call before it launches anything, and (test_gpu_chan_stream.py) by
+    # the stream; the message names rate, sps and span
+    x = np.zeros(50000, np.complex64)
+    for fs, span in ((1.0e6, 636), (1.5e6, 602)):
+        with pytest.raises(gpu_api.Gmr1HipError, match="-22") as e:
+            gpu_api.ddc_plan(fs, 1, 100000)
+        msg = str(e.value)
+        assert "%.1f" % fs in msg and "sps 1" in msg and "spans %d" % span in msg, msg
+        with pytest.raises(gpu_api.Gmr1HipError, match="-22"):
+            gpu_api.ddc(x, fs, [0.0, 31250.0], sps=1)
+        d1, d2, rs, n_out = gpu_api.ddc_plan(fs, 2, 50000)       # sps 2 runs: spans 367 and 350
+        assert gpu_api.ddc(x, fs, [0.0], sps=2).shape == (1, n_out)
 
 
 def test_direct_mode_decodes_end_to_end(gpu_api, pkg):

@@ -204,6 +204,13 @@ def test_refusals_leave_the_stream_as_it_was(gpu_api):
         gpu_api.ChanStream(1.9e6 + 0.5, [1])              # off the grid and not a whole number of Hz
     with pytest.raises(gpu_api.Gmr1HipError, match="-22"):
         gpu_api.ChanStream.direct(23400.0 * 4 * 20, [0.0])  # an exact multiple of 23400 x sps: the reference cannot run it
+    # plans whose resampler spans more than its window (csrc/chan_select.h) are refused when the handle is made, as the plan
+    # and the one-shot call refuse them (test_direct_mode_refusals), not at the first push that has an output
+    for fs in (1.0e6, 1.5e6):
+        with pytest.raises(gpu_api.Gmr1HipError, match="-22"):
+            gpu_api.ChanStream.direct(fs, [0.0, 31250.0], sps=1)
+        with gpu_api.ChanStream.direct(fs, [0.0, 31250.0], sps=2) as cs:
+            assert cs.out_len(50000) == gpu_api.ddc_plan(fs, 2, 50000)[3]
     n = 200000 + 11
     x = _capture(n, FS, 41)
     ref = gpu_api.channelize(x, FS, [5, 40])
