@@ -35,6 +35,7 @@
  *   gmr1_hip_fcch_snr_batch*     -> gmr1_fcch_snr         include/osmocom/gmr1/sdr/fcch.h:59-61
  *   gmr1_hip_fcch_acquire_batch* -> fcch_single_init / fcch_multi_process  src/gmr1_rx.c:605-733 (up to the survivor list)
  *   gmr1_hip_tch3_follow_batch*  -> rx_tch3, src/gmr1_rx.c:355-600
+ *   gmr1_hip_tch9_follow*_batch* -> rx_tch9, src/gmr1_rx.c:262-353
  */
 #ifndef GMR1_HIP_H
 #define GMR1_HIP_H
@@ -80,7 +81,7 @@ struct gmr1_hip_burst_flat {
  * Threads: gmr1_hip_last_error() is per thread; the burst-level _batch / _batch_dev calls keep no state
  * between calls and may run from several threads on different streams.  The calls that use the library's
  * grow-only per-device workspace -- gmr1_hip_fcch_rough*_batch*, gmr1_hip_fcch_acquire_batch*, gmr1_hip_channelize*, gmr1_hip_ddc*,
- * gmr1_hip_rx_run*, gmr1_hip_tch3_follow_batch*, gmr1_hip_detect_batch* with more than four candidates, and gmr1_hip_tch3_rx_batch* where it
+ * gmr1_hip_rx_run*, gmr1_hip_tch3_follow_batch*, gmr1_hip_tch9_follow*_batch*, gmr1_hip_detect_batch* with more than four candidates, and gmr1_hip_tch3_rx_batch* where it
  * runs as two launches without a caller's soft-bit buffer -- may ALSO be called from several threads and streams:
  * they take turns.  The host part of such a call runs under a per-device lock (a second thread waits), and a call
  * on another stream first makes its stream wait, on the device, for the previous user's kernels; nothing is
@@ -650,6 +651,76 @@ int gmr1_hip_tch3_follow_batch(int n_calls, int sps, int in_len, const float *iq
                                const int32_t *first, int n_frames,
                                const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                                struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
+
+/* ---- following a circuit-switched data call: rx_tch9 over many calls at once (gmr1_rx.c:262-353) -------------
+ * What gmr1_rx does per frame once an ASSIGNMENT COMMAND 1 has named a timeslot on the CSD carrier: demodulate the NT9
+ * burst, sync sequence 0 -> FACCH9, any other -> TCH9, decipher with A5/1 of the frame number (always) and decode; a TCH9
+ * block is decoded against the call's two previous TCH9 bursts (the depth-3 inter-burst de-interleaver, which only
+ * advances on TCH9 bursts).  The state of a call is the caller's, as for the TCH3 follower above: it goes in and comes
+ * back, and a call cut into any pieces gives byte for byte what one invocation gives.  Calls and frames are laid out as
+ * there (first[0] = 0, first[n_calls] = n_frames, non-decreasing); one record per frame handed in comes back at out[k].
+ *
+ * The bits form IS the follower: frame k is ebits[662 k ..] (the demodulator's soft bits), sync_id[k], rv[k] (the
+ * demodulator's return value; NULL: all 0) and fn[k].  The from-samples form demodulates frame k's window
+ * iq[offset[k] .. offset[k] + in_len) as an NT9 burst (in_len >= 351*sps, <= GMR1_HIP_MAX_IN_LEN; gmr1_rx cuts
+ * 351*sps + sps + sps/2, which fits up to sps 11) with freq_shift[k] into scratch and runs the bits form on it.  Both are
+ * entries because the reference's sync search keeps its correlation sums from one sync sequence to the next
+ * (pi4cxpsk.c:207-253), so an NT9 burst sent with sequence 0 is reported as 1: through the demodulator the FACCH9 route is
+ * practically unreachable, and a caller with a demodulator of its own wants the bits form anyway.
+ * mode: enum gmr1_tch9_mode (0 2k4, 1 4k8, 2 9k6; gmr1_rx hard-codes 9k6), one per invocation; the state does not depend
+ * on it.  In both Viterbi decoder modes (gmr1_hip_set_conv_decoder) payloads and conv follow the selected mode.
+ *
+ * _dev: every pointer is device memory; the call enqueues on `stream` and returns -- no copy to the host and no
+ * synchronisation (but for the workspace that has to grow); the entries of first are clamped to 0..n_frames.  The host
+ * forms copy the arrays in, state and out back, and also check first and the windows.  n_calls == 0 or n_frames == 0 does
+ * nothing; a call without frames keeps its state byte for byte.  -EINVAL, before anything is written and before the device
+ * is asked for: a negative count, a NULL array (rv excepted), mode outside 0..2, sps outside 1..16, in_len out of range,
+ * iq not aligned to 8 bytes.  -ENODEV without a device. */
+struct gmr1_hip_tch9_state {        /* struct tch9_state of gmr1_rx.c:82-91 plus the key; all-zero = no call; 1340 bytes */
+	int32_t active;             /* 0: every frame is GMR1_HIP_TCH9_OFF and nothing changes */
+	int32_t n_held;             /* TCH9 bursts the de-interleaver still needs: 0, 1 or 2 (saturates at 2) */
+	uint8_t kc[8];              /* the call's key (A5/1 is always applied, gmr1_rx.c:310, 326) */
+	int8_t  held[2 * 662];      /* [0..661] the previous TCH9 burst, [662..1323] the one before it: soft bits in
+	                               bits_e order AFTER deciphering (what tch9.c:152-160 leaves, status bits in place);
+	                               slots >= n_held are 0.  A key changed between invocations does not touch them */
+};
+
+enum { GMR1_HIP_TCH9_OFF = 0, GMR1_HIP_TCH9_FACCH9, GMR1_HIP_TCH9_TCH9, GMR1_HIP_TCH9_ERR };
+
+struct gmr1_hip_tch9_frame {        /* one per frame handed in, in the order handed in; 80 bytes */
+	uint8_t  cls;               /* enum above; ERR: the demodulation refused the window (rv != 0): no burst, the
+	                               de-interleaver does not advance (decision D8) */
+	uint8_t  type;              /* 0 nothing to report | 0x1a FACCH9 whose CRC passed | 0x18 a TCH9 block (always) */
+	uint8_t  len;               /* 0 | 38 | 18 / 30 / 60 by mode */
+	uint8_t  crc;               /* FACCH9: 0 pass, 1 fail; otherwise 0 */
+	uint32_t fn;                /* the frame's fn (every frame) */
+	int32_t  conv;              /* the decoder's value for every FACCH9 / TCH9 frame, CRC passed or not; else 0 */
+	uint8_t  l2[64];            /* beyond len: 0; a FACCH9 whose CRC failed: all 0 */
+	uint8_t  pad[4];            /* 0 */
+};
+
+/* rx_tch9_init (gmr1_rx.c:263-274) on a caller-held state: active = 1, n_held = 0, held cleared; kc stays.  Host
+ * arithmetic, needs no device.  -EINVAL: s is NULL. */
+int gmr1_hip_tch9_state_assign(struct gmr1_hip_tch9_state *s);
+/* The same on states in device memory: for j < n what gmr1_hip_tch9_state_assign(&state[call[j]]) does (call[j] < 0 is
+ * skipped, a call may be named twice).  call and state are device memory; enqueues on `stream` and returns.  -EINVAL:
+ * n < 0 or a NULL array; -ENODEV without a device. */
+int gmr1_hip_tch9_state_assign_batch_dev(void *stream, int n, const int32_t *call, struct gmr1_hip_tch9_state *state);
+
+int gmr1_hip_tch9_follow_bits_batch_dev(void *stream, int n_calls, int mode, const int32_t *first /* n_calls + 1 */,
+                                        int n_frames, const int8_t *ebits /* n_frames x 662 */, const int32_t *sync_id,
+                                        const int32_t *rv /* or NULL: all 0 */, const uint32_t *fn,
+                                        struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out);
+int gmr1_hip_tch9_follow_bits_batch(int n_calls, int mode, const int32_t *first, int n_frames, const int8_t *ebits,
+                                    const int32_t *sync_id, const int32_t *rv, const uint32_t *fn,
+                                    struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out);
+int gmr1_hip_tch9_follow_batch_dev(void *stream, int n_calls, int sps, int in_len, int mode, const float *iq,
+                                   const int32_t *first, int n_frames, const uint64_t *offset, const float *freq_shift,
+                                   const uint32_t *fn, struct gmr1_hip_tch9_state *state,
+                                   struct gmr1_hip_tch9_frame *out);
+int gmr1_hip_tch9_follow_batch(int n_calls, int sps, int in_len, int mode, const float *iq, uint64_t iq_len,
+                               const int32_t *first, int n_frames, const uint64_t *offset, const float *freq_shift,
+                               const uint32_t *fn, struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out);
 
 /* The whole application: gmr1_rx with all its optional arguments (tch.cfile, key, tch_csd.cfile; gmr1_rx.c:897-975).
  * csd holds, per carrier, the carrier of the TCH9 (circuit switched data) channel an ASSIGNMENT COMMAND 1

@@ -124,6 +124,12 @@ SIGNATURES = {
     "gmr1_hip_tch3_state_assign_batch_dev": (I, P, I, P, P, P, P),
     "gmr1_hip_tch3_follow_batch_dev": (I, P, I, I, I, P, P, I, P, P, P, P, P),
     "gmr1_hip_tch3_follow_batch": (I, I, I, I, P, U64, P, I, P, P, P, P, P),
+    "gmr1_hip_tch9_state_assign": (I, P),
+    "gmr1_hip_tch9_state_assign_batch_dev": (I, P, I, P, P),
+    "gmr1_hip_tch9_follow_bits_batch_dev": (I, P, I, I, P, I, P, P, P, P, P, P),
+    "gmr1_hip_tch9_follow_bits_batch": (I, I, I, P, I, P, P, P, P, P, P),
+    "gmr1_hip_tch9_follow_batch_dev": (I, P, I, I, I, I, P, P, I, P, P, P, P, P),
+    "gmr1_hip_tch9_follow_batch": (I, I, I, I, I, P, U64, P, I, P, P, P, P, P),
     "gmr1_hip_rx_run_full_dev": (I, P, I, I, P, P, P, P, P, P, P, P, I, P, P, I, P, P, P),
     "gmr1_hip_rx_run_full": (I, I, I, P, P, P, U64, P, P, P, P, P, I, P, P, I, P, P, P),
     "gmr1_hip_codec_state_bytes": (SZ,),
@@ -689,6 +695,73 @@ def tch3_follow_dev(stream, n_calls, n_frames, iq, first, offset, freq_shift, fn
     updated in place; out: n_frames x TCH3_FRAME.itemsize bytes."""
     _call("gmr1_hip_tch3_follow_batch_dev", stream, n_calls, sps, tch3_in_len(sps) if in_len is None else in_len, iq, first,
           n_frames, offset, freq_shift, fn, state, out)
+
+
+# ---------------------------------------------------------------------------
+# following a circuit-switched data call (rx_tch9)
+# ---------------------------------------------------------------------------
+TCH9_OFF, TCH9_FACCH9, TCH9_TCH9, TCH9_ERR = range(4)
+
+
+# struct gmr1_hip_tch9_state and struct gmr1_hip_tch9_frame (include/gmr1_hip.h) for arrays of them
+TCH9_STATE = np.dtype([("active", "<i4"), ("n_held", "<i4"), ("kc", "u1", (8,)), ("held", "i1", (1324,))])
+TCH9_FRAME = np.dtype([("cls", "u1"), ("type", "u1"), ("len", "u1"), ("crc", "u1"), ("fn", "<u4"), ("conv", "<i4"),
+                       ("l2", "u1", (64,)), ("pad", "u1", (4,))])
+
+
+def tch9_in_len(sps):
+    """The window rx_tch9 cuts for a frame (gmr1_rx.c:290-291): an NT9 burst and sps + sps/2 samples of search room."""
+    return 351 * sps + sps + sps // 2
+
+
+def tch9_state_assign(state, index=0):
+    """rx_tch9_init on state[index] of a TCH9_STATE array (in place; host arithmetic, needs no device) -> state."""
+    assert state.dtype == TCH9_STATE and state.flags.c_contiguous and state.flags.writeable
+    _call("gmr1_hip_tch9_state_assign", state.ctypes.data + index * TCH9_STATE.itemsize)
+    return state
+
+
+def tch9_state_assign_batch_dev(stream, n, call, state):
+    """rx_tch9_init on device-resident states (addresses): entry j < n assigns state[call[j]]; enqueues on `stream`."""
+    _call("gmr1_hip_tch9_state_assign_batch_dev", stream, n, call, state)
+
+
+def tch9_follow_bits(first, ebits, sync_id, fn, state, rv=None, mode=2):
+    """rx_tch9 behind the demodulator over the frames of len(first) - 1 calls: frame k is ebits[k] (662 soft bits),
+    sync_id[k], rv[k] (None: all 0), fn[k].  -> (TCH9_FRAME record per frame, the calls' TCH9_STATE after them); `state`
+    itself is left as it is."""
+    first, ebits = _arr(first, np.int32), _arr(ebits, np.int8, (-1, 662))
+    sync_id, rv, fn = _arr(sync_id, np.int32), _arr(rv, np.int32), _arr(fn, np.uint32)
+    state = np.array(state, TCH9_STATE, ndmin=1)
+    out = np.zeros(ebits.shape[0], TCH9_FRAME)
+    _call("gmr1_hip_tch9_follow_bits_batch", first.size - 1, mode, _p(first), ebits.shape[0], _p(ebits), _p(sync_id), _p(rv),
+          _p(fn), _p(state), _p(out))
+    return out, state
+
+
+def tch9_follow_bits_dev(stream, n_calls, n_frames, first, ebits, sync_id, rv, fn, state, out, mode=2):
+    """The same on device memory (addresses; rv may be None): enqueues on `stream` and returns; state: n_calls x
+    TCH9_STATE.itemsize bytes, updated in place; out: n_frames x TCH9_FRAME.itemsize bytes."""
+    _call("gmr1_hip_tch9_follow_bits_batch_dev", stream, n_calls, mode, first, n_frames, ebits, sync_id, rv, fn, state, out)
+
+
+def tch9_follow(iq, first, offset, freq_shift, fn, state, sps=4, in_len=None, mode=2):
+    """rx_tch9 from samples: frame k's window is iq[offset[k] : offset[k] + in_len], demodulated as an NT9 burst with
+    freq_shift[k].  -> (TCH9_FRAME record per frame, the calls' TCH9_STATE after them)."""
+    iq = _arr(iq, np.complex64, -1)
+    first, offset = _arr(first, np.int32), _arr(offset, np.uint64)
+    freq_shift, fn = _arr(freq_shift, np.float32), _arr(fn, np.uint32)
+    state = np.array(state, TCH9_STATE, ndmin=1)
+    out = np.zeros(offset.size, TCH9_FRAME)
+    _call("gmr1_hip_tch9_follow_batch", first.size - 1, sps, tch9_in_len(sps) if in_len is None else in_len, mode, _p(iq),
+          iq.size, _p(first), offset.size, _p(offset), _p(freq_shift), _p(fn), _p(state), _p(out))
+    return out, state
+
+
+def tch9_follow_dev(stream, n_calls, n_frames, iq, first, offset, freq_shift, fn, state, out, sps=4, in_len=None, mode=2):
+    """The same on device memory (addresses): enqueues on `stream` and returns."""
+    _call("gmr1_hip_tch9_follow_batch_dev", stream, n_calls, sps, tch9_in_len(sps) if in_len is None else in_len, mode, iq,
+          first, n_frames, offset, freq_shift, fn, state, out)
 
 
 # ---------------------------------------------------------------------------

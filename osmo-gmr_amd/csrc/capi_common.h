@@ -91,6 +91,9 @@ int rx_run_dev_counted(void *stream, int n_arfcn, int sps, const float *iq, cons
 int tch9_runs_dev_impl(hipStream_t st, int mode, int n, const int32_t *seq_pos, const int8_t *ebits, const uint8_t *ciph,
                        uint8_t *l2, int32_t *conv);
 
+// what an NT9 decoder launch of one kind (0..2 TCH9 mode, 3 FACCH9) shares, into a zeroed `a` (capi_nt9.cpp)
+int nt9_kind_args(int kind, Nt9Args *a);
+
 // gmr1_hip_demod_batch_dev of a built-in burst type, plus burst_energy() of each window (capi_demod.cpp)
 int demod_dev_energy(hipStream_t st, int burst_id, int n, int sps, int in_len, const float *iq,
                      const uint64_t *offset, const float *freq_shift, int8_t *ebits, int ebits_stride,

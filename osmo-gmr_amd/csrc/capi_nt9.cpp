@@ -129,13 +129,10 @@ int nt9_dev(hipStream_t st, int kind, int n, int seq_len, const int8_t *ebits, c
 	DevState *s;
 	int r = dev_state(&s);
 	if (r) return r;
-	const uint32_t *map;
-	r = get_map(kind, &map);
-	if (r) return r;
 	Nt9Args a;
 	std::memset(&a, 0, sizeof(a));
-	a.n = n; a.seq_len = seq_len; a.kind = kind; a.conv_acc = conv_acc(); a.N = kKinds[kind].N; a.len = kKinds[kind].len;
-	a.map = map; a.ebits = ebits; a.ciph = ciph; a.l2 = l2; a.l2_bytes = kKinds[kind].l2_bytes;
+	if ((r = nt9_kind_args(kind, &a))) return r;
+	a.n = n; a.seq_len = seq_len; a.ebits = ebits; a.ciph = ciph; a.l2 = l2;
 	a.sacch = sacch; a.status = status; a.crc = crc; a.conv = conv;
 	HIP_TRY(launch_nt9(a, st));
 	return 0;
@@ -154,14 +151,23 @@ int tch9_runs_dev_impl(hipStream_t st, int mode, int n, const int32_t *seq_pos, 
 	DevState *s;
 	int r = dev_state(&s);
 	if (r) return r;
-	const uint32_t *map;
-	r = get_map(mode, &map);
-	if (r) return r;
 	Nt9Args a;
 	std::memset(&a, 0, sizeof(a));
-	a.n = n; a.seq_len = 1; a.seq_pos = seq_pos; a.kind = mode; a.conv_acc = conv_acc(); a.N = kKinds[mode].N; a.len = kKinds[mode].len;
-	a.map = map; a.ebits = ebits; a.ciph = ciph; a.l2 = l2; a.l2_bytes = kKinds[mode].l2_bytes; a.conv = conv;
+	if ((r = nt9_kind_args(mode, &a))) return r;
+	a.n = n; a.seq_len = 1; a.seq_pos = seq_pos; a.ebits = ebits; a.ciph = ciph; a.l2 = l2; a.conv = conv;
 	HIP_TRY(launch_nt9(a, st));
+	return 0;
+}
+
+// What a launch of kind 0..2 (TCH9 mode) or 3 (FACCH9) shares, into `a`, which the caller has zeroed: the code's constants, the
+// selected Viterbi decoder and the current device's map (the TCH9 follower's launches, capi_tch9_follow.cpp)
+int nt9_kind_args(int kind, Nt9Args *a)
+{
+	const uint32_t *map;
+	int r = get_map(kind, &map);
+	if (r) return r;
+	a->kind = kind; a->conv_acc = conv_acc(); a->N = kKinds[kind].N; a->len = kKinds[kind].len;
+	a->map = map; a->l2_bytes = kKinds[kind].l2_bytes;
 	return 0;
 }
 }  // namespace gmr1

@@ -1,0 +1,255 @@
+// capi_tch9_follow.cpp -- C ABI of the batched TCH9 call follower (reference src/gmr1_rx.c:262-353: rx_tch9_init, rx_tch9).
+// The state of a call is the caller's; every decision between the frames is taken on the device (tch9_follow_kernels.hip,
+// tch9_follow.h).  The bits form is the follower; the from-samples form is the NT9 demodulator into scratch in front of it.
+#include "capi_common.h"
+#include "tch9_follow.h"
+
+#include <cstddef>
+
+#include "../../include/gmr1_hip.h"
+
+using namespace gmr1;
+
+namespace {
+
+int bits_check(int n_calls, int mode, const int32_t *first, int n_frames, const void *ebits, const void *sync_id, const uint32_t *fn,
+               const void *state, const void *out)
+{
+	if (n_calls < 0 || n_frames < 0)
+		return fail(-EINVAL, "tch9_follow: negative count");
+	if (!first || !ebits || !sync_id || !fn || !state || !out)
+		return fail(-EINVAL, "tch9_follow: NULL argument");
+	if (mode < 0 || mode > 2)
+		return fail(-EINVAL, "tch9_follow: mode %d unknown (0 2k4, 1 4k8, 2 9k6)", mode);
+	return 0;
+}
+
+int samples_check(int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first, int n_frames,
+                  const uint64_t *offset, const float *freq_shift, const uint32_t *fn, const void *state, const void *out)
+{
+	// (the demodulator's outputs stand in for the bits form's arrays: they are scratch)
+	int r = bits_check(n_calls, mode, first, n_frames, iq, offset, fn, state, out);
+	if (r) return r;
+	if (!freq_shift)
+		return fail(-EINVAL, "tch9_follow: NULL argument");
+	if (sps < 1 || sps > 16)
+		return fail(-EINVAL, "tch9_follow: sps=%d out of range (1..16)", sps);
+	if (in_len < 351 * sps || in_len > kMaxInLen)
+		return fail(-EINVAL, "tch9_follow: window of %d samples (%d..%d at sps=%d)", in_len, 351 * sps, kMaxInLen, sps);
+	if ((uintptr_t)iq & 7)
+		return fail(-EINVAL, "tch9_follow: iq is not aligned to a complex sample");
+	return 0;
+}
+
+int first_check(int n_calls, const int32_t *first, int n_frames)
+{
+	if (first[0] != 0 || first[n_calls] != n_frames)
+		return fail(-EINVAL, "tch9_follow: first[] must run from 0 to n_frames");
+	for (int c = 0; c < n_calls; c++)
+		if (first[c + 1] < first[c])
+			return fail(-EINVAL, "tch9_follow: first[%d] decreases", c + 1);
+	return 0;
+}
+
+size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
+
+// where the follower's scratch of n frames lies, from a 128-byte boundary: the demodulator's outputs (from-samples form),
+// the plan, keystreams, decodes
+struct Follow9Scratch {
+	size_t eb, sid, rv, cls, need, src, call, ks, fl2, tl2, fcrc, fcv, tcv, bytes;
+	explicit Follow9Scratch(size_t n)
+	{
+		size_t o = 0;
+		auto take = [&](size_t b) { const size_t at = o; o += up128(b); return at; };
+		eb = take(n * 662); sid = take(n * 4); rv = take(n * 4);
+		cls = take(n); need = take(n); src = take(n * 12); call = take(n * 4); ks = take(n * 658);
+		fl2 = take(n * 64); tl2 = take(n * 64); fcrc = take(n * 4); fcv = take(n * 4); tcv = take(n * 4);
+		bytes = o;
+	}
+};
+
+// The follower, enqueued on `st`; every pointer is device memory.  The caller has checked the arguments and holds a WsLease;
+// `scratch` is Follow9Scratch(n_frames).bytes of device memory on a 128-byte boundary.
+int bits_enqueue(hipStream_t st, void *scratch, int n_calls, int mode, const int32_t *first, int n_frames, const int8_t *ebits,
+                 const int32_t *sync_id, const int32_t *rv, const uint32_t *fn, struct gmr1_hip_tch9_state *state,
+                 struct gmr1_hip_tch9_frame *out)
+{
+	const Follow9Scratch o((size_t)n_frames);
+	unsigned char *d = static_cast<unsigned char *>(scratch);
+	auto I32 = [&](size_t at) { return reinterpret_cast<int32_t *>(d + at); };
+	auto U8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(d + at); };
+
+	Nt9Args f, t;
+	std::memset(&f, 0, sizeof(f));
+	std::memset(&t, 0, sizeof(t));
+	int r = nt9_kind_args(3, &f);
+	if (r) return r;
+	if ((r = nt9_kind_args(mode, &t))) return r;
+
+	Tch9FollowArgs a;
+	std::memset(&a, 0, sizeof(a));
+	a.n_calls = n_calls; a.n_frames = n_frames; a.l2_bytes = t.l2_bytes;
+	a.first = first; a.ebits = ebits; a.sync_id = sync_id; a.rv = rv; a.fn = fn; a.state = state; a.out = out;
+	a.cls = U8(o.cls); a.need = U8(o.need); a.src = I32(o.src); a.call_of = I32(o.call);
+	a.ks = U8(o.ks); a.fa_l2 = U8(o.fl2); a.t_l2 = U8(o.tl2);
+	a.fa_crc = I32(o.fcrc); a.fa_conv = I32(o.fcv); a.t_conv = I32(o.tcv);
+
+	// A. classes and sources, call by call (a frame no call owns -- first[] is the caller's device memory -- asks for nothing)
+	HIP_TRY(hipMemsetAsync(a.need, 0, (size_t)n_frames, st));
+	HIP_TRY(launch_tch9f_plan(a, st));
+
+	// B. keystreams and the two decodes over the frame slots
+	HIP_TRY(launch_a5_tch9f(a, st));
+	f.n = t.n = n_frames;
+	f.ebits = t.ebits = ebits; f.ciph = t.ciph = a.ks;
+	f.need = t.need = a.need; f.src = t.src = a.src; f.src_call = t.src_call = a.call_of;
+	f.held = t.held = reinterpret_cast<const int8_t *>(state) + offsetof(gmr1_hip_tch9_state, held);
+	f.held_stride = t.held_stride = sizeof(gmr1_hip_tch9_state);
+	f.want = kT9NeedFacch; f.l2 = U8(o.fl2); f.crc = I32(o.fcrc); f.conv = I32(o.fcv);
+	t.want = kT9NeedTch; t.l2 = U8(o.tl2); t.conv = I32(o.tcv);
+	HIP_TRY(launch_nt9_jobs(f, st));
+	HIP_TRY(launch_nt9_jobs(t, st));
+
+	// C. records in frame order, and the calls' last two TCH9 bursts into their states
+	HIP_TRY(launch_tch9f_emit(a, st));
+	return 0;
+}
+
+// the NT9 demodulator into the scratch's own slots, then the follower on them
+int samples_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,
+                    int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                    struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
+{
+	const Follow9Scratch o((size_t)n_frames);
+	unsigned char *d = static_cast<unsigned char *>(scratch);
+	int8_t *eb = reinterpret_cast<int8_t *>(d + o.eb);
+	int32_t *sid = reinterpret_cast<int32_t *>(d + o.sid), *rv = reinterpret_cast<int32_t *>(d + o.rv);
+	int r = demod_dev_energy(st, GMR1_HIP_NT9, n_frames, sps, in_len, iq, offset, freq_shift, eb, 662, sid, nullptr, nullptr, rv);
+	if (r) return r;
+	return bits_enqueue(st, scratch, n_calls, mode, first, n_frames, eb, sid, rv, fn, state, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmr1_hip_tch9_state_assign(struct gmr1_hip_tch9_state *s)
+{
+	if (!s)
+		return fail(-EINVAL, "tch9_state_assign: NULL state");
+	// rx_tch9_init, gmr1_rx.c:263-274: a fresh interleaver (k_tch9f_assign does the same on device-resident states)
+	s->active = 1;
+	s->n_held = 0;
+	std::memset(s->held, 0, sizeof(s->held));
+	return 0;
+}
+
+int gmr1_hip_tch9_state_assign_batch_dev(void *stream, int n, const int32_t *call, struct gmr1_hip_tch9_state *state)
+{
+	if (n < 0)
+		return fail(-EINVAL, "tch9_state_assign_batch: negative count");
+	if (!call || !state)
+		return fail(-EINVAL, "tch9_state_assign_batch: NULL argument");
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	HIP_TRY(launch_tch9f_assign(n, call, state, (hipStream_t)stream));
+	return 0;
+}
+
+int gmr1_hip_tch9_follow_bits_batch_dev(void *stream, int n_calls, int mode, const int32_t *first, int n_frames,
+                                        const int8_t *ebits, const int32_t *sync_id, const int32_t *rv, const uint32_t *fn,
+                                        struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
+{
+	int r = bits_check(n_calls, mode, first, n_frames, ebits, sync_id, fn, state, out);
+	if (r) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	WsLease lease;
+	if ((r = lease.acquire(s, (hipStream_t)stream))) return r;
+	Arena ws;                                      // the start of the device's workspace
+	if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
+	return bits_enqueue((hipStream_t)stream, ws.base, n_calls, mode, first, n_frames, ebits, sync_id, rv, fn, state, out);
+}
+
+int gmr1_hip_tch9_follow_bits_batch(int n_calls, int mode, const int32_t *first, int n_frames, const int8_t *ebits,
+                                    const int32_t *sync_id, const int32_t *rv, const uint32_t *fn,
+                                    struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
+{
+	int r = bits_check(n_calls, mode, first, n_frames, ebits, sync_id, fn, state, out);
+	if (r) return r;
+	if ((r = first_check(n_calls, first, n_frames))) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	Stage sg;
+	const int32_t *d_first = sg.in(first, (size_t)n_calls + 1);
+	const int8_t *d_eb = sg.in(ebits, (size_t)n_frames * 662);
+	const int32_t *d_sid = sg.in(sync_id, (size_t)n_frames);
+	const int32_t *d_rv = sg.in(rv, (size_t)n_frames);
+	const uint32_t *d_fn = sg.in(fn, (size_t)n_frames);
+	struct gmr1_hip_tch9_state *d_state = sg.inout(state, (size_t)n_calls);
+	struct gmr1_hip_tch9_frame *d_out = sg.out(out, (size_t)n_frames);
+	if ((r = sg.err())) return r;
+	{
+		WsLease lease;
+		if ((r = lease.acquire(s, nullptr))) return r;
+		Arena ws;
+		if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
+		if ((r = bits_enqueue(nullptr, ws.base, n_calls, mode, d_first, n_frames, d_eb, d_sid, d_rv, d_fn, d_state, d_out)))
+			return r;
+	}
+	return sg.fetch();
+}
+
+int gmr1_hip_tch9_follow_batch_dev(void *stream, int n_calls, int sps, int in_len, int mode, const float *iq,
+                                   const int32_t *first, int n_frames, const uint64_t *offset, const float *freq_shift,
+                                   const uint32_t *fn, struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
+{
+	int r = samples_check(n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	if (r) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	WsLease lease;
+	if ((r = lease.acquire(s, (hipStream_t)stream))) return r;
+	Arena ws;
+	if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
+	return samples_enqueue((hipStream_t)stream, ws.base, n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn,
+	                       state, out);
+}
+
+int gmr1_hip_tch9_follow_batch(int n_calls, int sps, int in_len, int mode, const float *iq, uint64_t iq_len,
+                               const int32_t *first, int n_frames, const uint64_t *offset, const float *freq_shift,
+                               const uint32_t *fn, struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
+{
+	int r = samples_check(n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	if (r) return r;
+	if ((r = first_check(n_calls, first, n_frames))) return r;
+	if ((r = bursts_fit(n_frames, offset, in_len, iq_len))) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const int32_t *d_first = sg.in(first, (size_t)n_calls + 1);
+	const uint64_t *d_off = sg.in(offset, (size_t)n_frames);
+	const float *d_fs = sg.in(freq_shift, (size_t)n_frames);
+	const uint32_t *d_fn = sg.in(fn, (size_t)n_frames);
+	struct gmr1_hip_tch9_state *d_state = sg.inout(state, (size_t)n_calls);
+	struct gmr1_hip_tch9_frame *d_out = sg.out(out, (size_t)n_frames);
+	if ((r = sg.err())) return r;
+	{
+		WsLease lease;
+		if ((r = lease.acquire(s, nullptr))) return r;
+		Arena ws;
+		if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
+		if ((r = samples_enqueue(nullptr, ws.base, n_calls, sps, in_len, mode, d_iq, d_first, n_frames, d_off, d_fs, d_fn, d_state,
+		                         d_out)))
+			return r;
+	}
+	return sg.fetch();
+}
+
+}  // extern "C"

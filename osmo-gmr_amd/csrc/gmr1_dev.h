@@ -458,8 +458,43 @@ struct Nt9Args {
 	int8_t *status;            // optional n x 4 soft bits
 	int32_t *crc;              // FACCH9 only
 	int32_t *conv;             // optional
+	// launch_nt9_jobs only (the TCH9 follower: one slot per frame handed in, l2 slots 64 bytes apart); launch_nt9 reads none
+	const uint8_t *need;       // n: slot g is decoded only where need[g] == want
+	int want;
+	const int32_t *src;        // n x 3: where the burst `back` bursts back of slot g comes from (tch9_follow.h): a slot of
+	                           // ebits / ciph, zeros, or a held burst -- deciphered already -- of the slot's call
+	const int32_t *src_call;   // n: the call of slot g ...
+	const int8_t *held;        // ... whose held bursts are held + src_call[g] * held_stride + 662 * {0, 1}
+	size_t held_stride;
 };
 hipError_t launch_nt9(const Nt9Args &a, hipStream_t stream);
+hipError_t launch_nt9_jobs(const Nt9Args &a, hipStream_t stream);
+
+// The batched TCH9 call follower (gmr1_hip_tch9_follow*: capi_tch9_follow.cpp, tch9_follow_kernels.hip, tch9_follow.h).
+// Everything is device memory; arrays "per frame" have n_frames slots in the order the frames were handed in.
+struct Tch9FollowArgs {
+	int n_calls, n_frames;
+	int l2_bytes;                      // of a TCH9 block in this invocation's mode
+	const int32_t *first;              // n_calls + 1
+	const int8_t *ebits;               // per frame x 662
+	const int32_t *sync_id, *rv;       // per frame; rv may be null (all 0)
+	const uint32_t *fn;                // per frame
+	struct gmr1_hip_tch9_state *state; // n_calls
+	struct gmr1_hip_tch9_frame *out;   // per frame
+	// k_tch9f_plan
+	uint8_t *cls, *need;               // need: zeroed in front of the plan (a frame no call owns asks for nothing)
+	int32_t *src;                      // x 3: the frame itself, the TCH9 burst one back, two back
+	int32_t *call_of;
+	// keystreams and decodes
+	uint8_t *ks;                       // x 658
+	const uint8_t *fa_l2, *t_l2;       // x 64
+	const int32_t *fa_crc, *fa_conv, *t_conv;
+};
+hipError_t launch_tch9f_plan(const Tch9FollowArgs &a, hipStream_t stream);
+hipError_t launch_a5_tch9f(const Tch9FollowArgs &a, hipStream_t stream);
+hipError_t launch_tch9f_emit(const Tch9FollowArgs &a, hipStream_t stream);
+// rx_tch9_init on device-resident states (k_tch9f_assign): entry j < n assigns state[call[j]]
+hipError_t launch_tch9f_assign(int n, const int32_t *call, struct gmr1_hip_tch9_state *state, hipStream_t stream);
 // RACH (nt9_kernels.hip, same K = 5 trellis) and xCH over DC12 (xch_kernels.hip, K = 9)
 struct RachArgs {
 	int n;

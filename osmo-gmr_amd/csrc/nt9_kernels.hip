@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "gmr1_dev.h"
+#include "tch9_follow.h"
 
 namespace gmr1 {
 
@@ -166,7 +167,10 @@ __device__ __forceinline__ uint32_t nt9_step(uint32_t w, const CT *__restrict__ 
 	return t1 < t2 ? t1 : t2;
 }
 
-template <int NW, bool ACC>
+// JOBS (launch_nt9_jobs, the TCH9 follower: tch9_follow_kernels.hip): one slot per frame handed in, decoded only where
+// need[g] == want -- a work-group none of whose four slots asks exits at once --, the bursts of the inter-burst
+// de-interleaver found through the per-slot source table instead of at g - back, l2 slots 64 bytes apart.
+template <int NW, bool ACC, bool JOBS = false>
 __global__ __launch_bounds__(64) void k_nt9(Nt9Args a)
 {
 	typedef typename std::conditional<ACC, uint16_t, uint8_t>::type CT;
@@ -182,27 +186,47 @@ __global__ __launch_bounds__(64) void k_nt9(Nt9Args a)
 	uint16_t *win = reinterpret_cast<uint16_t *>(lds_raw + (size_t)4 * kNt9MaxSteps * stride * sizeof(CT));   // kNt9MaxWin x 64
 	uint32_t *ub = reinterpret_cast<uint32_t *>(win + kNt9MaxWin * 64);            // 4 x 16 words
 	const int g0 = blockIdx.x * 4;
+	auto live = [&](int g) { return g < a.n && (!JOBS || a.need[g] == a.want); };
+	if (JOBS && !(live(g0) || live(g0 + 1) || live(g0 + 2) || live(g0 + 3)))
+		return;
 
 	// ---- cost tables of the four bursts: word A = coded bits (0, 1), B = (2, 3), C = (4)
 	for (int it = lane; it < 4 * S; it += 64) {
 		const int q = it / S, k = it % S;
 		const int g = g0 + q;
 		uint32_t c0[5] = {0, 0, 0, 0, 0}, c1[5] = {0, 0, 0, 0, 0};
-		if (g < a.n) {
+		if (live(g)) {
 			// position of the burst in its channel's sequence (runs of unequal length: given per burst)
-			const int pos = a.seq_pos ? a.seq_pos[g] : g % a.seq_len;
+			const int pos = JOBS ? 0 : a.seq_pos ? a.seq_pos[g] : g % a.seq_len;
 			for (int j = 0; j < N; j++) {
 				const uint32_t m = a.map[k * N + j];
 				if (m & kMapPunct)
 					continue;
 				const int back = (int)((m >> 21) & 3u);
-				if (back > pos)
-					continue;                            // before the first burst of the channel: zeros
-				const size_t src = (size_t)(g - back);
-				int v = a.ebits[src * 662 + (m & 0x3ffu)];
+				const int8_t *eb;
+				const uint8_t *ks;
+				if constexpr (JOBS) {
+					const int s = a.src[3 * (size_t)g + back];
+					if (s == kT9SrcZeros)
+						continue;                        // before the first burst of the call
+					if (s >= 0) {
+						eb = a.ebits + (size_t)s * 662;
+						ks = a.ciph ? a.ciph + (size_t)s * 658 : nullptr;
+					} else {                             // a burst the call's state holds: deciphered when it was taken in
+						eb = a.held + (size_t)a.src_call[g] * a.held_stride + (size_t)(-2 - s) * 662;
+						ks = nullptr;
+					}
+				} else {
+					if (back > pos)
+						continue;                        // before the first burst of the channel: zeros
+					const size_t src = (size_t)(g - back);
+					eb = a.ebits + src * 662;
+					ks = a.ciph ? a.ciph + src * 658 : nullptr;
+				}
+				int v = eb[m & 0x3ffu];
 				bool flip = ((m >> 10) & 1u) != 0;
-				if (a.ciph)
-					flip ^= a.ciph[src * 658 + ((m >> 11) & 0x3ffu)] != 0;
+				if (ks)
+					flip ^= ks[(m >> 11) & 0x3ffu] != 0;
 				if (flip)
 					v = (int8_t)(-v);
 				c0[j] = (uint32_t)sbit_cost<ACC, SC>(v, 0);
@@ -349,16 +373,17 @@ __global__ __launch_bounds__(64) void k_nt9(Nt9Args a)
 
 	// ---- outputs
 	const int g = g0 + row;
-	if (g >= a.n)
+	if (!live(g))
 		return;
 	const uint32_t *u = ub + row * 16;
+	const int l2_stride = JOBS ? 64 : a.l2_bytes;
 	// L2 bytes: decoded bits LSB first (osmo_ubit2pbit_ext lsb mode) = the words as they stand
 	for (int i = (int)loc; i < a.l2_bytes; i += 16) {
 		uint32_t byte = (u[i >> 2] >> (8 * (i & 3))) & 0xffu;
 		const int bits_left = a.len - (a.kind == 3 ? 16 : 0) - 8 * i;   // FACCH9: 300 message bits
 		if (bits_left < 8)
 			byte &= (1u << (bits_left > 0 ? bits_left : 0)) - 1u;
-		a.l2[(size_t)g * a.l2_bytes + i] = (uint8_t)byte;
+		a.l2[(size_t)g * l2_stride + i] = (uint8_t)byte;
 	}
 	// status = e[52..55]; SACCH = bits_my[52..61] = e[56..65] after deciphering (facch9.c:118-131, tch9.c:152-165)
 	if (a.status && loc < 4)
@@ -667,7 +692,8 @@ hipError_t launch_rach(const RachArgs &a, hipStream_t stream)
 	return hipGetLastError();
 }
 
-hipError_t launch_nt9(const Nt9Args &a, hipStream_t stream)
+template <bool JOBS>
+static hipError_t launch_nt9_as(const Nt9Args &a, hipStream_t stream)
 {
 	if (a.n <= 0)
 		return hipSuccess;
@@ -676,16 +702,21 @@ hipError_t launch_nt9(const Nt9Args &a, hipStream_t stream)
 	const size_t lds = (size_t)4 * kNt9MaxSteps * 4 * nw * (acc ? 2 : 1) + (size_t)kNt9MaxWin * 64 * 2 + 4 * 16 * 4;
 	const dim3 grid((a.n + 3) / 4);
 	if (nw == 1 && acc)
-		hipLaunchKernelGGL((k_nt9<1, true>), grid, dim3(64), lds, stream, a);
+		hipLaunchKernelGGL((k_nt9<1, true, JOBS>), grid, dim3(64), lds, stream, a);
 	else if (nw == 1)
-		hipLaunchKernelGGL((k_nt9<1, false>), grid, dim3(64), lds, stream, a);
+		hipLaunchKernelGGL((k_nt9<1, false, JOBS>), grid, dim3(64), lds, stream, a);
 	else if (nw == 2 && acc)
-		hipLaunchKernelGGL((k_nt9<2, true>), grid, dim3(64), lds, stream, a);
+		hipLaunchKernelGGL((k_nt9<2, true, JOBS>), grid, dim3(64), lds, stream, a);
 	else if (nw == 2)
-		hipLaunchKernelGGL((k_nt9<2, false>), grid, dim3(64), lds, stream, a);
+		hipLaunchKernelGGL((k_nt9<2, false, JOBS>), grid, dim3(64), lds, stream, a);
 	else
-		hipLaunchKernelGGL((k_nt9<3, false>), grid, dim3(64), lds, stream, a);
+		hipLaunchKernelGGL((k_nt9<3, false, JOBS>), grid, dim3(64), lds, stream, a);
 	return hipGetLastError();
 }
+
+hipError_t launch_nt9(const Nt9Args &a, hipStream_t stream) { return launch_nt9_as<false>(a, stream); }
+
+// the TCH9 follower's decodes: a.need / want / src / src_call / held are set
+hipError_t launch_nt9_jobs(const Nt9Args &a, hipStream_t stream) { return launch_nt9_as<true>(a, stream); }
 
 }  // namespace gmr1

@@ -279,6 +279,25 @@ __global__ __launch_bounds__(64) void k_a5_tch3f(Tch3FollowArgs a)
 		a5_1_stream(key, a.job_fn[(size_t)k * 4 + sub - 1], 96, a.ks_facch + (size_t)k * 384 + 96 * (sub - 1), nullptr);
 }
 
+// The TCH9 follower's keystreams (tch9_follow_kernels.hip), one lane per frame handed in: the 658 bits of a frame that asks
+// for a decode, FACCH9 or TCH9 (gmr1_rx.c:310, 326), from the key of the frame's call.  A lane with nothing to do returns
+// at once.
+__global__ __launch_bounds__(64) void k_a5_tch9f(Tch9FollowArgs a)
+{
+	const int k = blockIdx.x * 64 + threadIdx.x;
+	if (k >= a.n_frames || !a.need[k])
+		return;
+	a5_1_stream(a.state[a.call_of[k]].kc, a.fn[k], 658, a.ks + (size_t)k * 658, nullptr);
+}
+
+hipError_t launch_a5_tch9f(const Tch9FollowArgs &a, hipStream_t stream)
+{
+	if (a.n_frames <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_a5_tch9f, dim3((a.n_frames + 63) / 64), dim3(64), 0, stream, a);
+	return hipGetLastError();
+}
+
 hipError_t launch_a5(const A5Args &a, hipStream_t stream)
 {
 	if (a.n <= 0)
