@@ -520,8 +520,8 @@ int gmr1_hip_rx_run(int n_arfcn, int sps, const float *iq, uint64_t iq_len,
  *    one is refused (-EINVAL).
  *  - A chain whose walk outgrows the loop's buffers stops for good and its carrier's status becomes -EIO, as in
  *    gmr1_hip_rx_run; the carrier's other chains go on.
- *  - A handle made by _create follows no traffic channel; one made by _create_tch (below) follows TCH3 calls.  TCH9
- *    follow-ups are not performed by either.  Without a GPU every entry point returns -ENODEV. */
+ *  - A handle made by _create follows no traffic channel; one made by _create_tch (below) follows TCH3 calls, one made
+ *    by _create_full (below that) TCH3 and TCH9 calls.  Without a GPU every entry point returns -ENODEV. */
 struct gmr1_hip_rx_stream;
 int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struct gmr1_hip_rx_stream **h);
 int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_records);
@@ -558,6 +558,42 @@ int gmr1_hip_rx_stream_push_tch_dev(void *stream, struct gmr1_hip_rx_stream *h, 
                                     int max_records, int *n_records);
 int gmr1_hip_rx_stream_push_tch(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride,
                                 uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records);
+
+/* The streaming loop with both follow-ups: gmr1_hip_rx_run_full (below) over a capture pushed piece by piece.  kc as for
+ * _create_tch.  `csd` has the layout, stride and timing of `iq` and `tch`: carrier i's CSD samples of a push are
+ * csd[2*(i*iq_stride + k)], k < n.
+ *  - A handle made by _create_full takes only _push_full*, and _push_full* takes no other handle: the wrong pairing is
+ *    refused (-EINVAL) and leaves the handle as it was, as do tch == NULL or csd == NULL with n > 0, max_big below
+ *    gmr1_hip_rx_stream_max_big(h, n) and big_out == NULL with max_big > 0; n_records and n_big are then 0.
+ *    _max_records for a full handle is the tch handle's; _max_big (host arithmetic; 0 for the other kinds) is one big
+ *    record per frame a chain's walk can log, times the chains.  _status and _destroy serve all kinds, and the plain and
+ *    tch handles are what they were.
+ *  - The ordinary records of any sequence of pushes ending with `last`, stable-sorted by (carrier, chain), are
+ *    byte-identical to the `out` of one gmr1_hip_rx_run_full call on the whole capture with the same kc, and the big
+ *    records, sorted the same way, to its `big_out`: every field, conv included, in both Viterbi decoder modes, for any
+ *    push sizes (0 included).  Within a push both arrays come by carrier, chain, frame.  An ASSIGNMENT COMMAND 1 is
+ *    followed from its own frame on, so the call's first big records come out of the push that returns the FACCH3 record
+ *    carrying the command.
+ *  - The CSD samples are retained exactly as the other two carriers' are; every chain's struct gmr1_hip_tch9_state stays
+ *    in device memory between pushes, and a push runs the TCH9 call follower once, however many commands it holds.
+ *  - `out` and `big_out` are host memory.  Everything else is as for gmr1_hip_rx_stream_push_tch*, its -EIO included: a
+ *    frame the walk admitted holds its NT9 window (351 sps + sps + sps/2 samples) unless an SI1 moves the chain's timeslot
+ *    label down by more than 7 slots (a call on timeslot 31; 23 slots up to timeslot 15) inside the newest frame of a
+ *    push that is not the last.
+ *  - The NT9 window passes GMR1_HIP_MAX_IN_LEN from sps 12 on: _create_full refuses sps > 11 (-EINVAL) when it is called,
+ *    before anything is allocated.  gmr1_hip_rx_run_full takes such a capture and fails only once it meets an NT9 frame. */
+struct gmr1_hip_rx_big_record;       /* defined with gmr1_hip_rx_run_full below */
+int gmr1_hip_rx_stream_create_full(int n_arfcn, int sps, const uint16_t *arfcn,
+                                   const uint8_t *kc /* n_arfcn x 8, or NULL */, struct gmr1_hip_rx_stream **h);
+int gmr1_hip_rx_stream_max_big(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_big);
+int gmr1_hip_rx_stream_push_full_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch,
+                                     const float *csd, uint64_t iq_stride, uint64_t n, int last,
+                                     struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                     struct gmr1_hip_rx_big_record *big_out, int max_big, int *n_big);
+int gmr1_hip_rx_stream_push_full(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, const float *csd,
+                                 uint64_t iq_stride, uint64_t n, int last,
+                                 struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                 struct gmr1_hip_rx_big_record *big_out, int max_big, int *n_big);
 
 /* The same with the TCH3 follow-up (gmr1_rx's optional tch.cfile and key arguments, gmr1_rx.c:355-600,
  * 897-975): tch holds, for every carrier, the traffic carrier an IMMEDIATE ASSIGNMENT on its CCCH points
@@ -737,6 +773,19 @@ struct gmr1_hip_rx_big_record {
 	int32_t  conv;
 	uint8_t  l2[64];
 };
+/* The TCH9 follower's frames as gmr1_hip_rx_run_full reports them, closed up on the device: call c owns
+ * frames[first[c] .. first[c+1]) as in gmr1_hip_tch9_follow*_batch*, label[c] = arfcn | chain << 16 | tn << 24.  A frame
+ * with type == 0 gives nothing, every other one a big record -- arfcn, chain and tn from its call's label; fn, type, len,
+ * conv and l2[0..len) from the frame; crc, pad and the rest of l2 0 -- in call order, then frame order.  Only the first
+ * max_out records are stored; *n_out is the number found.  Every pointer is device memory (out on a 16-byte boundary); the
+ * call enqueues one kernel on `stream` and returns.  The entries of first are clamped to 0..n_frames.  -EINVAL, before the
+ * device is asked for: a negative count, a NULL array (out may be NULL when max_out == 0), a misaligned out.  -ENODEV
+ * without a device.  n_calls == 0 writes *n_out = 0. */
+int gmr1_hip_tch9_frames_to_records_dev(void *stream, int n_calls, const int32_t *first /* n_calls + 1 */, int n_frames,
+                                        const struct gmr1_hip_tch9_frame *frames,
+                                        const uint32_t *label /* n_calls */, struct gmr1_hip_rx_big_record *out,
+                                        int max_out, int32_t *n_out /* device */);
+
 /* Measurement aid: wall time, in microseconds, of the phases of the calling thread's last gmr1_hip_rx_run* call --
  * [0] FCCH acquisition (main() -> fcch_single_init / fcch_multi_process, gmr1_rx.c:605-744) incl. the chains set up from its result,
  * [1] the frame loop (process_bcch, :852-895) from its first launch until its kernels are through, [2] the records to the

@@ -117,6 +117,10 @@ SIGNATURES = {
     "gmr1_hip_rx_stream_create_tch": (I, I, I, P, P, P),
     "gmr1_hip_rx_stream_push_tch_dev": (I, P, P, P, P, U64, U64, I, P, I, P),
     "gmr1_hip_rx_stream_push_tch": (I, P, P, P, U64, U64, I, P, I, P),
+    "gmr1_hip_rx_stream_create_full": (I, I, I, P, P, P),
+    "gmr1_hip_rx_stream_max_big": (I, P, U64, P),
+    "gmr1_hip_rx_stream_push_full_dev": (I, P, P, P, P, P, U64, U64, I, P, I, P, P, I, P),
+    "gmr1_hip_rx_stream_push_full": (I, P, P, P, P, U64, U64, I, P, I, P, P, I, P),
     "gmr1_hip_rx_run_tch_dev": (I, P, I, I, P, P, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_tch": (I, I, I, P, P, U64, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_last_timing": (I, P),
@@ -130,6 +134,7 @@ SIGNATURES = {
     "gmr1_hip_tch9_follow_bits_batch": (I, I, I, P, I, P, P, P, P, P, P),
     "gmr1_hip_tch9_follow_batch_dev": (I, P, I, I, I, I, P, P, I, P, P, P, P, P),
     "gmr1_hip_tch9_follow_batch": (I, I, I, I, I, P, U64, P, I, P, P, P, P, P),
+    "gmr1_hip_tch9_frames_to_records_dev": (I, P, I, P, I, P, P, P, I, P),
     "gmr1_hip_rx_run_full_dev": (I, P, I, I, P, P, P, P, P, P, P, P, I, P, P, I, P, P, P),
     "gmr1_hip_rx_run_full": (I, I, I, P, P, P, U64, P, P, P, P, P, I, P, P, I, P, P, P),
     "gmr1_hip_codec_state_bytes": (SZ,),
@@ -1252,17 +1257,20 @@ class RxStream(_LibHandle):
     """gmr1_hip_rx_stream_*: the receive loop (rx_run) over a capture pushed piece by piece.  Each push returns the records
     that became final in it; all pushes' records up to the `last` one, stable-sorted by (carrier, chain), are identical to
     one rx_run() call on the whole capture.  tch=True: the loop also follows TCH3 calls (rx_run_tch with the same kc) --
-    every push then takes the traffic carriers' samples as well."""
+    every push then takes the traffic carriers' samples as well.  full=True: it follows TCH3 and TCH9 calls (rx_run_full
+    with the same kc) -- every push takes the traffic and the CSD carriers' samples and returns (records, big records)."""
     _destroy_fn = "gmr1_hip_rx_stream_destroy"
 
-    def __init__(self, n_arfcn, sps=4, arfcn=None, tch=False, kc=None):
+    def __init__(self, n_arfcn, sps=4, arfcn=None, tch=False, kc=None, full=False):
         self._h = C.c_void_p()
         self.n = int(n_arfcn)
-        self.tch = bool(tch)
+        self.full = bool(full)
+        self.tch = bool(tch) or self.full
         self._arfcn = _arr(arfcn, np.uint16)
         if self.tch:
             kc = _arr(kc, np.uint8, (self.n, 8))
-            _call("gmr1_hip_rx_stream_create_tch", self.n, sps, _p(self._arfcn), _p(kc), C.byref(self._h))
+            _call("gmr1_hip_rx_stream_create_full" if self.full else "gmr1_hip_rx_stream_create_tch", self.n, sps, _p(self._arfcn),
+                  _p(kc), C.byref(self._h))
         else:
             if kc is not None:
                 raise ValueError("kc belongs to a handle that follows TCH3 calls (tch=True)")
@@ -1274,23 +1282,40 @@ class RxStream(_LibHandle):
         _call("gmr1_hip_rx_stream_max_records", self._h, n, C.byref(m))
         return m.value
 
+    def max_big(self, n):
+        """the most big records the next push of n samples per carrier can return (0 unless full=True)"""
+        m = C.c_int()
+        _call("gmr1_hip_rx_stream_max_big", self._h, n, C.byref(m))
+        return m.value
+
     def _out(self, n, out):
         return _records(out, self.max_records(n))[0]
 
-    def _kind(self, tch):
+    def _kind(self, tch, csd=None):
         if self.tch and tch is None:
             raise ValueError("a handle that follows TCH3 calls takes the traffic carriers' samples with every push (tch=)")
         if not self.tch and tch is not None:
             raise ValueError("tch= belongs to a handle made with tch=True")
+        if self.full and csd is None:
+            raise ValueError("a handle that follows TCH9 calls takes the CSD carriers' samples with every push (csd=)")
+        if not self.full and csd is not None:
+            raise ValueError("csd= belongs to a handle made with full=True")
 
-    def push(self, iq, last=False, out=None, tch=None):
-        """host (n_arfcn, n) complex64 (and, on a tch handle, tch of the same shape) -> the records that became final
-        (RX_RECORD[])"""
-        self._kind(tch)
+    def push(self, iq, last=False, out=None, tch=None, csd=None):
+        """host (n_arfcn, n) complex64 (and, on a tch handle, tch of the same shape; on a full handle csd as well) -> the
+        records that became final (RX_RECORD[]); on a full handle (records, big records (RX_BIG_RECORD[]))"""
+        self._kind(tch, csd)
         iq = _arr(iq, np.complex64, (self.n, -1))
         n = iq.shape[1]
         out = self._out(n, out)
         got = C.c_int()
+        if self.full:
+            tch, csd = _arr(tch, np.complex64, (self.n, n)), _arr(csd, np.complex64, (self.n, n))
+            big = _records(None, self.max_big(n), RX_BIG_RECORD)[0]
+            got_big = C.c_int()
+            _call("gmr1_hip_rx_stream_push_full", self._h, _p(iq), _p(tch), _p(csd), n, n, 1 if last else 0, _p(out), out.size,
+                  C.byref(got), _p(big), big.size, C.byref(got_big))
+            return out[:got.value], big[:got_big.value]
         if self.tch:
             tch = _arr(tch, np.complex64, (self.n, n))
             _call("gmr1_hip_rx_stream_push_tch", self._h, _p(iq), _p(tch), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
@@ -1298,11 +1323,19 @@ class RxStream(_LibHandle):
             _call("gmr1_hip_rx_stream_push", self._h, _p(iq), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
         return out[:got.value]
 
-    def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None, tch_ptr=None):
+    def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None, tch_ptr=None, csd_ptr=None, big=None):
         """device samples (carrier i at iq_ptr + 8 * i * iq_stride; on a tch handle its traffic samples at tch_ptr + 8 * i *
-        iq_stride), read on `stream` -> the records (synchronous).
-        out: a host RX_RECORD array, or None; out_ptr (device / pinned) goes through push_dev_raw."""
+        iq_stride, on a full handle its CSD samples at csd_ptr + 8 * i * iq_stride), read on `stream` -> the records
+        (synchronous); on a full handle (records, big records).
+        out, big: host RX_RECORD / RX_BIG_RECORD arrays, or None; out_ptr (device / pinned) goes through push_dev_raw."""
         out = self._out(n, out)
+        if self.full:
+            self._kind(tch_ptr, csd_ptr)
+            big = _records(big, self.max_big(n), RX_BIG_RECORD)[0]
+            got, got_big = C.c_int(), C.c_int()
+            _call("gmr1_hip_rx_stream_push_full_dev", stream, self._h, iq_ptr, tch_ptr, csd_ptr, iq_stride, n, 1 if last else 0,
+                  out.ctypes.data, out.size, C.byref(got), big.ctypes.data, big.size, C.byref(got_big))
+            return out[:got.value], big[:got_big.value]
         got = self.push_dev_raw(stream, iq_ptr, iq_stride, n, last, out.ctypes.data, out.size, tch_ptr)
         return out[:got]
 
@@ -1485,6 +1518,23 @@ def rx_run_full(iq, tch, csd, offset, length, sps=4, arfcn=None, kc=None, max_re
                                           big=(_p(big), cap_big, C.addressof(n_big)))
     _check(run(), "gmr1_hip_rx_run_full")
     return out[:min(n_rec.value, cap)].copy(), big[:min(n_big.value, cap_big)].copy(), status, chains
+
+
+def rx_run_full_dev(stream, iq_ptr, tch_ptr, csd_ptr, offset, length, sps=4, arfcn=None, kc=None, max_records=1 << 16,
+                    max_big=1 << 14):
+    """gmr1_hip_rx_run_full_dev: rx_run_full with the three captures already in HBM (device addresses, same layout)."""
+    out, cap = _records(None, max_records)
+    big, cap_big = _records(None, max_big, RX_BIG_RECORD)
+    n_big = C.c_int(0)
+    run, n_rec, status, chains = _rx_loop("gmr1_hip_rx_run_full_dev", (stream, len(offset), sps, iq_ptr, tch_ptr, csd_ptr), offset,
+                                          length, arfcn, _p(out), cap, kc=kc, big=(_p(big), cap_big, C.addressof(n_big)))
+    _check(run(), "gmr1_hip_rx_run_full_dev")
+    return out[:min(n_rec.value, cap)].copy(), big[:min(n_big.value, cap_big)].copy(), status, chains
+
+
+def tch9_frames_to_records_dev(stream, n_calls, first, n_frames, frames, label, out, max_out, n_out):
+    """gmr1_hip_tch9_frames_to_records_dev: device pointers throughout; enqueues on `stream` and returns."""
+    _call("gmr1_hip_tch9_frames_to_records_dev", stream, n_calls, first, n_frames, frames, label, out, max_out, n_out)
 
 
 def gsmtap_pack_big(record, with_arfcn=False) -> bytes:

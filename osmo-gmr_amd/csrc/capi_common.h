@@ -125,6 +125,12 @@ int tch3_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int
                         int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                         struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
 
+// gmr1_hip_tch9_follow_batch_dev on scratch of the caller's (capi_tch9_follow.cpp), under the same terms
+size_t tch9_follow_scratch_bytes(int n_frames);
+int tch9_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,
+                        int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                        struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out);
+
 // Device scratch of a traffic pass: one carve-up of the grow-only device workspace (none of the kernels the
 // passes launch uses it) instead of dozens of hipMalloc / hipFree pairs per call.
 struct Arena {

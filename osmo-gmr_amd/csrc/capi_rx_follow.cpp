@@ -2,7 +2,8 @@
 // never feed back into the BCCH / CCCH loop, so they run after it as batched passes over chains and the walks the loop made
 // of them: tch3_follow_chains hands every chain with an IMMEDIATE ASSIGNMENT to the batched call follower, one invocation
 // per assignment a chain sees (a push of the streaming loop runs it over its own frames too); tch9_follow_chains
-// demodulates, classifies on the host and decodes.  Which frame belongs to which assignment, invocation and interleaver
+// demodulates, classifies on the host and decodes; tch9_follow_push is the TCH9 follow-up of one push of the streaming
+// loop, through the batched TCH9 call follower with every state and frame left on the device.  Which frame belongs to which assignment, invocation and interleaver
 // run is integer work: rx_follow.h.
 
 #include "rx_run.h"
@@ -314,6 +315,107 @@ int tch9_follow_chains(hipStream_t st, int sps, const float *csd, const uint16_t
 	if (jobs.facch.empty() && jobs.tch.empty())
 		return 0;
 	return tch9_decode_jobs(st, sg, arfcn, kc, chains, walks, items9, jobs, h_eb);
+}
+
+// ---- TCH9 follow-up of one push of the streaming loop -------------------------------------------
+// This push's frames of every chain with a data call through the batched call follower (tch9_follow_enqueue: what
+// gmr1_hip_tch9_follow_batch_dev runs), in ONE invocation however many commands the push holds: tch9_plan_push
+// (rx_follow.h) cuts a chain's frames into segments, one per command and one for the call carried in, and every segment
+// is a call of the follower.  The follower finds call q's state at slot q, and the big records come out in call order, so
+// the calls have to stand chain by chain, segment by segment: their states are gathered into that order in the pass's
+// scratch (k_tch9f_move: the chain's own state for the call carried in, and for a command, whose state is fresh anyway,
+// as the carrier of the key under k_tch9f_assign), and the last segment's state of every chain goes back to the chain's
+// slot of d_state afterwards.  No state and no frame visits the host: k_tch9f_big closes the reporting frames up into big
+// records on the device, the count comes back, then exactly that many records.
+int tch9_follow_push(hipStream_t st, int sps, const float *csd, const uint16_t *arfcn, bool horizon, const std::vector<RxChain> &chains,
+                     const std::vector<RxWalk> &walks, gmr1_hip_tch9_state *d_state, Tch9CallCarry *carry,
+                     gmr1_hip_rx_big_record *big_out, int max_big, int *n_big)
+{
+	int r = 0;
+	*n_big = 0;
+	std::vector<Tch9PushCall> pc(chains.size());
+	for (size_t ci = 0; ci < chains.size(); ci++)
+		pc[ci] = {&walks[ci].log, &walks[ci].events9, carry[ci], chains[ci].len};
+	Tch9PushPlan plan;
+	if (!tch9_plan_push(pc, sps, horizon, &plan))
+		return fail(-EIO, "tch9 follow-up: a frame the walk admitted does not hold its NT9 window");
+	for (size_t ci = 0; ci < chains.size(); ci++)
+		carry[ci] = plan.carry[ci];
+	const int n_seg = (int)plan.segs.size(), n = (int)plan.items.size();
+	if (!n_seg)
+		return 0;
+	std::vector<int32_t> first((size_t)n_seg + 1), at((size_t)n_seg), own((size_t)n_seg), fresh, back_at, back_own;
+	std::vector<uint32_t> label((size_t)n_seg), fn((size_t)n);
+	std::vector<uint64_t> off((size_t)n);
+	std::vector<float> fs((size_t)n);
+	for (int q = 0; q < n_seg; q++) {
+		const Tch9Seg &sgm = plan.segs[q];
+		const RxChain &c = chains[sgm.chain];
+		first[q] = (int32_t)sgm.first;
+		at[q] = q;
+		own[q] = sgm.chain;
+		label[q] = (uint32_t)rx_label(arfcn, c.a) | ((uint32_t)(c.chain & 0xff) << 16) | ((uint32_t)(sgm.tn & 0xff) << 24);
+		if (sgm.ev)
+			fresh.push_back(q);
+	}
+	first[n_seg] = n;
+	for (size_t ci = 0; ci < chains.size(); ci++)
+		if (plan.last_seg[ci] >= 0) {
+			back_at.push_back(plan.last_seg[ci]);
+			back_own.push_back((int32_t)ci);
+		}
+	for (int k = 0; k < n; k++) {
+		const Nt9Item &it = plan.items[k];
+		const FrameCtx &x = walks[it.chain].log[it.frame];
+		off[k] = chains[it.chain].base + (uint64_t)rx_tch9_begin(x.align, sps, it.tn);
+		fs[k] = -x.freq_err;
+		fn[k] = (uint32_t)x.fn;
+	}
+	// the calls' states, seven index arrays of at most a word per call, per frame 16 B staged, the follower's 80 B and a big
+	// record of 80 B, the count, the follower's scratch
+	Arena arena;
+	if ((r = arena.init(up128((size_t)n_seg * sizeof(gmr1_hip_tch9_state)) + 7 * up128(((size_t)n_seg + 1) * 4) +
+	                    up128((size_t)n * 8) + 2 * up128((size_t)n * 4) + 2 * up128((size_t)n * 80) + 16 * 128 +
+	                    tch9_follow_scratch_bytes(n)))) return r;
+	Stage sg(st, &arena);
+	gmr1_hip_tch9_state *d_call = sg.dev<gmr1_hip_tch9_state>((size_t)n_seg);
+	const int32_t *d_first = sg.in(first.data(), first.size());
+	const int32_t *d_at = sg.in(at.data(), at.size()), *d_own = sg.in(own.data(), own.size());
+	const int32_t *d_fresh = sg.in(fresh.data(), fresh.size());
+	const int32_t *d_back_at = sg.in(back_at.data(), back_at.size()), *d_back_own = sg.in(back_own.data(), back_own.size());
+	const uint32_t *d_label = sg.in(label.data(), label.size());
+	const uint64_t *d_off = sg.in(off.data(), (size_t)n);
+	const float *d_fs = sg.in(fs.data(), (size_t)n);
+	const uint32_t *d_fn = sg.in(fn.data(), (size_t)n);
+	gmr1_hip_tch9_frame *d_got = sg.dev<gmr1_hip_tch9_frame>((size_t)n);
+	gmr1_hip_rx_big_record *d_big = sg.dev<gmr1_hip_rx_big_record>((size_t)n);
+	int32_t h_count = 0;
+	int32_t *d_count = sg.dev<int32_t>(1);
+	unsigned char *scratch = sg.dev<unsigned char>(tch9_follow_scratch_bytes(n));
+	if ((r = sg.err())) return r;
+	HIP_TRY(launch_tch9f_move(n_seg, d_call, d_at, d_state, d_own, st));
+	HIP_TRY(launch_tch9f_assign((int)fresh.size(), d_fresh, d_call, st));
+	if (n) {
+		r = tch9_follow_enqueue(st, scratch, n_seg, sps, rx_tch9_in_len(sps), 2 /* GMR1_TCH9_9k6, gmr1_rx.c:333 */, csd, d_first, n,
+		                        d_off, d_fs, d_fn, d_call, d_got);
+		if (r) return r;
+	}
+	HIP_TRY(launch_tch9f_move((int)back_at.size(), d_state, d_back_own, d_call, d_back_at, st));
+	if (!n)
+		return sg.fetch();                        // (the staged arrays are the host's until the stream is through)
+	Tch9BigArgs ba;
+	std::memset(&ba, 0, sizeof(ba));
+	ba.n_calls = n_seg; ba.n_frames = n; ba.max_out = n;
+	ba.first = d_first; ba.frames = d_got; ba.label = d_label; ba.out = d_big; ba.n_out = d_count;
+	HIP_TRY(launch_tch9f_big(ba, st));
+	sg.back(&h_count, d_count, 1);
+	if ((r = sg.fetch())) return r;
+	*n_big = h_count;
+	const int fit = std::min((int)h_count, max_big);
+	if (fit > 0)
+		HIP_TRY(hipMemcpyAsync(big_out, d_big, (size_t)fit * sizeof(gmr1_hip_rx_big_record), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return 0;
 }
 
 }  // namespace gmr1

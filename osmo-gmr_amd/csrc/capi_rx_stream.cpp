@@ -18,6 +18,11 @@
 // continues.  The traffic windows of admitted frames fit the samples held for the same reason the walk's own do
 // (DESIGN.md 4.4b).  The handle keeps chains, never walks: what a push found reaches the next one only through the device
 // states and `carry`.
+//
+// A handle made by gmr1_hip_rx_stream_create_full follows TCH9 data calls as well (gmr1_hip_rx_run_full over pushes): a
+// third ping-pong pair for the CSD carrier, one struct gmr1_hip_tch9_state per chain in device memory and the timeslot of
+// each chain's last ASSIGNMENT COMMAND 1 on the host (`carry9`).  tch3_follow_chains notes this push's commands, and
+// tch9_follow_push (capi_rx_follow.cpp) follows them through the batched TCH9 call follower in one invocation.
 
 #include "fcch_acq.h"
 #include "rx_run.h"
@@ -61,9 +66,16 @@ struct gmr1_hip_rx_stream {
 	float2 *tbuf[2] = {nullptr, nullptr};          // the traffic carrier's samples: buf's layout, stride, held and keep
 	gmr1_hip_tch3_state *d_tstate = nullptr;       // one per chain, parallel to d_state
 	std::vector<TchCarry> carry;         // per chain
+	// a handle that follows TCH9 calls too (gmr1_hip_rx_stream_create_full; tch is set as well)
+	bool full = false;
+	float2 *cbuf[2] = {nullptr, nullptr};          // the CSD carrier's samples, held as tbuf is
+	gmr1_hip_tch9_state *d_t9state = nullptr;      // one per chain, parallel to d_state
+	std::vector<Tch9CallCarry> carry9;   // per chain
+	int kind() const { return full ? kRxStreamFull : tch ? kRxStreamTch : kRxStreamPlain; }
 	~gmr1_hip_rx_stream()
 	{
-		for (void *p : std::initializer_list<void *>{buf[0], buf[1], tbuf[0], tbuf[1], d_tstate, d_state, d_car, d_err, d_in})
+		for (void *p : std::initializer_list<void *>{buf[0], buf[1], tbuf[0], tbuf[1], cbuf[0], cbuf[1], d_tstate, d_t9state, d_state,
+		                                             d_car, d_err, d_in})
 			if (p) (void)hipFree(p);
 		for (void *p : std::initializer_list<void *>{h_car, h_err, h_in})
 			if (p) (void)hipHostFree(p);
@@ -110,17 +122,47 @@ long long rx_stream_bound(const gmr1_hip_rx_stream *h, uint64_t n)
 	return chains * (h->tch ? rx_stream_tch_rec_per_chain(len, h->sps) : rx_stream_rec_per_chain(len, h->sps));
 }
 
-// with_tch: the call is one of gmr1_hip_rx_stream_push_tch*
-int rx_stream_check(const gmr1_hip_rx_stream *h, bool with_tch, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
+long long rx_stream_big_bound(const gmr1_hip_rx_stream *h, uint64_t n)
+{
+	if (h->ended || !h->full)
+		return 0;
+	long long chains = 0, len = 0;
+	for (int i = 0; i < h->A; i++) {
+		if (rx_stream_dead(h, i))
+			continue;
+		chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
+		len = std::max(len, rx_stream_next_held(h, i, n));
+	}
+	return rx_stream_max_big(chains, len, h->sps);
+}
+
+// what a push entry hands in beside iq: `kind` says which entry it is (_push*, _push_tch*, _push_full*)
+struct RxStreamPush {
+	int kind;
+	const float *tch, *csd;
+	gmr1_hip_rx_big_record *big_out;
+	int max_big;
+	int *n_big;
+};
+
+int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, const float *iq, uint64_t iq_stride, uint64_t n,
                     const gmr1_hip_rx_record *out, int max_records, const int *n_records)
 {
 	if (!h || !n_records || max_records < 0 || (max_records > 0 && !out) || (n > 0 && !iq))
 		return fail(-EINVAL, "rx_stream_push: handle / n_records (and iq when n > 0, out when max_records > 0) are required");
-	if (h->tch != with_tch)
-		return fail(-EINVAL, h->tch ? "rx_stream_push: a handle of gmr1_hip_rx_stream_create_tch takes gmr1_hip_rx_stream_push_tch*"
-		                            : "rx_stream_push_tch: the handle was not made by gmr1_hip_rx_stream_create_tch");
-	if (with_tch && n > 0 && !tch)
+	if (h->kind() != p.kind) {
+		static const char *const entry[] = {"gmr1_hip_rx_stream_push*", "gmr1_hip_rx_stream_push_tch*", "gmr1_hip_rx_stream_push_full*"};
+		static const char *const maker[] = {"gmr1_hip_rx_stream_create", "gmr1_hip_rx_stream_create_tch", "gmr1_hip_rx_stream_create_full"};
+		return fail(-EINVAL, "rx_stream_push: a handle of %s takes %s, not %s", maker[h->kind()], entry[h->kind()], entry[p.kind]);
+	}
+	if (p.kind != kRxStreamPlain && n > 0 && !p.tch)
 		return fail(-EINVAL, "rx_stream_push_tch: tch is required when n > 0");
+	if (p.kind == kRxStreamFull) {
+		if (n > 0 && !p.csd)
+			return fail(-EINVAL, "rx_stream_push_full: csd is required when n > 0");
+		if (!p.n_big || p.max_big < 0 || (p.max_big > 0 && !p.big_out))
+			return fail(-EINVAL, "rx_stream_push_full: n_big (and big_out when max_big > 0) are required");
+	}
 	int dev = 0;
 	HIP_TRY(hipGetDevice(&dev));
 	if (dev != h->device)
@@ -139,6 +181,9 @@ int rx_stream_check(const gmr1_hip_rx_stream *h, bool with_tch, const float *iq,
 	const long long bound = rx_stream_bound(h, n);
 	if ((long long)max_records < bound)
 		return fail(-EINVAL, "rx_stream_push: max_records %d below the bound %lld", max_records, bound);
+	const long long big_bound = rx_stream_big_bound(h, n);
+	if (p.kind == kRxStreamFull && (long long)p.max_big < big_bound)
+		return fail(-EINVAL, "rx_stream_push_full: max_big %d below the bound %lld", p.max_big, big_bound);
 	return 0;
 }
 
@@ -159,7 +204,8 @@ int rx_stream_other(gmr1_hip_rx_stream *h, float2 **pair, long long need, bool g
 }
 
 // staging: [kept tail | chunk] -> the other buffer, states rebased; the handle's host mirror moves with it
-int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, const float2 *tch, uint64_t iq_stride, uint64_t n, int last)
+int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, const float2 *tch, const float2 *csd, uint64_t iq_stride,
+                    uint64_t n, int last)
 {
 	const int A = h->A;
 	std::vector<long long> next((size_t)A);
@@ -169,14 +215,15 @@ int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, con
 		need = std::max(need, next[i]);
 	}
 	need = (need + kRxKeepAlign - 1) / kRxKeepAlign * kRxKeepAlign;
-	float2 *src = h->buf[h->cur], *tsrc = h->tbuf[h->cur];
+	float2 *src = h->buf[h->cur], *tsrc = h->tbuf[h->cur], *csrc = h->cbuf[h->cur];
 	const long long src_stride = h->stride;
 	const bool grow = need > h->stride;
 	int r = rx_stream_other(h, h->buf, need, grow);
 	if (!r && h->tch) r = rx_stream_other(h, h->tbuf, need, grow);   // (the traffic pair follows the first one's decision)
+	if (!r && h->full) r = rx_stream_other(h, h->cbuf, need, grow);  // (and so does the CSD pair)
 	if (r) return r;
 	if (grow) h->stride = need;
-	float2 *dst = h->buf[1 - h->cur], *tdst = h->tbuf[1 - h->cur];
+	float2 *dst = h->buf[1 - h->cur], *tdst = h->tbuf[1 - h->cur], *cdst = h->cbuf[1 - h->cur];
 	for (int i = 0; i < A; i++) {
 		RxStageCarrier &c = h->h_car[i];
 		const bool dead = rx_stream_dead(h, i);
@@ -215,13 +262,23 @@ int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, con
 			sa.err = nullptr;
 			HIP_TRY(launch_rx_stage_copy(sa, st));
 		}
+		if (cdst) {
+			sa.src = csrc ? csrc : cdst;
+			sa.dst = cdst;
+			sa.iq = csd ? csd : cdst;
+			sa.state = nullptr;
+			sa.err = nullptr;
+			HIP_TRY(launch_rx_stage_copy(sa, st));
+		}
 	}
-	if (grow && (src || tsrc)) {
+	if (grow && (src || tsrc || csrc)) {
 		HIP_TRY(hipStreamSynchronize(st));     // the staging has read the old buffers
 		if (src) (void)hipFree(src);
 		if (tsrc) (void)hipFree(tsrc);
+		if (csrc) (void)hipFree(csrc);
 		h->buf[h->cur] = nullptr;
 		h->tbuf[h->cur] = nullptr;
+		h->cbuf[h->cur] = nullptr;
 	}
 	h->cur = 1 - h->cur;
 	for (int i = 0; i < A; i++) {
@@ -244,8 +301,9 @@ std::vector<int> all_chains(size_t n)
 }
 
 // the acquisition, once (nothing has been dropped yet: coordinates are absolute): the handle's chains and their states on the
-// device.  t0, the calls' first states, lives until the push's synchronisation.
-int rx_stream_acquire(gmr1_hip_rx_stream *h, RxRun &run, int last, std::vector<gmr1_hip_tch3_state> &t0)
+// device.  t0 and t9, the calls' first states, live until the push's synchronisation.
+int rx_stream_acquire(gmr1_hip_rx_stream *h, RxRun &run, int last, std::vector<gmr1_hip_tch3_state> &t0,
+                      std::vector<gmr1_hip_tch9_state> &t9)
 {
 	int r = run.acquire();
 	if (r) return r;
@@ -270,6 +328,16 @@ int rx_stream_acquire(gmr1_hip_rx_stream *h, RxRun &run, int last, std::vector<g
 			HIP_TRY(hipMalloc(&h->d_tstate, nc * sizeof(gmr1_hip_tch3_state)));
 			HIP_TRY(hipMemcpyAsync(h->d_tstate, t0.data(), nc * sizeof(gmr1_hip_tch3_state), hipMemcpyHostToDevice, run.st));
 			h->carry.assign(nc, TchCarry());
+		}
+		if (h->full) {
+			// no call, nothing held, the carrier's key (rx_tch9_init keeps the key)
+			t9.resize(nc);
+			std::memset(t9.data(), 0, nc * sizeof(gmr1_hip_tch9_state));
+			for (size_t k = 0; k < nc && !h->kc.empty(); k++)
+				std::memcpy(t9[k].kc, h->kc.data() + (size_t)h->chains[k].a * 8, 8);
+			HIP_TRY(hipMalloc(&h->d_t9state, nc * sizeof(gmr1_hip_tch9_state)));
+			HIP_TRY(hipMemcpyAsync(h->d_t9state, t9.data(), nc * sizeof(gmr1_hip_tch9_state), hipMemcpyHostToDevice, run.st));
+			h->carry9.assign(nc, Tch9CallCarry());
 		}
 	}
 	h->acquired = true;
@@ -319,13 +387,15 @@ void rx_stream_keep(gmr1_hip_rx_stream *h)
 }
 
 // the device part of a push -- stage, acquire (once), walk, follow, keep; the caller holds h->mu and the workspace lease,
-// and has validated everything (tch: the traffic carrier's chunk, laid out as iq, for a handle that follows TCH3 calls)
-int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, const float2 *tch, uint64_t iq_stride, uint64_t n,
+// and has validated everything (p.tch, p.csd: the traffic and the CSD carrier's chunks, laid out as iq, for a handle that
+// follows calls on them)
+int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, const RxStreamPush &p, uint64_t iq_stride, uint64_t n,
                         int last, gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
 	const int A = h->A, sps = h->sps;
 	int r;
-	if ((r = rx_stream_stage(st, h, iq, tch, iq_stride, n, last))) return r;
+	if ((r = rx_stream_stage(st, h, iq, reinterpret_cast<const float2 *>(p.tch), reinterpret_cast<const float2 *>(p.csd), iq_stride, n,
+	                         last))) return r;
 	std::vector<uint64_t> offset((size_t)A), length((size_t)A);
 	for (int i = 0; i < A; i++) {
 		offset[i] = (uint64_t)((long long)i * h->stride);
@@ -336,8 +406,9 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 	          nullptr, A, offset.data(), length.data(), h->arfcn.empty() ? nullptr : h->arfcn.data(), nullptr, out, max_records);
 	run.stat = h->stat; run.nch = h->nch;
 	std::vector<gmr1_hip_tch3_state> t0;
+	std::vector<gmr1_hip_tch9_state> t9;
 	// the acquisition, once every carrier holds what it reads
-	if (!h->acquired && ((long long)h->N >= rx_stream_acq_need(sps) || last) && (r = rx_stream_acquire(h, run, last, t0))) return r;
+	if (!h->acquired && ((long long)h->N >= rx_stream_acq_need(sps) || last) && (r = rx_stream_acquire(h, run, last, t0, t9))) return r;
 	const bool walking = h->acquired && !h->chains.empty();
 	if (walking && (r = rx_stream_walk(h, run))) return r;
 	HIP_TRY(hipMemcpyAsync(h->h_err, h->d_err, 4, hipMemcpyDeviceToHost, st));
@@ -349,19 +420,23 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 	*n_records = run.direct ? run.direct_total : 0;
 	// the TCH3 follow-up over this push's frames, and the records chain by chain in frame order
 	if (h->tch && walking) {
-		if ((r = tch3_follow_chains(st, sps, run.tch, run.arfcn, false, !last, h->chains, run.walks, all_chains(h->chains.size()), nullptr,
+		if ((r = tch3_follow_chains(st, sps, run.tch, run.arfcn, h->full, !last, h->chains, run.walks, all_chains(h->chains.size()), nullptr,
 		                            h->d_tstate, h->carry.data()))) return r;
 		*n_records = rx_hand_back(run.walks, out, max_records);
+		// the TCH9 follow-up over the same frames, from the commands the TCH3 records of this push carry
+		if (h->full && (r = tch9_follow_push(st, sps, reinterpret_cast<const float *>(h->cbuf[h->cur]), run.arfcn, !last, h->chains,
+		                                     run.walks, h->d_t9state, h->carry9.data(), p.big_out, p.max_big, p.n_big))) return r;
 	}
 	rx_stream_keep(h);
 	return 0;
 }
 
-// the host form's chunk goes up packed (stride n) through the handle's pinned block, the traffic carrier's *half bytes behind
-int rx_stream_pin_chunk(gmr1_hip_rx_stream *h, bool tch_entry, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n, size_t *half)
+// the host form's chunk goes up packed (stride n) through the handle's pinned block, the traffic carrier's *half bytes
+// behind, the CSD carrier's as many behind that
+int rx_stream_pin_chunk(gmr1_hip_rx_stream *h, const RxStreamPush &p, const float *iq, uint64_t iq_stride, uint64_t n, size_t *half)
 {
 	*half = (size_t)h->A * (size_t)n * sizeof(float2);
-	const size_t bytes = tch_entry ? 2 * *half : *half;
+	const size_t bytes = (size_t)(1 + p.kind) * *half;
 	if (bytes > h->h_in_bytes) {
 		if (h->h_in) (void)hipHostFree(h->h_in);
 		if (h->d_in) (void)hipFree(h->d_in);
@@ -373,40 +448,53 @@ int rx_stream_pin_chunk(gmr1_hip_rx_stream *h, bool tch_entry, const float *iq, 
 	}
 	for (int i = 0; i < h->A && n > 0; i++) {
 		std::memcpy(h->h_in + (size_t)i * n * 2, iq + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
-		if (tch_entry)
-			std::memcpy(h->h_in + *half / 4 + (size_t)i * n * 2, tch + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
+		if (p.kind != kRxStreamPlain)
+			std::memcpy(h->h_in + *half / 4 + (size_t)i * n * 2, p.tch + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
+		if (p.kind == kRxStreamFull)
+			std::memcpy(h->h_in + 2 * (*half / 4) + (size_t)i * n * 2, p.csd + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
 	}
 	return 0;
 }
 
-// every push entry: tch_entry for gmr1_hip_rx_stream_push_tch*, host for the forms that take host memory (on the null stream)
-int rx_stream_push_any(void *stream, gmr1_hip_rx_stream *h, bool tch_entry, bool host, const float *iq, const float *tch,
+// what needs neither the handle's contents nor the device to be refused
+int rx_stream_full_args(const gmr1_hip_rx_stream *h, int max_records, int *n_records, int max_big, int *n_big)
+{
+	if (n_records) *n_records = 0;
+	if (n_big) *n_big = 0;
+	if (!h || !n_records || !n_big || max_records < 0 || max_big < 0)
+		return fail(-EINVAL, "rx_stream_push_full: handle / n_records / n_big are required, and no negative count");
+	return 0;
+}
+
+// every push entry: p says which one, host is for the forms that take host memory (on the null stream)
+int rx_stream_push_any(void *stream, gmr1_hip_rx_stream *h, RxStreamPush p, bool host, const float *iq,
                        uint64_t iq_stride, uint64_t n, int last, gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
 	DevState *ds;
 	int r = dev_state(&ds);
 	if (r) return r;
 	if (n_records) *n_records = 0;
+	if (p.n_big) *p.n_big = 0;
 	std::unique_lock<std::mutex> lk;
 	if (h)
 		lk = std::unique_lock<std::mutex>(h->mu);
-	if ((r = rx_stream_check(h, tch_entry, iq, tch, iq_stride, n, out, max_records, n_records)))
+	if ((r = rx_stream_check(h, p, iq, iq_stride, n, out, max_records, n_records)))
 		return r;
 	hipStream_t st = host ? nullptr : (hipStream_t)stream;
 	size_t half = 0;
-	if (host && (r = rx_stream_pin_chunk(h, tch_entry, iq, tch, iq_stride, n, &half))) return r;
+	if (host && (r = rx_stream_pin_chunk(h, p, iq, iq_stride, n, &half))) return r;
 	// the loop holds the device's workspace, side stream and events: pushes of other handles wait their turn
 	WsLease lease;
 	if ((r = lease.acquire(ds, st))) return r;
 	if (host) {
 		if (half)
-			HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, tch_entry ? 2 * half : half, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, (size_t)(1 + p.kind) * half, hipMemcpyHostToDevice, st));
 		iq = h->d_in;
-		tch = tch_entry ? h->d_in + half / 4 : nullptr;
+		p.tch = p.kind != kRxStreamPlain ? h->d_in + half / 4 : nullptr;
+		p.csd = p.kind == kRxStreamFull ? h->d_in + 2 * (half / 4) : nullptr;
 		iq_stride = n;
 	}
-	r = rx_stream_push_impl(st, h, reinterpret_cast<const float2 *>(iq), reinterpret_cast<const float2 *>(tch), iq_stride, n, last,
-	                        out, max_records, n_records);
+	r = rx_stream_push_impl(st, h, reinterpret_cast<const float2 *>(iq), p, iq_stride, n, last, out, max_records, n_records);
 	if (r) h->broken = true;
 	return r;
 }
@@ -423,14 +511,15 @@ int rx_stream_create_check(const char *who, int n_arfcn, int sps, struct gmr1_hi
 	return 0;
 }
 
-// kc: the handle follows TCH3 calls (tch); n_arfcn x 8 key bytes, or NULL for the all-zero key
-int rx_stream_make(int n_arfcn, int sps, const uint16_t *arfcn, bool tch, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
+// kind: what the handle follows; kc: n_arfcn x 8 key bytes for a handle that follows calls, or NULL for the all-zero key
+int rx_stream_make(int n_arfcn, int sps, const uint16_t *arfcn, int kind, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
 {
 	std::unique_ptr<gmr1_hip_rx_stream> h(new gmr1_hip_rx_stream);
 	HIP_TRY(hipGetDevice(&h->device));
 	h->A = n_arfcn;
 	h->sps = sps;
-	h->tch = tch;
+	h->tch = kind != kRxStreamPlain;
+	h->full = kind == kRxStreamFull;
 	if (arfcn)
 		h->arfcn.assign(arfcn, arfcn + n_arfcn);
 	if (kc)
@@ -459,7 +548,7 @@ int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struc
 	int r = dev_state(&ds);
 	if (r) return r;
 	if ((r = rx_stream_create_check("rx_stream_create", n_arfcn, sps, out))) return r;
-	return rx_stream_make(n_arfcn, sps, arfcn, false, nullptr, out);
+	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamPlain, nullptr, out);
 }
 
 int gmr1_hip_rx_stream_create_tch(int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
@@ -468,7 +557,36 @@ int gmr1_hip_rx_stream_create_tch(int n_arfcn, int sps, const uint16_t *arfcn, c
 	if (r) return r;
 	DevState *ds;
 	if ((r = dev_state(&ds))) return r;
-	return rx_stream_make(n_arfcn, sps, arfcn, true, kc, out);
+	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamTch, kc, out);
+}
+
+int gmr1_hip_rx_stream_create_full(int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
+{
+	int r = rx_stream_create_check("rx_stream_create_full", n_arfcn, sps, out);
+	if (r) return r;
+	// the NT9 window of 351 sps + sps + sps / 2 samples has to fit the demodulator's (gmr1_hip_rx_run_full finds out at
+	// its first NT9 frame)
+	if (rx_tch9_in_len(sps) > kMaxInLen)
+		return fail(-EINVAL, "rx_stream_create_full: sps=%d: the NT9 window of %d samples is above %d (sps 1..%d)", sps,
+		            rx_tch9_in_len(sps), kMaxInLen, rx_stream_full_max_sps());
+	DevState *ds;
+	if ((r = dev_state(&ds))) return r;
+	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamFull, kc, out);
+}
+
+int gmr1_hip_rx_stream_max_big(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_big)
+{
+	if (!h || !max_big)
+		return fail(-EINVAL, "rx_stream_max_big: handle / max_big are required");
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	std::lock_guard<std::mutex> lk(h->mu);
+	const long long b = rx_stream_big_bound(h, n);
+	if (b > 0x7fffffffll)
+		return fail(-EINVAL, "rx_stream_max_big: %lld records do not fit an int", b);
+	*max_big = (int)b;
+	return 0;
 }
 
 int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_records)
@@ -489,26 +607,50 @@ int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t 
 int gmr1_hip_rx_stream_push_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n,
                                 int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	return rx_stream_push_any(stream, h, false, false, iq, nullptr, iq_stride, n, last, out, max_records, n_records);
+	return rx_stream_push_any(stream, h, {kRxStreamPlain, nullptr, nullptr, nullptr, 0, nullptr}, false, iq, iq_stride, n, last, out,
+	                          max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push(struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n, int last,
                             struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	return rx_stream_push_any(nullptr, h, false, true, iq, nullptr, iq_stride, n, last, out, max_records, n_records);
+	return rx_stream_push_any(nullptr, h, {kRxStreamPlain, nullptr, nullptr, nullptr, 0, nullptr}, true, iq, iq_stride, n, last, out,
+	                          max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push_tch_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch,
                                     uint64_t iq_stride, uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records,
                                     int *n_records)
 {
-	return rx_stream_push_any(stream, h, true, false, iq, tch, iq_stride, n, last, out, max_records, n_records);
+	return rx_stream_push_any(stream, h, {kRxStreamTch, tch, nullptr, nullptr, 0, nullptr}, false, iq, iq_stride, n, last, out, max_records,
+	                          n_records);
 }
 
 int gmr1_hip_rx_stream_push_tch(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
                                 int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	return rx_stream_push_any(nullptr, h, true, true, iq, tch, iq_stride, n, last, out, max_records, n_records);
+	return rx_stream_push_any(nullptr, h, {kRxStreamTch, tch, nullptr, nullptr, 0, nullptr}, true, iq, iq_stride, n, last, out, max_records,
+	                          n_records);
+}
+
+int gmr1_hip_rx_stream_push_full_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, const float *csd,
+                                     uint64_t iq_stride, uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records,
+                                     int *n_records, struct gmr1_hip_rx_big_record *big_out, int max_big, int *n_big)
+{
+	const int r = rx_stream_full_args(h, max_records, n_records, max_big, n_big);
+	if (r) return r;
+	return rx_stream_push_any(stream, h, {kRxStreamFull, tch, csd, big_out, max_big, n_big}, false, iq, iq_stride, n, last, out,
+	                          max_records, n_records);
+}
+
+int gmr1_hip_rx_stream_push_full(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, const float *csd, uint64_t iq_stride,
+                                 uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                 struct gmr1_hip_rx_big_record *big_out, int max_big, int *n_big)
+{
+	const int r = rx_stream_full_args(h, max_records, n_records, max_big, n_big);
+	if (r) return r;
+	return rx_stream_push_any(nullptr, h, {kRxStreamFull, tch, csd, big_out, max_big, n_big}, true, iq, iq_stride, n, last, out,
+	                          max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_status(const struct gmr1_hip_rx_stream *h, int32_t *status, int32_t *n_chains, uint64_t *retained)

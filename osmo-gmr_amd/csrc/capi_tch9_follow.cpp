@@ -1,6 +1,8 @@
 // capi_tch9_follow.cpp -- C ABI of the batched TCH9 call follower (reference src/gmr1_rx.c:262-353: rx_tch9_init, rx_tch9).
 // The state of a call is the caller's; every decision between the frames is taken on the device (tch9_follow_kernels.hip,
 // tch9_follow.h).  The bits form is the follower; the from-samples form is the NT9 demodulator into scratch in front of it.
+// tch9_follow_enqueue is the from-samples form for the library's own callers (the streaming receive loop), and
+// gmr1_hip_tch9_frames_to_records_dev closes a follower's frames up into the receive loop's big records (k_tch9f_big).
 #include "capi_common.h"
 #include "tch9_follow.h"
 
@@ -131,6 +133,19 @@ int samples_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_
 
 }  // namespace
 
+namespace gmr1 {
+
+size_t tch9_follow_scratch_bytes(int n_frames) { return Follow9Scratch((size_t)n_frames).bytes; }
+
+int tch9_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,
+                        int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                        struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
+{
+	return samples_enqueue(st, scratch, n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn, state, out);
+}
+
+}  // namespace gmr1
+
 extern "C" {
 
 int gmr1_hip_tch9_state_assign(struct gmr1_hip_tch9_state *s)
@@ -250,6 +265,31 @@ int gmr1_hip_tch9_follow_batch(int n_calls, int sps, int in_len, int mode, const
 			return r;
 	}
 	return sg.fetch();
+}
+
+int gmr1_hip_tch9_frames_to_records_dev(void *stream, int n_calls, const int32_t *first, int n_frames,
+                                        const struct gmr1_hip_tch9_frame *frames, const uint32_t *label,
+                                        struct gmr1_hip_rx_big_record *out, int max_out, int32_t *n_out)
+{
+	if (n_calls < 0 || n_frames < 0 || max_out < 0)
+		return fail(-EINVAL, "tch9_frames_to_records: negative count");
+	if (!first || !frames || !label || !n_out || (max_out > 0 && !out))
+		return fail(-EINVAL, "tch9_frames_to_records: NULL argument");
+	if (((uintptr_t)out & 15) || ((uintptr_t)frames & 3))
+		return fail(-EINVAL, "tch9_frames_to_records: out is not on a 16-byte boundary, or frames not on a 4-byte one");
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	if (n_calls == 0) {
+		HIP_TRY(hipMemsetAsync(n_out, 0, 4, (hipStream_t)stream));
+		return 0;
+	}
+	Tch9BigArgs a;
+	std::memset(&a, 0, sizeof(a));
+	a.n_calls = n_calls; a.n_frames = n_frames; a.max_out = max_out;
+	a.first = first; a.frames = frames; a.label = label; a.out = out; a.n_out = n_out;
+	HIP_TRY(launch_tch9f_big(a, (hipStream_t)stream));
+	return 0;
 }
 
 }  // extern "C"

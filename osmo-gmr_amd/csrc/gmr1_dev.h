@@ -495,6 +495,19 @@ hipError_t launch_a5_tch9f(const Tch9FollowArgs &a, hipStream_t stream);
 hipError_t launch_tch9f_emit(const Tch9FollowArgs &a, hipStream_t stream);
 // rx_tch9_init on device-resident states (k_tch9f_assign): entry j < n assigns state[call[j]]
 hipError_t launch_tch9f_assign(int n, const int32_t *call, struct gmr1_hip_tch9_state *state, hipStream_t stream);
+// the follower's frames as big records, closed up in call order (k_tch9f_big); everything is device memory
+struct Tch9BigArgs {
+	int n_calls, n_frames, max_out;
+	const int32_t *first;                       // n_calls + 1
+	const struct gmr1_hip_tch9_frame *frames;   // n_frames
+	const uint32_t *label;                      // n_calls: arfcn | chain << 16 | tn << 24
+	struct gmr1_hip_rx_big_record *out;         // max_out, on a 16-byte boundary
+	int32_t *n_out;
+};
+hipError_t launch_tch9f_big(const Tch9BigArgs &a, hipStream_t stream);
+// whole states between two device arrays (k_tch9f_move): for j < n, dst[dst_at[j]] = src[src_at[j]]
+hipError_t launch_tch9f_move(int n, struct gmr1_hip_tch9_state *dst, const int32_t *dst_at, const struct gmr1_hip_tch9_state *src,
+                             const int32_t *src_at, hipStream_t stream);
 // RACH (nt9_kernels.hip, same K = 5 trellis) and xCH over DC12 (xch_kernels.hip, K = 9)
 struct RachArgs {
 	int n;

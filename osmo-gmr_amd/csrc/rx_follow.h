@@ -94,6 +94,74 @@ inline void tch9_plan_items(int chain, const std::vector<FrameCtx> &log, const s
 	}
 }
 
+// ---- TCH9 over a push of the streaming loop (tch9_follow_push, capi_rx_follow.cpp) ----
+// What a chain's TCH9 follow-up carries from one push to the next, beside its state on the device
+struct Tch9CallCarry {
+	int tn = 0;               // the timeslot of the last ASSIGNMENT COMMAND 1
+	bool assigned = false;    // there was one
+};
+struct Tch9PushCall {                  // one chain's walk of this push, as the TCH9 follow-up sees it
+	const std::vector<FrameCtx> *log;
+	const std::vector<AssEvt> *events9; // this push's commands, frames counted in this push's log
+	Tch9CallCarry carry;                   // the call carried in
+	int len;                            // samples the carrier holds
+};
+struct Tch9Seg {                       // one call of the follower's invocation: a stretch of a chain's frames under one command
+	int chain;
+	int ev;                             // the command: 1 + its index in events9; 0: the call carried in (the chain's own state)
+	int tn;
+	size_t first;                       // its first item
+};
+struct Tch9PushPlan {
+	std::vector<Nt9Item> items;         // chain by chain, frame by frame; ass: the segment (index into segs)
+	std::vector<Tch9Seg> segs;          // chain by chain, in the order of the commands: items are contiguous over them
+	std::vector<int> last_seg;          // per chain: the segment whose state the chain keeps, -1: none ran
+	std::vector<Tch9CallCarry> carry;      // per chain: what the next push is carried
+};
+
+// tch9_plan_items over a capture cut into pushes.  rx_tch9_init leaves a state that depends on nothing before it, so
+// every command of the push starts a segment with a fresh state and all segments go into ONE invocation of the follower;
+// the frames in front of the push's first command belong to the call carried in (segment 0, only if there is one).  A
+// frame moves to the next segment by tch9_plan_items' own rule, events9[ev + 1].frame <= f.  A window that begins before
+// the samples is dropped as burst_map drops it; one that ends past them too -- unless `horizon` says more samples follow:
+// the walk admitted the frame against them, so that is an error, and the plan returns false.
+inline bool tch9_plan_push(const std::vector<Tch9PushCall> &calls, int sps, bool horizon, Tch9PushPlan *out)
+{
+	const int in_len = rx_tch9_in_len(sps);
+	*out = Tch9PushPlan();
+	for (size_t q = 0; q < calls.size(); q++) {
+		const Tch9PushCall &c = calls[q];
+		const std::vector<AssEvt> &ev9 = *c.events9;
+		out->carry.push_back(ev9.empty() ? c.carry : Tch9CallCarry{ev9.back().tn, true});
+		out->last_seg.push_back(-1);
+		if (!c.carry.assigned && ev9.empty())
+			continue;
+		const size_t seg0 = out->segs.size();
+		if (c.carry.assigned)
+			out->segs.push_back({(int)q, 0, c.carry.tn, out->items.size()});
+		size_t ev = 0;                    // commands applied so far
+		for (int f = c.carry.assigned ? 0 : ev9[0].frame; f < (int)c.log->size(); f++) {
+			while (ev < ev9.size() && ev9[ev].frame <= f) {
+				out->segs.push_back({(int)q, (int)ev + 1, ev9[ev].tn, out->items.size()});
+				ev++;
+			}
+			const int tn = out->segs.back().tn;
+			const long long begin = rx_tch9_begin((*c.log)[f].align, sps, tn);
+			if (begin + in_len > c.len && horizon)
+				return false;
+			if (begin < 0 || begin + in_len > c.len)
+				continue;
+			out->items.push_back({(int)q, f, tn, (int)out->segs.size() - 1});
+		}
+		// (a command behind the log's last frame cannot be: it came out of a frame of the log; it would still start a segment)
+		for (; ev < ev9.size(); ev++)
+			out->segs.push_back({(int)q, (int)ev + 1, ev9[ev].tn, out->items.size()});
+		if (out->segs.size() > seg0)
+			out->last_seg.back() = (int)out->segs.size() - 1;
+	}
+	return true;
+}
+
 struct Tch9Jobs {
 	std::vector<int> facch, tch;        // item indices: FACCH9 jobs, TCH9 jobs (run-major: one run per interleaver life)
 	std::vector<int32_t> pos;           // per TCH9 job: its position in its run

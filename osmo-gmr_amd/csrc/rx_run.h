@@ -91,6 +91,12 @@ int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t
 int tch9_follow_chains(hipStream_t st, int sps, const float *csd, const uint16_t *arfcn, const uint8_t *kc,
                        const std::vector<RxChain> &chains, std::vector<RxWalk> &walks);
 
+// the TCH9 follow-up of one push of the streaming loop: d_state holds one state per chain, carry one entry per chain;
+// big_out is host memory
+int tch9_follow_push(hipStream_t st, int sps, const float *csd, const uint16_t *arfcn, bool horizon, const std::vector<RxChain> &chains,
+                     const std::vector<RxWalk> &walks, gmr1_hip_tch9_state *d_state, Tch9CallCarry *carry,
+                     gmr1_hip_rx_big_record *big_out, int max_big, int *n_big);
+
 inline size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
 
 // what a carrier's records carry: its ARFCN, or its index

@@ -77,4 +77,18 @@ GMR1_HD long long rx_stream_tch_rec_per_chain(long long len, int sps)
 	return rx_stream_rec_per_chain(len, sps) + rx_stream_frames_per_chain(len, sps);
 }
 
+// ---- a handle that follows TCH9 data calls too (gmr1_hip_rx_stream_create_full) ----
+// what a handle follows, and which push entry it therefore takes
+constexpr int kRxStreamPlain = 0, kRxStreamTch = 1, kRxStreamFull = 2;
+
+// The window rx_tch9 cuts on the CSD carrier is 351 * sps + sps + sps / 2 samples (rx_tch9_in_len, rx_follow.h), and the
+// demodulator takes windows up to kMaxInLen: the largest sps a full handle can be made for
+GMR1_HD int rx_stream_full_max_sps() { return 11; }
+
+// A full handle hands back at most one big record (FACCH9 / TCH9) per frame a chain's walk can log
+GMR1_HD long long rx_stream_max_big(long long chains, long long len, int sps)
+{
+	return chains > 0 ? chains * rx_stream_frames_per_chain(len, sps) : 0;
+}
+
 }  // namespace gmr1

@@ -7,6 +7,9 @@
 //   k_nt9 <JOBS>   (nt9_kernels.hip) twice over the frame slots: the FACCH9 frames, the TCH9 frames
 //   k_tch9f_emit   one wavefront per call: the caller's records, and the call's last two TCH9 bursts, deciphered, into its state
 // and, between two invocations, k_tch9f_assign (gmr1_hip_tch9_state_assign_batch_dev): rx_tch9_init on the states where they lie.
+// For the receive loop's callers: k_tch9f_big (gmr1_hip_tch9_frames_to_records_dev) closes the reporting frames up into big
+// records, and k_tch9f_move copies whole states between two device arrays (the streaming push gathers its calls' states
+// and adopts the last one of every chain).
 //
 // Nothing here is a chain: a frame's class depends on nothing before it, and its sources are the nearest two TCH9 frames
 // below it -- one ballot of "is TCH9" per 64 frames and two highest-set-bit searches below the lane, the last two TCH9
@@ -21,6 +24,10 @@ namespace gmr1 {
 
 static_assert(sizeof(gmr1_hip_tch9_state) == 1340 && sizeof(gmr1_hip_tch9_frame) == 80, "public layout");
 static_assert(offsetof(gmr1_hip_tch9_state, held) == 16 && offsetof(gmr1_hip_tch9_frame, l2) == 12, "public layout");
+static_assert(sizeof(gmr1_hip_rx_big_record) == 80 && offsetof(gmr1_hip_rx_big_record, l2) == 16 &&
+              offsetof(gmr1_hip_rx_big_record, tn) == 8 && offsetof(gmr1_hip_rx_big_record, conv) == 12, "public layout");
+static_assert(offsetof(gmr1_hip_tch9_frame, type) == 1 && offsetof(gmr1_hip_tch9_frame, fn) == 4 &&
+              offsetof(gmr1_hip_tch9_frame, conv) == 8 && sizeof(gmr1_hip_tch9_state) % 4 == 0, "public layout");
 static_assert(kT9Off == GMR1_HIP_TCH9_OFF && kT9Facch == GMR1_HIP_TCH9_FACCH9 && kT9Tch == GMR1_HIP_TCH9_TCH9 &&
               kT9Err == GMR1_HIP_TCH9_ERR, "classes");
 
@@ -150,6 +157,93 @@ __global__ __launch_bounds__(64 * kT9Waves) void k_tch9f_assign(int n, const int
 		st->active = 1;
 		st->n_held = 0;
 	}
+}
+
+// The follower's frames as gmr1_hip_rx_run_full reports them: one wavefront per call.  A frame reports when its type is
+// not 0; its slot in `out` is the number of reporting frames in front of it, over all calls -- frames are contiguous over
+// calls, so a wave counts the frames below its call's first one with the same ballot and popcount it then uses on its
+// own, 64 frames a step, and nobody waits for anybody.  A record is five 16-byte stores: lane w of a step writes part
+// w % 5 of the step's frame w / 5, whose slot it takes from that frame's lane.  Only slots below max_out are stored; the
+// wave of the last call writes the count.  first[] is the caller's device memory: clamped as in the follower.
+__global__ __launch_bounds__(64 * kT9Waves) void k_tch9f_big(Tch9BigArgs a)
+{
+	const int lane = threadIdx.x & 63;
+	const int c = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kT9Waves + (threadIdx.x >> 6)));
+	if (c >= a.n_calls)
+		return;
+	const int kf = clamp_frame9(a.first[0], 0, a.n_frames);
+	const int k0 = clamp_frame9(a.first[c], 0, a.n_frames), k1 = clamp_frame9(a.first[c + 1], k0, a.n_frames);
+	int base = 0;
+	for (int kb = kf; kb < k0; kb += 64) {
+		const int k = kb + lane;
+		base += __popcll(__ballot(k < k0 && a.frames[k].type != 0));
+	}
+	const uint32_t lab = a.label[c];
+	for (int kb = k0; kb < k1; kb += 64) {
+		const int k = kb + lane;
+		const unsigned long long rep = __ballot(k < k1 && a.frames[k].type != 0);
+		const int slot = base + __popcll(rep & ((1ull << lane) - 1ull));
+		for (int w = lane; w < 64 * 5; w += 64) {
+			const int i = w / 5, j = w % 5;
+			const int s = __shfl(slot, i);
+			if (!((rep >> i) & 1ull) || s >= a.max_out)
+				continue;
+			const uint32_t *f = reinterpret_cast<const uint32_t *>(a.frames + kb + i);
+			const uint32_t w0 = f[0];
+			const uint32_t type = (w0 >> 8) & 0xffu, len = (w0 >> 16) & 0xffu;
+			uint4 v;
+			if (j == 0) {
+				v.x = (lab & 0x00ffffffu) | (type << 24);        // arfcn, chain, type
+				v.y = f[1];                                      // fn
+				v.z = (lab >> 24) | (len << 16);                 // tn, crc 0, len, pad 0
+				v.w = f[2];                                      // conv
+			} else {
+				uint32_t q[4];
+				for (int t = 0; t < 4; t++) {
+					const int b = 16 * (j - 1) + 4 * t;          // first byte of the word in l2
+					const int left = (int)len - b;
+					q[t] = left <= 0 ? 0u : f[3 + b / 4] & (left >= 4 ? 0xffffffffu : (1u << (8 * left)) - 1u);
+				}
+				v = make_uint4(q[0], q[1], q[2], q[3]);
+			}
+			reinterpret_cast<uint4 *>(a.out + s)[j] = v;
+		}
+		base += __popcll(rep);
+	}
+	if (c == a.n_calls - 1 && lane == 0)
+		*a.n_out = base;
+}
+
+// whole states from one device array to another: pair j copies src[src_at[j]] to dst[dst_at[j]], one wavefront per pair
+// (no two pairs of a launch name one destination)
+__global__ __launch_bounds__(64 * kT9Waves) void k_tch9f_move(int n, gmr1_hip_tch9_state *dst, const int32_t *__restrict__ dst_at,
+                                                                const gmr1_hip_tch9_state *src, const int32_t *__restrict__ src_at)
+{
+	const int lane = threadIdx.x & 63;
+	const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kT9Waves + (threadIdx.x >> 6)));
+	if (w >= n)
+		return;
+	const uint32_t *s = reinterpret_cast<const uint32_t *>(src + src_at[w]);
+	uint32_t *d = reinterpret_cast<uint32_t *>(dst + dst_at[w]);
+	for (int i = lane; i < (int)(sizeof(gmr1_hip_tch9_state) / 4); i += 64)
+		d[i] = s[i];
+}
+
+hipError_t launch_tch9f_big(const Tch9BigArgs &a, hipStream_t stream)
+{
+	if (a.n_calls <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_tch9f_big, dim3((a.n_calls + kT9Waves - 1) / kT9Waves), dim3(64 * kT9Waves), 0, stream, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_tch9f_move(int n, struct gmr1_hip_tch9_state *dst, const int32_t *dst_at, const struct gmr1_hip_tch9_state *src,
+                             const int32_t *src_at, hipStream_t stream)
+{
+	if (n <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_tch9f_move, dim3((n + kT9Waves - 1) / kT9Waves), dim3(64 * kT9Waves), 0, stream, n, dst, dst_at, src, src_at);
+	return hipGetLastError();
 }
 
 hipError_t launch_tch9f_assign(int n, const int32_t *call, struct gmr1_hip_tch9_state *state, hipStream_t stream)

@@ -630,7 +630,8 @@ def synth_tch3_carrier(fmt_speech: BurstFormat, fmt_facch: BurstFormat, n_sample
     Bursts from frame index `cipher_from` on are A5/1-ciphered with kc (speech: fn of the burst,
     FACCH3: fn of each of its four bursts; reference src/gmr1_rx.c:390-399, 500-503).
     ass_cmd = (k, tn9): every FACCH3 message sent at frame index >= k is an ASSIGNMENT COMMAND 1 to
-    timeslot tn9 (facch3_is_ass_cmd_1 / facch3_ass_cmd_1_parse, gmr1_rx.c:248-258).
+    timeslot tn9 (facch3_is_ass_cmd_1 / facch3_ass_cmd_1_parse, gmr1_rx.c:248-258).  A list of such pairs: a message
+    sent at frame index >= k names the timeslot of the last entry whose k it has reached.
     Returns (stream, sent list of dicts)."""
     frame_len = 24 * 39 * sps
     sigma = np.sqrt(10.0 ** (-esn0_db / 10.0) / 2.0)
@@ -641,6 +642,7 @@ def synth_tch3_carrier(fmt_speech: BurstFormat, fmt_facch: BurstFormat, n_sample
     if k_stop is not None:
         n_frames = min(n_frames, k_stop)
     sent = []
+    cmds = [] if ass_cmd is None else [ass_cmd] if isinstance(ass_cmd, tuple) else sorted(tuple(c) for c in ass_cmd)
 
     def put(k, symbols):
         body = shape_bursts(symbols[None, :], sps, frac, span)[0]
@@ -677,10 +679,11 @@ def synth_tch3_carrier(fmt_speech: BurstFormat, fmt_facch: BurstFormat, n_sample
             l2[0, 9] &= 0x0F                                  # 76 bits
             if l2[0, 3] == 0x06 and l2[0, 4] == 0x2E:
                 l2[0, 4] = 0                                  # never an ASSIGNMENT COMMAND 1 by accident
-            if ass_cmd is not None and k >= ass_cmd[0]:
+            named = [tn9 for k_cmd, tn9 in cmds if k >= k_cmd]
+            if named:
                 l2[0, 3], l2[0, 4] = 0x06, 0x2E
-                l2[0, 5] = (l2[0, 5] & 0xFC) | ((ass_cmd[1] >> 3) & 0x03)
-                l2[0, 6] = ((ass_cmd[1] & 0x07) << 5) | (l2[0, 6] & 0x1F)
+                l2[0, 5] = (l2[0, 5] & 0xFC) | ((named[-1] >> 3) & 0x03)
+                l2[0, 6] = ((named[-1] & 0x07) << 5) | (l2[0, 6] & 0x1F)
             sb = rng.integers(0, 2, size=(1, 32), dtype=np.uint8)
             ciph = None
             if ciphered(k):

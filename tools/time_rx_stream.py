@@ -9,8 +9,11 @@ ChanStream.push_dev -> RxStream.push_dev on one stream, against channelize + rx_
 --tch: every carrier has a traffic carrier with one call on it (an IMMEDIATE ASSIGNMENT around frame 40, some ciphered),
 the handle follows TCH3 calls (push_tch_dev) and the one-shot call is gmr1_hip_rx_run_tch_dev; the chained pipeline is
 left out.
+--full: every carrier also has a CSD carrier with one data call on it (an ASSIGNMENT COMMAND 1 on the call's FACCH3 from
+call frame 25 on), the handle follows TCH3 and TCH9 calls (push_full_dev) and the one-shot call is
+gmr1_hip_rx_run_full_dev; records and big records are compared, the chained pipeline is left out.
 
-    python tools/time_rx_stream.py [--seconds 60] [--pushes 0.01,0.1,1] [--tch] [--wide-seconds 0] [--out result.json]
+    python tools/time_rx_stream.py [--seconds 60] [--pushes 0.01,0.1,1] [--tch | --full] [--wide-seconds 0] [--out result.json]
 """
 import argparse
 import json
@@ -45,8 +48,11 @@ def main():
     ap.add_argument("--wide-seconds", type=float, default=10.0,
                     help="length of the chained pipeline's wideband capture (0: leave the pipeline out)")
     ap.add_argument("--tch", action="store_true", help="follow TCH3 calls: one call per carrier")
+    ap.add_argument("--full", action="store_true", help="follow TCH3 and TCH9 calls: one voice and one data call per carrier")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.tch and args.full:
+        ap.error("--tch and --full are two kinds of handle: give one")
     import torch
     import workloads
     from __graft_entry__ import load_package
@@ -56,8 +62,18 @@ def main():
     api.load()
     api.init(0)
     sps, A, rate = 4, 64, 23400 * 4
-    kc = dt = None
-    if args.tch:
+    kc = dt = dc = None
+    if args.full:
+        import oracle_lib as orc
+        orc.build()
+        orc.lib()
+        keys = [np.arange(8, dtype=np.uint8) + k if k % 2 else None for k in range(8)]
+        pairs = [workloads.bcch_tch_csd_triple(pkg, orc, 900 + k, seconds=args.seconds, sps=sps, stn=(7 * k) % 32, delay=k % 8,
+                                               tn=(5 * k + 3) % 32, p=(7 * k) % 40, tn9=(3 * k + 2) % 24, k_ass=40, k_cmd=25, kc=keys[k],
+                                               cfo_hz=40.0 * k - 150.0)[:3] for k in range(8)]
+        base = [b for b, _, _ in pairs]
+        kc = np.stack([keys[i % 8] if keys[i % 8] is not None else np.zeros(8, np.uint8) for i in range(A)])
+    elif args.tch:
         keys = [np.arange(8, dtype=np.uint8) + k if k % 2 else None for k in range(8)]
         pairs = [workloads.bcch_tch_pair(pkg, 900 + k, seconds=args.seconds, sps=sps, stn=(7 * k) % 32, delay=k % 8, tn=(5 * k + 3) % 32,
                                          p=(7 * k) % 40, k_ass=40, kc=keys[k], cipher_after=None if keys[k] is None else 25,
@@ -71,15 +87,23 @@ def main():
     x = np.stack([base[i % 8][:n] for i in range(A)]).astype(np.complex64)
     arfcn = np.arange(A, dtype=np.uint16) + 100
     d = torch.from_numpy(x.view(np.float32).reshape(A, -1)).cuda()
-    if args.tch:
+    if args.tch or args.full:
         dt = torch.from_numpy(np.stack([pairs[i % 8][1][:n] for i in range(A)]).astype(np.complex64).view(np.float32).reshape(A, -1)).cuda()
+    if args.full:
+        dc = torch.from_numpy(np.stack([pairs[i % 8][2][:n] for i in range(A)]).astype(np.complex64).view(np.float32).reshape(A, -1)).cuda()
     stream = torch.cuda.current_stream()
     st = stream.cuda_stream
     offset = np.arange(A, dtype=np.uint64) * np.uint64(n)
     length = np.full(A, n, np.uint64)
-    res = {"carriers": A, "capture_s": n / rate, "sps": sps, "tch": bool(args.tch)}
+    res = {"carriers": A, "capture_s": n / rate, "sps": sps, "tch": bool(args.tch), "full": bool(args.full)}
     out = np.empty(1 << 21, api.RX_RECORD)
-    if args.tch:
+    ref_big = None
+    if args.full:
+        def one_shot():
+            rec, big, status, chains = api.rx_run_full_dev(st, d.data_ptr(), dt.data_ptr(), dc.data_ptr(), offset, length, sps=sps,
+                                                           arfcn=arfcn, kc=kc, max_records=1 << 21, max_big=1 << 20)
+            return (rec, big), status, chains, None
+    elif args.tch:
         one_shot = lambda: api.rx_run_tch_dev(st, d.data_ptr(), dt.data_ptr(), offset, length, sps=sps, arfcn=arfcn, kc=kc,
                                               max_records=1 << 21)
     else:
@@ -91,6 +115,9 @@ def main():
         t0 = time.perf_counter()
         ref, rst, rch, _ = one_shot()
         t.append(time.perf_counter() - t0)
+    if args.full:
+        ref, ref_big = ref
+        res["big_records"] = int(len(ref_big))
     ref = ref.copy()
     res["one_shot_ms"] = 1e3 * min(t)
     res["records"] = int(len(ref))
@@ -99,33 +126,44 @@ def main():
         p = int(round(p_s * rate))
         best = None
         for _ in range(2):
-            per, got, evs = [], [], []
+            per, got, got_big, evs = [], [], [], []
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            with api.RxStream(A, sps=sps, arfcn=arfcn, tch=args.tch, kc=kc) as s:
+            with api.RxStream(A, sps=sps, arfcn=arfcn, tch=args.tch, full=args.full, kc=kc) as s:
                 at = 0
                 buf = np.empty(max(s.max_records(p), 1), api.RX_RECORD)
+                bbuf = np.empty(max(s.max_big(p), 1), api.RX_BIG_RECORD)
                 while at < n:
                     k = min(p, n - at)
                     if s.max_records(k) > buf.size:
                         buf = np.empty(s.max_records(k), api.RX_RECORD)
+                    if s.max_big(k) > bbuf.size:
+                        bbuf = np.empty(s.max_big(k), api.RX_BIG_RECORD)
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(stream)
                     q0 = time.perf_counter()
-                    r = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf,
-                                   tch_ptr=dt.data_ptr() + 8 * at if args.tch else None)
+                    if args.full:
+                        r, rb = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf, tch_ptr=dt.data_ptr() + 8 * at,
+                                           csd_ptr=dc.data_ptr() + 8 * at, big=bbuf)
+                    else:
+                        r = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf,
+                                       tch_ptr=dt.data_ptr() + 8 * at if args.tch else None)
                     per.append(time.perf_counter() - q0)
                     e1.record(stream)
                     evs.append((e0, e1))
                     got.append(r.copy())
+                    if args.full:
+                        got_big.append(rb.copy())
                     at += k
             total = time.perf_counter() - t0
             torch.cuda.synchronize()
             dev = [a.elapsed_time(b) for a, b in evs]
             if best is None or total < best[0]:
-                best = (total, per, got, dev)
-        total, per, got, dev = best
+                best = (total, per, got, dev, got_big)
+        total, per, got, dev, got_big = best
         same = _sorted(np.concatenate(got), arfcn).tobytes() == ref.tobytes()
+        if args.full:
+            same = same and _sorted(np.concatenate(got_big), arfcn).tobytes() == ref_big.tobytes()
         per_ms = np.array(per) * 1e3
         dev_ms = np.array(dev)
         steady = per_ms[len(per_ms) // 4:] if len(per_ms) > 8 else per_ms
@@ -138,7 +176,7 @@ def main():
                                  "push_dev_ms_max": float(dev_ms.max()), "identical": bool(same)}
         print(json.dumps({("push_%gs" % p_s): res["push_%gs" % p_s]}), flush=True)
     # the chained pipeline
-    if args.tch or args.wide_seconds <= 0:
+    if args.tch or args.full or args.wide_seconds <= 0:
         return finish(res, args.out)
     fs = 2.0e6
     carriers = tuple((c, dict(stn=(3 * c) % 32, delay=c % 8, cfo_hz=float(c))) for c in (3, 17, 33, 60))
