@@ -36,6 +36,8 @@
  *   gmr1_hip_fcch_acquire_batch* -> fcch_single_init / fcch_multi_process  src/gmr1_rx.c:605-733 (up to the survivor list)
  *   gmr1_hip_tch3_follow_batch*  -> rx_tch3, src/gmr1_rx.c:355-600
  *   gmr1_hip_tch9_follow*_batch* -> rx_tch9, src/gmr1_rx.c:262-353
+ *   gmr1_hip_tch3_frames_to_pcm* -> gmr1_codec_decode_frame / _decode_dtx over a call's bursts  include/osmocom/gmr1/codec/codec.h:41-45
+ *   gmr1_hip_tch3_voice_batch*   -> rx_tch3 and the above: samples in, audio out (gmr1_rx and gmr1_ambe_decode in one call)
  */
 #ifndef GMR1_HIP_H
 #define GMR1_HIP_H
@@ -81,7 +83,7 @@ struct gmr1_hip_burst_flat {
  * Threads: gmr1_hip_last_error() is per thread; the burst-level _batch / _batch_dev calls keep no state
  * between calls and may run from several threads on different streams.  The calls that use the library's
  * grow-only per-device workspace -- gmr1_hip_fcch_rough*_batch*, gmr1_hip_fcch_acquire_batch*, gmr1_hip_channelize*, gmr1_hip_ddc*,
- * gmr1_hip_rx_run*, gmr1_hip_tch3_follow_batch*, gmr1_hip_tch9_follow*_batch*, gmr1_hip_detect_batch* with more than four candidates, and gmr1_hip_tch3_rx_batch* where it
+ * gmr1_hip_rx_run*, gmr1_hip_tch3_follow_batch*, gmr1_hip_tch3_voice_batch*, gmr1_hip_tch9_follow*_batch*, gmr1_hip_detect_batch* with more than four candidates, and gmr1_hip_tch3_rx_batch* where it
  * runs as two launches without a caller's soft-bit buffer -- may ALSO be called from several threads and streams:
  * they take turns.  The host part of such a call runs under a per-device lock (a second thread waits), and a call
  * on another stream first makes its stream wait, on the device, for the previous user's kernels; nothing is
@@ -687,6 +689,49 @@ int gmr1_hip_tch3_follow_batch(int n_calls, int sps, int in_len, const float *iq
                                const int32_t *first, int n_frames,
                                const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                                struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
+
+/* ---- a followed voice call to audio: the follower's records through the AMBE decoder, on the device ------------
+ * gmr1_rx logs the speech bursts it decodes and gmr1_ambe_decode reads a file of frames (src/gmr1_rx.c:551-600,
+ * src/gmr1_ambe_decode.c:122-150); here the records of n_calls calls of any lengths go to 8 kHz PCM in one launch, one
+ * wavefront per call.  Call c owns records first[c] .. first[c+1]-1 of `frames`, as in the follower.  Record k gives
+ * pcm[320 k .. 320 k + 320) and, where rv is given, rv[2 k], rv[2 k + 1]:
+ *   type 0x10    l2[0..10) is decoded into samples 0..159 and l2[10..20) into samples 160..319, exactly as
+ *                gmr1_hip_codec_decode_batch* decodes two consecutive frames (tone and silence frames included); rv gets
+ *                the two verdicts (0, or -EINVAL for a tone frame with an unassigned code).
+ *   any other    (type 0, 0x12; class OFF, DKAB, DKAB_MISSING, FACCH, ERR) 320 zero samples, rv 0, 0, and the decoder is
+ *                not touched: two gmr1_codec_decode_dtx calls (src/codec/ambe.c:130-141).  Only `type` is looked at;
+ *                l2 of such a record is ignored whatever it holds.
+ * codec_state: gmr1_hip_codec_state_bytes() per call, 16-byte aligned: the opaque state of gmr1_hip_codec_decode_batch*,
+ * so a call can move between that entry and these, and travels with the call's gmr1_hip_tch3_state: both go in and come
+ * back, and a call cut into any pieces gives the samples and the states of one invocation.  A call without records
+ * keeps its codec_state byte for byte.
+ *
+ * gmr1_hip_tch3_voice_batch* is gmr1_hip_tch3_follow_batch* and gmr1_hip_tch3_frames_to_pcm* back to back on the stream:
+ * the follower's record array `out` is the decoder's input; arguments up to `out` are the follower's.
+ *
+ * _dev: every pointer is device memory; the call enqueues on `stream` and returns -- no copy to the host and no
+ * synchronisation (but for the first use on a device, which builds the decoder's tables, and a workspace that has to
+ * grow); gmr1_hip_codec_init_dev makes fresh decoders; the entries of first are clamped to 0..n_frames.  Host forms: flags
+ * and codec_state == NULL as for gmr1_hip_codec_decode_batch (GMR1_HIP_CODEC_FRESH, GMR1_HIP_CODEC_CLEARED; NULL: fresh
+ * decoders, nothing written back); first is checked as the follower's host form checks it.
+ * n_calls == 0 or n_frames == 0 does nothing.  -EINVAL: a negative count, a NULL required array (rv is optional;
+ * codec_state in the _dev forms is not), pcm not 2-byte or codec_state not 16-byte aligned, unknown flag bits, and for the
+ * samples forms everything the follower refuses.  -ENODEV without a device.  Nothing is written on either: the arguments are
+ * checked before the device is asked for. */
+int gmr1_hip_tch3_frames_to_pcm_dev(void *stream, int n_calls, const int32_t *first /* n_calls + 1 */, int n_frames,
+                                    const struct gmr1_hip_tch3_frame *frames, void *codec_state,
+                                    int16_t *pcm /* n_frames x 320 */, int32_t *rv /* n_frames x 2, or NULL */);
+int gmr1_hip_tch3_frames_to_pcm(int n_calls, const int32_t *first, int n_frames,
+                                const struct gmr1_hip_tch3_frame *frames, void *codec_state, int flags,
+                                int16_t *pcm, int32_t *rv);
+int gmr1_hip_tch3_voice_batch_dev(void *stream, int n_calls, int sps, int in_len, const float *iq,
+                                  const int32_t *first, int n_frames, const uint64_t *offset, const float *freq_shift,
+                                  const uint32_t *fn, struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out,
+                                  void *codec_state, int16_t *pcm, int32_t *rv);
+int gmr1_hip_tch3_voice_batch(int n_calls, int sps, int in_len, const float *iq, uint64_t iq_len, const int32_t *first,
+                              int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                              struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out,
+                              void *codec_state, int flags, int16_t *pcm, int32_t *rv);
 
 /* ---- following a circuit-switched data call: rx_tch9 over many calls at once (gmr1_rx.c:262-353) -------------
  * What gmr1_rx does per frame once an ASSIGNMENT COMMAND 1 has named a timeslot on the CSD carrier: demodulate the NT9

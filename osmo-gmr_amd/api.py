@@ -128,6 +128,10 @@ SIGNATURES = {
     "gmr1_hip_tch3_state_assign_batch_dev": (I, P, I, P, P, P, P),
     "gmr1_hip_tch3_follow_batch_dev": (I, P, I, I, I, P, P, I, P, P, P, P, P),
     "gmr1_hip_tch3_follow_batch": (I, I, I, I, P, U64, P, I, P, P, P, P, P),
+    "gmr1_hip_tch3_frames_to_pcm_dev": (I, P, I, P, I, P, P, P, P),
+    "gmr1_hip_tch3_frames_to_pcm": (I, I, P, I, P, P, I, P, P),
+    "gmr1_hip_tch3_voice_batch_dev": (I, P, I, I, I, P, P, I, P, P, P, P, P, P, P, P),
+    "gmr1_hip_tch3_voice_batch": (I, I, I, I, P, U64, P, I, P, P, P, P, P, P, I, P, P),
     "gmr1_hip_tch9_state_assign": (I, P),
     "gmr1_hip_tch9_state_assign_batch_dev": (I, P, I, P, P),
     "gmr1_hip_tch9_follow_bits_batch_dev": (I, P, I, I, P, I, P, P, P, P, P, P),
@@ -1795,6 +1799,70 @@ def codec_init_dev(stream, n_ch, state_ptr, flags=0):
 
 def codec_decode_batch_dev(stream, n_ch, n_frames, frames_ptr, pcm_ptr, rv_ptr, state_ptr):
     _call("gmr1_hip_codec_decode_batch_dev", stream, n_ch, n_frames, frames_ptr, pcm_ptr, rv_ptr, state_ptr)
+
+
+# ---------------------------------------------------------------------------
+# a followed voice call to audio (gmr1_hip_tch3_frames_to_pcm*, gmr1_hip_tch3_voice_batch*)
+# ---------------------------------------------------------------------------
+def _codec_state(state, n_calls, flags):
+    """-> (a 16-byte aligned (n_calls, codec_state_bytes()) uint8 array: a copy of `state`, or zeros for fresh decoders;
+    flags with CODEC_FRESH set in the latter case)"""
+    nb = codec_state_bytes()
+    raw = np.zeros(n_calls * nb + 16, np.uint8)
+    at = -raw.ctypes.data % 16
+    own = raw[at:at + n_calls * nb].reshape(n_calls, nb)
+    if state is None:
+        return own, flags | CODEC_FRESH
+    state = _arr(state, np.uint8)
+    assert state.shape == (n_calls, nb)
+    own[:] = state
+    return own, flags
+
+
+def tch3_frames_to_pcm(frames, first, state=None, flags=0):
+    """The TCH3 follower's records (TCH3_FRAME array) of len(first) - 1 calls, call c owning records first[c] .. first[c+1]
+    -> (pcm (n_frames, 320) int16, rv (n_frames, 2) int32, state): a speech record (type 0x10) is its two frames decoded, any
+    other record 320 zeros that leave the decoder alone.  state: None = fresh decoders, or the uint8 array a previous call
+    (or codec_decode_batch) returned: continues those calls."""
+    frames = np.ascontiguousarray(frames, TCH3_FRAME).reshape(-1)
+    first = _arr(first, np.int32)
+    n_calls, n_fr = first.size - 1, frames.size
+    pcm = np.zeros((n_fr, 320), np.int16)
+    rv = np.zeros((n_fr, 2), np.int32)
+    state, flags = _codec_state(state, n_calls, flags)
+    _call("gmr1_hip_tch3_frames_to_pcm", n_calls, _p(first), n_fr, _p(frames), _p(state), flags, _p(pcm), _p(rv))
+    return pcm, rv, state
+
+
+def tch3_frames_to_pcm_dev(stream, n_calls, n_frames, first, frames, state, pcm, rv=None):
+    """The same on device memory (addresses): enqueues on `stream` and returns; state: n_calls x codec_state_bytes() bytes
+    (codec_init_dev makes fresh ones), updated in place; pcm: n_frames x 320 int16; rv: n_frames x 2 int32 or None."""
+    _call("gmr1_hip_tch3_frames_to_pcm_dev", stream, n_calls, first, n_frames, frames, state, pcm, rv)
+
+
+def tch3_voice(iq, first, offset, freq_shift, fn, state, codec_state=None, flags=0, sps=4, in_len=None):
+    """tch3_follow and tch3_frames_to_pcm in one call, the records staying on the device in between
+    -> (TCH3_FRAME record per frame, the calls' TCH3_STATE, pcm (n_frames, 320), rv (n_frames, 2), the calls' decoder state)."""
+    iq = _arr(iq, np.complex64, -1)
+    first, offset = _arr(first, np.int32), _arr(offset, np.uint64)
+    freq_shift, fn = _arr(freq_shift, np.float32), _arr(fn, np.uint32)
+    state = np.array(state, TCH3_STATE, ndmin=1)
+    n_calls, n_fr = first.size - 1, offset.size
+    out = np.zeros(n_fr, TCH3_FRAME)
+    pcm = np.zeros((n_fr, 320), np.int16)
+    rv = np.zeros((n_fr, 2), np.int32)
+    codec_state, flags = _codec_state(codec_state, n_calls, flags)
+    _call("gmr1_hip_tch3_voice_batch", n_calls, sps, tch3_in_len(sps) if in_len is None else in_len, _p(iq), iq.size,
+          _p(first), n_fr, _p(offset), _p(freq_shift), _p(fn), _p(state), _p(out), _p(codec_state), flags, _p(pcm), _p(rv))
+    return out, state, pcm, rv, codec_state
+
+
+def tch3_voice_dev(stream, n_calls, n_frames, iq, first, offset, freq_shift, fn, state, out, codec_state, pcm, rv=None, sps=4,
+                   in_len=None):
+    """The same on device memory (addresses): enqueues on `stream` and returns; state, out as for tch3_follow_dev, codec_state,
+    pcm, rv as for tch3_frames_to_pcm_dev."""
+    _call("gmr1_hip_tch3_voice_batch_dev", stream, n_calls, sps, tch3_in_len(sps) if in_len is None else in_len, iq, first,
+          n_frames, offset, freq_shift, fn, state, out, codec_state, pcm, rv)
 
 
 class Codec(_Handle):

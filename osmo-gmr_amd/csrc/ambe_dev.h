@@ -92,7 +92,24 @@ struct AmbeArgs {
 	int dbg;                           // timing experiments only (GMR1_HIP_AMBE_DBG): 1 no noise path, 2 no oscillators, 4 no parameter decode
 };
 
+// The same decoder over the records of the TCH3 call follower (ambe_calls.h): one wavefront per call, record k of the
+// invocation -> pcm[320 k ..], rv[2 k], rv[2 k + 1].  A tone frame covers 160 samples, as in the dense batches.
+struct AmbeCallArgs {
+	int n_calls, n_frames;             // n_frames: records in the invocation
+	const int32_t *first;              // [n_calls + 1], clamped to 0..n_frames (ambe_calls_span)
+	const uint8_t *rec;                // [n_frames] struct gmr1_hip_tch3_frame
+	int16_t *pcm;                      // [n_frames][320]
+	int32_t *rv;                       // optional [n_frames][2]
+	AmbeState *state;                  // [n_calls]; a call without records keeps its bytes
+	const AmbeTab *tab;
+	const AmbeBig *big;
+	const ambe_libm::LibmTab *libm;
+	int tone_n;                        // 160; an argument and not a constant so that the tone frames' loops stay loops
+	int dbg;                           // as AmbeArgs::dbg
+};
+
 hipError_t launch_ambe(const AmbeArgs &a, hipStream_t stream);
+hipError_t launch_ambe_calls(const AmbeCallArgs &a, hipStream_t stream);
 hipError_t launch_ambe_init(AmbeState *state, int n_ch, int flags, hipStream_t stream);
 hipError_t launch_ambe_big(const AmbeTab *tab, AmbeBig *big, hipStream_t stream);
 

@@ -8,6 +8,10 @@
 // decode, enhancement and oscillator set-up; the DFT bins (64) for the noise spectrum; the output samples for the
 // inverse DFT, the oscillator bank and the overlap-add.
 //
+// The decoder is one device function, ambe_wave, over a source policy that says where the frames lie and the samples go:
+// k_ambe walks a dense [channels][frames] block, k_ambe_calls the records of the TCH3 call follower (calls of unequal
+// length, speech records among records that are silence: ambe_calls.h).
+//
 // The arithmetic is the reference's, operation for operation: its cosine is a 1024-entry table indexed by a truncated
 // float product, so a sum added in another order or a fused multiply-add moves table indices and flips PCM bits.
 // Hence: -ffp-contract=off, sums over harmonics added lane after lane in index order (seq_sum), the DFT / inverse DFT /
@@ -20,6 +24,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ambe_calls.h"
 #include "ambe_dev.h"
 #include "profile_env.h"
 
@@ -268,12 +273,79 @@ __global__ __launch_bounds__(128) void k_ambe_cs_table(const AmbeTab *tab, AmbeB
 	big->cs[bin][n] = make_float2(tab->cosv[idx & 1023], tab->cosv[(idx + 768) & 1023]);
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ambe(AmbeArgs a)
+// Where a wavefront's frames come from and its samples go: the one thing the two decoder kernels differ in.  `ch` is the
+// wavefront's channel or call, `f` counts 10-byte frames: lo .. hi - 1 of span(), in order.
+namespace {
+
+// [n_ch][n_frames] frames, samples and verdicts, every slot a frame (gmr1_hip_codec_decode_batch*, gmr1_codec_decode_frame)
+struct AmbeDense {
+	using Args = AmbeArgs;
+	static constexpr bool kRecords = false;
+	static __device__ __forceinline__ int count(const Args &a) { return a.n_ch; }
+	static __device__ __forceinline__ bool span(const Args &a, int, int &lo, int &hi)
+	{
+		lo = 0;
+		hi = a.n_frames;
+		return true;
+	}
+	static __device__ __forceinline__ bool speech(const Args &, int) { return true; }
+	static __device__ __forceinline__ const uint8_t *frame(const Args &a, int ch, int f)
+	{
+		return a.frames + ((size_t)ch * a.n_frames + f) * kAmbeFrameBytes;
+	}
+	static __device__ __forceinline__ int16_t *pcm(const Args &a, int ch, int f)
+	{
+		return a.pcm + ((size_t)ch * a.n_frames + f) * a.pcm_stride;
+	}
+	static __device__ __forceinline__ int32_t *rv(const Args &a, int ch, int f) { return a.rv + ((size_t)ch * a.n_frames + f); }
+	static __device__ __forceinline__ int tone_n(const Args &a) { return a.tone_n; }
+};
+
+// The records of the TCH3 call follower (ambe_calls.h): call `ch` owns records lo .. hi - 1, record k is frames 2k and
+// 2k + 1 -- the two halves of l2 where its type says speech, 160 zeros each and no step of the decoder where it does not.
+struct AmbeCalls {
+	using Args = AmbeCallArgs;
+	static constexpr bool kRecords = true;
+	static __device__ __forceinline__ int count(const Args &a) { return a.n_calls; }
+	static __device__ __forceinline__ bool span(const Args &a, int ch, int &lo, int &hi)
+	{
+		const AmbeSpan s = ambe_calls_span(a.first, ch, a.n_frames);
+		lo = uni(s.lo) * kAmbeRecFrames;
+		hi = uni(s.hi) * kAmbeRecFrames;
+		return hi > lo;                                // a call without records keeps its state byte for byte
+	}
+	static __device__ __forceinline__ const uint8_t *record(const Args &a, int f)
+	{
+		return a.rec + (size_t)(f >> 1) * kAmbeRecBytes;
+	}
+	// wave-uniform: every lane reads the one byte, the branch on it is scalar
+	static __device__ __forceinline__ bool speech(const Args &a, int f)
+	{
+		return ambe_calls_is_speech((unsigned)uni((int)record(a, f)[kAmbeRecType]));
+	}
+	static __device__ __forceinline__ const uint8_t *frame(const Args &a, int, int f)
+	{
+		return record(a, f) + kAmbeRecL2 + (f & 1) * kAmbeFrameBytes;
+	}
+	static __device__ __forceinline__ int16_t *pcm(const Args &a, int, int f) { return a.pcm + (size_t)f * kAmbeFrameSamples; }
+	static __device__ __forceinline__ int32_t *rv(const Args &a, int, int f) { return a.rv + (size_t)f; }
+	static __device__ __forceinline__ int tone_n(const Args &a) { return a.tone_n; }
+};
+
+static_assert(kAmbeRecFrames == 2, "a record is two frames: f >> 1, f & 1");
+
+}  // namespace
+
+template <class Src>
+__device__ __forceinline__ void ambe_wave(const typename Src::Args &a)
 {
 	__shared__ AmbeLds s;
 	const int lane = (int)threadIdx.x;
 	const int ch = (int)blockIdx.x;
-	if (ch >= a.n_ch)
+	if (ch >= Src::count(a))
+		return;
+	int f_lo, f_hi;
+	if (!Src::span(a, ch, f_lo, f_hi))
 		return;
 	const AmbeTab &T = *a.tab;
 	AmbeState &S = a.state[ch];
@@ -303,26 +375,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 	// window weights of this lane's two output samples (i = lane and lane + 64 < 80)
 	const int i0 = lane, i1 = lane + 64;
 
-	for (int f = 0; f < a.n_frames; f++) {
-		const uint8_t *fr = a.frames + ((size_t)ch * a.n_frames + f) * kAmbeFrameBytes;
-		int16_t *out = a.pcm + ((size_t)ch * a.n_frames + f) * a.pcm_stride;
+	for (int f = f_lo; f < f_hi; f++) {
+		int16_t *out = Src::pcm(a, ch, f);
+		// a record that is not speech is what gmr1_codec_decode_dtx is for (ambe.c:130-141): its bytes are not looked at
+		const bool dtx = Src::kRecords && !Src::speech(a, f);
+		const uint8_t *fr = Src::frame(a, ch, f);
 		uint64_t hi16 = 0, lo64 = 0;
-		for (int k = 0; k < 2; k++)
-			hi16 = (hi16 << 8) | fr[k];
-		for (int k = 2; k < 10; k++)
-			lo64 = (lo64 << 8) | fr[k];
-		hi16 = ((uint64_t)(unsigned)uni((int)(hi16 >> 32)) << 32) | (unsigned)uni((int)hi16);
-		lo64 = ((uint64_t)(unsigned)uni((int)(lo64 >> 32)) << 32) | (unsigned)uni((int)lo64);
+		if (!dtx) {
+			for (int k = 0; k < 2; k++)
+				hi16 = (hi16 << 8) | fr[k];
+			for (int k = 2; k < 10; k++)
+				lo64 = (lo64 << 8) | fr[k];
+			hi16 = ((uint64_t)(unsigned)uni((int)(hi16 >> 32)) << 32) | (unsigned)uni((int)hi16);
+			lo64 = ((uint64_t)(unsigned)uni((int)(lo64 >> 32)) << 32) | (unsigned)uni((int)lo64);
+		}
 		const unsigned byte0 = (unsigned)(hi16 >> 8) & 0xff, byte1 = (unsigned)hi16 & 0xff;
 		int rv = 0;
 
-		if ((byte0 & 0xfc) == 0xf8) {
-			// silence indication: 160 zeros, nothing else changes (ambe.c:115-118)
+		if (dtx || (byte0 & 0xfc) == 0xf8) {
+			// silence indication: 160 zeros, nothing else changes (ambe.c:115-118).  2-byte stores: pcm is aligned to no
+			// more, and the offsets of wider ones are two more registers than the kernel has (they spill)
 			for (int i = lane; i < kAmbeFrameSamples; i += 64)
 				out[i] = 0;
 		} else if ((byte0 & 0xfc) == 0xfc) {
 			// ---- tone frame (tone.c:115-204) ----
-			const int N = a.tone_n;
+			const int N = Src::tone_n(a);
 			const int sel = byte0 & 3;
 			int code = 0;
 			for (int bit = 0; bit < 8; bit++) {
@@ -766,7 +843,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 			WSYNC();
 		}
 		if (a.rv && lane == 0)
-			a.rv[(size_t)ch * a.n_frames + f] = rv;
+			*Src::rv(a, ch, f) = rv;
 	}
 
 	// state back
@@ -798,18 +875,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 		S.uw[i] = s.uw[i];
 }
 
-hipError_t launch_ambe(const AmbeArgs &a, hipStream_t stream)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ambe(AmbeArgs a)
 {
-	if (a.n_ch <= 0 || a.n_frames <= 0)
-		return hipSuccess;
+	ambe_wave<AmbeDense>(a);
+}
+
+// the calls of gmr1_hip_tch3_frames_to_pcm* / gmr1_hip_tch3_voice_batch*: one wavefront per call over its follower records
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ambe_calls(AmbeCallArgs a)
+{
+	ambe_wave<AmbeCalls>(a);
+}
+
+static int ambe_dbg()
+{
 	static int dbg = -1;
 	if (dbg < 0) {
 		const char *e = profile_env("GMR1_HIP_AMBE_DBG");
 		dbg = e ? atoi(e) : 0;
 	}
+	return dbg;
+}
+
+hipError_t launch_ambe(const AmbeArgs &a, hipStream_t stream)
+{
+	if (a.n_ch <= 0 || a.n_frames <= 0)
+		return hipSuccess;
 	AmbeArgs b = a;
-	b.dbg = dbg;
+	b.dbg = ambe_dbg();
 	hipLaunchKernelGGL(k_ambe, dim3(a.n_ch), dim3(64), 0, stream, b);
+	return hipGetLastError();
+}
+
+hipError_t launch_ambe_calls(const AmbeCallArgs &a, hipStream_t stream)
+{
+	if (a.n_calls <= 0 || a.n_frames <= 0)
+		return hipSuccess;
+	AmbeCallArgs b = a;
+	b.dbg = ambe_dbg();
+	hipLaunchKernelGGL(k_ambe_calls, dim3(a.n_calls), dim3(64), 0, stream, b);
 	return hipGetLastError();
 }
 

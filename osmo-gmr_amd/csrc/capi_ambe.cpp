@@ -1,6 +1,8 @@
 // capi_ambe.cpp -- C ABI of the AMBE speech decoder: the reference's codec object (include/osmocom/gmr1/codec/codec.h:37-45:
 // gmr1_codec_alloc / _release / _decode_frame / _decode_dtx) and batched forms over many voice channels
-// (gmr1_hip_codec_*).  All samples are produced on the GPU (ambe_kernels.hip); there is no CPU path.
+// (gmr1_hip_codec_*), and over the records of the TCH3 call follower, one decoder per call (gmr1_hip_tch3_frames_to_pcm*;
+// the tch3_pcm_* helpers also serve gmr1_hip_tch3_voice_batch*, capi_tch3_follow.cpp).  All samples are produced on the
+// GPU (ambe_kernels.hip); there is no CPU path.
 //
 // What the host contributes is tables: the codebooks (ambe_tables.cpp), and every value the reference obtains from
 // libm on an argument that can be enumerated - computed here with the same libm calls on the same float arguments,
@@ -9,8 +11,10 @@
 #include "capi_common.h"
 
 #include <cmath>
+#include <cstddef>
 #include <new>
 
+#include "ambe_calls.h"
 #include "ambe_dev.h"
 #include "ambe_tables.h"
 
@@ -224,7 +228,73 @@ int init_dev(hipStream_t st, int n_ch, void *state, int flags)
 	return 0;
 }
 
+static_assert(sizeof(gmr1_hip_tch3_frame) == kAmbeRecBytes && offsetof(gmr1_hip_tch3_frame, type) == kAmbeRecType &&
+              offsetof(gmr1_hip_tch3_frame, l2) == kAmbeRecL2 && sizeof(gmr1_hip_tch3_frame().l2) == kAmbeRecFrames * kAmbeFrameBytes,
+              "ambe_calls.h describes struct gmr1_hip_tch3_frame");
+
 }  // namespace
+
+namespace gmr1 {
+
+// ---- the decoder over the TCH3 follower's records (gmr1_hip_tch3_frames_to_pcm*, gmr1_hip_tch3_voice_batch*) ----
+
+int tch3_pcm_check(const char *who, int n_calls, const int32_t *first, int n_frames, const void *frames, const void *codec_state,
+                   bool state_required, int flags, int flags_known, const void *pcm)
+{
+	if (n_calls < 0 || n_frames < 0)
+		return fail(-EINVAL, "%s: negative count", who);
+	if (!first || !frames || !pcm || (state_required && !codec_state))
+		return fail(-EINVAL, "%s: NULL argument", who);
+	if (flags & ~flags_known)
+		return fail(-EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+	if ((reinterpret_cast<uintptr_t>(pcm) & 1u) || (reinterpret_cast<uintptr_t>(codec_state) & 15u))
+		return fail(-EINVAL, "%s: pcm must be 2-byte and codec_state 16-byte aligned", who);
+	return 0;
+}
+
+int tch3_pcm_first_check(const char *who, int n_calls, const int32_t *first, int n_frames)
+{
+	if (first[0] != 0 || first[n_calls] != n_frames)
+		return fail(-EINVAL, "%s: first[] must run from 0 to n_frames", who);
+	for (int c = 0; c < n_calls; c++)
+		if (first[c + 1] < first[c])
+			return fail(-EINVAL, "%s: first[%d] decreases", who, c + 1);
+	return 0;
+}
+
+int tch3_pcm_prepare()
+{
+	const AmbeTab *t;
+	const AmbeBig *big;
+	const ambe_libm::LibmTab *libm;
+	return dev_tab(&t, &big, &libm);
+}
+
+int tch3_pcm_fresh(hipStream_t st, int n_calls, void *codec_state, int flags)
+{
+	return init_dev(st, n_calls, codec_state, flags & GMR1_HIP_CODEC_CLEARED);
+}
+
+int tch3_pcm_enqueue(hipStream_t st, int n_calls, const int32_t *first, int n_frames, const struct gmr1_hip_tch3_frame *frames,
+                     void *codec_state, int16_t *pcm, int32_t *rv)
+{
+	AmbeCallArgs a;
+	int r = dev_tab(&a.tab, &a.big, &a.libm);
+	if (r) return r;
+	a.n_calls = n_calls;
+	a.n_frames = n_frames;
+	a.first = first;
+	a.rec = reinterpret_cast<const uint8_t *>(frames);
+	a.pcm = pcm;
+	a.rv = rv;
+	a.state = static_cast<AmbeState *>(codec_state);
+	a.tone_n = kAmbeFrameSamples;
+	a.dbg = 0;
+	HIP_TRY(launch_ambe_calls(a, st));
+	return 0;
+}
+
+}  // namespace gmr1
 
 // the reference's opaque decoder (src/codec/codec.c:37-40): here a device-resident state plus a block of pinned
 // host memory the kernel reads the frame from and writes the samples to
@@ -336,6 +406,43 @@ int gmr1_hip_codec_decode_batch(int n_ch, int n_frames, const uint8_t *frames, i
 	}
 	r = decode_dev(nullptr, n_ch, n_frames, d_fr, d_pcm, kAmbeFrameSamples, d_rv, d_st, kAmbeFrameSamples);
 	if (r) return r;
+	return sg.fetch();
+}
+
+// ---- the TCH3 follower's records to audio: the arguments are checked before the device is asked for ----
+
+int gmr1_hip_tch3_frames_to_pcm_dev(void *stream, int n_calls, const int32_t *first, int n_frames,
+                                    const struct gmr1_hip_tch3_frame *frames, void *codec_state, int16_t *pcm, int32_t *rv)
+{
+	int r = tch3_pcm_check("tch3_frames_to_pcm", n_calls, first, n_frames, frames, codec_state, true, 0, 0, pcm);
+	if (r) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	return tch3_pcm_enqueue((hipStream_t)stream, n_calls, first, n_frames, frames, codec_state, pcm, rv);
+}
+
+int gmr1_hip_tch3_frames_to_pcm(int n_calls, const int32_t *first, int n_frames, const struct gmr1_hip_tch3_frame *frames,
+                                void *codec_state, int flags, int16_t *pcm, int32_t *rv)
+{
+	int r = tch3_pcm_check("tch3_frames_to_pcm", n_calls, first, n_frames, frames, codec_state, false, flags,
+	                       GMR1_HIP_CODEC_CLEARED | GMR1_HIP_CODEC_FRESH, pcm);
+	if (r) return r;
+	if ((r = tch3_pcm_first_check("tch3_frames_to_pcm", n_calls, first, n_frames))) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	Stage sg;
+	AmbeState *h_st = static_cast<AmbeState *>(codec_state);
+	const bool carry = codec_state && !(flags & GMR1_HIP_CODEC_FRESH);
+	const int32_t *d_first = sg.in(first, (size_t)n_calls + 1);
+	const struct gmr1_hip_tch3_frame *d_fr = sg.in(frames, (size_t)n_frames);
+	int16_t *d_pcm = sg.out(pcm, (size_t)n_frames * kAmbeRecFrames * kAmbeFrameSamples);
+	int32_t *d_rv = sg.out(rv, (size_t)n_frames * kAmbeRecFrames);
+	AmbeState *d_st = carry ? sg.inout(h_st, (size_t)n_calls) : sg.out_always(h_st, (size_t)n_calls);
+	if ((r = sg.err())) return r;
+	if (!carry && (r = tch3_pcm_fresh(nullptr, n_calls, d_st, flags))) return r;
+	if ((r = tch3_pcm_enqueue(nullptr, n_calls, d_first, n_frames, d_fr, d_st, d_pcm, d_rv))) return r;
 	return sg.fetch();
 }
 

@@ -125,6 +125,19 @@ int tch3_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int
                         int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                         struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
 
+// The speech decoder over the TCH3 follower's records (capi_ambe.cpp), shared by gmr1_hip_tch3_frames_to_pcm* and
+// gmr1_hip_tch3_voice_batch*.  _check: counts, required pointers (codec_state only where state_required), flag bits outside
+// flags_known, alignment -- needs no device.  _first_check: first[] is a partition of 0..n_frames (host memory).  _prepare: the
+// decoder's tables are on the current device (the first use uploads and builds them).  _fresh: gmr1_hip_codec_init_dev.
+// _enqueue: one launch on `st`, device pointers, arguments not checked.
+int tch3_pcm_check(const char *who, int n_calls, const int32_t *first, int n_frames, const void *frames, const void *codec_state,
+                   bool state_required, int flags, int flags_known, const void *pcm);
+int tch3_pcm_first_check(const char *who, int n_calls, const int32_t *first, int n_frames);
+int tch3_pcm_prepare();
+int tch3_pcm_fresh(hipStream_t st, int n_calls, void *codec_state, int flags);
+int tch3_pcm_enqueue(hipStream_t st, int n_calls, const int32_t *first, int n_frames, const struct gmr1_hip_tch3_frame *frames,
+                     void *codec_state, int16_t *pcm, int32_t *rv);
+
 // gmr1_hip_tch9_follow_batch_dev on scratch of the caller's (capi_tch9_follow.cpp), under the same terms
 size_t tch9_follow_scratch_bytes(int n_frames);
 int tch9_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,

@@ -1,6 +1,7 @@
 // capi_tch3_follow.cpp -- C ABI of the batched TCH3 call follower (reference src/gmr1_rx.c:355-600: rx_tch3_init, rx_tch3
 // and its helpers).  The state of a call is the caller's; every decision between the frames is taken on the device
-// (tch3_follow_kernels.hip, tch3_follow.h).
+// (tch3_follow_kernels.hip, tch3_follow.h).  gmr1_hip_tch3_voice_batch* puts the speech decoder behind it (capi_ambe.cpp:
+// tch3_pcm_*).
 #include "capi_common.h"
 #include "tch3_follow.h"
 
@@ -214,6 +215,78 @@ int gmr1_hip_tch3_follow_batch(int n_calls, int sps, int in_len, const float *iq
 		                             d_out)))
 			return r;
 	}
+	return sg.fetch();
+}
+
+// ---- samples to records and audio: the follower, then the speech decoder over its records (ambe_kernels.hip: k_ambe_calls),
+// back to back on the stream.  No kernel of their own: `out` is the decoder's input. ----
+
+int gmr1_hip_tch3_voice_batch_dev(void *stream, int n_calls, int sps, int in_len, const float *iq,
+                                  const int32_t *first, int n_frames, const uint64_t *offset, const float *freq_shift,
+                                  const uint32_t *fn, struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out,
+                                  void *codec_state, int16_t *pcm, int32_t *rv)
+{
+	int r = follow_check(n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	if (r) return r;
+	if ((r = tch3_pcm_check("tch3_voice", n_calls, first, n_frames, out, codec_state, true, 0, 0, pcm))) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	if ((r = tch3_pcm_prepare())) return r;            // nothing is enqueued unless both halves can be
+	hipStream_t st = (hipStream_t)stream;
+	{
+		WsLease lease;
+		if ((r = lease.acquire(s, st))) return r;
+		Arena ws;
+		if ((r = ws.init(tch3_follow_scratch_bytes(n_frames)))) return r;
+		if ((r = tch3_follow_enqueue(st, ws.base, n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state, out)))
+			return r;
+	}
+	return tch3_pcm_enqueue(st, n_calls, first, n_frames, out, codec_state, pcm, rv);
+}
+
+int gmr1_hip_tch3_voice_batch(int n_calls, int sps, int in_len, const float *iq, uint64_t iq_len, const int32_t *first,
+                              int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
+                              struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out,
+                              void *codec_state, int flags, int16_t *pcm, int32_t *rv)
+{
+	int r = follow_check(n_calls, sps, in_len, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	if (r) return r;
+	if ((r = tch3_pcm_check("tch3_voice", n_calls, first, n_frames, out, codec_state, false, flags,
+	                        GMR1_HIP_CODEC_CLEARED | GMR1_HIP_CODEC_FRESH, pcm)))
+		return r;
+	if ((r = tch3_pcm_first_check("tch3_voice", n_calls, first, n_frames))) return r;
+	if ((r = bursts_fit(n_frames, offset, in_len, iq_len))) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n_calls == 0 || n_frames == 0) return 0;
+	if ((r = tch3_pcm_prepare())) return r;
+	Stage sg;
+	const bool carry = codec_state && !(flags & GMR1_HIP_CODEC_FRESH);
+	const size_t cs_bytes = (size_t)n_calls * gmr1_hip_codec_state_bytes();
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const int32_t *d_first = sg.in(first, (size_t)n_calls + 1);
+	const uint64_t *d_off = sg.in(offset, (size_t)n_frames);
+	const float *d_fs = sg.in(freq_shift, (size_t)n_frames);
+	const uint32_t *d_fn = sg.in(fn, (size_t)n_frames);
+	struct gmr1_hip_tch3_state *d_state = sg.inout(state, (size_t)n_calls);
+	struct gmr1_hip_tch3_frame *d_out = sg.out(out, (size_t)n_frames);
+	unsigned char *h_cs = static_cast<unsigned char *>(codec_state);
+	unsigned char *d_cs = carry ? sg.inout(h_cs, cs_bytes) : sg.out_always(h_cs, cs_bytes);
+	int16_t *d_pcm = sg.out(pcm, (size_t)n_frames * 320);
+	int32_t *d_rv = sg.out(rv, (size_t)n_frames * 2);
+	if ((r = sg.err())) return r;
+	if (!carry && (r = tch3_pcm_fresh(nullptr, n_calls, d_cs, flags))) return r;
+	{
+		WsLease lease;
+		if ((r = lease.acquire(s, nullptr))) return r;
+		Arena ws;
+		if ((r = ws.init(tch3_follow_scratch_bytes(n_frames)))) return r;
+		if ((r = tch3_follow_enqueue(nullptr, ws.base, n_calls, sps, in_len, d_iq, d_first, n_frames, d_off, d_fs, d_fn, d_state,
+		                             d_out)))
+			return r;
+	}
+	if ((r = tch3_pcm_enqueue(nullptr, n_calls, d_first, n_frames, d_out, d_cs, d_pcm, d_rv))) return r;
 	return sg.fetch();
 }
 
