@@ -38,6 +38,8 @@
  *   gmr1_hip_tch9_follow*_batch* -> rx_tch9, src/gmr1_rx.c:262-353
  *   gmr1_hip_tch3_frames_to_pcm* -> gmr1_codec_decode_frame / _decode_dtx over a call's bursts  include/osmocom/gmr1/codec/codec.h:41-45
  *   gmr1_hip_tch3_voice_batch*   -> rx_tch3 and the above: samples in, audio out (gmr1_rx and gmr1_ambe_decode in one call)
+ *   gmr1_hip_rx_run_voice*, gmr1_hip_rx_stream_*voice* -> main() of src/gmr1_rx.c with the calls it follows decoded as
+ *                                   gmr1_ambe_decode decodes them (src/gmr1_ambe_decode.c:122-150), one-shot and streaming
  */
 #ifndef GMR1_HIP_H
 #define GMR1_HIP_H
@@ -561,6 +563,33 @@ int gmr1_hip_rx_stream_push_tch_dev(void *stream, struct gmr1_hip_rx_stream *h, 
 int gmr1_hip_rx_stream_push_tch(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride,
                                 uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records);
 
+/* The streaming loop with the followed calls decoded to audio: gmr1_hip_rx_run_voice (below) over a capture pushed piece
+ * by piece.  kc, tch and the records are the tch handle's; audio_out (host memory) takes struct gmr1_hip_rx_audio blocks.
+ *  - A handle made by _create_voice takes only _push_voice*, and _push_voice* takes no other handle: the wrong pairing is
+ *    refused (-EINVAL) and leaves the handle as it was, as do max_audio below gmr1_hip_rx_stream_max_audio(h, n), a NULL
+ *    n_audio and audio_out == NULL with max_audio > 0; n_records and n_audio are then 0.  _max_records is the tch
+ *    handle's; _max_audio (host arithmetic; 0 for the other kinds) is one block per frame a chain's walk can log, times
+ *    the chains -- what _max_big counts.  _status and _destroy serve all kinds.
+ *  - The handle keeps one AMBE decoder state per chain in device memory beside the chain's struct gmr1_hip_tch3_state,
+ *    and each chain's count of assignments on the host: a call's audio goes on in the next push where this one left it.
+ *  - The audio of any sequence of pushes ending with `last`, stable-sorted by (carrier, chain), is byte-identical to the
+ *    audio_out of one gmr1_hip_rx_run_voice call on the whole capture with the same kc, and the records to its `out`, for
+ *    any push sizes (0 included) and in both Viterbi decoder modes.  Within a push both come by carrier, chain, frame; a
+ *    call's first blocks come out of the push that returns its IMMEDIATE ASSIGNMENT.
+ *  - Everything else, -EIO included, is as for gmr1_hip_rx_stream_push_tch*.  Audio on a _create_full handle is not
+ *    provided. */
+struct gmr1_hip_rx_audio;            /* defined with gmr1_hip_tch3_frames_to_audio_dev below */
+int gmr1_hip_rx_stream_create_voice(int n_arfcn, int sps, const uint16_t *arfcn,
+                                    const uint8_t *kc /* n_arfcn x 8, or NULL */, struct gmr1_hip_rx_stream **h);
+int gmr1_hip_rx_stream_max_audio(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_audio);
+int gmr1_hip_rx_stream_push_voice_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch,
+                                      uint64_t iq_stride, uint64_t n, int last, struct gmr1_hip_rx_record *out,
+                                      int max_records, int *n_records,
+                                      struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio);
+int gmr1_hip_rx_stream_push_voice(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride,
+                                  uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                  struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio);
+
 /* The streaming loop with both follow-ups: gmr1_hip_rx_run_full (below) over a capture pushed piece by piece.  kc as for
  * _create_tch.  `csd` has the layout, stride and timing of `iq` and `tch`: carrier i's CSD samples of a push are
  * csd[2*(i*iq_stride + k)], k < n.
@@ -615,6 +644,29 @@ int gmr1_hip_rx_run_tch(int n_arfcn, int sps, const float *iq, const float *tch,
                         const uint64_t *offset, const uint64_t *length, const uint16_t *arfcn, const uint8_t *kc,
                         struct gmr1_hip_rx_record *out, int max_records, int *n_records,
                         int32_t *status, int32_t *n_chains);
+
+/* The same with the followed calls decoded to audio: gmr1_hip_rx_run_tch* plus struct gmr1_hip_rx_audio blocks (defined
+ * with gmr1_hip_tch3_frames_to_audio_dev below; audio_out is host memory).  The records, status and n_chains are
+ * byte-identical to gmr1_hip_rx_run_tch* on the same inputs.  Every chain with an assignment owns one AMBE decoder, made
+ * fresh (gmr1_hip_codec_init_dev, flags 0: what gmr1_ambe_decode computes) by every IMMEDIATE ASSIGNMENT the chain
+ * follows; every frame the follower walks with the call running gives one block -- a speech frame its 320 samples and two
+ * verdicts, every other frame 320 zeros -- with `call` counting the chain's assignments from 1.  The decoder runs behind
+ * the follower on the frames where they lie in device memory; no frame and no decoder state visits the host for it.
+ * Blocks come ordered by carrier, chain, frame.  Only the first max_audio blocks are stored; *n_audio is the number found.
+ * tch == NULL gives no audio and gmr1_hip_rx_run*'s records.  -EINVAL also for a NULL n_audio, a negative max_audio, and
+ * a NULL audio_out with max_audio > 0. */
+struct gmr1_hip_rx_audio;
+int gmr1_hip_rx_run_voice_dev(void *stream, int n_arfcn, int sps, const float *iq, const float *tch,
+                              const uint64_t *offset, const uint64_t *length, const uint16_t *arfcn,
+                              const uint8_t *kc,
+                              struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                              int32_t *status, int32_t *n_chains,
+                              struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio);
+int gmr1_hip_rx_run_voice(int n_arfcn, int sps, const float *iq, const float *tch, uint64_t iq_len,
+                          const uint64_t *offset, const uint64_t *length, const uint16_t *arfcn, const uint8_t *kc,
+                          struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                          int32_t *status, int32_t *n_chains,
+                          struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio);
 
 /* ---- following a voice call: rx_tch3 over many calls at once (gmr1_rx.c:355-600) ------------------------
  * What gmr1_rx does per frame once an IMMEDIATE ASSIGNMENT has named a timeslot -- burst energy against the running
@@ -732,6 +784,41 @@ int gmr1_hip_tch3_voice_batch(int n_calls, int sps, int in_len, const float *iq,
                               int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                               struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out,
                               void *codec_state, int flags, int16_t *pcm, int32_t *rv);
+
+/* The frames of running calls closed up into audio blocks on the device: what gmr1_hip_rx_run_voice* reports, and what a
+ * caller that follows calls with gmr1_hip_tch3_follow_batch_dev can hand to a sound device.  Call c owns
+ * frames[first[c] .. first[c+1]) as in the follower, fn[k] is frame k's own fn as handed to the follower, label[c] =
+ * arfcn | chain << 16 | tn << 24 | call << 32.
+ *   cls != GMR1_HIP_TCH3_OFF   one block: arfcn, chain, tn and call from the call's label, cls from the frame, fn = fn[k]
+ *                              (also for a FACCH3 message, whose record carries fn - 3), pad 0.  type == 0x10: pcm and rv
+ *                              are what gmr1_hip_tch3_frames_to_pcm* gives for the record (rv as int16_t).  Any other
+ *                              type: 320 zero samples, rv 0, 0, and the decoder is not touched.
+ *   cls == GMR1_HIP_TCH3_OFF   nothing, and the decoder is not touched.
+ * Blocks come in call order, then frame order.  Only the first max_out blocks are stored; *n_out is the number found.
+ * The decoders step over every speech frame whether its block is stored or not: codec_state afterwards does not depend
+ * on max_out, and equals gmr1_hip_tch3_frames_to_pcm_dev's on the same frames.  A call cut into any pieces gives the
+ * blocks and the states of one invocation.
+ * Every pointer is device memory; the call enqueues two kernels on `stream` and returns (no synchronisation but for the
+ * first use on a device, which builds the decoder's tables, and a workspace that has to grow).  The entries of first are
+ * clamped to 0..n_frames.  n_calls == 0 writes *n_out = 0.  -EINVAL, before the device is asked for and with nothing
+ * written: everything gmr1_hip_tch3_frames_to_pcm_dev refuses (out taking the place of pcm; it may be NULL when max_out
+ * == 0), a negative max_out, a NULL fn, label or n_out, an out that is not on a 16-byte boundary.  -ENODEV without a
+ * device. */
+struct gmr1_hip_rx_audio {          /* 656 bytes, pcm at offset 16 */
+	uint16_t arfcn;
+	uint8_t  chain;
+	uint8_t  cls;       /* the follower's class of the frame (GMR1_HIP_TCH3_*, never OFF) */
+	uint32_t fn;        /* the frame's own fn, as handed to the follower */
+	uint8_t  tn;
+	uint8_t  call;      /* IMMEDIATE ASSIGNMENTs this chain has followed so far, mod 256 (>= 1) */
+	int16_t  rv[2];     /* the decoder's two verdicts: 0, or -EINVAL for a tone frame with an unassigned code */
+	uint8_t  pad[2];    /* 0 */
+	int16_t  pcm[320];  /* 40 ms of 8 kHz audio */
+};
+int gmr1_hip_tch3_frames_to_audio_dev(void *stream, int n_calls, const int32_t *first /* n_calls + 1 */, int n_frames,
+                                      const struct gmr1_hip_tch3_frame *frames, const uint32_t *fn /* n_frames */,
+                                      const uint64_t *label /* n_calls */, void *codec_state,
+                                      struct gmr1_hip_rx_audio *out, int max_out, int32_t *n_out /* device */);
 
 /* ---- following a circuit-switched data call: rx_tch9 over many calls at once (gmr1_rx.c:262-353) -------------
  * What gmr1_rx does per frame once an ASSIGNMENT COMMAND 1 has named a timeslot on the CSD carrier: demodulate the NT9
@@ -864,6 +951,12 @@ int gmr1_hip_rx_run_full(int n_arfcn, int sps, const float *iq, const float *tch
 #define GMR1_HIP_CODEC_FRESH   2
 size_t gmr1_hip_codec_state_bytes(void);
 int gmr1_hip_codec_init_dev(void *stream, int n_ch, void *state, int flags);
+/* Fresh decoders for a list of channels, between two invocations, so that a decoder's state never visits the host: for
+ * j < n what gmr1_hip_codec_init_dev(stream, 1, state + call[j], flags) does (call[j] < 0 is skipped, a channel may be named
+ * twice); every other state keeps its bytes.  It is the codec-state counterpart of gmr1_hip_tch3_state_assign_batch_dev.
+ * call and state are device memory; enqueues on `stream` and returns.  -EINVAL: n < 0, a NULL array, state not 16-byte
+ * aligned, unknown flag bits; -ENODEV without a device. */
+int gmr1_hip_codec_init_list_dev(void *stream, int n, const int32_t *call, void *state, int flags);
 int gmr1_hip_codec_decode_batch_dev(void *stream, int n_ch, int n_frames, const uint8_t *frames, int16_t *pcm,
                                     int32_t *rv, void *state);
 int gmr1_hip_codec_decode_batch(int n_ch, int n_frames, const uint8_t *frames, int16_t *pcm, int32_t *rv, void *state,

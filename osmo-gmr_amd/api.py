@@ -121,6 +121,12 @@ SIGNATURES = {
     "gmr1_hip_rx_stream_max_big": (I, P, U64, P),
     "gmr1_hip_rx_stream_push_full_dev": (I, P, P, P, P, P, U64, U64, I, P, I, P, P, I, P),
     "gmr1_hip_rx_stream_push_full": (I, P, P, P, P, U64, U64, I, P, I, P, P, I, P),
+    "gmr1_hip_rx_stream_create_voice": (I, I, I, P, P, P),
+    "gmr1_hip_rx_stream_max_audio": (I, P, U64, P),
+    "gmr1_hip_rx_stream_push_voice_dev": (I, P, P, P, P, U64, U64, I, P, I, P, P, I, P),
+    "gmr1_hip_rx_stream_push_voice": (I, P, P, P, U64, U64, I, P, I, P, P, I, P),
+    "gmr1_hip_rx_run_voice_dev": (I, P, I, I, P, P, P, P, P, P, P, I, P, P, P, P, I, P),
+    "gmr1_hip_rx_run_voice": (I, I, I, P, P, U64, P, P, P, P, P, I, P, P, P, P, I, P),
     "gmr1_hip_rx_run_tch_dev": (I, P, I, I, P, P, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_tch": (I, I, I, P, P, U64, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run_last_timing": (I, P),
@@ -130,6 +136,7 @@ SIGNATURES = {
     "gmr1_hip_tch3_follow_batch": (I, I, I, I, P, U64, P, I, P, P, P, P, P),
     "gmr1_hip_tch3_frames_to_pcm_dev": (I, P, I, P, I, P, P, P, P),
     "gmr1_hip_tch3_frames_to_pcm": (I, I, P, I, P, P, I, P, P),
+    "gmr1_hip_tch3_frames_to_audio_dev": (I, P, I, P, I, P, P, P, P, P, I, P),
     "gmr1_hip_tch3_voice_batch_dev": (I, P, I, I, I, P, P, I, P, P, P, P, P, P, P, P),
     "gmr1_hip_tch3_voice_batch": (I, I, I, I, P, U64, P, I, P, P, P, P, P, P, I, P, P),
     "gmr1_hip_tch9_state_assign": (I, P),
@@ -143,6 +150,7 @@ SIGNATURES = {
     "gmr1_hip_rx_run_full": (I, I, I, P, P, P, U64, P, P, P, P, P, I, P, P, I, P, P, P),
     "gmr1_hip_codec_state_bytes": (SZ,),
     "gmr1_hip_codec_init_dev": (I, P, I, P, I),
+    "gmr1_hip_codec_init_list_dev": (I, P, I, P, P, I),
     "gmr1_hip_codec_decode_batch_dev": (I, P, I, I, P, P, P, P),
     "gmr1_hip_codec_decode_batch": (I, I, I, P, P, P, P, I),
     "gmr1_hip_codec_host_tables": (I, P, P),
@@ -1136,6 +1144,39 @@ def rx_run_tch_dev(stream, iq_ptr, tch_ptr, offset, length, sps=4, arfcn=None, k
     return out[:min(n_rec.value, cap)].copy(), status, chains, n_rec.value
 
 
+# struct gmr1_hip_rx_audio: 40 ms of a followed call's audio, one block per frame the follower walked with the call running
+RX_AUDIO = np.dtype([("arfcn", "<u2"), ("chain", "u1"), ("cls", "u1"), ("fn", "<u4"), ("tn", "u1"), ("call", "u1"),
+                     ("rv", "<i2", (2,)), ("pad", "u1", (2,)), ("pcm", "<i2", (320,))])
+assert RX_AUDIO.itemsize == 656 and RX_AUDIO.fields["pcm"][1] == 16
+
+
+def rx_run_voice(iq, tch, offset, length, sps=4, arfcn=None, kc=None, max_records=1 << 16, max_audio=1 << 12):
+    """gmr1_hip_rx_run_voice: rx_run_tch with the followed calls decoded to audio
+    -> (records, audio RX_AUDIO[], status, n_chains, n_records found, n_audio found)"""
+    iq = _arr(iq, np.complex64, -1)
+    tch = _same_size(tch, iq)
+    out, cap = _records(None, max_records)
+    audio, cap_audio = _records(None, max_audio, RX_AUDIO)
+    n_audio = C.c_int(0)
+    run, n_rec, status, chains = _rx_loop("gmr1_hip_rx_run_voice", (len(offset), sps, _p(iq), _p(tch), iq.size), offset,
+                                          length, arfcn, _p(out), cap, kc=kc, tail=(_p(audio), cap_audio, C.addressof(n_audio)))
+    _check(run(), "gmr1_hip_rx_run_voice")
+    return (out[:min(n_rec.value, cap)].copy(), audio[:min(n_audio.value, cap_audio)].copy(), status, chains, n_rec.value,
+            n_audio.value)
+
+
+def rx_run_voice_dev(stream, iq_ptr, tch_ptr, offset, length, sps=4, arfcn=None, kc=None, max_records=1 << 16, max_audio=1 << 12):
+    """gmr1_hip_rx_run_voice_dev: rx_run_voice with both captures already in HBM (device addresses, same layout)."""
+    out, cap = _records(None, max_records)
+    audio, cap_audio = _records(None, max_audio, RX_AUDIO)
+    n_audio = C.c_int(0)
+    run, n_rec, status, chains = _rx_loop("gmr1_hip_rx_run_voice_dev", (stream, len(offset), sps, iq_ptr, tch_ptr), offset,
+                                          length, arfcn, _p(out), cap, kc=kc, tail=(_p(audio), cap_audio, C.addressof(n_audio)))
+    _check(run(), "gmr1_hip_rx_run_voice_dev")
+    return (out[:min(n_rec.value, cap)].copy(), audio[:min(n_audio.value, cap_audio)].copy(), status, chains, n_rec.value,
+            n_audio.value)
+
+
 # ---------------------------------------------------------------------------
 # wideband -> per-ARFCN channelizer (reference utils/gmr1_rx_sdr.py:391-602)
 # ---------------------------------------------------------------------------
@@ -1262,19 +1303,25 @@ class RxStream(_LibHandle):
     that became final in it; all pushes' records up to the `last` one, stable-sorted by (carrier, chain), are identical to
     one rx_run() call on the whole capture.  tch=True: the loop also follows TCH3 calls (rx_run_tch with the same kc) --
     every push then takes the traffic carriers' samples as well.  full=True: it follows TCH3 and TCH9 calls (rx_run_full
-    with the same kc) -- every push takes the traffic and the CSD carriers' samples and returns (records, big records)."""
+    with the same kc) -- every push takes the traffic and the CSD carriers' samples and returns (records, big records).
+    voice=True: it follows TCH3 calls and decodes them (rx_run_voice with the same kc) -- every push takes the traffic
+    carriers' samples and returns (records, audio blocks (RX_AUDIO[]))."""
     _destroy_fn = "gmr1_hip_rx_stream_destroy"
 
-    def __init__(self, n_arfcn, sps=4, arfcn=None, tch=False, kc=None, full=False):
+    def __init__(self, n_arfcn, sps=4, arfcn=None, tch=False, kc=None, full=False, voice=False):
         self._h = C.c_void_p()
         self.n = int(n_arfcn)
         self.full = bool(full)
-        self.tch = bool(tch) or self.full
+        self.voice = bool(voice)
+        if self.full and self.voice:
+            raise ValueError("a handle is made with full=True or with voice=True, not both")
+        self.tch = bool(tch) or self.full or self.voice
         self._arfcn = _arr(arfcn, np.uint16)
         if self.tch:
             kc = _arr(kc, np.uint8, (self.n, 8))
-            _call("gmr1_hip_rx_stream_create_full" if self.full else "gmr1_hip_rx_stream_create_tch", self.n, sps, _p(self._arfcn),
-                  _p(kc), C.byref(self._h))
+            make = "gmr1_hip_rx_stream_create_full" if self.full else "gmr1_hip_rx_stream_create_voice" if self.voice else \
+                "gmr1_hip_rx_stream_create_tch"
+            _call(make, self.n, sps, _p(self._arfcn), _p(kc), C.byref(self._h))
         else:
             if kc is not None:
                 raise ValueError("kc belongs to a handle that follows TCH3 calls (tch=True)")
@@ -1292,6 +1339,12 @@ class RxStream(_LibHandle):
         _call("gmr1_hip_rx_stream_max_big", self._h, n, C.byref(m))
         return m.value
 
+    def max_audio(self, n):
+        """the most audio blocks the next push of n samples per carrier can return (0 unless voice=True)"""
+        m = C.c_int()
+        _call("gmr1_hip_rx_stream_max_audio", self._h, n, C.byref(m))
+        return m.value
+
     def _out(self, n, out):
         return _records(out, self.max_records(n))[0]
 
@@ -1307,7 +1360,8 @@ class RxStream(_LibHandle):
 
     def push(self, iq, last=False, out=None, tch=None, csd=None):
         """host (n_arfcn, n) complex64 (and, on a tch handle, tch of the same shape; on a full handle csd as well) -> the
-        records that became final (RX_RECORD[]); on a full handle (records, big records (RX_BIG_RECORD[]))"""
+        records that became final (RX_RECORD[]); on a full handle (records, big records (RX_BIG_RECORD[])); on a voice handle
+        (records, audio blocks (RX_AUDIO[]))"""
         self._kind(tch, csd)
         iq = _arr(iq, np.complex64, (self.n, -1))
         n = iq.shape[1]
@@ -1320,6 +1374,13 @@ class RxStream(_LibHandle):
             _call("gmr1_hip_rx_stream_push_full", self._h, _p(iq), _p(tch), _p(csd), n, n, 1 if last else 0, _p(out), out.size,
                   C.byref(got), _p(big), big.size, C.byref(got_big))
             return out[:got.value], big[:got_big.value]
+        if self.voice:
+            tch = _arr(tch, np.complex64, (self.n, n))
+            audio = _records(None, self.max_audio(n), RX_AUDIO)[0]
+            got_audio = C.c_int()
+            _call("gmr1_hip_rx_stream_push_voice", self._h, _p(iq), _p(tch), n, n, 1 if last else 0, _p(out), out.size,
+                  C.byref(got), _p(audio), audio.size, C.byref(got_audio))
+            return out[:got.value], audio[:got_audio.value]
         if self.tch:
             tch = _arr(tch, np.complex64, (self.n, n))
             _call("gmr1_hip_rx_stream_push_tch", self._h, _p(iq), _p(tch), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
@@ -1327,12 +1388,20 @@ class RxStream(_LibHandle):
             _call("gmr1_hip_rx_stream_push", self._h, _p(iq), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
         return out[:got.value]
 
-    def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None, tch_ptr=None, csd_ptr=None, big=None):
+    def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None, tch_ptr=None, csd_ptr=None, big=None, audio=None):
         """device samples (carrier i at iq_ptr + 8 * i * iq_stride; on a tch handle its traffic samples at tch_ptr + 8 * i *
         iq_stride, on a full handle its CSD samples at csd_ptr + 8 * i * iq_stride), read on `stream` -> the records
-        (synchronous); on a full handle (records, big records).
-        out, big: host RX_RECORD / RX_BIG_RECORD arrays, or None; out_ptr (device / pinned) goes through push_dev_raw."""
+        (synchronous); on a full handle (records, big records), on a voice handle (records, audio blocks).
+        out, big, audio: host RX_RECORD / RX_BIG_RECORD / RX_AUDIO arrays, or None; out_ptr (device / pinned) goes through
+        push_dev_raw."""
         out = self._out(n, out)
+        if self.voice:
+            self._kind(tch_ptr)
+            audio = _records(audio, self.max_audio(n), RX_AUDIO)[0]
+            got, got_audio = C.c_int(), C.c_int()
+            _call("gmr1_hip_rx_stream_push_voice_dev", stream, self._h, iq_ptr, tch_ptr, iq_stride, n, 1 if last else 0,
+                  out.ctypes.data, out.size, C.byref(got), audio.ctypes.data, audio.size, C.byref(got_audio))
+            return out[:got.value], audio[:got_audio.value]
         if self.full:
             self._kind(tch_ptr, csd_ptr)
             big = _records(big, self.max_big(n), RX_BIG_RECORD)[0]
@@ -1797,6 +1866,11 @@ def codec_init_dev(stream, n_ch, state_ptr, flags=0):
     _call("gmr1_hip_codec_init_dev", stream, n_ch, state_ptr, flags)
 
 
+def codec_init_list_dev(stream, n, call_ptr, state_ptr, flags=0):
+    """gmr1_hip_codec_init_list_dev: fresh decoders for state[call[j]], j < n (device pointers; call[j] < 0 is skipped)."""
+    _call("gmr1_hip_codec_init_list_dev", stream, n, call_ptr, state_ptr, flags)
+
+
 def codec_decode_batch_dev(stream, n_ch, n_frames, frames_ptr, pcm_ptr, rv_ptr, state_ptr):
     _call("gmr1_hip_codec_decode_batch_dev", stream, n_ch, n_frames, frames_ptr, pcm_ptr, rv_ptr, state_ptr)
 
@@ -1838,6 +1912,17 @@ def tch3_frames_to_pcm_dev(stream, n_calls, n_frames, first, frames, state, pcm,
     """The same on device memory (addresses): enqueues on `stream` and returns; state: n_calls x codec_state_bytes() bytes
     (codec_init_dev makes fresh ones), updated in place; pcm: n_frames x 320 int16; rv: n_frames x 2 int32 or None."""
     _call("gmr1_hip_tch3_frames_to_pcm_dev", stream, n_calls, first, n_frames, frames, state, pcm, rv)
+
+
+def tch3_frames_to_audio_dev(stream, n_calls, n_frames, first, frames, fn, label, state, out, max_out, n_out):
+    """gmr1_hip_tch3_frames_to_audio_dev: device pointers throughout; enqueues on `stream` and returns.  fn: n_frames uint32;
+    label: n_calls uint64 (tch3_audio_label); out: max_out RX_AUDIO blocks on a 16-byte boundary; n_out: one int32."""
+    _call("gmr1_hip_tch3_frames_to_audio_dev", stream, n_calls, first, n_frames, frames, fn, label, state, out, max_out, n_out)
+
+
+def tch3_audio_label(arfcn, chain, tn, call):
+    """a call's label for tch3_frames_to_audio_dev: arfcn | chain << 16 | tn << 24 | call << 32"""
+    return (int(arfcn) & 0xffff) | (int(chain) & 0xff) << 16 | (int(tn) & 0xff) << 24 | (int(call) & 0xff) << 32
 
 
 def tch3_voice(iq, first, offset, freq_shift, fn, state, codec_state=None, flags=0, sps=4, in_len=None):

@@ -108,9 +108,31 @@ struct AmbeCallArgs {
 	int dbg;                           // as AmbeArgs::dbg
 };
 
+// The same walk with the samples closed up into audio blocks (tch3_audio.h; struct gmr1_hip_rx_audio): record k goes to
+// block slot[k] -- pcm[320] and rv[2] of out[slot[k]] -- where k_tch3f_audio has written the slots and the headers.  A
+// record without a slot is not looked at; one whose slot is at or past max_out is decoded into the call's sink block, so
+// the decoder's state afterwards does not depend on max_out.
+struct AmbeAudioArgs {
+	int n_calls, n_frames, max_out;
+	const int32_t *first;              // [n_calls + 1], clamped to 0..n_frames (ambe_calls_span)
+	const uint8_t *rec;                // [n_frames] struct gmr1_hip_tch3_frame
+	const int32_t *slot;               // [n_frames]
+	unsigned char *out;                // [max_out] struct gmr1_hip_rx_audio
+	unsigned char *sink;               // [n_calls] blocks nobody reads
+	AmbeState *state;                  // [n_calls]
+	const AmbeTab *tab;
+	const AmbeBig *big;
+	const ambe_libm::LibmTab *libm;
+	int tone_n;                        // 160, as AmbeCallArgs::tone_n
+	int dbg;                           // as AmbeArgs::dbg
+};
+
 hipError_t launch_ambe(const AmbeArgs &a, hipStream_t stream);
 hipError_t launch_ambe_calls(const AmbeCallArgs &a, hipStream_t stream);
+hipError_t launch_ambe_audio(const AmbeAudioArgs &a, hipStream_t stream);
 hipError_t launch_ambe_init(AmbeState *state, int n_ch, int flags, hipStream_t stream);
+// fresh decoders for state[call[j]], j < n (call[j] < 0 is skipped)
+hipError_t launch_ambe_init_list(AmbeState *state, int n, const int32_t *call, int flags, hipStream_t stream);
 hipError_t launch_ambe_big(const AmbeTab *tab, AmbeBig *big, hipStream_t stream);
 
 }  // namespace gmr1

@@ -10,7 +10,8 @@
 //
 // The decoder is one device function, ambe_wave, over a source policy that says where the frames lie and the samples go:
 // k_ambe walks a dense [channels][frames] block, k_ambe_calls the records of the TCH3 call follower (calls of unequal
-// length, speech records among records that are silence: ambe_calls.h).
+// length, speech records among records that are silence: ambe_calls.h), k_ambe_audio the same records with the samples
+// closed up into the audio blocks of the receive loop (records that give no block passed over: tch3_audio.h).
 //
 // The arithmetic is the reference's, operation for operation: its cosine is a 1024-entry table indexed by a truncated
 // float product, so a sum added in another order or a fused multiply-add moves table indices and flips PCM bits.
@@ -27,6 +28,7 @@
 #include "ambe_calls.h"
 #include "ambe_dev.h"
 #include "profile_env.h"
+#include "tch3_audio.h"
 
 namespace gmr1 {
 
@@ -192,24 +194,42 @@ __device__ __noinline__ float fourth_root(const ambe_libm::LibmTab *T, float x)
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void k_ambe_init(AmbeState *state, int n_ch, int flags)
+// ambe.c:36-46, synth.c:306-311: one wavefront makes one decoder fresh
+__device__ __forceinline__ void ambe_fresh(AmbeState *st, int flags)
 {
-	// ambe.c:36-46, synth.c:306-311
-	const int ch = blockIdx.x;
-	if (ch >= n_ch)
-		return;
-	uint32_t *w = reinterpret_cast<uint32_t *>(state + ch);
+	uint32_t *w = reinterpret_cast<uint32_t *>(st);
 	for (unsigned i = threadIdx.x; i < sizeof(AmbeState) / 4; i += 64)
 		w[i] = 0;
 	WSYNC();
 	if (threadIdx.x == 0) {
-		AmbeState &s = state[ch];
+		AmbeState &s = *st;
 		s.u_last = 3147;
 		s.w0 = 0.09378f;
 		s.L = 30;
 		s.pitch_idx = 128;
 		s.flags = flags;
 	}
+}
+
+__global__ __launch_bounds__(64) void k_ambe_init(AmbeState *state, int n_ch, int flags)
+{
+	const int ch = blockIdx.x;
+	if (ch >= n_ch)
+		return;
+	ambe_fresh(state + ch, flags);
+}
+
+// the same for state[call[j]]: entry j is work-group j.  An entry below 0 is skipped; a channel named twice is written
+// twice with the same bytes.
+__global__ __launch_bounds__(64) void k_ambe_init_list(AmbeState *state, int n, const int32_t *__restrict__ call, int flags)
+{
+	const int j = blockIdx.x;
+	if (j >= n)
+		return;
+	const int ch = call[j];
+	if (ch < 0)
+		return;
+	ambe_fresh(state + ch, flags);
 }
 
 // AmbeBig::noise_dft, one generator state per work-group: the noise sequence (synth.c:98-110), its window
@@ -281,6 +301,7 @@ namespace {
 struct AmbeDense {
 	using Args = AmbeArgs;
 	static constexpr bool kRecords = false;
+	static constexpr bool kSlots = false;
 	static __device__ __forceinline__ int count(const Args &a) { return a.n_ch; }
 	static __device__ __forceinline__ bool span(const Args &a, int, int &lo, int &hi)
 	{
@@ -297,14 +318,20 @@ struct AmbeDense {
 	{
 		return a.pcm + ((size_t)ch * a.n_frames + f) * a.pcm_stride;
 	}
-	static __device__ __forceinline__ int32_t *rv(const Args &a, int ch, int f) { return a.rv + ((size_t)ch * a.n_frames + f); }
+	static __device__ __forceinline__ bool has_rv(const Args &a) { return a.rv != nullptr; }
+	static __device__ __forceinline__ int32_t *rv(const Args &a, int ch, int f, const int16_t *)
+	{
+		return a.rv + ((size_t)ch * a.n_frames + f);
+	}
 	static __device__ __forceinline__ int tone_n(const Args &a) { return a.tone_n; }
 };
 
 // The records of the TCH3 call follower (ambe_calls.h): call `ch` owns records lo .. hi - 1, record k is frames 2k and
 // 2k + 1 -- the two halves of l2 where its type says speech, 160 zeros each and no step of the decoder where it does not.
-struct AmbeCalls {
-	using Args = AmbeCallArgs;
+// (AmbeRecords: what every walk over records shares -- which records, which of them speak, where the ten bytes lie)
+template <class A>
+struct AmbeRecords {
+	using Args = A;
 	static constexpr bool kRecords = true;
 	static __device__ __forceinline__ int count(const Args &a) { return a.n_calls; }
 	static __device__ __forceinline__ bool span(const Args &a, int ch, int &lo, int &hi)
@@ -327,12 +354,40 @@ struct AmbeCalls {
 	{
 		return record(a, f) + kAmbeRecL2 + (f & 1) * kAmbeFrameBytes;
 	}
-	static __device__ __forceinline__ int16_t *pcm(const Args &a, int, int f) { return a.pcm + (size_t)f * kAmbeFrameSamples; }
-	static __device__ __forceinline__ int32_t *rv(const Args &a, int, int f) { return a.rv + (size_t)f; }
 	static __device__ __forceinline__ int tone_n(const Args &a) { return a.tone_n; }
 };
 
+// record k -> pcm[320 k ..], rv[2 k], rv[2 k + 1] (gmr1_hip_tch3_frames_to_pcm*, gmr1_hip_tch3_voice_batch*)
+struct AmbeCalls : AmbeRecords<AmbeCallArgs> {
+	static constexpr bool kSlots = false;
+	static __device__ __forceinline__ int16_t *pcm(const Args &a, int, int f) { return a.pcm + (size_t)f * kAmbeFrameSamples; }
+	static __device__ __forceinline__ bool has_rv(const Args &a) { return a.rv != nullptr; }
+	static __device__ __forceinline__ int32_t *rv(const Args &a, int, int f, const int16_t *) { return a.rv + (size_t)f; }
+};
+
+// record k -> the audio block out[slot[k]] (tch3_audio.h; gmr1_hip_tch3_frames_to_audio_dev, the receive loop): a record
+// without a slot is passed over -- its bytes are not looked at, the decoder stays as it is -- and one whose slot the
+// caller's array does not hold goes to the call's sink block, decoded all the same.  The slot is wave-uniform and read
+// once per frame: pcm() is null where there is none, and the verdict's place is found from the samples'.
+struct AmbeAudio : AmbeRecords<AmbeAudioArgs> {
+	static constexpr bool kSlots = true;
+	static __device__ __forceinline__ int16_t *pcm(const Args &a, int ch, int f)
+	{
+		const int s = uni(a.slot[f >> 1]);
+		if (s < 0)
+			return nullptr;
+		unsigned char *block = s < a.max_out ? a.out + (size_t)s * kAudioBytes : a.sink + (size_t)ch * kAudioBytes;
+		return reinterpret_cast<int16_t *>(block + kAudioPcm) + (f & 1) * kAmbeFrameSamples;
+	}
+	static __device__ __forceinline__ bool has_rv(const Args &) { return true; }
+	static __device__ __forceinline__ int16_t *rv(const Args &, int, int f, int16_t *samples)
+	{
+		return samples - (f & 1) * kAmbeFrameSamples - (kAudioPcm - kAudioRv) / 2 + (f & 1);
+	}
+};
+
 static_assert(kAmbeRecFrames == 2, "a record is two frames: f >> 1, f & 1");
+static_assert(kAudioPcm % 2 == 0 && kAudioRv % 2 == 0 && kAudioBytes % 16 == 0, "a block's samples and verdicts are 2-byte aligned");
 
 }  // namespace
 
@@ -377,6 +432,10 @@ __device__ __forceinline__ void ambe_wave(const typename Src::Args &a)
 
 	for (int f = f_lo; f < f_hi; f++) {
 		int16_t *out = Src::pcm(a, ch, f);
+		if constexpr (Src::kSlots) {
+			if (!out)
+				continue;
+		}
 		// a record that is not speech is what gmr1_codec_decode_dtx is for (ambe.c:130-141): its bytes are not looked at
 		const bool dtx = Src::kRecords && !Src::speech(a, f);
 		const uint8_t *fr = Src::frame(a, ch, f);
@@ -842,8 +901,8 @@ __device__ __forceinline__ void ambe_wave(const typename Src::Args &a)
 			s.mlog_prev[lane] = s.mlog[1][lane];
 			WSYNC();
 		}
-		if (a.rv && lane == 0)
-			*Src::rv(a, ch, f) = rv;
+		if (Src::has_rv(a) && lane == 0)
+			*Src::rv(a, ch, f, out) = rv;
 	}
 
 	// state back
@@ -886,6 +945,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 	ambe_wave<AmbeCalls>(a);
 }
 
+// the calls of gmr1_hip_tch3_frames_to_audio_dev and of the receive loop's voice entries: the same walk, the samples and
+// verdicts closed up into audio blocks
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ambe_audio(AmbeAudioArgs a)
+{
+	ambe_wave<AmbeAudio>(a);
+}
+
 static int ambe_dbg()
 {
 	static int dbg = -1;
@@ -913,6 +979,24 @@ hipError_t launch_ambe_calls(const AmbeCallArgs &a, hipStream_t stream)
 	AmbeCallArgs b = a;
 	b.dbg = ambe_dbg();
 	hipLaunchKernelGGL(k_ambe_calls, dim3(a.n_calls), dim3(64), 0, stream, b);
+	return hipGetLastError();
+}
+
+hipError_t launch_ambe_audio(const AmbeAudioArgs &a, hipStream_t stream)
+{
+	if (a.n_calls <= 0 || a.n_frames <= 0)
+		return hipSuccess;
+	AmbeAudioArgs b = a;
+	b.dbg = ambe_dbg();
+	hipLaunchKernelGGL(k_ambe_audio, dim3(a.n_calls), dim3(64), 0, stream, b);
+	return hipGetLastError();
+}
+
+hipError_t launch_ambe_init_list(AmbeState *state, int n, const int32_t *call, int flags, hipStream_t stream)
+{
+	if (n <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_ambe_init_list, dim3(n), dim3(64), 0, stream, state, n, call, flags);
 	return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@
 #include "ambe_calls.h"
 #include "ambe_dev.h"
 #include "ambe_tables.h"
+#include "tch3_audio.h"
 
 #include "../../include/gmr1_hip.h"
 #include "../../include/osmocom/gmr1/codec/codec.h"
@@ -231,6 +232,11 @@ int init_dev(hipStream_t st, int n_ch, void *state, int flags)
 static_assert(sizeof(gmr1_hip_tch3_frame) == kAmbeRecBytes && offsetof(gmr1_hip_tch3_frame, type) == kAmbeRecType &&
               offsetof(gmr1_hip_tch3_frame, l2) == kAmbeRecL2 && sizeof(gmr1_hip_tch3_frame().l2) == kAmbeRecFrames * kAmbeFrameBytes,
               "ambe_calls.h describes struct gmr1_hip_tch3_frame");
+static_assert(sizeof(gmr1_hip_rx_audio) == kAudioBytes && offsetof(gmr1_hip_rx_audio, pcm) == kAudioPcm &&
+              offsetof(gmr1_hip_rx_audio, rv) == kAudioRv && offsetof(gmr1_hip_tch3_frame, cls) == kAudioRecCls &&
+              offsetof(gmr1_hip_rx_audio, cls) == 3 && offsetof(gmr1_hip_rx_audio, fn) == 4 && offsetof(gmr1_hip_rx_audio, tn) == 8 &&
+              offsetof(gmr1_hip_rx_audio, call) == 9 && kAudioClsOff == GMR1_HIP_TCH3_OFF,
+              "tch3_audio.h describes struct gmr1_hip_rx_audio");
 
 }  // namespace
 
@@ -291,6 +297,62 @@ int tch3_pcm_enqueue(hipStream_t st, int n_calls, const int32_t *first, int n_fr
 	a.tone_n = kAmbeFrameSamples;
 	a.dbg = 0;
 	HIP_TRY(launch_ambe_calls(a, st));
+	return 0;
+}
+
+// ---- the follower's records closed up into audio blocks (gmr1_hip_tch3_frames_to_audio_dev, the receive loop) ----
+
+int codec_init_list(hipStream_t st, int n, const int32_t *call, void *state, int flags)
+{
+	if (n < 0)
+		return fail(-EINVAL, "codec_init_list: negative count");
+	if (!call || !state)
+		return fail(-EINVAL, "codec_init_list: NULL argument");
+	if (flags & ~GMR1_HIP_CODEC_CLEARED)
+		return fail(-EINVAL, "codec_init_list: unknown flag bits 0x%x", flags);
+	if (reinterpret_cast<uintptr_t>(state) & 15u)
+		return fail(-EINVAL, "codec_init_list: state must be 16-byte aligned");
+	DevState *s;
+	int r = dev_state(&s);
+	if (r) return r;
+	HIP_TRY(launch_ambe_init_list(static_cast<AmbeState *>(state), n, call, flags, st));
+	return 0;
+}
+
+// a slot per frame, a sink block per call, each from a 128-byte boundary
+size_t tch3_audio_scratch_bytes(int n_calls, int n_frames)
+{
+	auto up = [](size_t x) { return (x + 127) & ~(size_t)127; };
+	return up((size_t)n_frames * 4) + up((size_t)n_calls * kAudioBytes);
+}
+
+int tch3_audio_enqueue(hipStream_t st, void *scratch, int n_calls, const int32_t *first, int n_frames,
+                       const struct gmr1_hip_tch3_frame *frames, const uint32_t *fn, const uint64_t *label, void *codec_state,
+                       struct gmr1_hip_rx_audio *out, int max_out, int32_t *call_base, int32_t *n_out)
+{
+	AmbeAudioArgs a;
+	int r = dev_tab(&a.tab, &a.big, &a.libm);
+	if (r) return r;
+	unsigned char *d = static_cast<unsigned char *>(scratch);
+	Tch3AudioArgs c;
+	std::memset(&c, 0, sizeof(c));
+	c.n_calls = n_calls; c.n_frames = n_frames; c.max_out = max_out;
+	c.first = first; c.frames = frames; c.fn = fn; c.label = label; c.out = out;
+	c.slot = reinterpret_cast<int32_t *>(d);
+	c.call_base = call_base; c.n_out = n_out;
+	HIP_TRY(launch_tch3f_audio(c, st));
+	a.n_calls = n_calls;
+	a.n_frames = n_frames;
+	a.max_out = max_out;
+	a.first = first;
+	a.rec = reinterpret_cast<const uint8_t *>(frames);
+	a.slot = c.slot;
+	a.out = reinterpret_cast<unsigned char *>(out);
+	a.sink = d + (((size_t)n_frames * 4 + 127) & ~(size_t)127);
+	a.state = static_cast<AmbeState *>(codec_state);
+	a.tone_n = kAmbeFrameSamples;
+	a.dbg = 0;
+	HIP_TRY(launch_ambe_audio(a, st));
 	return 0;
 }
 
@@ -444,6 +506,41 @@ int gmr1_hip_tch3_frames_to_pcm(int n_calls, const int32_t *first, int n_frames,
 	if (!carry && (r = tch3_pcm_fresh(nullptr, n_calls, d_st, flags))) return r;
 	if ((r = tch3_pcm_enqueue(nullptr, n_calls, d_first, n_frames, d_fr, d_st, d_pcm, d_rv))) return r;
 	return sg.fetch();
+}
+
+int gmr1_hip_codec_init_list_dev(void *stream, int n, const int32_t *call, void *state, int flags)
+{
+	return codec_init_list((hipStream_t)stream, n, call, state, flags);
+}
+
+int gmr1_hip_tch3_frames_to_audio_dev(void *stream, int n_calls, const int32_t *first, int n_frames,
+                                      const struct gmr1_hip_tch3_frame *frames, const uint32_t *fn, const uint64_t *label,
+                                      void *codec_state, struct gmr1_hip_rx_audio *out, int max_out, int32_t *n_out)
+{
+	// (a NULL out passes tch3_pcm_check's pointer test only when there is nothing to store)
+	static const int16_t nothing_to_store = 0;
+	int r = tch3_pcm_check("tch3_frames_to_audio", n_calls, first, n_frames, frames, codec_state, true, 0, 0,
+	                       max_out == 0 && !out ? static_cast<const void *>(&nothing_to_store) : out);
+	if (r) return r;
+	if (max_out < 0)
+		return fail(-EINVAL, "tch3_frames_to_audio: negative max_out");
+	if (!fn || !label || !n_out)
+		return fail(-EINVAL, "tch3_frames_to_audio: NULL argument");
+	if (reinterpret_cast<uintptr_t>(out) & 15u)
+		return fail(-EINVAL, "tch3_frames_to_audio: out is not on a 16-byte boundary");
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	hipStream_t st = (hipStream_t)stream;
+	if (n_calls == 0 || n_frames == 0) {
+		HIP_TRY(hipMemsetAsync(n_out, 0, 4, st));
+		return 0;
+	}
+	if ((r = tch3_pcm_prepare())) return r;
+	WsLease lease;
+	if ((r = lease.acquire(s, st))) return r;
+	Arena ws;                                      // the start of the device's workspace
+	if ((r = ws.init(tch3_audio_scratch_bytes(n_calls, n_frames)))) return r;
+	return tch3_audio_enqueue(st, ws.base, n_calls, first, n_frames, frames, fn, label, codec_state, out, max_out, nullptr, n_out);
 }
 
 // ---- the reference's own calls (include/osmocom/gmr1/codec/codec.h:37-45) ----

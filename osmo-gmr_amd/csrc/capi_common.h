@@ -138,6 +138,16 @@ int tch3_pcm_fresh(hipStream_t st, int n_calls, void *codec_state, int flags);
 int tch3_pcm_enqueue(hipStream_t st, int n_calls, const int32_t *first, int n_frames, const struct gmr1_hip_tch3_frame *frames,
                      void *codec_state, int16_t *pcm, int32_t *rv);
 
+// The follower's records closed up into audio blocks (capi_ambe.cpp; the rule: tch3_audio.h): what
+// gmr1_hip_tch3_frames_to_audio_dev runs, on scratch of the caller's -- tch3_audio_scratch_bytes of device memory on a
+// 128-byte boundary -- with the arguments not checked.  call_base (optional, device, n_calls entries): the blocks in front
+// of each call.  codec_init_list: gmr1_hip_codec_init_list_dev.
+size_t tch3_audio_scratch_bytes(int n_calls, int n_frames);
+int tch3_audio_enqueue(hipStream_t st, void *scratch, int n_calls, const int32_t *first, int n_frames,
+                       const struct gmr1_hip_tch3_frame *frames, const uint32_t *fn, const uint64_t *label, void *codec_state,
+                       struct gmr1_hip_rx_audio *out, int max_out, int32_t *call_base, int32_t *n_out);
+int codec_init_list(hipStream_t st, int n, const int32_t *call, void *state, int flags);
+
 // gmr1_hip_tch9_follow_batch_dev on scratch of the caller's (capi_tch9_follow.cpp), under the same terms
 size_t tch9_follow_scratch_bytes(int n_frames);
 int tch9_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,

@@ -317,11 +317,15 @@ int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const
                      const uint16_t *arfcn, const uint8_t *kc,
                      struct gmr1_hip_rx_record *out, int max_records, int *n_records,
                      struct gmr1_hip_rx_big_record *big_out, int max_big, int *n_big,
-                     int32_t *status, int32_t *n_chains, int32_t *rec_per_carrier)
+                     int32_t *status, int32_t *n_chains, int32_t *rec_per_carrier,
+                     bool want_audio = false, struct gmr1_hip_rx_audio *audio_out = nullptr, int max_audio = 0, int *n_audio = nullptr)
 {
 	hipStream_t st = (hipStream_t)stream_;
 	if (n_records) *n_records = 0;
 	if (n_big) *n_big = 0;
+	if (n_audio) *n_audio = 0;
+	if (want_audio && (!n_audio || max_audio < 0 || (max_audio > 0 && !audio_out)))
+		return fail(-EINVAL, "rx_run_voice: n_audio (and audio_out when max_audio > 0) are required, and no negative count");
 	if (csd && (!tch || !n_big || max_big < 0 || (max_big > 0 && !big_out)))
 		return fail(-EINVAL, "rx_run: the CSD carrier needs the traffic carrier and the big-record outputs");
 	if (n_arfcn < 0 || !iq || !offset || !length || !n_records || (max_records > 0 && !out) || max_records < 0)
@@ -340,6 +344,12 @@ int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const
 			return fail(-EINVAL, "rx_run: carrier %d longer than 2^31-1 samples", i);
 
 	RxRun run(st, sps, iq, tch, csd, n_arfcn, offset, length, arfcn, kc, out, max_records);
+	RxVoice voice;
+	if (want_audio && tch) {
+		voice.out = audio_out;
+		voice.max_out = max_audio;
+		run.voice = &voice;
+	}
 	const auto t0 = RxClock::now();
 	if ((r = run.acquire())) return r;
 	const auto t1 = RxClock::now();
@@ -362,6 +372,7 @@ int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const
 	// ---- hand back: carriers in order, chains in order, frames in order -------------------------
 	// (a direct run's records are already in the caller's buffer, in this very order: k_rx_pack)
 	*n_records = run.direct ? run.direct_total : rx_hand_back(run.walks, out, max_records);
+	if (n_audio) *n_audio = voice.found;
 	if (n_big) {
 		int tb = 0;
 		for (const RxWalk &w : run.walks)
@@ -425,6 +436,43 @@ int gmr1_hip_rx_run_tch_dev(void *stream, int n_arfcn, int sps, const float *iq,
 {
 	return gmr1_hip_rx_run_full_dev(stream, n_arfcn, sps, iq, tch, nullptr, offset, length, arfcn, kc,
 	                                out, max_records, n_records, nullptr, 0, nullptr, status, n_chains);
+}
+
+// the TCH3 follow-up with the followed calls decoded to audio: the pass hands its frames to the speech decoder where they lie
+int gmr1_hip_rx_run_voice_dev(void *stream, int n_arfcn, int sps, const float *iq, const float *tch,
+                              const uint64_t *offset, const uint64_t *length, const uint16_t *arfcn, const uint8_t *kc,
+                              struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                              int32_t *status, int32_t *n_chains,
+                              struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
+{
+	return rx_run_full_impl(stream, n_arfcn, sps, iq, tch, nullptr, offset, length, arfcn, kc, out, max_records,
+	                        n_records, nullptr, 0, nullptr, status, n_chains, nullptr, true, audio_out, max_audio, n_audio);
+}
+
+int gmr1_hip_rx_run_voice(int n_arfcn, int sps, const float *iq, const float *tch, uint64_t iq_len,
+                          const uint64_t *offset, const uint64_t *length, const uint16_t *arfcn, const uint8_t *kc,
+                          struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                          int32_t *status, int32_t *n_chains,
+                          struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
+{
+	if (n_records) *n_records = 0;
+	if (n_audio) *n_audio = 0;
+	if (!n_audio || max_audio < 0 || (max_audio > 0 && !audio_out))
+		return fail(-EINVAL, "rx_run_voice: n_audio (and audio_out when max_audio > 0) are required, and no negative count");
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (n_arfcn < 0 || !iq || !offset || !length)
+		return fail(-EINVAL, "rx_run: iq/offset/length are required");
+	for (int i = 0; i < n_arfcn; i++)
+		if (offset[i] + length[i] > iq_len)
+			return fail(-EINVAL, "rx_run: carrier %d runs past the end of iq", i);
+	Stage sg;
+	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
+	const float *d_tch = sg.in(tch, (size_t)iq_len * 2);
+	if ((r = sg.err())) return r;
+	return gmr1_hip_rx_run_voice_dev(nullptr, n_arfcn, sps, d_iq, d_tch, offset, length, arfcn, kc, out, max_records, n_records,
+	                                 status, n_chains, audio_out, max_audio, n_audio);
 }
 
 int gmr1_hip_rx_run_full(int n_arfcn, int sps, const float *iq, const float *tch, const float *csd, uint64_t iq_len,

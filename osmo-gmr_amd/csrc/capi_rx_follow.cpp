@@ -7,6 +7,7 @@
 // run is integer work: rx_follow.h.
 
 #include "rx_run.h"
+#include "tch3_audio.h"
 
 using namespace gmr1;
 
@@ -41,11 +42,18 @@ struct Tch3Batch {
 	std::vector<uint64_t> t_off;
 	std::vector<uint32_t> t_fn;
 	std::vector<gmr1_hip_tch3_frame> got;
+	// with audio: the calls' labels going in; coming back, the blocks in front of each call and, last, their number
+	std::vector<uint64_t> label;
+	std::vector<int32_t> call_base;
+	gmr1_hip_rx_audio *d_audio = nullptr;        // the blocks, in the pass's arena until the next invocation
 };
 
 // one invocation: staged, rx_tch3_init on the states where they lie, the follower, b.got on the host (one synchronisation,
-// which also comes ahead of the next invocation's staging: the vectors are reused)
-int tch3_invoke(hipStream_t st, Arena &arena, int n_calls, int sps, const float *tch, gmr1_hip_tch3_state *d_state, Tch3Batch &b)
+// which also comes ahead of the next invocation's staging: the vectors are reused).  d_codec: the calls' decoders, for a
+// pass that gives audio -- made fresh for the very calls rx_tch3_init runs on, then run over the frames where they lie;
+// the block counts come back with b.got.
+int tch3_invoke(hipStream_t st, Arena &arena, int n_calls, int sps, const float *tch, gmr1_hip_tch3_state *d_state, Tch3Batch &b,
+                void *d_codec)
 {
 	int r = 0;
 	const size_t n = b.item.size(), n_assign = b.a_call.size();
@@ -56,7 +64,10 @@ int tch3_invoke(hipStream_t st, Arena &arena, int n_calls, int sps, const float 
 		const float *d_en = sg.in(b.a_en.data(), n_assign);
 		if ((r = sg.err())) return r;
 		if ((r = gmr1_hip_tch3_state_assign_batch_dev(st, (int)n_assign, d_call, d_p, d_en, d_state))) return r;
+		if (d_codec && (r = codec_init_list(st, (int)n_assign, d_call, d_codec, 0))) return r;
 	}
+	b.d_audio = nullptr;
+	b.call_base.assign((size_t)n_calls + 1, 0);
 	if (n) {
 		const int32_t *d_first = sg.in(b.first.data(), b.first.size());
 		const uint64_t *d_off = sg.in(b.t_off.data(), n);
@@ -67,6 +78,16 @@ int tch3_invoke(hipStream_t st, Arena &arena, int n_calls, int sps, const float 
 		if ((r = sg.err())) return r;
 		r = tch3_follow_enqueue(st, scratch, n_calls, sps, rx_tch3_in_len(sps), tch, d_first, (int)n, d_off, d_fs, d_fn, d_state, d_got);
 		if (r) return r;
+		if (d_codec) {
+			const uint64_t *d_label = sg.in(b.label.data(), (size_t)n_calls);
+			int32_t *d_base = sg.out(b.call_base.data(), (size_t)n_calls + 1);
+			b.d_audio = sg.dev<gmr1_hip_rx_audio>(n);
+			unsigned char *a_scratch = sg.dev<unsigned char>(tch3_audio_scratch_bytes(n_calls, (int)n));
+			if ((r = sg.err())) return r;
+			r = tch3_audio_enqueue(st, a_scratch, n_calls, d_first, (int)n, d_got, d_fn, d_label, d_codec, b.d_audio, (int)n, d_base,
+			                       d_base + n_calls);
+			if (r) return r;
+		}
 	}
 	return sg.fetch();
 }
@@ -95,14 +116,19 @@ namespace gmr1 {
 // per-frame work, the state machine, the decodes and the ciphering state are the follower's, on the device.  rx_tch3_init
 // runs between two invocations (k_tch3f_assign, on the states where they lie): a chain that is assigned once -- the usual
 // case -- costs one invocation and one synchronisation.
+// voice: the pass also gives audio (RxVoice, rx_run.h).  Every invocation then makes the decoders of its assigned calls
+// fresh on the device and closes its frames up into audio blocks behind the follower (tch3_invoke); the block counts come
+// back with the frames, then the blocks are copied -- straight to the caller where one invocation holds them all (rx_follow.h).
 // horizon: a push that is not the last.  Every logged frame was admitted by align + 2 * frame_len <= len, which its TCH3
 // window fits, so a window that does not is an error (-EIO), not a frame dropped that the one-shot reads.
 int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t *arfcn, bool want9, bool horizon,
                        const std::vector<RxChain> &chains, std::vector<RxWalk> &walks, const std::vector<int> &calls,
-                       const gmr1_hip_tch3_state *h_state0, gmr1_hip_tch3_state *d_state, TchCarry *carry)
+                       const gmr1_hip_tch3_state *h_state0, gmr1_hip_tch3_state *d_state, TchCarry *carry, RxVoice *voice)
 {
 	int r = 0;
 	const int n_calls = (int)calls.size();
+	if (voice)
+		voice->found = 0;
 	std::vector<Tch3Call> pc((size_t)n_calls);
 	for (int q = 0; q < n_calls; q++) {
 		const RxWalk &w = walks[calls[q]];
@@ -117,15 +143,31 @@ int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t
 		return 0;
 	// the states if they start here, first[] and an assignment per call, per frame 56 B staged and the follower's scratch;
 	// no invocation has more than nt frames
+	// with audio: the decoders if they start here, a label and a block count per call, a block per frame, the close-up's scratch
+	const size_t codec_bytes = gmr1_hip_codec_state_bytes();
+	const bool own_codec = voice && !voice->d_codec;
+	const size_t voice_bytes = !voice ? 0 : (own_codec ? up128((size_t)n_calls * codec_bytes) : 0) + up128((size_t)n_calls * 8) +
+	                           up128(((size_t)n_calls + 1) * 4) + up128((size_t)nt * sizeof(gmr1_hip_rx_audio)) +
+	                           tch3_audio_scratch_bytes(n_calls, nt) + 2 * 128;
+	if (voice && (r = tch3_pcm_prepare())) return r;  // the decoder's tables, before anything is enqueued
 	Arena arena;
 	if ((r = arena.init((h_state0 ? (size_t)n_calls * sizeof(gmr1_hip_tch3_state) + 128 : 0) + ((size_t)n_calls + 1) * 4 +
-	                    (size_t)n_calls * 12 + (size_t)nt * 56 + 10 * 128 + tch3_follow_scratch_bytes(nt)))) return r;
-	if (h_state0) {
+	                    (size_t)n_calls * 12 + (size_t)nt * 56 + 10 * 128 + tch3_follow_scratch_bytes(nt) + voice_bytes))) return r;
+	void *d_codec = voice ? voice->d_codec : nullptr;
+	if (h_state0 || own_codec) {
 		Stage s0(st, &arena);
-		d_state = const_cast<gmr1_hip_tch3_state *>(s0.in(h_state0, (size_t)n_calls));
+		if (h_state0)
+			d_state = const_cast<gmr1_hip_tch3_state *>(s0.in(h_state0, (size_t)n_calls));
+		// (no decoder is read before an assignment made it fresh: frames are handed in from a call's first assignment on)
+		if (own_codec)
+			d_codec = s0.dev<unsigned char>((size_t)n_calls * codec_bytes);
 		if ((r = s0.err())) return r;
 	}
 	const size_t arena_kept = arena.off;
+	// where the blocks go (rx_follow.h): straight to the caller when one invocation has them all
+	const bool direct = voice && tch3_voice_invocations(plan) <= 1;
+	struct Kept { std::vector<gmr1_hip_rx_audio> blocks; std::vector<int32_t> call_base; };
+	std::vector<Kept> kept;
 	std::vector<size_t> next(plan.start.begin(), plan.start.end() - 1);   // per call: its first item no invocation has taken yet
 	std::vector<char> touched((size_t)n_calls, 0);
 	Tch3Batch b;
@@ -158,7 +200,32 @@ int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t
 		if (b.item.empty() && b.a_call.empty())
 			continue;
 		arena.off = arena_kept;                   // the invocation before is through (fetch)
-		if ((r = tch3_invoke(st, arena, n_calls, sps, tch, d_state, b))) return r;
+		if (voice) {
+			b.label.assign((size_t)n_calls, 0);
+			for (int q = 0; q < n_calls; q++)
+				if (b.first[q + 1] > b.first[q]) {
+					const RxChain &c = chains[calls[q]];
+					b.label[q] = tch3_audio_label(rx_label(arfcn, c.a), (unsigned)c.chain, (unsigned)titems[b.item[b.first[q]]].tn,
+					                              (unsigned)tch3_voice_call(voice->count ? voice->count[q] : 0, (int)g));
+				}
+		}
+		if ((r = tch3_invoke(st, arena, n_calls, sps, tch, d_state, b, d_codec))) return r;
+		// the invocation's blocks: the count came back with the frames, now exactly that many (one more synchronisation)
+		if (voice && b.d_audio) {
+			const int count = b.call_base[n_calls];
+			gmr1_hip_rx_audio *to = voice->out;
+			int fit = std::min(count, voice->max_out);
+			if (!direct) {
+				kept.push_back({std::vector<gmr1_hip_rx_audio>((size_t)count), b.call_base});
+				to = kept.back().blocks.data();
+				fit = count;
+			}
+			voice->found += count;
+			if (fit > 0) {
+				HIP_TRY(hipMemcpyAsync(to, b.d_audio, (size_t)fit * sizeof(gmr1_hip_rx_audio), hipMemcpyDeviceToHost, st));
+				HIP_TRY(hipStreamSynchronize(st));
+			}
+		}
 		// records, chain by chain in frame order
 		for (size_t k = 0; k < b.item.size(); k++) {
 			const Tch3Item &ti = titems[b.item[k]];
@@ -169,8 +236,22 @@ int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t
 		}
 	}
 
+	// blocks of more than one invocation: call by call, and within a call in the invocations' order, which is the frames'
+	if (voice && !direct) {
+		int total = 0;
+		for (int q = 0; q < n_calls; q++)
+			for (const Kept &k : kept) {
+				const int cnt = k.call_base[q + 1] - k.call_base[q];
+				const int fit = std::max(0, std::min(cnt, voice->max_out - total));
+				if (fit)
+					std::memcpy(voice->out + total, k.blocks.data() + k.call_base[q], (size_t)fit * sizeof(gmr1_hip_rx_audio));
+				total += cnt;
+			}
+	}
 	for (int q = 0; q < n_calls; q++) {
 		RxWalk &w = walks[calls[q]];
+		if (voice && voice->count)
+			voice->count[q] = tch3_voice_carry(voice->count[q], w.events.size());
 		if (carry && !w.events.empty())
 			carry[q] = {w.events.back().tn, true};
 		if (touched[q])
@@ -191,7 +272,7 @@ int RxRun::tch3_pass()
 	if (calls.empty())
 		return 0;
 	const std::vector<gmr1_hip_tch3_state> state = tch3_first_states(chains, calls, kc);
-	return r = tch3_follow_chains(st, sps, tch, arfcn, csd != nullptr, false, chains, walks, calls, state.data(), nullptr, nullptr);
+	return r = tch3_follow_chains(st, sps, tch, arfcn, csd != nullptr, false, chains, walks, calls, state.data(), nullptr, nullptr, voice);
 }
 
 }  // namespace gmr1

@@ -23,6 +23,11 @@
 // third ping-pong pair for the CSD carrier, one struct gmr1_hip_tch9_state per chain in device memory and the timeslot of
 // each chain's last ASSIGNMENT COMMAND 1 on the host (`carry9`).  tch3_follow_chains notes this push's commands, and
 // tch9_follow_push (capi_rx_follow.cpp) follows them through the batched TCH9 call follower in one invocation.
+//
+// A handle made by gmr1_hip_rx_stream_create_voice is a tch handle that also decodes the calls it follows
+// (gmr1_hip_rx_run_voice over pushes): one AMBE decoder state per chain in device memory beside d_tstate and each chain's
+// count of assignments on the host (`n_assigned`), handed to tch3_follow_chains as an RxVoice; a push's audio blocks come
+// back beside its records.  It brings two carriers a push, as a tch handle does: rx_stream_planes (rx_stream.h).
 
 #include "fcch_acq.h"
 #include "rx_run.h"
@@ -71,11 +76,15 @@ struct gmr1_hip_rx_stream {
 	float2 *cbuf[2] = {nullptr, nullptr};          // the CSD carrier's samples, held as tbuf is
 	gmr1_hip_tch9_state *d_t9state = nullptr;      // one per chain, parallel to d_state
 	std::vector<Tch9CallCarry> carry9;   // per chain
-	int kind() const { return full ? kRxStreamFull : tch ? kRxStreamTch : kRxStreamPlain; }
+	// a handle that decodes the TCH3 calls it follows (gmr1_hip_rx_stream_create_voice; tch is set as well)
+	bool voice = false;
+	void *d_codec = nullptr;             // one AMBE decoder state per chain, beside d_tstate
+	std::vector<int> n_assigned;         // per chain: IMMEDIATE ASSIGNMENTs followed so far
+	int kind() const { return full ? kRxStreamFull : voice ? kRxStreamVoice : tch ? kRxStreamTch : kRxStreamPlain; }
 	~gmr1_hip_rx_stream()
 	{
 		for (void *p : std::initializer_list<void *>{buf[0], buf[1], tbuf[0], tbuf[1], cbuf[0], cbuf[1], d_tstate, d_t9state, d_state,
-		                                             d_car, d_err, d_in})
+		                                             d_codec, d_car, d_err, d_in})
 			if (p) (void)hipFree(p);
 		for (void *p : std::initializer_list<void *>{h_car, h_err, h_in})
 			if (p) (void)hipHostFree(p);
@@ -136,13 +145,30 @@ long long rx_stream_big_bound(const gmr1_hip_rx_stream *h, uint64_t n)
 	return rx_stream_max_big(chains, len, h->sps);
 }
 
-// what a push entry hands in beside iq: `kind` says which entry it is (_push*, _push_tch*, _push_full*)
+long long rx_stream_audio_bound(const gmr1_hip_rx_stream *h, uint64_t n)
+{
+	if (h->ended || !h->voice)
+		return 0;
+	long long chains = 0, len = 0;
+	for (int i = 0; i < h->A; i++) {
+		if (rx_stream_dead(h, i))
+			continue;
+		chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
+		len = std::max(len, rx_stream_next_held(h, i, n));
+	}
+	return rx_stream_max_audio(chains, len, h->sps);
+}
+
+// what a push entry hands in beside iq: `kind` says which entry it is (_push*, _push_tch*, _push_full*, _push_voice*)
 struct RxStreamPush {
 	int kind;
 	const float *tch, *csd;
 	gmr1_hip_rx_big_record *big_out;
 	int max_big;
 	int *n_big;
+	gmr1_hip_rx_audio *audio_out = nullptr;
+	int max_audio = 0;
+	int *n_audio = nullptr;
 };
 
 int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, const float *iq, uint64_t iq_stride, uint64_t n,
@@ -151,8 +177,10 @@ int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, const fl
 	if (!h || !n_records || max_records < 0 || (max_records > 0 && !out) || (n > 0 && !iq))
 		return fail(-EINVAL, "rx_stream_push: handle / n_records (and iq when n > 0, out when max_records > 0) are required");
 	if (h->kind() != p.kind) {
-		static const char *const entry[] = {"gmr1_hip_rx_stream_push*", "gmr1_hip_rx_stream_push_tch*", "gmr1_hip_rx_stream_push_full*"};
-		static const char *const maker[] = {"gmr1_hip_rx_stream_create", "gmr1_hip_rx_stream_create_tch", "gmr1_hip_rx_stream_create_full"};
+		static const char *const entry[kRxStreamKinds] = {"gmr1_hip_rx_stream_push*", "gmr1_hip_rx_stream_push_tch*",
+		                                                  "gmr1_hip_rx_stream_push_full*", "gmr1_hip_rx_stream_push_voice*"};
+		static const char *const maker[kRxStreamKinds] = {"gmr1_hip_rx_stream_create", "gmr1_hip_rx_stream_create_tch",
+		                                                  "gmr1_hip_rx_stream_create_full", "gmr1_hip_rx_stream_create_voice"};
 		return fail(-EINVAL, "rx_stream_push: a handle of %s takes %s, not %s", maker[h->kind()], entry[h->kind()], entry[p.kind]);
 	}
 	if (p.kind != kRxStreamPlain && n > 0 && !p.tch)
@@ -163,6 +191,8 @@ int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, const fl
 		if (!p.n_big || p.max_big < 0 || (p.max_big > 0 && !p.big_out))
 			return fail(-EINVAL, "rx_stream_push_full: n_big (and big_out when max_big > 0) are required");
 	}
+	if (p.kind == kRxStreamVoice && (!p.n_audio || p.max_audio < 0 || (p.max_audio > 0 && !p.audio_out)))
+		return fail(-EINVAL, "rx_stream_push_voice: n_audio (and audio_out when max_audio > 0) are required");
 	int dev = 0;
 	HIP_TRY(hipGetDevice(&dev));
 	if (dev != h->device)
@@ -184,6 +214,9 @@ int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, const fl
 	const long long big_bound = rx_stream_big_bound(h, n);
 	if (p.kind == kRxStreamFull && (long long)p.max_big < big_bound)
 		return fail(-EINVAL, "rx_stream_push_full: max_big %d below the bound %lld", p.max_big, big_bound);
+	const long long audio_bound = rx_stream_audio_bound(h, n);
+	if (p.kind == kRxStreamVoice && (long long)p.max_audio < audio_bound)
+		return fail(-EINVAL, "rx_stream_push_voice: max_audio %d below the bound %lld", p.max_audio, audio_bound);
 	return 0;
 }
 
@@ -329,6 +362,13 @@ int rx_stream_acquire(gmr1_hip_rx_stream *h, RxRun &run, int last, std::vector<g
 			HIP_TRY(hipMemcpyAsync(h->d_tstate, t0.data(), nc * sizeof(gmr1_hip_tch3_state), hipMemcpyHostToDevice, run.st));
 			h->carry.assign(nc, TchCarry());
 		}
+		if (h->voice) {
+			// no decoder is read before an assignment made it fresh; zeros until then
+			const size_t bytes = nc * gmr1_hip_codec_state_bytes();
+			HIP_TRY(hipMalloc(&h->d_codec, bytes));
+			HIP_TRY(hipMemsetAsync(h->d_codec, 0, bytes, run.st));
+			h->n_assigned.assign(nc, 0);
+		}
 		if (h->full) {
 			// no call, nothing held, the carrier's key (rx_tch9_init keeps the key)
 			t9.resize(nc);
@@ -420,8 +460,16 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 	*n_records = run.direct ? run.direct_total : 0;
 	// the TCH3 follow-up over this push's frames, and the records chain by chain in frame order
 	if (h->tch && walking) {
+		RxVoice voice;
+		if (h->voice) {
+			voice.d_codec = h->d_codec;
+			voice.count = h->n_assigned.data();
+			voice.out = p.audio_out;
+			voice.max_out = p.max_audio;
+		}
 		if ((r = tch3_follow_chains(st, sps, run.tch, run.arfcn, h->full, !last, h->chains, run.walks, all_chains(h->chains.size()), nullptr,
-		                            h->d_tstate, h->carry.data()))) return r;
+		                            h->d_tstate, h->carry.data(), h->voice ? &voice : nullptr))) return r;
+		if (h->voice) *p.n_audio = voice.found;
 		*n_records = rx_hand_back(run.walks, out, max_records);
 		// the TCH9 follow-up over the same frames, from the commands the TCH3 records of this push carry
 		if (h->full && (r = tch9_follow_push(st, sps, reinterpret_cast<const float *>(h->cbuf[h->cur]), run.arfcn, !last, h->chains,
@@ -436,7 +484,7 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 int rx_stream_pin_chunk(gmr1_hip_rx_stream *h, const RxStreamPush &p, const float *iq, uint64_t iq_stride, uint64_t n, size_t *half)
 {
 	*half = (size_t)h->A * (size_t)n * sizeof(float2);
-	const size_t bytes = (size_t)(1 + p.kind) * *half;
+	const size_t bytes = (size_t)rx_stream_planes(p.kind) * *half;
 	if (bytes > h->h_in_bytes) {
 		if (h->h_in) (void)hipHostFree(h->h_in);
 		if (h->d_in) (void)hipFree(h->d_in);
@@ -475,6 +523,7 @@ int rx_stream_push_any(void *stream, gmr1_hip_rx_stream *h, RxStreamPush p, bool
 	if (r) return r;
 	if (n_records) *n_records = 0;
 	if (p.n_big) *p.n_big = 0;
+	if (p.n_audio) *p.n_audio = 0;
 	std::unique_lock<std::mutex> lk;
 	if (h)
 		lk = std::unique_lock<std::mutex>(h->mu);
@@ -488,7 +537,7 @@ int rx_stream_push_any(void *stream, gmr1_hip_rx_stream *h, RxStreamPush p, bool
 	if ((r = lease.acquire(ds, st))) return r;
 	if (host) {
 		if (half)
-			HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, (size_t)(1 + p.kind) * half, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, (size_t)rx_stream_planes(p.kind) * half, hipMemcpyHostToDevice, st));
 		iq = h->d_in;
 		p.tch = p.kind != kRxStreamPlain ? h->d_in + half / 4 : nullptr;
 		p.csd = p.kind == kRxStreamFull ? h->d_in + 2 * (half / 4) : nullptr;
@@ -520,6 +569,7 @@ int rx_stream_make(int n_arfcn, int sps, const uint16_t *arfcn, int kind, const 
 	h->sps = sps;
 	h->tch = kind != kRxStreamPlain;
 	h->full = kind == kRxStreamFull;
+	h->voice = kind == kRxStreamVoice;
 	if (arfcn)
 		h->arfcn.assign(arfcn, arfcn + n_arfcn);
 	if (kc)
@@ -572,6 +622,47 @@ int gmr1_hip_rx_stream_create_full(int n_arfcn, int sps, const uint16_t *arfcn, 
 	DevState *ds;
 	if ((r = dev_state(&ds))) return r;
 	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamFull, kc, out);
+}
+
+int gmr1_hip_rx_stream_create_voice(int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
+{
+	int r = rx_stream_create_check("rx_stream_create_voice", n_arfcn, sps, out);
+	if (r) return r;
+	DevState *ds;
+	if ((r = dev_state(&ds))) return r;
+	if ((r = tch3_pcm_prepare())) return r;       // the decoder's tables, built once per device
+	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamVoice, kc, out);
+}
+
+int gmr1_hip_rx_stream_max_audio(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_audio)
+{
+	if (!h || !max_audio)
+		return fail(-EINVAL, "rx_stream_max_audio: handle / max_audio are required");
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	std::lock_guard<std::mutex> lk(h->mu);
+	const long long b = rx_stream_audio_bound(h, n);
+	if (b > 0x7fffffffll)
+		return fail(-EINVAL, "rx_stream_max_audio: %lld blocks do not fit an int", b);
+	*max_audio = (int)b;
+	return 0;
+}
+
+int gmr1_hip_rx_stream_push_voice_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride,
+                                      uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                      struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
+{
+	return rx_stream_push_any(stream, h, {kRxStreamVoice, tch, nullptr, nullptr, 0, nullptr, audio_out, max_audio, n_audio}, false, iq,
+	                          iq_stride, n, last, out, max_records, n_records);
+}
+
+int gmr1_hip_rx_stream_push_voice(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
+                                  int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                  struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
+{
+	return rx_stream_push_any(nullptr, h, {kRxStreamVoice, tch, nullptr, nullptr, 0, nullptr, audio_out, max_audio, n_audio}, true, iq,
+	                          iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_max_big(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_big)

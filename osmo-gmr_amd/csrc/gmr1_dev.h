@@ -440,6 +440,20 @@ hipError_t launch_tch3f_emit(const Tch3FollowArgs &a, hipStream_t stream);
 // rx_tch3_init on device-resident states (k_tch3f_assign): entry j < n assigns state[call[j]], entries of one call in order
 hipError_t launch_tch3f_assign(int n, const int32_t *call, const int32_t *p, const float *ref_energy,
                                struct gmr1_hip_tch3_state *state, hipStream_t stream);
+// the follower's frames closed up into audio blocks (k_tch3f_audio; the rule: tch3_audio.h): headers into `out`, and per
+// frame the slot the decoder's audio instantiation (k_ambe_audio, ambe_dev.h) writes its samples to; everything is device memory
+struct Tch3AudioArgs {
+	int n_calls, n_frames, max_out;
+	const int32_t *first;                       // n_calls + 1
+	const struct gmr1_hip_tch3_frame *frames;   // n_frames
+	const uint32_t *fn;                         // n_frames: the frames' own fn, as handed to the follower
+	const uint64_t *label;                      // n_calls: arfcn | chain << 16 | tn << 24 | call << 32
+	struct gmr1_hip_rx_audio *out;              // max_out, on a 16-byte boundary
+	int32_t *slot;                              // n_frames: kAudioNoSlot where a frame gives no block
+	int32_t *call_base;                         // optional n_calls: blocks in front of each call
+	int32_t *n_out;
+};
+hipError_t launch_tch3f_audio(const Tch3AudioArgs &a, hipStream_t stream);
 // NT9 bursts: FACCH9 and the three TCH9 modes share one decoder kernel (nt9_kernels.hip)
 struct Nt9Args {
 	int n;                     // bursts

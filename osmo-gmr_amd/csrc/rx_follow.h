@@ -69,6 +69,29 @@ inline bool tch3_plan(const std::vector<Tch3Call> &calls, int sps, bool horizon,
 	return true;
 }
 
+// ---- the audio of the followed calls (gmr1_hip_rx_run_voice*, a voice handle's pushes) ----
+// A block's `call` counts the IMMEDIATE ASSIGNMENTs its chain has followed: invocation `gen` of a run (Tch3Item::gen) comes
+// behind `gen` of the run's own assignments, on top of the `carried` ones of the pushes before (0 in the one-shot pass).
+// The next push is carried what this one was, plus its events: cut anywhere, the counts are the one-shot pass's.
+inline int tch3_voice_call(int carried, int gen) { return carried + gen; }
+inline int tch3_voice_carry(int carried, size_t n_events) { return carried + (int)n_events; }
+
+// Where a run's blocks go.  Every invocation hands its blocks back call by call, so a run in which one invocation has
+// frames -- a chain assigned once, the usual case, and almost every push -- has them in the caller's order already, and
+// they are copied from the device straight to the caller.  Otherwise they are kept per invocation and handed back
+// call by call, invocation by invocation.
+inline size_t tch3_voice_invocations(const Tch3Plan &plan)
+{
+	std::vector<char> seen(plan.n_gen + 1, 0);
+	size_t n = 0;
+	for (const Tch3Item &it : plan.items)
+		if (!seen[(size_t)it.gen]) {
+			seen[(size_t)it.gen] = 1;
+			n++;
+		}
+	return n;
+}
+
 // ---- TCH9 (rx_tch9, gmr1_rx.c:262-353) ----
 struct Nt9Item { int chain, frame, tn, ass; };     // ass: the ASSIGNMENT COMMAND 1 in force (index into the chain's events)
 

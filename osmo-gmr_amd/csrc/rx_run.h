@@ -47,6 +47,17 @@ struct TchCarry {
 	bool assigned = false;    // there was one
 };
 
+// The audio of one run of tch3_follow_chains (gmr1_hip_rx_run_voice*, a push of a voice handle): behind every invocation
+// of the call follower its frames are closed up into audio blocks and decoded where they lie (tch3_audio_enqueue,
+// capi_ambe.cpp), one AMBE decoder per call, made fresh where the follower's state is assigned.
+struct RxVoice {
+	void *d_codec = nullptr;             // one decoder state per call in device memory; NULL: the run's own, which die with it
+	int *count = nullptr;                // per call: IMMEDIATE ASSIGNMENTs followed before this run, brought up to date by it; NULL: none
+	gmr1_hip_rx_audio *out = nullptr;    // host memory: the first max_out blocks, by call, then frame
+	int max_out = 0;
+	int found = 0;
+};
+
 // One call of gmr1_hip_rx_run*, or one push of the streaming loop: what the phases share.  The phases run in the order
 // the reference's main() runs them (gmr1_rx.c:897-975).
 struct RxRun {
@@ -73,6 +84,7 @@ struct RxRun {
 	// the streaming loop (gmr1_hip_rx_stream_*): the chains' states live in this device array across pushes -- the walk
 	// starts from and writes back to it, nothing is uploaded
 	RxLoopState *loop_state = nullptr;
+	RxVoice *voice = nullptr;                // gmr1_hip_rx_run_voice*: the TCH3 pass decodes the calls it follows
 
 	RxRun(hipStream_t st_, int sps_, const float *iq_, const float *tch_, const float *csd_, int A_, const uint64_t *offset_,
 	      const uint64_t *length_, const uint16_t *arfcn_, const uint8_t *kc_, gmr1_hip_rx_record *out_, int max_records_)
@@ -87,7 +99,7 @@ struct RxRun {
 // the traffic follow-ups over chains and their walks (capi_rx_follow.cpp)
 int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t *arfcn, bool want9, bool horizon,
                        const std::vector<RxChain> &chains, std::vector<RxWalk> &walks, const std::vector<int> &calls,
-                       const gmr1_hip_tch3_state *h_state0, gmr1_hip_tch3_state *d_state, TchCarry *carry);
+                       const gmr1_hip_tch3_state *h_state0, gmr1_hip_tch3_state *d_state, TchCarry *carry, RxVoice *voice = nullptr);
 int tch9_follow_chains(hipStream_t st, int sps, const float *csd, const uint16_t *arfcn, const uint8_t *kc,
                        const std::vector<RxChain> &chains, std::vector<RxWalk> &walks);
 

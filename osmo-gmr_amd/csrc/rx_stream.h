@@ -80,6 +80,18 @@ GMR1_HD long long rx_stream_tch_rec_per_chain(long long len, int sps)
 // ---- a handle that follows TCH9 data calls too (gmr1_hip_rx_stream_create_full) ----
 // what a handle follows, and which push entry it therefore takes
 constexpr int kRxStreamPlain = 0, kRxStreamTch = 1, kRxStreamFull = 2;
+// a handle that follows TCH3 calls and decodes them to audio (gmr1_hip_rx_stream_create_voice): a tch handle with a decoder per chain
+constexpr int kRxStreamVoice = 3;
+constexpr int kRxStreamKinds = 4;
+
+// carriers a push of the kind brings: the BCCH carrier, the traffic carrier, the CSD carrier
+GMR1_HD int rx_stream_planes(int kind) { return kind == kRxStreamPlain ? 1 : kind == kRxStreamFull ? 3 : 2; }
+
+// A voice handle hands back at most one audio block per frame a chain's walk can log: what rx_stream_max_big counts
+GMR1_HD long long rx_stream_max_audio(long long chains, long long len, int sps)
+{
+	return chains > 0 ? chains * rx_stream_frames_per_chain(len, sps) : 0;
+}
 
 // The window rx_tch9 cuts on the CSD carrier is 351 * sps + sps + sps / 2 samples (rx_tch9_in_len, rx_follow.h), and the
 // demodulator takes windows up to kMaxInLen: the largest sps a full handle can be made for

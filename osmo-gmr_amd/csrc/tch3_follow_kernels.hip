@@ -18,6 +18,7 @@
 #include <cstddef>
 
 #include "gmr1_dev.h"
+#include "tch3_audio.h"
 #include "tch3_follow.h"
 #include "wave_ops.h"
 
@@ -243,6 +244,56 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_tch3f_assign(int n, const i
 		st->active = s.active; st->p = s.p; st->weak_cnt = s.weak_cnt; st->sync_id = s.sync_id;
 		st->energy_dkab = s.energy_dkab; st->energy_burst = s.energy_burst;
 	}
+}
+
+// The follower's frames closed up into audio blocks (tch3_audio.h): one wavefront per call.  A frame reports when its
+// class is not OFF; its slot is the number of reporting frames in front of it, over all calls -- frames are contiguous
+// over calls, so a wave counts the frames below its call's first one with the same ballot and popcount it then uses on its
+// own, 64 frames a step (as k_tch9f_big does).  Lane j of a step writes frame j's slot into a.slot for the decoder that
+// follows on the stream (k_ambe_audio), and the block's 16-byte header where the slot is below max_out.  The wave of the
+// last call writes the count.  first[] is the caller's device memory: clamped as in the follower.
+__global__ __launch_bounds__(64 * kWalkWaves) void k_tch3f_audio(Tch3AudioArgs a)
+{
+	const int lane = threadIdx.x & 63;
+	const int c = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWalkWaves + (threadIdx.x >> 6)));
+	if (c >= a.n_calls)
+		return;
+	const int kf = ambe_calls_span(a.first, 0, a.n_frames).lo;
+	const AmbeSpan sp = ambe_calls_span(a.first, c, a.n_frames);
+	const uint8_t *rec = reinterpret_cast<const uint8_t *>(a.frames);
+	int base = 0;
+	for (int kb = kf; kb < sp.lo; kb += 64) {
+		const int k = kb + lane;
+		base += __popcll(__ballot(k < sp.lo && tch3_audio_reports(rec[(size_t)k * kAmbeRecBytes + kAudioRecCls])));
+	}
+	if (a.call_base && lane == 0)
+		a.call_base[c] = base;
+	const uint64_t lab = a.label[c];
+	for (int kb = sp.lo; kb < sp.hi; kb += 64) {
+		const int k = kb + lane;
+		const unsigned cls = k < sp.hi ? rec[(size_t)k * kAmbeRecBytes + kAudioRecCls] : (unsigned)kAudioClsOff;
+		const bool mine = k < sp.hi && tch3_audio_reports(cls);
+		const unsigned long long rep = __ballot(mine);
+		const int slot = tch3_audio_slot(base, rep, lane);
+		if (k < sp.hi)
+			a.slot[k] = mine ? slot : kAudioNoSlot;
+		if (mine && slot < a.max_out) {
+			const AudioHead h = tch3_audio_head(lab, cls, a.fn[k]);
+			*reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(a.out) + (size_t)slot * kAudioBytes) =
+			    make_uint4(h.w[0], h.w[1], h.w[2], h.w[3]);
+		}
+		base += __popcll(rep);
+	}
+	if (c == a.n_calls - 1 && lane == 0)
+		*a.n_out = base;
+}
+
+hipError_t launch_tch3f_audio(const Tch3AudioArgs &a, hipStream_t stream)
+{
+	if (a.n_calls <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_tch3f_audio, dim3((a.n_calls + kWalkWaves - 1) / kWalkWaves), dim3(64 * kWalkWaves), 0, stream, a);
+	return hipGetLastError();
 }
 
 hipError_t launch_tch3f_assign(int n, const int32_t *call, const int32_t *p, const float *ref_energy,

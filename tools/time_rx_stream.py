@@ -12,8 +12,11 @@ left out.
 --full: every carrier also has a CSD carrier with one data call on it (an ASSIGNMENT COMMAND 1 on the call's FACCH3 from
 call frame 25 on), the handle follows TCH3 and TCH9 calls (push_full_dev) and the one-shot call is
 gmr1_hip_rx_run_full_dev; records and big records are compared, the chained pipeline is left out.
+--voice: --tch's capture through a handle that also decodes the calls (push_voice_dev) against gmr1_hip_rx_run_voice_dev,
+records and audio blocks compared; every push size is also run through a tch handle in the same process, the passes
+alternating, and "voice_extra_ms" is the voice push's median time over the tch push's (wall and device).
 
-    python tools/time_rx_stream.py [--seconds 60] [--pushes 0.01,0.1,1] [--tch | --full] [--wide-seconds 0] [--out result.json]
+    python tools/time_rx_stream.py [--seconds 60] [--pushes 0.01,0.1,1] [--tch | --voice | --full] [--wide-seconds 0] [--out result.json]
 """
 import argparse
 import json
@@ -49,10 +52,13 @@ def main():
                     help="length of the chained pipeline's wideband capture (0: leave the pipeline out)")
     ap.add_argument("--tch", action="store_true", help="follow TCH3 calls: one call per carrier")
     ap.add_argument("--full", action="store_true", help="follow TCH3 and TCH9 calls: one voice and one data call per carrier")
+    ap.add_argument("--voice", action="store_true", help="follow TCH3 calls and decode them: --tch's capture, audio blocks out")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.tch and args.full:
-        ap.error("--tch and --full are two kinds of handle: give one")
+    if args.tch + args.full + args.voice > 1:
+        ap.error("--tch, --voice and --full are three kinds of handle: give one")
+    voice = args.voice
+    args.tch = args.tch or voice           # a voice handle takes what a tch handle takes
     import torch
     import workloads
     from __graft_entry__ import load_package
@@ -95,10 +101,16 @@ def main():
     st = stream.cuda_stream
     offset = np.arange(A, dtype=np.uint64) * np.uint64(n)
     length = np.full(A, n, np.uint64)
-    res = {"carriers": A, "capture_s": n / rate, "sps": sps, "tch": bool(args.tch), "full": bool(args.full)}
+    res = {"carriers": A, "capture_s": n / rate, "sps": sps, "tch": bool(args.tch), "full": bool(args.full), "voice": bool(voice)}
     out = np.empty(1 << 21, api.RX_RECORD)
-    ref_big = None
-    if args.full:
+    ref_big = ref_audio = None
+    if voice:
+        def one_shot():
+            rec, audio, status, chains, _, n_audio = api.rx_run_voice_dev(st, d.data_ptr(), dt.data_ptr(), offset, length, sps=sps,
+                                                                          arfcn=arfcn, kc=kc, max_records=1 << 21, max_audio=1 << 18)
+            assert n_audio == len(audio)
+            return (rec, audio), status, chains, None
+    elif args.full:
         def one_shot():
             rec, big, status, chains = api.rx_run_full_dev(st, d.data_ptr(), dt.data_ptr(), dc.data_ptr(), offset, length, sps=sps,
                                                            arfcn=arfcn, kc=kc, max_records=1 << 21, max_big=1 << 20)
@@ -118,31 +130,43 @@ def main():
     if args.full:
         ref, ref_big = ref
         res["big_records"] = int(len(ref_big))
+    if voice:
+        ref, ref_audio = ref
+        res["audio_blocks"] = int(len(ref_audio))
+        res["audio_speech_blocks"] = int(np.sum(ref_audio["cls"] == 4))
     ref = ref.copy()
     res["one_shot_ms"] = 1e3 * min(t)
     res["records"] = int(len(ref))
     res["tch_records"] = int(np.sum(ref["type"] >= 0x10))
     for p_s in [float(v) for v in args.pushes.split(",")]:
         p = int(round(p_s * rate))
-        best = None
-        for _ in range(2):
+        best = best_tch = None
+        # (with --voice the passes alternate: tch handle, voice handle, tch handle, voice handle)
+        for rep_i in range(4 if voice else 2):
+            as_voice = voice and rep_i % 2 == 1
             per, got, got_big, evs = [], [], [], []
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            with api.RxStream(A, sps=sps, arfcn=arfcn, tch=args.tch, full=args.full, kc=kc) as s:
+            with api.RxStream(A, sps=sps, arfcn=arfcn, tch=args.tch and not as_voice, full=args.full, voice=as_voice, kc=kc) as s:
                 at = 0
                 buf = np.empty(max(s.max_records(p), 1), api.RX_RECORD)
                 bbuf = np.empty(max(s.max_big(p), 1), api.RX_BIG_RECORD)
+                abuf = np.empty(max(s.max_audio(p), 1), api.RX_AUDIO) if as_voice else None
                 while at < n:
                     k = min(p, n - at)
                     if s.max_records(k) > buf.size:
                         buf = np.empty(s.max_records(k), api.RX_RECORD)
                     if s.max_big(k) > bbuf.size:
                         bbuf = np.empty(s.max_big(k), api.RX_BIG_RECORD)
+                    if as_voice and s.max_audio(k) > abuf.size:
+                        abuf = np.empty(s.max_audio(k), api.RX_AUDIO)
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(stream)
                     q0 = time.perf_counter()
-                    if args.full:
+                    if as_voice:
+                        r, rb = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf, tch_ptr=dt.data_ptr() + 8 * at,
+                                           audio=abuf)
+                    elif args.full:
                         r, rb = s.push_dev(st, d.data_ptr() + 8 * at, n, k, last=at + k >= n, out=buf, tch_ptr=dt.data_ptr() + 8 * at,
                                            csd_ptr=dc.data_ptr() + 8 * at, big=bbuf)
                     else:
@@ -152,18 +176,24 @@ def main():
                     e1.record(stream)
                     evs.append((e0, e1))
                     got.append(r.copy())
-                    if args.full:
+                    if args.full or as_voice:
                         got_big.append(rb.copy())
                     at += k
             total = time.perf_counter() - t0
             torch.cuda.synchronize()
             dev = [a.elapsed_time(b) for a, b in evs]
-            if best is None or total < best[0]:
+            if voice and not as_voice:
+                if best_tch is None or total < best_tch[0]:
+                    best_tch = (total, per, got, dev, got_big)
+            elif best is None or total < best[0]:
                 best = (total, per, got, dev, got_big)
         total, per, got, dev, got_big = best
         same = _sorted(np.concatenate(got), arfcn).tobytes() == ref.tobytes()
         if args.full:
             same = same and _sorted(np.concatenate(got_big), arfcn).tobytes() == ref_big.tobytes()
+        if voice:
+            same = same and _sorted(np.concatenate(got_big), arfcn).tobytes() == ref_audio.tobytes()
+            same = same and _sorted(np.concatenate(best_tch[2]), arfcn).tobytes() == ref.tobytes()
         per_ms = np.array(per) * 1e3
         dev_ms = np.array(dev)
         steady = per_ms[len(per_ms) // 4:] if len(per_ms) > 8 else per_ms
@@ -174,6 +204,16 @@ def main():
                                  "push_dev_ms_median": float(np.median(steady_dev)),
                                  "push_dev_ms_p99": float(np.percentile(steady_dev, 99)),
                                  "push_dev_ms_max": float(dev_ms.max()), "identical": bool(same)}
+        if voice:
+            t_per, t_dev = np.array(best_tch[1]) * 1e3, np.array(best_tch[3])
+            t_steady = t_per[len(t_per) // 4:] if len(t_per) > 8 else t_per
+            t_steady_dev = t_dev[len(t_dev) // 4:] if len(t_dev) > 8 else t_dev
+            res["push_%gs" % p_s].update({
+                "tch_total_ms": 1e3 * best_tch[0], "tch_push_wall_ms_median": float(np.median(t_steady)),
+                "tch_push_dev_ms_median": float(np.median(t_steady_dev)),
+                "voice_extra_ms": {"wall_median": float(np.median(steady) - np.median(t_steady)),
+                                   "dev_median": float(np.median(steady_dev) - np.median(t_steady_dev)),
+                                   "total": 1e3 * (total - best_tch[0])}})
         print(json.dumps({("push_%gs" % p_s): res["push_%gs" % p_s]}), flush=True)
     # the chained pipeline
     if args.tch or args.full or args.wide_seconds <= 0:

@@ -2,7 +2,9 @@
 """Device-resident timing of the speech decoder's calls entry (gmr1_hip_tch3_frames_to_pcm_dev) against the dense entry
 (gmr1_hip_codec_decode_batch_dev) on the same frames, in one process, the two alternating (no copies in the timed
 region; device events).  Shape: the AMBE side workload's, 8192 calls x 50 all-speech records = 819 200 frames.  Then the
-calls entry again with every second record not speech.  Run by hand on the GPU: time_voice.py [calls] [records] [rounds]"""
+calls entry again with every second record not speech, and the audio entry (gmr1_hip_tch3_frames_to_audio_dev: the close-up
+kernel and the decoder's audio instantiation, samples into 656-byte blocks) on the all-speech records.  Run by hand on the
+GPU: time_voice.py [calls] [records] [rounds]"""
 import json
 import os
 import sys
@@ -59,6 +61,16 @@ def calls_on(records):
 
 
 calls_all, calls_half = calls_on(d_rec), calls_on(d_half)
+d_audio = torch.zeros((n_calls * n_rec, api.RX_AUDIO.itemsize), dtype=torch.uint8, device="cuda")
+d_fn = torch.arange(n_calls * n_rec, dtype=torch.int32, device="cuda")
+d_label = dev(np.array([api.tch3_audio_label(c & 0xffff, c >> 16, 0, 1) for c in range(n_calls)], np.uint64))
+d_found = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+
+def audio():
+    api.tch3_frames_to_audio_dev(stream, n_calls, n_calls * n_rec, d_first.data_ptr(), d_rec.data_ptr(), d_fn.data_ptr(),
+                                 d_label.data_ptr(), d_state.data_ptr(), d_audio.data_ptr(), n_calls * n_rec, d_found.data_ptr())
+
 
 
 def fresh():
@@ -86,7 +98,14 @@ calls_all(d_pcm2)
 torch.cuda.synchronize()
 assert torch.equal(d_pcm, d_pcm2) and torch.equal(s_dense, d_state), "the calls entry and the dense entry differ"
 
-steps = {"dense": dense, "calls": calls_all, "calls_half_speech": calls_half}
+fresh()
+audio()
+torch.cuda.synchronize()
+blocks = d_audio.view(torch.int16).reshape(n_calls * n_rec, -1)
+assert int(d_found[0]) == n_calls * n_rec and torch.equal(blocks[:, 8:].reshape(-1, 160), d_pcm) and torch.equal(s_dense, d_state), \
+    "the audio entry and the dense entry differ"
+
+steps = {"dense": dense, "calls": calls_all, "calls_half_speech": calls_half, "audio": audio}
 for step in steps.values():                     # warm-up: every shape the timed windows use
     window(step)
 ms = {k: [] for k in steps}
@@ -103,6 +122,7 @@ for k, v in ms.items():
           (k, res[k]["median_ms"], v.min(), v.max(), v.max() - v.min()))
 d, c, h = (res[k]["median_ms"] for k in ("dense", "calls", "calls_half_speech"))
 res["calls_minus_dense_ms"] = c - d
+res["audio_minus_calls_ms"] = res["audio"]["median_ms"] - c
 res["frames_per_s_dense"] = n_calls * n_frames / (d * 1e-3)
 res["frames_per_s_calls"] = n_calls * n_frames / (c * 1e-3)
 # every call has the same records, so the launch's time divides by record position: a position that is not speech costs what
@@ -110,6 +130,8 @@ res["frames_per_s_calls"] = n_calls * n_frames / (c * 1e-3)
 res["us_per_speech_position"] = c * 1e3 / n_rec
 res["us_per_zero_position"] = (h - c / 2) * 1e3 / (n_rec / 2)
 print("calls - dense: %+.3f ms (%.2f %% of dense; spread of dense %.3f ms)" % (c - d, 100 * (c - d) / d, res["dense"]["spread_ms"]))
+print("audio - calls: %+.3f ms (%.2f %% of calls; spread of calls %.3f ms)" %
+      (res["audio_minus_calls_ms"], 100 * res["audio_minus_calls_ms"] / c, res["calls"]["spread_ms"]))
 print("of the launch's time, a record position takes %.1f us where it is speech and %.2f us where it is not" %
       (res["us_per_speech_position"], res["us_per_zero_position"]))
 print(json.dumps(res))
