@@ -3,12 +3,16 @@
 //   TCH3 (gmr1_rx.c:836-841, 881): in each frame the CCCH's IMMEDIATE ASSIGNMENT re-initialises the call first, then rx_tch3
 //   runs if a call is active, on the current timeslot; burst_map refuses a window that leaves the carrier.
 //   TCH9 (gmr1_rx.c:248-258, 262-353): ASSIGNMENT COMMAND 1 on the FACCH3 activates and re-initialises the interleaver, then
-//   rx_tch9 runs in that very frame; sync sequence 0 is a FACCH9, anything else a TCH9 burst that advances the interleaver.
+//   rx_tch9 runs in that very frame; sync sequence 0 is a FACCH9, anything else a TCH9 burst that advances the interleaver
+//   (restated in rx_tch9_ref.h, which the streaming planner's test shares).  Held against it: the one-shot call's planner,
+//   and tch9_plan_push with nothing carried in followed by the call follower's routing (tch9_follow.h) over every segment.
 // tests/test_rx_follow_host.py builds and runs it (once more under the address and undefined-behaviour sanitizers).
 #include <cstdio>
 #include <vector>
 
 #include "rx_follow.h"
+#include "rx_tch9_ref.h"
+#include "tch9_follow.h"
 
 using namespace gmr1;
 
@@ -33,15 +37,7 @@ std::vector<FrameCtx> make_log(int n, int a0, int sps)
 	return log;
 }
 
-// burst_map (gmr1_rx.c:149-170) of a burst of `syms` symbols with sps + sps / 2 samples of search room: the window or nothing
-bool burst_window(int align, int sps, int tn, int syms, int len, long long *begin, bool *past_end)
-{
-	const int win = sps + sps / 2, etoa = win >> 1;
-	*begin = (long long)align + (long long)sps * tn * 39 - etoa;
-	const long long in_len = (long long)syms * sps + win;
-	*past_end = *begin + in_len > len;
-	return *begin >= 0 && !*past_end;
-}
+using ref9::burst_window;
 
 // gmr1_rx's frame loop over one call: the items, and whether a window ran past the end of the carrier
 std::vector<Tch3Item> ref_tch3(int q, const Call &c, int sps, bool *past)
@@ -223,71 +219,128 @@ struct Chain9 {
 	int len = 0;
 };
 
-// gmr1_rx's frame loop over the chains' TCH9 follow-up.  The plan's first half is checked against the frames it maps, then
-// sid / rv of every mapped frame (`draw`) decide what the second half must say.
+// Both ways the library has of following a whole capture's TCH9 calls against the reference's frame loop (rx_tch9_ref.h):
+// what the one-shot call runs, tch9_plan_items / tch9_plan_jobs; and what a push runs, here over the whole log --
+// tch9_plan_push with nothing carried in and no horizon, then the follower's routing (tch9_follow.h) over every segment
+// from a fresh state, 64 frames a step as the device walks it.  sid / rv of every mapped frame are drawn from sid_in /
+// rv_in.  *items_out: the items; *jobs_out: the FACCH9 frames, the TCH9 frames and their positions -- the same from the
+// one-shot planner and from the routing (a TCH9 frame's position there: one more than its s1's, 0 where s1 is zeros).
 int check_tch9(const std::vector<Chain9> &chains, int sps, const std::vector<int> &sid_in, const std::vector<int> &rv_in,
-               std::vector<Nt9Item> *items_out, Tch9Jobs *jobs_out)
+               std::vector<Nt9Item> *items_out, ref9::Jobs *jobs_out)
 {
-	std::vector<Nt9Item> items;
-	for (size_t ci = 0; ci < chains.size(); ci++)
-		tch9_plan_items((int)ci, chains[ci].log, chains[ci].events9, chains[ci].len, sps, &items);
+	std::vector<ref9::Chain> rc;
+	std::vector<Tch9PushCall> pc;
+	for (const Chain9 &c : chains) {
+		rc.push_back({&c.log, &c.events9, c.len});
+		pc.push_back({&c.log, &c.events9, Tch9CallCarry(), c.len});
+	}
+	const std::vector<ref9::Frame> want = ref9::frames(rc, sps);
+	Tch9PushPlan plan;
+	CHECK(tch9_plan_push(pc, sps, false, &plan));
+	// the items are the reference's mapped frames, in order, each in the segment of the command in force
+	const std::vector<Nt9Item> &items = plan.items;
+	CHECK(items.size() == want.size());
+	for (size_t k = 0; k < want.size(); k++) {
+		const Chain9 &c = chains[(size_t)want[k].chain];
+		CHECK(items[k].chain == want[k].chain && items[k].frame == want[k].frame && items[k].tn == want[k].tn);
+		CHECK(want[k].begin == rx_tch9_begin(c.log[(size_t)want[k].frame].align, sps, want[k].tn) &&
+		      want[k].begin + rx_tch9_in_len(sps) <= c.len);
+		CHECK(items[k].ass >= 0 && items[k].ass < (int)plan.segs.size());
+		const Tch9Seg &sg = plan.segs[(size_t)items[k].ass];
+		CHECK(sg.chain == want[k].chain && sg.ev == want[k].run + 1 && sg.tn == want[k].tn);
+		CHECK(sg.first <= k && (items[k].ass + 1 == (int)plan.segs.size() || k < plan.segs[(size_t)items[k].ass + 1].first));
+	}
+	// no call is carried in, a segment per command, chain by chain
+	size_t n_cmd = 0;
+	for (size_t ci = 0; ci < chains.size(); ci++) {
+		n_cmd += chains[ci].events9.size();
+		CHECK(plan.carry[ci].assigned == !chains[ci].events9.empty());
+	}
+	CHECK(plan.segs.size() == n_cmd);
 	std::vector<int32_t> sid(items.size()), rv(items.size());
 	for (size_t k = 0; k < items.size(); k++) {
 		sid[k] = sid_in.empty() ? 0 : sid_in[k % sid_in.size()];
 		rv[k] = rv_in.empty() ? 0 : rv_in[k % rv_in.size()];
 	}
-	const Tch9Jobs jobs = tch9_plan_jobs(items, sid.data(), rv.data());
-	// the reference
-	std::vector<int> facch, tch, pos;
-	size_t k = 0;
-	for (size_t ci = 0; ci < chains.size(); ci++) {
-		const Chain9 &c = chains[ci];
-		bool active = false;
-		int tn = 0, il = 0;
-		for (int f = 0; f < (int)c.log.size(); f++) {
-			for (const AssEvt &e : c.events9)
-				if (e.frame == f) {                       // rx_tch3 -> rx_tch9_init: activate, timeslot, gmr1_interleaver_init
-					active = true;
-					tn = e.tn;
-					il = 0;
-				}
-			if (!active)
-				continue;
-			long long begin;
-			bool pe;
-			if (!burst_window(c.log[f].align, sps, tn, 351, c.len, &begin, &pe))
-				continue;
-			CHECK(k < items.size());
-			CHECK(items[k].chain == (int)ci && items[k].frame == f && items[k].tn == tn);
-			CHECK(begin == rx_tch9_begin(c.log[f].align, sps, tn) && begin + rx_tch9_in_len(sps) <= c.len);
-			if (!rv[k]) {
-				if (sid[k] == 0) {
-					facch.push_back((int)k);
-				} else {
-					tch.push_back((int)k);
-					pos.push_back(il++);                  // gmr1_deinterleave_inter advances on TCH9 bursts only
-				}
-			}
-			k++;
+	const ref9::Jobs ref = ref9::jobs(want, sid, rv);
+	// the one-shot planner: the same frames, each under the command in force, and the reference's jobs and positions
+	{
+		std::vector<Nt9Item> one;
+		for (size_t ci = 0; ci < chains.size(); ci++)
+			tch9_plan_items((int)ci, chains[ci].log, chains[ci].events9, chains[ci].len, sps, &one);
+		CHECK(one.size() == want.size());
+		for (size_t k = 0; k < want.size(); k++)
+			CHECK(one[k].chain == want[k].chain && one[k].frame == want[k].frame && one[k].tn == want[k].tn && one[k].ass == want[k].run);
+		const Tch9Jobs jobs = tch9_plan_jobs(one, sid.data(), rv.data());
+		CHECK(jobs.facch == ref.facch && jobs.tch == ref.tch);
+		CHECK(jobs.pos.size() == ref.pos.size());
+		for (size_t i = 0; i < ref.pos.size(); i++)
+			CHECK(jobs.pos[i] == ref.pos[i]);
+		// the two lists merge back into frame order by item index: every burst once, ascending
+		size_t a = 0, b = 0;
+		int prev = -1;
+		while (a < jobs.facch.size() || b < jobs.tch.size()) {
+			const bool take_f = b >= jobs.tch.size() || (a < jobs.facch.size() && jobs.facch[a] < jobs.tch[b]);
+			const int i = take_f ? jobs.facch[a++] : jobs.tch[b++];
+			CHECK(i > prev && !rv[(size_t)i] && (sid[(size_t)i] == 0) == take_f);
+			prev = i;
 		}
 	}
-	CHECK(k == items.size());
-	CHECK(jobs.facch == facch && jobs.tch == tch);
-	CHECK(jobs.pos.size() == pos.size());
-	for (size_t i = 0; i < pos.size(); i++)
-		CHECK(jobs.pos[i] == pos[i]);
-	// the two lists merge back into frame order by item index: every burst once, ascending
-	size_t a = 0, b = 0;
-	int prev = -1;
-	while (a < facch.size() || b < tch.size()) {
-		const bool take_f = b >= tch.size() || (a < facch.size() && jobs.facch[a] < jobs.tch[b]);
-		const int i = take_f ? jobs.facch[a++] : jobs.tch[b++];
-		CHECK(i > prev && !rv[i] && (sid[i] == 0) == take_f);
-		CHECK(prev < 0 || items[i].chain > items[prev].chain || (items[i].chain == items[prev].chain && items[i].frame > items[prev].frame));
-		prev = i;
+	// the follower over each segment: rx_tch9_init's state (active, nothing held), then k_tch9f_plan's steps
+	std::vector<int> cls(items.size(), -1), s1(items.size(), 0), s2(items.size(), 0);
+	for (size_t q = 0; q < plan.segs.size(); q++) {
+		const int k0 = (int)plan.segs[q].first, k1 = q + 1 < plan.segs.size() ? (int)plan.segs[q + 1].first : (int)items.size();
+		Tch9Carry carry = tch9f_seed(0);
+		for (int kb = k0; kb < k1; kb += 64) {
+			unsigned long long tch = 0;
+			for (int lane = 0; lane < 64 && kb + lane < k1; lane++) {
+				cls[(size_t)(kb + lane)] = tch9f_class(1, rv[(size_t)(kb + lane)], sid[(size_t)(kb + lane)]);
+				if (cls[(size_t)(kb + lane)] == kT9Tch)
+					tch |= 1ull << lane;
+			}
+			for (int lane = 0; lane < 64 && kb + lane < k1; lane++) {
+				const Tch9Carry s = tch9f_sources(tch, lane, kb, carry);
+				s1[(size_t)(kb + lane)] = s.s1;
+				s2[(size_t)(kb + lane)] = s.s2;
+			}
+			carry = tch9f_sources(tch, 64, kb, carry);
+		}
 	}
+	// a frame's class is FACCH9, TCH9 or error exactly where the reference says, and it asks for that decode
+	ref9::Jobs got;
+	size_t a = 0, b = 0;
+	std::vector<int> pos_of(items.size(), -1);
+	std::vector<int> seg_tch;                                // the TCH9 frames of the segment so far
+	for (size_t k = 0; k < items.size(); k++) {
+		if (!k || items[k].ass != items[k - 1].ass)
+			seg_tch.clear();
+		const bool is_f = a < ref.facch.size() && ref.facch[a] == (int)k, is_t = b < ref.tch.size() && ref.tch[b] == (int)k;
+		CHECK(cls[k] == (is_f ? kT9Facch : is_t ? kT9Tch : kT9Err));
+		CHECK((cls[k] == kT9Err) == (rv[k] != 0));
+		CHECK(tch9f_need(cls[k]) == (is_f ? kT9NeedFacch : is_t ? kT9NeedTch : kT9NeedNone));
+		if (is_f) {
+			got.facch.push_back((int)k);
+			a++;
+		}
+		if (!is_t)
+			continue;
+		// at reference position pos: the previous two TCH9 frames of the same segment, zeros in front of the run's first
+		const int pos = ref.pos[b++];
+		CHECK(pos == (int)seg_tch.size());
+		CHECK(s1[k] == (pos < 1 ? kT9SrcZeros : seg_tch[(size_t)pos - 1]));
+		CHECK(s2[k] == (pos < 2 ? kT9SrcZeros : seg_tch[(size_t)pos - 2]));
+		pos_of[k] = s1[k] == kT9SrcZeros ? 0 : pos_of[(size_t)s1[k]] + 1;
+		got.tch.push_back((int)k);
+		got.pos.push_back(pos_of[k]);
+		seg_tch.push_back((int)k);
+	}
+	CHECK(a == ref.facch.size() && b == ref.tch.size());
+	CHECK(got.facch == ref.facch && got.tch == ref.tch && got.pos == ref.pos);
+	// the big records come out in item order: chain by chain, and within a chain frame by frame
+	for (size_t k = 1; k < items.size(); k++)
+		CHECK(items[k].chain > items[k - 1].chain || (items[k].chain == items[k - 1].chain && items[k].frame > items[k - 1].frame));
 	if (items_out) *items_out = items;
-	if (jobs_out) *jobs_out = jobs;
+	if (jobs_out) *jobs_out = got;
 	return 0;
 }
 
@@ -295,7 +348,7 @@ int tch9_cases(int sps)
 {
 	const int fl = sps * 24 * 39, n = 24, a0 = 5000 * sps;
 	std::vector<Nt9Item> items;
-	Tch9Jobs jobs;
+	ref9::Jobs jobs;
 	Chain9 c;
 	c.log = make_log(n, a0, sps);
 	c.len = a0 + (n + 3) * fl;

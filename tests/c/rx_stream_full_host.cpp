@@ -1,12 +1,13 @@
 // Host-side check of what lets the streaming receive loop follow TCH9 data calls (osmo-gmr_amd/csrc/rx_follow.h,
-// rx_stream.h): tch9_plan_push over a frame log cut into pushes gives, concatenated, the items of the
-// one-shot rules tch9_plan_items / tch9_plan_jobs on the whole log, with a new segment exactly where the command in force
-// changes; the NT9 window of a frame the walk admitted lies inside the samples held; the big-record bound.
+// rx_stream.h): tch9_plan_push over a frame log cut into pushes gives, concatenated, the frames the
+// reference's own frame loop maps on the whole log (restated in rx_tch9_ref.h), with a new segment exactly where the
+// command in force changes and interleaver positions that are the reference's; the NT9 window of a frame the walk admitted lies inside the samples held; the big-record bound.
 // tests/test_rx_stream_full_host.py builds and runs it, plain and under the address / undefined-behaviour sanitizers.
 #include <cstdio>
 #include <random>
 
 #include "rx_follow.h"
+#include "rx_tch9_ref.h"
 
 using namespace gmr1;
 
@@ -42,9 +43,9 @@ Capture make_capture(std::mt19937 &rng, int sps, int n_frames, const std::vector
 }
 
 // the log cut at `cuts` (ascending frame indices, all <= n_adm) and planned push by push: every item must be the
-// one-shot's, in order, and its run (the command in force, counted over the whole capture) the one-shot's `ass`
-int streamed_is_one_shot(const Capture &c, int sps, const std::vector<int> &cuts, const std::vector<Nt9Item> &want,
-                         const Tch9Jobs &want_jobs, const std::vector<int32_t> &sync_id, const std::vector<int32_t> &rv)
+// reference's, in order, and its run (the command in force, counted over the whole capture) the reference's
+int streamed_is_one_shot(const Capture &c, int sps, const std::vector<int> &cuts, const std::vector<ref9::Frame> &want,
+                         const ref9::Jobs &want_jobs, const std::vector<int32_t> &sync_id, const std::vector<int32_t> &rv)
 {
 	const int fl = rx_stream_frame_len(sps);
 	const int n = (int)c.log.size();
@@ -92,8 +93,8 @@ int streamed_is_one_shot(const Capture &c, int sps, const std::vector<int> &cuts
 			CHECK(sg.first <= k && (it.ass + 1 == (int)plan.segs.size() || k < plan.segs[it.ass + 1].first));
 			CHECK(it.tn == sg.tn);
 			const int run = sg.ev ? (int)ev_first + sg.ev - 1 : run_in;
-			CHECK(run == want[at].ass);
-			// tch9_plan_jobs: a fresh state where the run changes, the carried one otherwise
+			CHECK(run == want[at].run);
+			// a fresh state where the run changes, the carried one otherwise
 			if (run != pos_run) {
 				pos_run = run;
 				pos = 0;
@@ -130,17 +131,16 @@ int planner(int sps)
 		}                                                    // (round % 4 == 3: no command at all)
 		const Capture c = make_capture(rng, sps, n, cmds);
 		CHECK(c.n_adm >= n - 2 && c.n_adm >= 4);
-		std::vector<Nt9Item> want;
-		tch9_plan_items(0, c.log, c.ev9, c.len, sps, &want);
+		const std::vector<ref9::Frame> want = ref9::frames({{&c.log, &c.ev9, c.len}}, sps);
 		CHECK(!cmds.empty() || want.empty());
 		std::vector<int32_t> sync_id(want.size()), rv(want.size());
 		for (size_t k = 0; k < want.size(); k++) {
 			sync_id[k] = (int32_t)(rng() % 3u);
 			rv[k] = rng() % 7u == 0 ? -1 : 0;
 		}
-		const Tch9Jobs jobs = tch9_plan_jobs(want, sync_id.data(), rv.data());
-		// every window of the one-shot plan lies in the capture, and one past the end was dropped
-		for (const Nt9Item &it : want)
+		const ref9::Jobs jobs = ref9::jobs(want, sync_id, rv);
+		// every window the reference maps lies in the capture, and one past the end was dropped
+		for (const ref9::Frame &it : want)
 			CHECK(rx_tch9_begin(c.log[it.frame].align, sps, it.tn) >= 0 &&
 			      rx_tch9_begin(c.log[it.frame].align, sps, it.tn) + rx_tch9_in_len(sps) <= c.len);
 		if (streamed_is_one_shot(c, sps, {}, want, jobs, sync_id, rv)) return 1;

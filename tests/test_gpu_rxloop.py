@@ -1,10 +1,12 @@
 """GPU parity of the batched receive loop (gmr1_hip_rx_run*, reference src/gmr1_rx.c:605-895)
 against the oracle's restatement of the same loop, carrier by carrier."""
+import contextlib
 import functools
 
 import numpy as np
 import pytest
 
+import rx_stream_full_cases as cases
 import workloads
 
 pytestmark = pytest.mark.gpu
@@ -379,6 +381,46 @@ def test_rx_loop_tch9_follow_up_matches_oracle(gpu_api, orc, pkg, decoder):
     rec2, big2, _, _ = gpu_api.rx_run_full(np.concatenate(bc), np.concatenate(tc), None, offset, length, sps=SPS,
                                            kc=np.stack(kcs))
     assert len(big2) == 0 and _key_n(rec2) == _key_n(rec)
+
+
+@pytest.mark.parametrize("case, acc", [("two_slots", False), ("two_slots", True), ("sps2", None), ("sps11", None)],
+                         ids=["two_slots-generic", "two_slots-acc", "sps2", "sps11"])
+def test_rx_loop_tch9_small_captures_match_oracle(gpu_api, orc, pkg, case, acc):
+    """The captures the streaming tests (test_gpu_rx_stream_full.py) hold against the one-shot call, held against the oracle
+    themselves, so that their reference does not rest on the one-shot call alone: two commands to two timeslots on one
+    chain (both Viterbi decoder modes), and one carrier at 2 and at 11 samples per symbol -- records, big records and the
+    chain count.  The captures are judged on what the oracle finds in them; and with room for ten big records the call
+    returns the first ten."""
+    if case == "two_slots":
+        cap, sps, arfcn = cases.two_slots(pkg, orc), SPS, 7
+    else:
+        sps, arfcn = int(case[3:]), 3
+        cap = cases.at_sps(pkg, orc, sps)
+    mode = contextlib.nullcontext()
+    if acc is not None:
+        mode = contextlib.ExitStack()
+        mode.enter_context(gpu_api.conv_decoder(gpu_api.CONV_ACC if acc else gpu_api.CONV_GENERIC))
+        mode.enter_context(orc.conv_mode(1 if acc else 0))
+    x, t, c, kc = cap["x"][0], cap["t"][0], cap["c"][0], cap["kc"]
+    with mode:
+        orv, orec, obig, och = orc.rx_run_full(x, t, c, sps=sps, arfcn=arfcn, kc=kc[0])
+        if case == "two_slots":
+            per_tn = [int(np.sum(obig["tn"] == tn9)) for _, tn9 in cases.TWO_SLOTS]
+            print(case, "oracle big records per timeslot", per_tn, "of", len(obig))
+            assert min(per_tn) >= 10 and sum(per_tn) == len(obig), (per_tn, len(obig))
+        else:
+            print(case, "oracle big records", len(obig))
+            assert len(obig) > 20
+        run = lambda **kw: gpu_api.rx_run_full(x, t, c, [0], [x.size], sps=sps, arfcn=np.array([arfcn], np.uint16), kc=kc, **kw)
+        rec, big, status, chains = run()
+        assert orv == 0 and not status.any() and chains[0] == och
+        assert _key_n(rec) == _key_n(orec)
+        assert _key_big(big) == _key_big(obig)
+        if case == "two_slots":
+            # fewer slots than records: the first ten, byte for byte
+            rec10, big10, _, _ = run(max_big=10)
+            assert len(big10) == 10 and big10.tobytes() == big[:10].tobytes()
+            assert rec10.tobytes() == rec.tobytes()
 
 
 @pytest.mark.timeout(120)

@@ -1,7 +1,10 @@
 """The integer rules of the receive loop's traffic follow-ups without a GPU (osmo-gmr_amd/csrc/rx_follow.h, compiled for the
 host): which frames of which chain belong to which TCH3 assignment and invocation, what a push carries in, when a missing
-window is an error, and how a chain's NT9 bursts split into FACCH9 jobs and TCH9 interleaver runs -- against the reference's
-frame-by-frame rule restated in tests/c/rx_follow_host.cpp, at sps 1, 4 and 16.  Once plain, once under the address and
+window is an error, and how a chain's NT9 bursts split into FACCH9 jobs and TCH9 interleaver runs -- by the one-shot
+call's planner, and by tch9_plan_push with nothing carried in followed by the call follower's routing
+(osmo-gmr_amd/csrc/tch9_follow.h) over every segment: which NT9 frames are mapped, which are FACCH9, TCH9 or failed, and
+which two earlier TCH9 bursts of its interleaver run a TCH9 frame reads -- against the reference's
+frame-by-frame rule restated in tests/c/rx_follow_host.cpp and tests/c/rx_tch9_ref.h, at sps 1, 4 and 16.  Once plain, once under the address and
 undefined-behaviour sanitizers (a stand-alone program: nothing is preloaded)."""
 import os
 import shutil

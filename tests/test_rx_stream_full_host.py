@@ -1,7 +1,8 @@
 """The streaming receive loop's TCH9 follow-up without a GPU: the new entries are declared, exported and bound, refuse bad
 arguments before the device is asked for and say -ENODEV without one; and the integer rules that make a push's NT9 frames
-the one-shot call's (tch9_plan_push of osmo-gmr_amd/csrc/rx_follow.h against tch9_plan_items / tch9_plan_jobs, the window
-fit and the big-record bound of rx_stream.h; tests/c/rx_stream_full_host.cpp, compiled for the host) hold -- once plain,
+the one-shot call's (tch9_plan_push of osmo-gmr_amd/csrc/rx_follow.h, cut into pushes, against the reference's frame loop
+restated in tests/c/rx_tch9_ref.h: the frames it maps, the command in force and every TCH9 burst's interleaver position;
+the window fit and the big-record bound of rx_stream.h; tests/c/rx_stream_full_host.cpp, compiled for the host) hold -- once plain,
 once under the address and undefined-behaviour sanitizers (a stand-alone program: nothing is preloaded)."""
 import ctypes as C
 import os
