@@ -6,6 +6,7 @@ if the library is missing or no GPU is usable they raise.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import functools
 import os
@@ -1305,48 +1306,52 @@ class RxStream(_LibHandle):
     every push then takes the traffic carriers' samples as well.  full=True: it follows TCH3 and TCH9 calls (rx_run_full
     with the same kc) -- every push takes the traffic and the CSD carriers' samples and returns (records, big records).
     voice=True: it follows TCH3 calls and decodes them (rx_run_voice with the same kc) -- every push takes the traffic
-    carriers' samples and returns (records, audio blocks (RX_AUDIO[]))."""
+    carriers' samples and returns (records, audio blocks (RX_AUDIO[])).  What was asked for is `kind` ("plain", "tch",
+    "full", "voice"); everything below asks _RX_STREAM_KINDS[kind] (beside RX_BIG_RECORD, whose dtype it holds)."""
     _destroy_fn = "gmr1_hip_rx_stream_destroy"
 
     def __init__(self, n_arfcn, sps=4, arfcn=None, tch=False, kc=None, full=False, voice=False):
         self._h = C.c_void_p()
         self.n = int(n_arfcn)
-        self.full = bool(full)
-        self.voice = bool(voice)
-        if self.full and self.voice:
+        if full and voice:
             raise ValueError("a handle is made with full=True or with voice=True, not both")
-        self.tch = bool(tch) or self.full or self.voice
+        self.kind = "full" if full else "voice" if voice else "tch" if tch else "plain"
+        self._k = _RX_STREAM_KINDS[self.kind]
         self._arfcn = _arr(arfcn, np.uint16)
-        if self.tch:
-            kc = _arr(kc, np.uint8, (self.n, 8))
-            make = "gmr1_hip_rx_stream_create_full" if self.full else "gmr1_hip_rx_stream_create_voice" if self.voice else \
-                "gmr1_hip_rx_stream_create_tch"
-            _call(make, self.n, sps, _p(self._arfcn), _p(kc), C.byref(self._h))
-        else:
-            if kc is not None:
-                raise ValueError("kc belongs to a handle that follows TCH3 calls (tch=True)")
-            _call("gmr1_hip_rx_stream_create", self.n, sps, _p(self._arfcn), C.byref(self._h))
+        if not self.tch and kc is not None:
+            raise ValueError("kc belongs to a handle that follows TCH3 calls (tch=True)")
+        kc = _arr(kc, np.uint8, (self.n, 8))        # (held here until the create entry has copied the keys)
+        _call(self._k.create, self.n, sps, _p(self._arfcn), *((_p(kc),) if self.tch else ()), C.byref(self._h))
+
+    tch = property(lambda self: self._k.planes > 1, doc="follows TCH3 calls: a tch, full or voice handle")
+    full = property(lambda self: self.kind == "full")
+    voice = property(lambda self: self.kind == "voice")
+
+    def _max(self, fname, n):
+        m = C.c_int()
+        _call(fname, self._h, n, C.byref(m))
+        return m.value
 
     def max_records(self, n):
         """the most records the next push of n samples per carrier can return"""
-        m = C.c_int()
-        _call("gmr1_hip_rx_stream_max_records", self._h, n, C.byref(m))
-        return m.value
+        return self._max("gmr1_hip_rx_stream_max_records", n)
 
     def max_big(self, n):
         """the most big records the next push of n samples per carrier can return (0 unless full=True)"""
-        m = C.c_int()
-        _call("gmr1_hip_rx_stream_max_big", self._h, n, C.byref(m))
-        return m.value
+        return self._max("gmr1_hip_rx_stream_max_big", n)
 
     def max_audio(self, n):
         """the most audio blocks the next push of n samples per carrier can return (0 unless voice=True)"""
-        m = C.c_int()
-        _call("gmr1_hip_rx_stream_max_audio", self._h, n, C.byref(m))
-        return m.value
+        return self._max("gmr1_hip_rx_stream_max_audio", n)
 
     def _out(self, n, out):
         return _records(out, self.max_records(n))[0]
+
+    def _extra(self, n, given):
+        """the second array a push of n fills, the caller's own (checked) or a fresh one; None for a kind that has none"""
+        if self._k.extra is None:
+            return None
+        return _records(given, self._max(self._k.max_extra, n), self._k.extra)[0]
 
     def _kind(self, tch, csd=None):
         if self.tch and tch is None:
@@ -1358,6 +1363,14 @@ class RxStream(_LibHandle):
         if not self.full and csd is not None:
             raise ValueError("csd= belongs to a handle made with full=True")
 
+    def _push(self, fname, head, chunks, stride, n, last, out_ptr, max_records, extra=None):
+        """The one marshalling of every push entry: `head` is what the entry takes before the handle, `chunks` the addresses
+        of iq, tch and csd (as many as the entry takes), `extra` its second array or None -> (records, extra entries) written"""
+        got, got_extra = C.c_int(), C.c_int()
+        tail = () if extra is None else (extra.ctypes.data, extra.size, C.byref(got_extra))
+        _call(fname, *head, self._h, *chunks, stride, n, 1 if last else 0, out_ptr, max_records, C.byref(got), *tail)
+        return got.value, got_extra.value
+
     def push(self, iq, last=False, out=None, tch=None, csd=None):
         """host (n_arfcn, n) complex64 (and, on a tch handle, tch of the same shape; on a full handle csd as well) -> the
         records that became final (RX_RECORD[]); on a full handle (records, big records (RX_BIG_RECORD[])); on a voice handle
@@ -1366,64 +1379,31 @@ class RxStream(_LibHandle):
         iq = _arr(iq, np.complex64, (self.n, -1))
         n = iq.shape[1]
         out = self._out(n, out)
-        got = C.c_int()
-        if self.full:
-            tch, csd = _arr(tch, np.complex64, (self.n, n)), _arr(csd, np.complex64, (self.n, n))
-            big = _records(None, self.max_big(n), RX_BIG_RECORD)[0]
-            got_big = C.c_int()
-            _call("gmr1_hip_rx_stream_push_full", self._h, _p(iq), _p(tch), _p(csd), n, n, 1 if last else 0, _p(out), out.size,
-                  C.byref(got), _p(big), big.size, C.byref(got_big))
-            return out[:got.value], big[:got_big.value]
-        if self.voice:
-            tch = _arr(tch, np.complex64, (self.n, n))
-            audio = _records(None, self.max_audio(n), RX_AUDIO)[0]
-            got_audio = C.c_int()
-            _call("gmr1_hip_rx_stream_push_voice", self._h, _p(iq), _p(tch), n, n, 1 if last else 0, _p(out), out.size,
-                  C.byref(got), _p(audio), audio.size, C.byref(got_audio))
-            return out[:got.value], audio[:got_audio.value]
-        if self.tch:
-            tch = _arr(tch, np.complex64, (self.n, n))
-            _call("gmr1_hip_rx_stream_push_tch", self._h, _p(iq), _p(tch), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
-        else:
-            _call("gmr1_hip_rx_stream_push", self._h, _p(iq), n, n, 1 if last else 0, _p(out), out.size, C.byref(got))
-        return out[:got.value]
+        chunks = [iq] + [_arr(x, np.complex64, (self.n, n)) for x in (tch, csd)[:self._k.planes - 1]]
+        extra = self._extra(n, None)
+        got, got_extra = self._push(self._k.push, (), [_p(x) for x in chunks], n, n, last, _p(out), out.size, extra)
+        return out[:got] if extra is None else (out[:got], extra[:got_extra])
 
     def push_dev(self, stream, iq_ptr, iq_stride, n, last=False, out=None, tch_ptr=None, csd_ptr=None, big=None, audio=None):
         """device samples (carrier i at iq_ptr + 8 * i * iq_stride; on a tch handle its traffic samples at tch_ptr + 8 * i *
         iq_stride, on a full handle its CSD samples at csd_ptr + 8 * i * iq_stride), read on `stream` -> the records
         (synchronous); on a full handle (records, big records), on a voice handle (records, audio blocks).
         out, big, audio: host RX_RECORD / RX_BIG_RECORD / RX_AUDIO arrays, or None; out_ptr (device / pinned) goes through
-        push_dev_raw."""
+        push_dev_raw.  (csd_ptr, big and audio are looked at only on a handle that takes them.)"""
         out = self._out(n, out)
-        if self.voice:
-            self._kind(tch_ptr)
-            audio = _records(audio, self.max_audio(n), RX_AUDIO)[0]
-            got, got_audio = C.c_int(), C.c_int()
-            _call("gmr1_hip_rx_stream_push_voice_dev", stream, self._h, iq_ptr, tch_ptr, iq_stride, n, 1 if last else 0,
-                  out.ctypes.data, out.size, C.byref(got), audio.ctypes.data, audio.size, C.byref(got_audio))
-            return out[:got.value], audio[:got_audio.value]
-        if self.full:
-            self._kind(tch_ptr, csd_ptr)
-            big = _records(big, self.max_big(n), RX_BIG_RECORD)[0]
-            got, got_big = C.c_int(), C.c_int()
-            _call("gmr1_hip_rx_stream_push_full_dev", stream, self._h, iq_ptr, tch_ptr, csd_ptr, iq_stride, n, 1 if last else 0,
-                  out.ctypes.data, out.size, C.byref(got), big.ctypes.data, big.size, C.byref(got_big))
-            return out[:got.value], big[:got_big.value]
-        got = self.push_dev_raw(stream, iq_ptr, iq_stride, n, last, out.ctypes.data, out.size, tch_ptr)
-        return out[:got]
+        self._kind(tch_ptr, csd_ptr if self.full else None)
+        extra = self._extra(n, {"big": big, "audio": audio}.get(self._k.extra_arg))
+        got, got_extra = self._push(self._k.push_dev, (stream,), (iq_ptr, tch_ptr, csd_ptr)[:self._k.planes], iq_stride, n, last,
+                                    out.ctypes.data, out.size, extra)
+        return out[:got] if extra is None else (out[:got], extra[:got_extra])
 
     def push_dev_raw(self, stream, iq_ptr, iq_stride, n, last, out_ptr, max_records, tch_ptr=None):
         """gmr1_hip_rx_stream_push_dev with a caller's record buffer (any memory rx_run_dev takes) -> records written; on a
-        tch handle gmr1_hip_rx_stream_push_tch_dev, whose record buffer is host memory"""
+        tch handle gmr1_hip_rx_stream_push_tch_dev, whose record buffer is host memory.  (A full or a voice handle has no raw
+        form: the tch entry refuses it.)"""
         self._kind(tch_ptr)
-        got = C.c_int()
-        if self.tch:
-            _call("gmr1_hip_rx_stream_push_tch_dev", stream, self._h, iq_ptr, tch_ptr, iq_stride, n, 1 if last else 0, out_ptr,
-                  max_records, C.byref(got))
-        else:
-            _call("gmr1_hip_rx_stream_push_dev", stream, self._h, iq_ptr, iq_stride, n, 1 if last else 0, out_ptr,
-                  max_records, C.byref(got))
-        return got.value
+        k = self._k if self._k.extra is None else _RX_STREAM_KINDS["tch"]
+        return self._push(k.push_dev, (stream,), (iq_ptr, tch_ptr)[:k.planes], iq_stride, n, last, out_ptr, max_records)[0]
 
     def status(self):
         """(status[n], n_chains[n], retained[n]) per carrier"""
@@ -1577,6 +1557,21 @@ RX_BIG_RECORD = np.dtype([("arfcn", "<u2"), ("chain", "u1"), ("type", "u1"), ("f
                           ("tn", "u1"), ("crc", "u1"), ("len", "u1"), ("pad", "u1"),
                           ("conv", "<i4"), ("l2", "u1", (64,))])
 assert RX_BIG_RECORD.itemsize == 80
+
+
+# What RxStream needs to know of a kind of handle, once: its create and push entries, the carriers a push brings, and --
+# for a kind whose push returns a second array -- that array's dtype, the entry that bounds it and the push_dev keyword
+# that takes a caller's own.  (It stands here, below the class, because the dtypes do.)
+_RxStreamKind = collections.namedtuple("_RxStreamKind", ["create", "push", "push_dev", "planes", "extra", "max_extra", "extra_arg"],
+                                       defaults=[None, None, None])      # (no second array)
+_RX_STREAM_KINDS = {
+    "plain": _RxStreamKind("gmr1_hip_rx_stream_create", "gmr1_hip_rx_stream_push", "gmr1_hip_rx_stream_push_dev", 1),
+    "tch": _RxStreamKind("gmr1_hip_rx_stream_create_tch", "gmr1_hip_rx_stream_push_tch", "gmr1_hip_rx_stream_push_tch_dev", 2),
+    "full": _RxStreamKind("gmr1_hip_rx_stream_create_full", "gmr1_hip_rx_stream_push_full", "gmr1_hip_rx_stream_push_full_dev", 3,
+                          RX_BIG_RECORD, "gmr1_hip_rx_stream_max_big", "big"),
+    "voice": _RxStreamKind("gmr1_hip_rx_stream_create_voice", "gmr1_hip_rx_stream_push_voice", "gmr1_hip_rx_stream_push_voice_dev", 2,
+                           RX_AUDIO, "gmr1_hip_rx_stream_max_audio", "audio"),
+}
 
 
 def rx_run_full(iq, tch, csd, offset, length, sps=4, arfcn=None, kc=None, max_records=1 << 16, max_big=1 << 14):

@@ -311,43 +311,60 @@ int RxRun::frame_loop()
 
 namespace {
 
-// gmr1_hip_rx_run_full_dev, plus (optional) how many of the records each carrier contributed
-int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const float *tch,
-                     const float *csd, const uint64_t *offset, const uint64_t *length,
-                     const uint16_t *arfcn, const uint8_t *kc,
-                     struct gmr1_hip_rx_record *out, int max_records, int *n_records,
-                     struct gmr1_hip_rx_big_record *big_out, int max_big, int *n_big,
-                     int32_t *status, int32_t *n_chains, int32_t *rec_per_carrier,
-                     bool want_audio = false, struct gmr1_hip_rx_audio *audio_out = nullptr, int max_audio = 0, int *n_audio = nullptr)
+// What one device-form call hands in: the arguments of gmr1_hip_rx_run_full_dev under their names, plus what only some
+// entries have, in the order the entries name them.  Everything is device memory but the outputs named otherwise in gmr1_hip.h.
+struct RxRunCall {
+	void *stream = nullptr;
+	int n_arfcn = 0, sps = 0;
+	const float *iq = nullptr, *tch = nullptr, *csd = nullptr;
+	const uint64_t *offset = nullptr, *length = nullptr;
+	const uint16_t *arfcn = nullptr;
+	const uint8_t *kc = nullptr;
+	gmr1_hip_rx_record *out = nullptr;
+	int max_records = 0;
+	int *n_records = nullptr;
+	gmr1_hip_rx_big_record *big_out = nullptr;
+	int max_big = 0;
+	int *n_big = nullptr;
+	int32_t *status = nullptr, *n_chains = nullptr;
+	int32_t *rec_per_carrier = nullptr;          // optional: how many of the records each carrier contributed
+	bool want_audio = false;                     // gmr1_hip_rx_run_voice*: the audio outputs are required
+	gmr1_hip_rx_audio *audio_out = nullptr;
+	int max_audio = 0;
+	int *n_audio = nullptr;
+};
+
+// every one-shot entry
+int rx_run_full_impl(const RxRunCall &c)
 {
-	hipStream_t st = (hipStream_t)stream_;
-	if (n_records) *n_records = 0;
-	if (n_big) *n_big = 0;
-	if (n_audio) *n_audio = 0;
-	if (want_audio && (!n_audio || max_audio < 0 || (max_audio > 0 && !audio_out)))
+	hipStream_t st = (hipStream_t)c.stream;
+	if (c.n_records) *c.n_records = 0;
+	if (c.n_big) *c.n_big = 0;
+	if (c.n_audio) *c.n_audio = 0;
+	if (c.want_audio && (!c.n_audio || c.max_audio < 0 || (c.max_audio > 0 && !c.audio_out)))
 		return fail(-EINVAL, "rx_run_voice: n_audio (and audio_out when max_audio > 0) are required, and no negative count");
-	if (csd && (!tch || !n_big || max_big < 0 || (max_big > 0 && !big_out)))
+	if (c.csd && (!c.tch || !c.n_big || c.max_big < 0 || (c.max_big > 0 && !c.big_out)))
 		return fail(-EINVAL, "rx_run: the CSD carrier needs the traffic carrier and the big-record outputs");
-	if (n_arfcn < 0 || !iq || !offset || !length || !n_records || (max_records > 0 && !out) || max_records < 0)
+	if (c.n_arfcn < 0 || !c.iq || !c.offset || !c.length || !c.n_records || (c.max_records > 0 && !c.out) || c.max_records < 0)
 		return fail(-EINVAL, "rx_run: iq/offset/length/n_records (and out when max_records > 0) are required");
-	if (sps < 1 || sps > 16)                  // gmr1_rx.c:919-922
-		return fail(-EINVAL, "rx_run: sps=%d unsupported (1..16)", sps);
+	if (c.sps < 1 || c.sps > 16)                  // gmr1_rx.c:919-922
+		return fail(-EINVAL, "rx_run: sps=%d unsupported (1..16)", c.sps);
 	DevState *ds;
 	int r = dev_state(&ds);
 	if (r) return r;
-	if (n_arfcn == 0) return 0;
+	if (c.n_arfcn == 0) return 0;
 	// the whole call holds the device's workspace, the loop's side stream and its events: calls from other threads wait
 	WsLease lease;
 	if ((r = lease.acquire(ds, st))) return r;
-	for (int i = 0; i < n_arfcn; i++)
-		if (length[i] > 0x7fffffffull)
+	for (int i = 0; i < c.n_arfcn; i++)
+		if (c.length[i] > 0x7fffffffull)
 			return fail(-EINVAL, "rx_run: carrier %d longer than 2^31-1 samples", i);
 
-	RxRun run(st, sps, iq, tch, csd, n_arfcn, offset, length, arfcn, kc, out, max_records);
+	RxRun run(st, c.sps, c.iq, c.tch, c.csd, c.n_arfcn, c.offset, c.length, c.arfcn, c.kc, c.out, c.max_records);
 	RxVoice voice;
-	if (want_audio && tch) {
-		voice.out = audio_out;
-		voice.max_out = max_audio;
+	if (c.want_audio && c.tch) {
+		voice.out = c.audio_out;
+		voice.max_out = c.max_audio;
 		run.voice = &voice;
 	}
 	const auto t0 = RxClock::now();
@@ -355,8 +372,8 @@ int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const
 	const auto t1 = RxClock::now();
 	if ((r = run.frame_loop())) return r;
 	const auto t2 = RxClock::now();
-	if (tch && (r = run.tch3_pass())) return r;
-	if (csd && (r = tch9_follow_chains(st, sps, csd, arfcn, kc, run.chains, run.walks))) return r;
+	if (c.tch && (r = run.tch3_pass())) return r;
+	if (c.csd && (r = tch9_follow_chains(st, c.sps, c.csd, c.arfcn, c.kc, run.chains, run.walks))) return r;
 	const double t_acq = us_between(t0, t1), t_loop = us_between(t1, t2), t_tch = us_since(t2);
 	const double chain = run.t_chain_us > 0 ? run.t_chain_us : run.t_loop_gpu_us;
 	t_last_timing[0] = t_acq;                                   // FCCH acquisition incl. the chains set up from its result
@@ -371,26 +388,26 @@ int rx_run_full_impl(void *stream_, int n_arfcn, int sps, const float *iq, const
 
 	// ---- hand back: carriers in order, chains in order, frames in order -------------------------
 	// (a direct run's records are already in the caller's buffer, in this very order: k_rx_pack)
-	*n_records = run.direct ? run.direct_total : rx_hand_back(run.walks, out, max_records);
-	if (n_audio) *n_audio = voice.found;
-	if (n_big) {
+	*c.n_records = run.direct ? run.direct_total : rx_hand_back(run.walks, c.out, c.max_records);
+	if (c.n_audio) *c.n_audio = voice.found;
+	if (c.n_big) {
 		int tb = 0;
 		for (const RxWalk &w : run.walks)
 			for (const gmr1_hip_rx_big_record &rec : w.big) {
-				if (tb < max_big)
-					big_out[tb] = rec;
+				if (tb < c.max_big)
+					c.big_out[tb] = rec;
 				tb++;
 			}
-		*n_big = tb;
+		*c.n_big = tb;
 	}
-	for (int i = 0; i < n_arfcn; i++) {
-		if (status) status[i] = run.stat[i];
-		if (n_chains) n_chains[i] = run.nch[i];
-		if (rec_per_carrier) rec_per_carrier[i] = 0;
+	for (int i = 0; i < c.n_arfcn; i++) {
+		if (c.status) c.status[i] = run.stat[i];
+		if (c.n_chains) c.n_chains[i] = run.nch[i];
+		if (c.rec_per_carrier) c.rec_per_carrier[i] = 0;
 	}
-	if (rec_per_carrier)
+	if (c.rec_per_carrier)
 		for (size_t ci = 0; ci < run.walks.size(); ci++)
-			rec_per_carrier[run.chains[ci].a] += run.direct ? run.walks[ci].n_rec : (int)run.walks[ci].rec.size();
+			c.rec_per_carrier[run.chains[ci].a] += run.direct ? run.walks[ci].n_rec : (int)run.walks[ci].rec.size();
 	return 0;
 }
 
@@ -401,10 +418,33 @@ int rx_run_dev_counted(void *stream, int n_arfcn, int sps, const float *iq, cons
                        const uint16_t *arfcn, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
                        int32_t *status, int32_t *n_chains, int32_t *rec_per_carrier)
 {
-	return rx_run_full_impl(stream, n_arfcn, sps, iq, nullptr, nullptr, offset, length, arfcn, nullptr, out, max_records, n_records,
-	                        nullptr, 0, nullptr, status, n_chains, rec_per_carrier);
+	return rx_run_full_impl({.stream = stream, .n_arfcn = n_arfcn, .sps = sps, .iq = iq, .offset = offset, .length = length, .arfcn = arfcn,
+	                         .out = out, .max_records = max_records, .n_records = n_records, .status = status, .n_chains = n_chains,
+	                         .rec_per_carrier = rec_per_carrier});
 }
 }  // namespace gmr1
+
+namespace {
+
+// what the host forms do before their device form: the carriers lie inside iq_len, and iq / tch / csd (each iq_len
+// samples, or NULL; csd itself may be NULL: the entry has none) go to the device, their device copies put in their place
+int rx_run_stage_in(Stage &sg, int n_arfcn, uint64_t iq_len, const uint64_t *offset, const uint64_t *length, const float **iq,
+                    const float **tch, const float **csd)
+{
+	DevState *ds;
+	int r = dev_state(&ds);
+	if (r) return r;
+	if (n_arfcn < 0 || !*iq || !offset || !length)
+		return fail(-EINVAL, "rx_run: iq/offset/length are required");
+	for (int i = 0; i < n_arfcn; i++)
+		if (offset[i] + length[i] > iq_len)
+			return fail(-EINVAL, "rx_run: carrier %d runs past the end of iq", i);
+	for (const float **x : {iq, tch, csd})
+		if (x) *x = sg.in(*x, (size_t)iq_len * 2);
+	return sg.err();
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -424,8 +464,9 @@ int gmr1_hip_rx_run_full_dev(void *stream_, int n_arfcn, int sps, const float *i
                              struct gmr1_hip_rx_big_record *big_out, int max_big, int *n_big,
                              int32_t *status, int32_t *n_chains)
 {
-	return rx_run_full_impl(stream_, n_arfcn, sps, iq, tch, csd, offset, length, arfcn, kc, out, max_records, n_records,
-	                        big_out, max_big, n_big, status, n_chains, nullptr);
+	return rx_run_full_impl({.stream = stream_, .n_arfcn = n_arfcn, .sps = sps, .iq = iq, .tch = tch, .csd = csd, .offset = offset,
+	                         .length = length, .arfcn = arfcn, .kc = kc, .out = out, .max_records = max_records, .n_records = n_records,
+	                         .big_out = big_out, .max_big = max_big, .n_big = n_big, .status = status, .n_chains = n_chains});
 }
 
 int gmr1_hip_rx_run_tch_dev(void *stream, int n_arfcn, int sps, const float *iq, const float *tch,
@@ -445,8 +486,9 @@ int gmr1_hip_rx_run_voice_dev(void *stream, int n_arfcn, int sps, const float *i
                               int32_t *status, int32_t *n_chains,
                               struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
 {
-	return rx_run_full_impl(stream, n_arfcn, sps, iq, tch, nullptr, offset, length, arfcn, kc, out, max_records,
-	                        n_records, nullptr, 0, nullptr, status, n_chains, nullptr, true, audio_out, max_audio, n_audio);
+	return rx_run_full_impl({.stream = stream, .n_arfcn = n_arfcn, .sps = sps, .iq = iq, .tch = tch, .offset = offset, .length = length,
+	                         .arfcn = arfcn, .kc = kc, .out = out, .max_records = max_records, .n_records = n_records, .status = status,
+	                         .n_chains = n_chains, .want_audio = true, .audio_out = audio_out, .max_audio = max_audio, .n_audio = n_audio});
 }
 
 int gmr1_hip_rx_run_voice(int n_arfcn, int sps, const float *iq, const float *tch, uint64_t iq_len,
@@ -459,19 +501,10 @@ int gmr1_hip_rx_run_voice(int n_arfcn, int sps, const float *iq, const float *tc
 	if (n_audio) *n_audio = 0;
 	if (!n_audio || max_audio < 0 || (max_audio > 0 && !audio_out))
 		return fail(-EINVAL, "rx_run_voice: n_audio (and audio_out when max_audio > 0) are required, and no negative count");
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if (n_arfcn < 0 || !iq || !offset || !length)
-		return fail(-EINVAL, "rx_run: iq/offset/length are required");
-	for (int i = 0; i < n_arfcn; i++)
-		if (offset[i] + length[i] > iq_len)
-			return fail(-EINVAL, "rx_run: carrier %d runs past the end of iq", i);
 	Stage sg;
-	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
-	const float *d_tch = sg.in(tch, (size_t)iq_len * 2);
-	if ((r = sg.err())) return r;
-	return gmr1_hip_rx_run_voice_dev(nullptr, n_arfcn, sps, d_iq, d_tch, offset, length, arfcn, kc, out, max_records, n_records,
+	const int r = rx_run_stage_in(sg, n_arfcn, iq_len, offset, length, &iq, &tch, nullptr);
+	if (r) return r;
+	return gmr1_hip_rx_run_voice_dev(nullptr, n_arfcn, sps, iq, tch, offset, length, arfcn, kc, out, max_records, n_records,
 	                                 status, n_chains, audio_out, max_audio, n_audio);
 }
 
@@ -483,20 +516,10 @@ int gmr1_hip_rx_run_full(int n_arfcn, int sps, const float *iq, const float *tch
 {
 	if (n_records) *n_records = 0;
 	if (n_big) *n_big = 0;
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if (n_arfcn < 0 || !iq || !offset || !length)
-		return fail(-EINVAL, "rx_run: iq/offset/length are required");
-	for (int i = 0; i < n_arfcn; i++)
-		if (offset[i] + length[i] > iq_len)
-			return fail(-EINVAL, "rx_run: carrier %d runs past the end of iq", i);
 	Stage sg;
-	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
-	const float *d_tch = sg.in(tch, (size_t)iq_len * 2);
-	const float *d_csd = sg.in(csd, (size_t)iq_len * 2);
-	if ((r = sg.err())) return r;
-	return gmr1_hip_rx_run_full_dev(nullptr, n_arfcn, sps, d_iq, d_tch, d_csd, offset, length, arfcn, kc, out, max_records,
+	const int r = rx_run_stage_in(sg, n_arfcn, iq_len, offset, length, &iq, &tch, &csd);
+	if (r) return r;
+	return gmr1_hip_rx_run_full_dev(nullptr, n_arfcn, sps, iq, tch, csd, offset, length, arfcn, kc, out, max_records,
 	                                n_records, big_out, max_big, n_big, status, n_chains);
 }
 

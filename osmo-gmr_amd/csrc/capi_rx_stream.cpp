@@ -10,8 +10,12 @@
 // horizon adds is a stop that the next push may lift (rx_stream_next_done).  A carrier then keeps its samples from
 // rx_stream_keep_from(min chain align): no window of the next walk starts before that (rx_stream_reach_back).
 //
-// A handle made by gmr1_hip_rx_stream_create_tch also follows TCH3 calls (gmr1_hip_rx_run_tch over pushes).  It holds the
-// traffic carrier's samples in a second ping-pong pair with the first one's stride, held and keep (k_rx_stage_copy), one
+// What a handle follows is its `kind`, and the kind's one description (RxStreamKind, rx_stream.h) is what the handle, the
+// entries and the checks ask: how many carriers a push brings -- the handle holds one ping-pong pair per such carrier,
+// plane[0] the BCCH carrier's, plane[1] the traffic carrier's, plane[2] the CSD carrier's, all with the first one's stride,
+// held and keep (k_rx_stage_copy) -- and which follow-ups run behind the walk.
+//
+// A handle made by gmr1_hip_rx_stream_create_tch also follows TCH3 calls (gmr1_hip_rx_run_tch over pushes).  It holds one
 // struct gmr1_hip_tch3_state per chain in device memory and, on the host, each chain's assigned timeslot.  A push walks the
 // chains with the frame log on, then hands this push's frames to tch3_follow_chains (capi_rx_follow.cpp) -- the one-shot
 // pass's own rule for frames, assignments and windows -- on those states: the call a push leaves is the call the next one
@@ -19,15 +23,15 @@
 // (DESIGN.md 4.4b).  The handle keeps chains, never walks: what a push found reaches the next one only through the device
 // states and `carry`.
 //
-// A handle made by gmr1_hip_rx_stream_create_full follows TCH9 data calls as well (gmr1_hip_rx_run_full over pushes): a
-// third ping-pong pair for the CSD carrier, one struct gmr1_hip_tch9_state per chain in device memory and the timeslot of
+// A handle made by gmr1_hip_rx_stream_create_full follows TCH9 data calls as well (gmr1_hip_rx_run_full over pushes): the
+// CSD carrier's samples, one struct gmr1_hip_tch9_state per chain in device memory and the timeslot of
 // each chain's last ASSIGNMENT COMMAND 1 on the host (`carry9`).  tch3_follow_chains notes this push's commands, and
 // tch9_follow_push (capi_rx_follow.cpp) follows them through the batched TCH9 call follower in one invocation.
 //
 // A handle made by gmr1_hip_rx_stream_create_voice is a tch handle that also decodes the calls it follows
 // (gmr1_hip_rx_run_voice over pushes): one AMBE decoder state per chain in device memory beside d_tstate and each chain's
 // count of assignments on the host (`n_assigned`), handed to tch3_follow_chains as an RxVoice; a push's audio blocks come
-// back beside its records.  It brings two carriers a push, as a tch handle does: rx_stream_planes (rx_stream.h).
+// back beside its records.  It brings two carriers a push, as a tch handle does.
 
 #include "fcch_acq.h"
 #include "rx_run.h"
@@ -53,7 +57,8 @@ struct gmr1_hip_rx_stream {
 	std::vector<int> rebased;            // per carrier: 1 once samples were dropped
 	std::vector<RxChain> chains;         // host mirror of the chains (carrier by carrier, chain by chain)
 	std::vector<int> c0;                 // per carrier: its first chain (A + 1 entries, all 0 until the acquisition)
-	float2 *buf[2] = {nullptr, nullptr};
+	int kind = kRxStreamPlain;           // what it follows; everything that depends on it asks what()
+	float2 *plane[kRxStreamMaxPlanes][2] = {};     // per carrier a push brings (what().planes of them): its ping-pong pair
 	int cur = 0;
 	long long stride = 0;                // samples per carrier in each buffer (a multiple of kRxKeepAlign)
 	RxLoopState *d_state = nullptr;
@@ -65,26 +70,23 @@ struct gmr1_hip_rx_stream {
 	size_t h_in_bytes = 0;
 	float *d_in = nullptr;
 	size_t d_in_bytes = 0;
-	// a handle that follows TCH3 calls (gmr1_hip_rx_stream_create_tch)
-	bool tch = false;
-	std::vector<uint8_t> kc;             // A x 8 (empty: the all-zero key)
-	float2 *tbuf[2] = {nullptr, nullptr};          // the traffic carrier's samples: buf's layout, stride, held and keep
+	std::vector<uint8_t> kc;             // a handle that follows calls: A x 8 (empty: the all-zero key)
+	// what().tch3: the TCH3 follow-up
 	gmr1_hip_tch3_state *d_tstate = nullptr;       // one per chain, parallel to d_state
 	std::vector<TchCarry> carry;         // per chain
-	// a handle that follows TCH9 calls too (gmr1_hip_rx_stream_create_full; tch is set as well)
-	bool full = false;
-	float2 *cbuf[2] = {nullptr, nullptr};          // the CSD carrier's samples, held as tbuf is
+	// what().tch9: the TCH9 follow-up
 	gmr1_hip_tch9_state *d_t9state = nullptr;      // one per chain, parallel to d_state
 	std::vector<Tch9CallCarry> carry9;   // per chain
-	// a handle that decodes the TCH3 calls it follows (gmr1_hip_rx_stream_create_voice; tch is set as well)
-	bool voice = false;
+	// what().audio: the decoders of the TCH3 calls
 	void *d_codec = nullptr;             // one AMBE decoder state per chain, beside d_tstate
 	std::vector<int> n_assigned;         // per chain: IMMEDIATE ASSIGNMENTs followed so far
-	int kind() const { return full ? kRxStreamFull : voice ? kRxStreamVoice : tch ? kRxStreamTch : kRxStreamPlain; }
+	const RxStreamKind &what() const { return rx_stream_kind(kind); }
 	~gmr1_hip_rx_stream()
 	{
-		for (void *p : std::initializer_list<void *>{buf[0], buf[1], tbuf[0], tbuf[1], cbuf[0], cbuf[1], d_tstate, d_t9state, d_state,
-		                                             d_codec, d_car, d_err, d_in})
+		for (float2 *(&pair)[2] : plane)
+			for (float2 *p : pair)
+				if (p) (void)hipFree(p);
+		for (void *p : std::initializer_list<void *>{d_tstate, d_t9state, d_state, d_codec, d_car, d_err, d_in})
 			if (p) (void)hipFree(p);
 		for (void *p : std::initializer_list<void *>{h_car, h_err, h_in})
 			if (p) (void)hipHostFree(p);
@@ -115,83 +117,69 @@ long long rx_stream_next_held(const gmr1_hip_rx_stream *h, int i, uint64_t n)
 	return h->held[i] - h->keep[i] + (long long)n;
 }
 
-long long rx_stream_bound(const gmr1_hip_rx_stream *h, uint64_t n)
-{
-	if (h->ended)
-		return 0;
+// the chains a push of n can walk, and the most samples one of them walks over
+struct RxStreamReach {
 	long long chains = 0, len = 0;
-	for (int i = 0; i < h->A; i++) {
+};
+
+RxStreamReach rx_stream_reach(const gmr1_hip_rx_stream *h, uint64_t n)
+{
+	RxStreamReach r;
+	for (int i = 0; i < h->A && !h->ended; i++) {
 		if (rx_stream_dead(h, i))
 			continue;
-		chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
-		len = std::max(len, rx_stream_next_held(h, i, n));
+		r.chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
+		r.len = std::max(r.len, rx_stream_next_held(h, i, n));
 	}
-	if (!chains)
-		return 0;
-	return chains * (h->tch ? rx_stream_tch_rec_per_chain(len, h->sps) : rx_stream_rec_per_chain(len, h->sps));
+	return r;
+}
+
+// the most records, big records and audio blocks a push of n can hand back
+long long rx_stream_bound(const gmr1_hip_rx_stream *h, uint64_t n)
+{
+	const RxStreamReach r = rx_stream_reach(h, n);
+	return r.chains * (h->what().tch3 ? rx_stream_tch_rec_per_chain(r.len, h->sps) : rx_stream_rec_per_chain(r.len, h->sps));
 }
 
 long long rx_stream_big_bound(const gmr1_hip_rx_stream *h, uint64_t n)
 {
-	if (h->ended || !h->full)
-		return 0;
-	long long chains = 0, len = 0;
-	for (int i = 0; i < h->A; i++) {
-		if (rx_stream_dead(h, i))
-			continue;
-		chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
-		len = std::max(len, rx_stream_next_held(h, i, n));
-	}
-	return rx_stream_max_big(chains, len, h->sps);
+	const RxStreamReach r = rx_stream_reach(h, n);
+	return h->what().tch9 ? rx_stream_max_big(r.chains, r.len, h->sps) : 0;
 }
 
 long long rx_stream_audio_bound(const gmr1_hip_rx_stream *h, uint64_t n)
 {
-	if (h->ended || !h->voice)
-		return 0;
-	long long chains = 0, len = 0;
-	for (int i = 0; i < h->A; i++) {
-		if (rx_stream_dead(h, i))
-			continue;
-		chains += h->acquired ? h->c0[i + 1] - h->c0[i] : kMaxPeaks;
-		len = std::max(len, rx_stream_next_held(h, i, n));
-	}
-	return rx_stream_max_audio(chains, len, h->sps);
+	const RxStreamReach r = rx_stream_reach(h, n);
+	return h->what().audio ? rx_stream_max_audio(r.chains, r.len, h->sps) : 0;
 }
 
-// what a push entry hands in beside iq: `kind` says which entry it is (_push*, _push_tch*, _push_full*, _push_voice*)
+// what a push entry hands in: `kind` says which entry it is (_push*, _push_tch*, _push_full*, _push_voice*)
 struct RxStreamPush {
-	int kind;
-	const float *tch, *csd;
-	gmr1_hip_rx_big_record *big_out;
-	int max_big;
-	int *n_big;
-	gmr1_hip_rx_audio *audio_out = nullptr;
+	int kind = kRxStreamPlain;
+	const float *chunk[kRxStreamMaxPlanes] = {};   // by plane: iq (rx_stream_push_any puts it there), tch, csd
+	gmr1_hip_rx_big_record *big_out = nullptr;     // _push_full*
+	int max_big = 0;
+	int *n_big = nullptr;
+	gmr1_hip_rx_audio *audio_out = nullptr;        // _push_voice*
 	int max_audio = 0;
 	int *n_audio = nullptr;
 };
 
-int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, const float *iq, uint64_t iq_stride, uint64_t n,
-                    const gmr1_hip_rx_record *out, int max_records, const int *n_records)
+int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, uint64_t iq_stride, uint64_t n, const gmr1_hip_rx_record *out,
+                    int max_records, const int *n_records)
 {
-	if (!h || !n_records || max_records < 0 || (max_records > 0 && !out) || (n > 0 && !iq))
+	if (!h || !n_records || max_records < 0 || (max_records > 0 && !out) || (n > 0 && !p.chunk[0]))
 		return fail(-EINVAL, "rx_stream_push: handle / n_records (and iq when n > 0, out when max_records > 0) are required");
-	if (h->kind() != p.kind) {
-		static const char *const entry[kRxStreamKinds] = {"gmr1_hip_rx_stream_push*", "gmr1_hip_rx_stream_push_tch*",
-		                                                  "gmr1_hip_rx_stream_push_full*", "gmr1_hip_rx_stream_push_voice*"};
-		static const char *const maker[kRxStreamKinds] = {"gmr1_hip_rx_stream_create", "gmr1_hip_rx_stream_create_tch",
-		                                                  "gmr1_hip_rx_stream_create_full", "gmr1_hip_rx_stream_create_voice"};
-		return fail(-EINVAL, "rx_stream_push: a handle of %s takes %s, not %s", maker[h->kind()], entry[h->kind()], entry[p.kind]);
-	}
-	if (p.kind != kRxStreamPlain && n > 0 && !p.tch)
-		return fail(-EINVAL, "rx_stream_push_tch: tch is required when n > 0");
-	if (p.kind == kRxStreamFull) {
-		if (n > 0 && !p.csd)
-			return fail(-EINVAL, "rx_stream_push_full: csd is required when n > 0");
-		if (!p.n_big || p.max_big < 0 || (p.max_big > 0 && !p.big_out))
-			return fail(-EINVAL, "rx_stream_push_full: n_big (and big_out when max_big > 0) are required");
-	}
-	if (p.kind == kRxStreamVoice && (!p.n_audio || p.max_audio < 0 || (p.max_audio > 0 && !p.audio_out)))
+	const RxStreamKind &k = h->what();
+	if (h->kind != p.kind)
+		return fail(-EINVAL, "rx_stream_push: a handle of %s takes %s, not %s", k.maker, k.entry, rx_stream_kind(p.kind).entry);
+	static const char *const chunk_of[kRxStreamMaxPlanes] = {nullptr, "rx_stream_push_tch: tch", "rx_stream_push_full: csd"};
+	for (int pl = 1; pl < k.planes; pl++)
+		if (n > 0 && !p.chunk[pl])
+			return fail(-EINVAL, "%s is required when n > 0", chunk_of[pl]);
+	if (k.tch9 && (!p.n_big || p.max_big < 0 || (p.max_big > 0 && !p.big_out)))
+		return fail(-EINVAL, "rx_stream_push_full: n_big (and big_out when max_big > 0) are required");
+	if (k.audio && (!p.n_audio || p.max_audio < 0 || (p.max_audio > 0 && !p.audio_out)))
 		return fail(-EINVAL, "rx_stream_push_voice: n_audio (and audio_out when max_audio > 0) are required");
 	int dev = 0;
 	HIP_TRY(hipGetDevice(&dev));
@@ -212,16 +200,16 @@ int rx_stream_check(const gmr1_hip_rx_stream *h, const RxStreamPush &p, const fl
 	if ((long long)max_records < bound)
 		return fail(-EINVAL, "rx_stream_push: max_records %d below the bound %lld", max_records, bound);
 	const long long big_bound = rx_stream_big_bound(h, n);
-	if (p.kind == kRxStreamFull && (long long)p.max_big < big_bound)
+	if (k.tch9 && (long long)p.max_big < big_bound)
 		return fail(-EINVAL, "rx_stream_push_full: max_big %d below the bound %lld", p.max_big, big_bound);
 	const long long audio_bound = rx_stream_audio_bound(h, n);
-	if (p.kind == kRxStreamVoice && (long long)p.max_audio < audio_bound)
+	if (k.audio && (long long)p.max_audio < audio_bound)
 		return fail(-EINVAL, "rx_stream_push_voice: max_audio %d below the bound %lld", p.max_audio, audio_bound);
 	return 0;
 }
 
 // the destination of a staging of `need` samples per carrier in a ping-pong pair
-int rx_stream_other(gmr1_hip_rx_stream *h, float2 **pair, long long need, bool grow)
+int rx_stream_other(gmr1_hip_rx_stream *h, float2 *(&pair)[2], long long need, bool grow)
 {
 	float2 *&o = pair[1 - h->cur];
 	if (grow) {
@@ -236,11 +224,10 @@ int rx_stream_other(gmr1_hip_rx_stream *h, float2 **pair, long long need, bool g
 	return 0;
 }
 
-// staging: [kept tail | chunk] -> the other buffer, states rebased; the handle's host mirror moves with it
-int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, const float2 *tch, const float2 *csd, uint64_t iq_stride,
-                    uint64_t n, int last)
+// staging: [kept tail | chunk] -> the other buffer of every plane, states rebased; the handle's host mirror moves with it
+int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float *const *chunk, uint64_t iq_stride, uint64_t n, int last)
 {
-	const int A = h->A;
+	const int A = h->A, planes = h->what().planes;
 	std::vector<long long> next((size_t)A);
 	long long need = 0, max_pairs = 0;
 	for (int i = 0; i < A; i++) {
@@ -248,15 +235,15 @@ int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, con
 		need = std::max(need, next[i]);
 	}
 	need = (need + kRxKeepAlign - 1) / kRxKeepAlign * kRxKeepAlign;
-	float2 *src = h->buf[h->cur], *tsrc = h->tbuf[h->cur], *csrc = h->cbuf[h->cur];
+	float2 *src[kRxStreamMaxPlanes] = {};
 	const long long src_stride = h->stride;
-	const bool grow = need > h->stride;
-	int r = rx_stream_other(h, h->buf, need, grow);
-	if (!r && h->tch) r = rx_stream_other(h, h->tbuf, need, grow);   // (the traffic pair follows the first one's decision)
-	if (!r && h->full) r = rx_stream_other(h, h->cbuf, need, grow);  // (and so does the CSD pair)
-	if (r) return r;
+	const bool grow = need > h->stride;         // (every pair follows the first one's decision)
+	for (int pl = 0; pl < planes; pl++) {
+		src[pl] = h->plane[pl][h->cur];
+		const int r = rx_stream_other(h, h->plane[pl], need, grow);
+		if (r) return r;
+	}
 	if (grow) h->stride = need;
-	float2 *dst = h->buf[1 - h->cur], *tdst = h->tbuf[1 - h->cur], *cdst = h->cbuf[1 - h->cur];
 	for (int i = 0; i < A; i++) {
 		RxStageCarrier &c = h->h_car[i];
 		const bool dead = rx_stream_dead(h, i);
@@ -275,43 +262,29 @@ int rx_stream_stage(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, con
 	*h->h_err = 0;
 	HIP_TRY(hipMemcpyAsync(h->d_car, h->h_car, (size_t)A * sizeof(RxStageCarrier), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(h->d_err, h->h_err, 4, hipMemcpyHostToDevice, st));
-	if (dst) {
+	// (no destination: nothing is held and nothing came; the pairs are allocated together)
+	for (int pl = 0; pl < planes; pl++) {
+		float2 *dst = h->plane[pl][1 - h->cur];
+		if (!dst) break;
 		RxStageArgs sa;
 		std::memset(&sa, 0, sizeof(sa));
 		sa.n_carriers = A; sa.sps = h->sps; sa.last = last ? 1 : 0;
 		sa.max_pairs = (int)std::min<long long>(max_pairs, 0x7fffffff);
-		sa.src = src ? src : dst;
+		sa.src = src[pl] ? src[pl] : dst;
 		sa.dst = dst;
-		sa.iq = iq ? iq : dst;
+		sa.iq = chunk[pl] ? reinterpret_cast<const float2 *>(chunk[pl]) : dst;
 		sa.car = h->d_car;
-		sa.state = h->d_state;
-		sa.err = h->d_err;
-		HIP_TRY(launch_rx_stage(sa, st));
-		if (tdst) {
-			sa.src = tsrc ? tsrc : tdst;
-			sa.dst = tdst;
-			sa.iq = tch ? tch : tdst;
-			sa.state = nullptr;
-			sa.err = nullptr;
-			HIP_TRY(launch_rx_stage_copy(sa, st));
-		}
-		if (cdst) {
-			sa.src = csrc ? csrc : cdst;
-			sa.dst = cdst;
-			sa.iq = csd ? csd : cdst;
-			sa.state = nullptr;
-			sa.err = nullptr;
-			HIP_TRY(launch_rx_stage_copy(sa, st));
-		}
+		// the first plane's staging also rebases the states; the others only move samples
+		sa.state = pl ? nullptr : h->d_state;
+		sa.err = pl ? nullptr : h->d_err;
+		HIP_TRY(pl ? launch_rx_stage_copy(sa, st) : launch_rx_stage(sa, st));
 	}
-	if (grow && (src || tsrc || csrc)) {
+	if (grow && std::any_of(src, src + planes, [](const float2 *s) { return s != nullptr; })) {
 		HIP_TRY(hipStreamSynchronize(st));     // the staging has read the old buffers
-		if (src) (void)hipFree(src);
-		if (tsrc) (void)hipFree(tsrc);
-		if (csrc) (void)hipFree(csrc);
-		h->buf[h->cur] = nullptr;
-		h->tbuf[h->cur] = nullptr;
-		h->cbuf[h->cur] = nullptr;
+		for (int pl = 0; pl < planes; pl++) {
+			if (src[pl]) (void)hipFree(src[pl]);
+			h->plane[pl][h->cur] = nullptr;
+		}
 	}
 	h->cur = 1 - h->cur;
 	for (int i = 0; i < A; i++) {
@@ -356,20 +329,20 @@ int rx_stream_acquire(gmr1_hip_rx_stream *h, RxRun &run, int last, std::vector<g
 		for (const RxChain &c : h->chains)
 			s0.push_back(rx_first_state(c, rx_label(run.arfcn, c.a), rx_stream_next_done(kRxDoneUnstarted, c.align, c.len, h->sps, last)));
 		HIP_TRY(hipMemcpyAsync(h->d_state, s0.data(), nc * sizeof(RxLoopState), hipMemcpyHostToDevice, run.st));
-		if (h->tch) {
+		if (h->what().tch3) {
 			t0 = tch3_first_states(h->chains, all_chains(nc), h->kc.empty() ? nullptr : h->kc.data());
 			HIP_TRY(hipMalloc(&h->d_tstate, nc * sizeof(gmr1_hip_tch3_state)));
 			HIP_TRY(hipMemcpyAsync(h->d_tstate, t0.data(), nc * sizeof(gmr1_hip_tch3_state), hipMemcpyHostToDevice, run.st));
 			h->carry.assign(nc, TchCarry());
 		}
-		if (h->voice) {
+		if (h->what().audio) {
 			// no decoder is read before an assignment made it fresh; zeros until then
 			const size_t bytes = nc * gmr1_hip_codec_state_bytes();
 			HIP_TRY(hipMalloc(&h->d_codec, bytes));
 			HIP_TRY(hipMemsetAsync(h->d_codec, 0, bytes, run.st));
 			h->n_assigned.assign(nc, 0);
 		}
-		if (h->full) {
+		if (h->what().tch9) {
 			// no call, nothing held, the carrier's key (rx_tch9_init keeps the key)
 			t9.resize(nc);
 			std::memset(t9.data(), 0, nc * sizeof(gmr1_hip_tch9_state));
@@ -427,23 +400,24 @@ void rx_stream_keep(gmr1_hip_rx_stream *h)
 }
 
 // the device part of a push -- stage, acquire (once), walk, follow, keep; the caller holds h->mu and the workspace lease,
-// and has validated everything (p.tch, p.csd: the traffic and the CSD carrier's chunks, laid out as iq, for a handle that
-// follows calls on them)
-int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq, const RxStreamPush &p, uint64_t iq_stride, uint64_t n,
-                        int last, gmr1_hip_rx_record *out, int max_records, int *n_records)
+// and has validated everything (p.chunk: device memory, the traffic and the CSD carrier's chunks laid out as iq)
+int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const RxStreamPush &p, uint64_t iq_stride, uint64_t n, int last,
+                        gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
 	const int A = h->A, sps = h->sps;
+	const RxStreamKind &k = h->what();
 	int r;
-	if ((r = rx_stream_stage(st, h, iq, reinterpret_cast<const float2 *>(p.tch), reinterpret_cast<const float2 *>(p.csd), iq_stride, n,
-	                         last))) return r;
+	if ((r = rx_stream_stage(st, h, p.chunk, iq_stride, n, last))) return r;
 	std::vector<uint64_t> offset((size_t)A), length((size_t)A);
 	for (int i = 0; i < A; i++) {
 		offset[i] = (uint64_t)((long long)i * h->stride);
 		length[i] = (uint64_t)h->held[i];
 	}
-	// (a traffic carrier makes the walk log its frames and hand its records back chain by chain, as in gmr1_hip_rx_run_tch)
-	RxRun run(st, sps, reinterpret_cast<const float *>(h->buf[h->cur]), h->tch ? reinterpret_cast<const float *>(h->tbuf[h->cur]) : nullptr,
-	          nullptr, A, offset.data(), length.data(), h->arfcn.empty() ? nullptr : h->arfcn.data(), nullptr, out, max_records);
+	// (a traffic carrier makes the walk log its frames and hand its records back chain by chain, as in gmr1_hip_rx_run_tch;
+	// a plain handle has none: its plane[1] is null)
+	const auto held = [&](int pl) { return reinterpret_cast<const float *>(h->plane[pl][h->cur]); };
+	RxRun run(st, sps, held(0), held(1), nullptr, A, offset.data(), length.data(), h->arfcn.empty() ? nullptr : h->arfcn.data(), nullptr,
+	          out, max_records);
 	run.stat = h->stat; run.nch = h->nch;
 	std::vector<gmr1_hip_tch3_state> t0;
 	std::vector<gmr1_hip_tch9_state> t9;
@@ -459,32 +433,33 @@ int rx_stream_push_impl(hipStream_t st, gmr1_hip_rx_stream *h, const float2 *iq,
 	}
 	*n_records = run.direct ? run.direct_total : 0;
 	// the TCH3 follow-up over this push's frames, and the records chain by chain in frame order
-	if (h->tch && walking) {
+	if (k.tch3 && walking) {
 		RxVoice voice;
-		if (h->voice) {
+		if (k.audio) {
 			voice.d_codec = h->d_codec;
 			voice.count = h->n_assigned.data();
 			voice.out = p.audio_out;
 			voice.max_out = p.max_audio;
 		}
-		if ((r = tch3_follow_chains(st, sps, run.tch, run.arfcn, h->full, !last, h->chains, run.walks, all_chains(h->chains.size()), nullptr,
-		                            h->d_tstate, h->carry.data(), h->voice ? &voice : nullptr))) return r;
-		if (h->voice) *p.n_audio = voice.found;
+		if ((r = tch3_follow_chains(st, sps, run.tch, run.arfcn, k.tch9, !last, h->chains, run.walks, all_chains(h->chains.size()), nullptr,
+		                            h->d_tstate, h->carry.data(), k.audio ? &voice : nullptr))) return r;
+		if (k.audio) *p.n_audio = voice.found;
 		*n_records = rx_hand_back(run.walks, out, max_records);
 		// the TCH9 follow-up over the same frames, from the commands the TCH3 records of this push carry
-		if (h->full && (r = tch9_follow_push(st, sps, reinterpret_cast<const float *>(h->cbuf[h->cur]), run.arfcn, !last, h->chains,
-		                                     run.walks, h->d_t9state, h->carry9.data(), p.big_out, p.max_big, p.n_big))) return r;
+		if (k.tch9 && (r = tch9_follow_push(st, sps, held(2), run.arfcn, !last, h->chains, run.walks, h->d_t9state, h->carry9.data(),
+		                                    p.big_out, p.max_big, p.n_big))) return r;
 	}
 	rx_stream_keep(h);
 	return 0;
 }
 
-// the host form's chunk goes up packed (stride n) through the handle's pinned block, the traffic carrier's *half bytes
-// behind, the CSD carrier's as many behind that
-int rx_stream_pin_chunk(gmr1_hip_rx_stream *h, const RxStreamPush &p, const float *iq, uint64_t iq_stride, uint64_t n, size_t *half)
+// the host form's chunks go up packed (stride n) through the handle's pinned block, plane after plane, *each bytes apart
+// (rx_stream_check has passed: p is of the handle's kind and holds a chunk for every plane when n > 0)
+int rx_stream_pin_chunk(gmr1_hip_rx_stream *h, const RxStreamPush &p, uint64_t iq_stride, uint64_t n, size_t *each)
 {
-	*half = (size_t)h->A * (size_t)n * sizeof(float2);
-	const size_t bytes = (size_t)rx_stream_planes(p.kind) * *half;
+	const int planes = h->what().planes;
+	*each = (size_t)h->A * (size_t)n * sizeof(float2);
+	const size_t bytes = (size_t)planes * *each;
 	if (bytes > h->h_in_bytes) {
 		if (h->h_in) (void)hipHostFree(h->h_in);
 		if (h->d_in) (void)hipFree(h->d_in);
@@ -494,13 +469,9 @@ int rx_stream_pin_chunk(gmr1_hip_rx_stream *h, const RxStreamPush &p, const floa
 		HIP_TRY(hipMalloc(&h->d_in, bytes));
 		h->d_in_bytes = bytes;
 	}
-	for (int i = 0; i < h->A && n > 0; i++) {
-		std::memcpy(h->h_in + (size_t)i * n * 2, iq + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
-		if (p.kind != kRxStreamPlain)
-			std::memcpy(h->h_in + *half / 4 + (size_t)i * n * 2, p.tch + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
-		if (p.kind == kRxStreamFull)
-			std::memcpy(h->h_in + 2 * (*half / 4) + (size_t)i * n * 2, p.csd + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
-	}
+	for (int pl = 0; pl < planes; pl++)
+		for (int i = 0; i < h->A && n > 0; i++)
+			std::memcpy(h->h_in + pl * (*each / 4) + (size_t)i * n * 2, p.chunk[pl] + (size_t)i * iq_stride * 2, (size_t)n * sizeof(float2));
 	return 0;
 }
 
@@ -524,32 +495,60 @@ int rx_stream_push_any(void *stream, gmr1_hip_rx_stream *h, RxStreamPush p, bool
 	if (n_records) *n_records = 0;
 	if (p.n_big) *p.n_big = 0;
 	if (p.n_audio) *p.n_audio = 0;
+	p.chunk[0] = iq;
 	std::unique_lock<std::mutex> lk;
 	if (h)
 		lk = std::unique_lock<std::mutex>(h->mu);
-	if ((r = rx_stream_check(h, p, iq, iq_stride, n, out, max_records, n_records)))
+	if ((r = rx_stream_check(h, p, iq_stride, n, out, max_records, n_records)))
 		return r;
 	hipStream_t st = host ? nullptr : (hipStream_t)stream;
-	size_t half = 0;
-	if (host && (r = rx_stream_pin_chunk(h, p, iq, iq_stride, n, &half))) return r;
+	size_t each = 0;
+	if (host && (r = rx_stream_pin_chunk(h, p, iq_stride, n, &each))) return r;
 	// the loop holds the device's workspace, side stream and events: pushes of other handles wait their turn
 	WsLease lease;
 	if ((r = lease.acquire(ds, st))) return r;
 	if (host) {
-		if (half)
-			HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, (size_t)rx_stream_planes(p.kind) * half, hipMemcpyHostToDevice, st));
-		iq = h->d_in;
-		p.tch = p.kind != kRxStreamPlain ? h->d_in + half / 4 : nullptr;
-		p.csd = p.kind == kRxStreamFull ? h->d_in + 2 * (half / 4) : nullptr;
+		const int planes = h->what().planes;
+		if (each)
+			HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, (size_t)planes * each, hipMemcpyHostToDevice, st));
+		for (int pl = 0; pl < planes; pl++)
+			p.chunk[pl] = h->d_in + pl * (each / 4);
 		iq_stride = n;
 	}
-	r = rx_stream_push_impl(st, h, reinterpret_cast<const float2 *>(iq), p, iq_stride, n, last, out, max_records, n_records);
+	r = rx_stream_push_impl(st, h, p, iq_stride, n, last, out, max_records, n_records);
 	if (r) h->broken = true;
 	return r;
 }
 
-int rx_stream_create_check(const char *who, int n_arfcn, int sps, struct gmr1_hip_rx_stream **out)
+// the three gmr1_hip_rx_stream_max_* entries: `what` is the entry's output ("max_big"), `unit` what it counts.  (_max_records
+// asks for the device before it looks at its arguments, the other two after: each entry's order is kept.)
+int rx_stream_max_any(const char *what, const char *unit, bool device_first, const gmr1_hip_rx_stream *h, uint64_t n,
+                      long long (*bound)(const gmr1_hip_rx_stream *, uint64_t), int *out)
 {
+	DevState *ds;
+	int r;
+	if (device_first && (r = dev_state(&ds))) return r;
+	if (!h || !out)
+		return fail(-EINVAL, "rx_stream_%s: handle / %s are required", what, what);
+	if (!device_first && (r = dev_state(&ds))) return r;
+	std::lock_guard<std::mutex> lk(h->mu);
+	const long long b = bound(h, n);
+	if (b > 0x7fffffffll)
+		return fail(-EINVAL, "rx_stream_%s: %lld %s do not fit an int", what, b, unit);
+	*out = (int)b;
+	return 0;
+}
+
+// the four create entries.  kind: what the handle follows; kc: n_arfcn x 8 key bytes for a handle that follows calls, or
+// NULL for the all-zero key.  (The plain entry asks for the device before it looks at its arguments, the others after.)
+int rx_stream_create(int kind, int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
+{
+	const RxStreamKind &k = rx_stream_kind(kind);
+	const char *who = k.maker + sizeof("gmr1_hip_") - 1;
+	const bool device_first = kind == kRxStreamPlain;
+	DevState *ds;
+	int r;
+	if (device_first && (r = dev_state(&ds))) return r;
 	if (!out)
 		return fail(-EINVAL, "%s: h is required", who);
 	*out = nullptr;
@@ -557,19 +556,18 @@ int rx_stream_create_check(const char *who, int n_arfcn, int sps, struct gmr1_hi
 		return fail(-EINVAL, "%s: n_arfcn=%d (1..65535)", who, n_arfcn);
 	if (sps < 1 || sps > 16)                  // gmr1_rx.c:919-922
 		return fail(-EINVAL, "%s: sps=%d unsupported (1..16)", who, sps);
-	return 0;
-}
-
-// kind: what the handle follows; kc: n_arfcn x 8 key bytes for a handle that follows calls, or NULL for the all-zero key
-int rx_stream_make(int n_arfcn, int sps, const uint16_t *arfcn, int kind, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
-{
+	// the NT9 window of 351 sps + sps + sps / 2 samples has to fit the demodulator's (gmr1_hip_rx_run_full finds out at
+	// its first NT9 frame)
+	if (k.tch9 && rx_tch9_in_len(sps) > kMaxInLen)
+		return fail(-EINVAL, "%s: sps=%d: the NT9 window of %d samples is above %d (sps 1..%d)", who, sps, rx_tch9_in_len(sps), kMaxInLen,
+		            rx_stream_full_max_sps());
+	if (!device_first && (r = dev_state(&ds))) return r;
+	if (k.audio && (r = tch3_pcm_prepare())) return r;       // the decoder's tables, built once per device
 	std::unique_ptr<gmr1_hip_rx_stream> h(new gmr1_hip_rx_stream);
 	HIP_TRY(hipGetDevice(&h->device));
 	h->A = n_arfcn;
 	h->sps = sps;
-	h->tch = kind != kRxStreamPlain;
-	h->full = kind == kRxStreamFull;
-	h->voice = kind == kRxStreamVoice;
+	h->kind = kind;
 	if (arfcn)
 		h->arfcn.assign(arfcn, arfcn + n_arfcn);
 	if (kc)
@@ -594,134 +592,64 @@ extern "C" {
 
 int gmr1_hip_rx_stream_create(int n_arfcn, int sps, const uint16_t *arfcn, struct gmr1_hip_rx_stream **out)
 {
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if ((r = rx_stream_create_check("rx_stream_create", n_arfcn, sps, out))) return r;
-	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamPlain, nullptr, out);
+	return rx_stream_create(kRxStreamPlain, n_arfcn, sps, arfcn, nullptr, out);
 }
 
 int gmr1_hip_rx_stream_create_tch(int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
 {
-	int r = rx_stream_create_check("rx_stream_create_tch", n_arfcn, sps, out);
-	if (r) return r;
-	DevState *ds;
-	if ((r = dev_state(&ds))) return r;
-	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamTch, kc, out);
+	return rx_stream_create(kRxStreamTch, n_arfcn, sps, arfcn, kc, out);
 }
 
 int gmr1_hip_rx_stream_create_full(int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
 {
-	int r = rx_stream_create_check("rx_stream_create_full", n_arfcn, sps, out);
-	if (r) return r;
-	// the NT9 window of 351 sps + sps + sps / 2 samples has to fit the demodulator's (gmr1_hip_rx_run_full finds out at
-	// its first NT9 frame)
-	if (rx_tch9_in_len(sps) > kMaxInLen)
-		return fail(-EINVAL, "rx_stream_create_full: sps=%d: the NT9 window of %d samples is above %d (sps 1..%d)", sps,
-		            rx_tch9_in_len(sps), kMaxInLen, rx_stream_full_max_sps());
-	DevState *ds;
-	if ((r = dev_state(&ds))) return r;
-	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamFull, kc, out);
+	return rx_stream_create(kRxStreamFull, n_arfcn, sps, arfcn, kc, out);
 }
 
 int gmr1_hip_rx_stream_create_voice(int n_arfcn, int sps, const uint16_t *arfcn, const uint8_t *kc, struct gmr1_hip_rx_stream **out)
 {
-	int r = rx_stream_create_check("rx_stream_create_voice", n_arfcn, sps, out);
-	if (r) return r;
-	DevState *ds;
-	if ((r = dev_state(&ds))) return r;
-	if ((r = tch3_pcm_prepare())) return r;       // the decoder's tables, built once per device
-	return rx_stream_make(n_arfcn, sps, arfcn, kRxStreamVoice, kc, out);
-}
-
-int gmr1_hip_rx_stream_max_audio(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_audio)
-{
-	if (!h || !max_audio)
-		return fail(-EINVAL, "rx_stream_max_audio: handle / max_audio are required");
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	std::lock_guard<std::mutex> lk(h->mu);
-	const long long b = rx_stream_audio_bound(h, n);
-	if (b > 0x7fffffffll)
-		return fail(-EINVAL, "rx_stream_max_audio: %lld blocks do not fit an int", b);
-	*max_audio = (int)b;
-	return 0;
-}
-
-int gmr1_hip_rx_stream_push_voice_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride,
-                                      uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
-                                      struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
-{
-	return rx_stream_push_any(stream, h, {kRxStreamVoice, tch, nullptr, nullptr, 0, nullptr, audio_out, max_audio, n_audio}, false, iq,
-	                          iq_stride, n, last, out, max_records, n_records);
-}
-
-int gmr1_hip_rx_stream_push_voice(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
-                                  int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
-                                  struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
-{
-	return rx_stream_push_any(nullptr, h, {kRxStreamVoice, tch, nullptr, nullptr, 0, nullptr, audio_out, max_audio, n_audio}, true, iq,
-	                          iq_stride, n, last, out, max_records, n_records);
-}
-
-int gmr1_hip_rx_stream_max_big(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_big)
-{
-	if (!h || !max_big)
-		return fail(-EINVAL, "rx_stream_max_big: handle / max_big are required");
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	std::lock_guard<std::mutex> lk(h->mu);
-	const long long b = rx_stream_big_bound(h, n);
-	if (b > 0x7fffffffll)
-		return fail(-EINVAL, "rx_stream_max_big: %lld records do not fit an int", b);
-	*max_big = (int)b;
-	return 0;
+	return rx_stream_create(kRxStreamVoice, n_arfcn, sps, arfcn, kc, out);
 }
 
 int gmr1_hip_rx_stream_max_records(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_records)
 {
-	DevState *ds;
-	int r = dev_state(&ds);
-	if (r) return r;
-	if (!h || !max_records)
-		return fail(-EINVAL, "rx_stream_max_records: handle / max_records are required");
-	std::lock_guard<std::mutex> lk(h->mu);
-	const long long b = rx_stream_bound(h, n);
-	if (b > 0x7fffffffll)
-		return fail(-EINVAL, "rx_stream_max_records: %lld records do not fit an int", b);
-	*max_records = (int)b;
-	return 0;
+	return rx_stream_max_any("max_records", "records", true, h, n, rx_stream_bound, max_records);
+}
+
+int gmr1_hip_rx_stream_max_big(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_big)
+{
+	return rx_stream_max_any("max_big", "records", false, h, n, rx_stream_big_bound, max_big);
+}
+
+int gmr1_hip_rx_stream_max_audio(const struct gmr1_hip_rx_stream *h, uint64_t n, int *max_audio)
+{
+	return rx_stream_max_any("max_audio", "blocks", false, h, n, rx_stream_audio_bound, max_audio);
 }
 
 int gmr1_hip_rx_stream_push_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n,
                                 int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	return rx_stream_push_any(stream, h, {kRxStreamPlain, nullptr, nullptr, nullptr, 0, nullptr}, false, iq, iq_stride, n, last, out,
-	                          max_records, n_records);
+	return rx_stream_push_any(stream, h, RxStreamPush(), false, iq, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push(struct gmr1_hip_rx_stream *h, const float *iq, uint64_t iq_stride, uint64_t n, int last,
                             struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	return rx_stream_push_any(nullptr, h, {kRxStreamPlain, nullptr, nullptr, nullptr, 0, nullptr}, true, iq, iq_stride, n, last, out,
-	                          max_records, n_records);
+	return rx_stream_push_any(nullptr, h, RxStreamPush(), true, iq, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push_tch_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch,
                                     uint64_t iq_stride, uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records,
                                     int *n_records)
 {
-	return rx_stream_push_any(stream, h, {kRxStreamTch, tch, nullptr, nullptr, 0, nullptr}, false, iq, iq_stride, n, last, out, max_records,
-	                          n_records);
+	const RxStreamPush p = {.kind = kRxStreamTch, .chunk = {nullptr, tch}};
+	return rx_stream_push_any(stream, h, p, false, iq, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push_tch(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
                                 int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records)
 {
-	return rx_stream_push_any(nullptr, h, {kRxStreamTch, tch, nullptr, nullptr, 0, nullptr}, true, iq, iq_stride, n, last, out, max_records,
-	                          n_records);
+	const RxStreamPush p = {.kind = kRxStreamTch, .chunk = {nullptr, tch}};
+	return rx_stream_push_any(nullptr, h, p, true, iq, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push_full_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, const float *csd,
@@ -730,8 +658,8 @@ int gmr1_hip_rx_stream_push_full_dev(void *stream, struct gmr1_hip_rx_stream *h,
 {
 	const int r = rx_stream_full_args(h, max_records, n_records, max_big, n_big);
 	if (r) return r;
-	return rx_stream_push_any(stream, h, {kRxStreamFull, tch, csd, big_out, max_big, n_big}, false, iq, iq_stride, n, last, out,
-	                          max_records, n_records);
+	const RxStreamPush p = {.kind = kRxStreamFull, .chunk = {nullptr, tch, csd}, .big_out = big_out, .max_big = max_big, .n_big = n_big};
+	return rx_stream_push_any(stream, h, p, false, iq, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_push_full(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, const float *csd, uint64_t iq_stride,
@@ -740,8 +668,24 @@ int gmr1_hip_rx_stream_push_full(struct gmr1_hip_rx_stream *h, const float *iq, 
 {
 	const int r = rx_stream_full_args(h, max_records, n_records, max_big, n_big);
 	if (r) return r;
-	return rx_stream_push_any(nullptr, h, {kRxStreamFull, tch, csd, big_out, max_big, n_big}, true, iq, iq_stride, n, last, out,
-	                          max_records, n_records);
+	const RxStreamPush p = {.kind = kRxStreamFull, .chunk = {nullptr, tch, csd}, .big_out = big_out, .max_big = max_big, .n_big = n_big};
+	return rx_stream_push_any(nullptr, h, p, true, iq, iq_stride, n, last, out, max_records, n_records);
+}
+
+int gmr1_hip_rx_stream_push_voice_dev(void *stream, struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride,
+                                      uint64_t n, int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                      struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
+{
+	const RxStreamPush p = {.kind = kRxStreamVoice, .chunk = {nullptr, tch}, .audio_out = audio_out, .max_audio = max_audio, .n_audio = n_audio};
+	return rx_stream_push_any(stream, h, p, false, iq, iq_stride, n, last, out, max_records, n_records);
+}
+
+int gmr1_hip_rx_stream_push_voice(struct gmr1_hip_rx_stream *h, const float *iq, const float *tch, uint64_t iq_stride, uint64_t n,
+                                  int last, struct gmr1_hip_rx_record *out, int max_records, int *n_records,
+                                  struct gmr1_hip_rx_audio *audio_out, int max_audio, int *n_audio)
+{
+	const RxStreamPush p = {.kind = kRxStreamVoice, .chunk = {nullptr, tch}, .audio_out = audio_out, .max_audio = max_audio, .n_audio = n_audio};
+	return rx_stream_push_any(nullptr, h, p, true, iq, iq_stride, n, last, out, max_records, n_records);
 }
 
 int gmr1_hip_rx_stream_status(const struct gmr1_hip_rx_stream *h, int32_t *status, int32_t *n_chains, uint64_t *retained)

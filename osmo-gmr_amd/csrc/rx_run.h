@@ -59,7 +59,9 @@ struct RxVoice {
 };
 
 // One call of gmr1_hip_rx_run*, or one push of the streaming loop: what the phases share.  The phases run in the order
-// the reference's main() runs them (gmr1_rx.c:897-975).
+// the reference's main() runs them (gmr1_rx.c:897-975).  Which follow-ups run behind the walk is said by what is handed
+// in: a one-shot entry's arguments arrive under their names as an RxRunCall (capi_rx.cpp) and a carrier that is there is
+// followed; a push's arrive as an RxStreamPush on a handle whose kind (RxStreamKind, rx_stream.h) says it.
 struct RxRun {
 	hipStream_t st;
 	int sps;

@@ -77,30 +77,36 @@ GMR1_HD long long rx_stream_tch_rec_per_chain(long long len, int sps)
 	return rx_stream_rec_per_chain(len, sps) + rx_stream_frames_per_chain(len, sps);
 }
 
-// ---- a handle that follows TCH9 data calls too (gmr1_hip_rx_stream_create_full) ----
-// what a handle follows, and which push entry it therefore takes
-constexpr int kRxStreamPlain = 0, kRxStreamTch = 1, kRxStreamFull = 2;
-// a handle that follows TCH3 calls and decodes them to audio (gmr1_hip_rx_stream_create_voice): a tch handle with a decoder per chain
-constexpr int kRxStreamVoice = 3;
+// ---- what a handle follows ----
+// plain: BCCH / CCCH only; tch: TCH3 calls as well; full: TCH3 and TCH9 calls; voice: TCH3 calls, decoded to audio
+constexpr int kRxStreamPlain = 0, kRxStreamTch = 1, kRxStreamFull = 2, kRxStreamVoice = 3;
 constexpr int kRxStreamKinds = 4;
+constexpr int kRxStreamMaxPlanes = 3;
 
-// carriers a push of the kind brings: the BCCH carrier, the traffic carrier, the CSD carrier
-GMR1_HD int rx_stream_planes(int kind) { return kind == kRxStreamPlain ? 1 : kind == kRxStreamFull ? 3 : 2; }
-
-// A voice handle hands back at most one audio block per frame a chain's walk can log: what rx_stream_max_big counts
-GMR1_HD long long rx_stream_max_audio(long long chains, long long len, int sps)
-{
-	return chains > 0 ? chains * rx_stream_frames_per_chain(len, sps) : 0;
-}
+// A kind, described once: the handle, its entries and their messages ask this and nothing else (host only)
+struct RxStreamKind {
+	int planes;                  // carriers a push brings: the BCCH carrier, the traffic carrier, the CSD carrier
+	bool tch3, tch9, audio;      // follows TCH3 calls; follows TCH9 calls; decodes the TCH3 calls it follows
+	const char *maker, *entry;   // who makes such a handle and who pushes to it
+};
+inline constexpr RxStreamKind kRxStreamKind[kRxStreamKinds] = {
+	{1, false, false, false, "gmr1_hip_rx_stream_create", "gmr1_hip_rx_stream_push*"},
+	{2, true, false, false, "gmr1_hip_rx_stream_create_tch", "gmr1_hip_rx_stream_push_tch*"},
+	{3, true, true, false, "gmr1_hip_rx_stream_create_full", "gmr1_hip_rx_stream_push_full*"},
+	{2, true, false, true, "gmr1_hip_rx_stream_create_voice", "gmr1_hip_rx_stream_push_voice*"},
+};
+inline const RxStreamKind &rx_stream_kind(int kind) { return kRxStreamKind[kind]; }
 
 // The window rx_tch9 cuts on the CSD carrier is 351 * sps + sps + sps / 2 samples (rx_tch9_in_len, rx_follow.h), and the
 // demodulator takes windows up to kMaxInLen: the largest sps a full handle can be made for
 GMR1_HD int rx_stream_full_max_sps() { return 11; }
 
-// A full handle hands back at most one big record (FACCH9 / TCH9) per frame a chain's walk can log
+// Beside its records a handle hands back at most one more thing per frame a chain's walk can log: a full handle a big
+// record (FACCH9 / TCH9), a voice handle an audio block
 GMR1_HD long long rx_stream_max_big(long long chains, long long len, int sps)
 {
 	return chains > 0 ? chains * rx_stream_frames_per_chain(len, sps) : 0;
 }
+GMR1_HD long long rx_stream_max_audio(long long chains, long long len, int sps) { return rx_stream_max_big(chains, len, sps); }
 
 }  // namespace gmr1

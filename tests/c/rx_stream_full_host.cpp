@@ -1,7 +1,7 @@
 // Host-side check of what lets the streaming receive loop follow TCH9 data calls (osmo-gmr_amd/csrc/rx_follow.h,
 // rx_stream.h): tch9_plan_push over a frame log cut into pushes gives, concatenated, the frames the
 // reference's own frame loop maps on the whole log (restated in rx_tch9_ref.h), with a new segment exactly where the
-// command in force changes and interleaver positions that are the reference's; the NT9 window of a frame the walk admitted lies inside the samples held; the big-record bound.
+// command in force changes and interleaver positions that are the reference's; the NT9 window of a frame the walk admitted lies inside the samples held; the big-record bound, the audio bound that is the same one, and the one description of the four kinds of handle.
 // tests/test_rx_stream_full_host.py builds and runs it, plain and under the address / undefined-behaviour sanitizers.
 #include <cstdio>
 #include <random>
@@ -247,13 +247,29 @@ int main()
 	// a full handle is made for sps 1..11: from 12 on the NT9 window passes the demodulator's
 	CHECK(rx_stream_full_max_sps() == 11 && rx_tch9_in_len(11) <= 4096 && rx_tch9_in_len(12) > 4096);
 	CHECK(kRxStreamPlain == 0 && kRxStreamTch == 1 && kRxStreamFull == 2);
-	// the big-record bound: one per frame a chain's walk can log, times the chains
-	for (int sps = 1; sps <= 11; sps++) {
+	// the kinds, described once: carriers a push brings, what is followed, and a handle decodes audio or follows TCH9, never both
+	CHECK(kRxStreamVoice == 3 && kRxStreamKinds == 4);
+	const int planes[kRxStreamKinds] = {1, 2, 3, 2};
+	for (int kind = 0; kind < kRxStreamKinds; kind++) {
+		const RxStreamKind &k = rx_stream_kind(kind);
+		CHECK(k.planes == planes[kind] && k.planes <= kRxStreamMaxPlanes);
+		CHECK(k.tch3 == (kind != kRxStreamPlain) && k.tch9 == (kind == kRxStreamFull) && k.audio == (kind == kRxStreamVoice));
+		CHECK(!(k.tch9 && k.audio) && (k.tch3 || !(k.tch9 || k.audio)));
+		CHECK(k.planes == 1 + (k.tch3 ? 1 : 0) + (k.tch9 ? 1 : 0));
+		CHECK(k.maker && k.entry);
+	}
+	// the big-record bound: one per frame a chain's walk can log, times the chains; the audio bound is the same one; and a
+	// tch handle's records are the plain ones plus one per frame
+	for (int sps = 1; sps <= 16; sps++) {
+		g_sps = sps;
 		const long long fl = rx_stream_frame_len(sps);
-		for (long long len = 0; len < 50 * fl; len += 1013)
-			for (long long chains : {0LL, 1LL, 5LL, 1024LL}) {
+		for (long long len = 0; len <= 50 * fl; len += 1013)
+			for (long long c = 0; c <= 65; c++) {
+				const long long chains = c < 65 ? c : 1024;       // 0..64, and 1024
 				CHECK(rx_stream_max_big(chains, len, sps) == chains * (len / fl + 2));
 				CHECK(rx_stream_max_big(chains, len, sps) == chains * rx_stream_frames_per_chain(len, sps));
+				CHECK(rx_stream_max_audio(chains, len, sps) == rx_stream_max_big(chains, len, sps));
+				CHECK(rx_stream_tch_rec_per_chain(len, sps) == rx_stream_rec_per_chain(len, sps) + rx_stream_frames_per_chain(len, sps));
 			}
 	}
 	std::printf("ok\n");

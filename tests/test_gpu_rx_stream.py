@@ -1,5 +1,6 @@
 """GPU tests of the streaming receive loop (gmr1_hip_rx_stream_*): any sequence of pushes gives, once sorted by
 (carrier, chain), byte for byte the records of one gmr1_hip_rx_run call on the same samples, and its status / n_chains."""
+import ctypes as C
 import threading
 
 import numpy as np
@@ -366,3 +367,46 @@ def test_stream_push_from_another_device_is_refused(gpu_api, pkg):
         status, chains, _ = s.status()
     assert np.array_equal(status, rst) and np.array_equal(chains, rch)
     assert _sorted(rec, arfcn).tobytes() == ref.tobytes()
+
+
+@pytest.mark.timeout(60)
+def test_each_kind_of_handle_takes_its_own_push_entry_and_no_other(gpu_api):
+    """The four kinds of handle against the four device push entries, no samples moved (n = 0, not the last push): the
+    twelve wrong pairings are refused with every count zeroed and a message that names the handle's maker, its entry and
+    the entry tried; the right pairing, made after them on the same handle, goes through with nothing found, and the
+    handle then holds nothing and reports no error."""
+    api = gpu_api
+    kinds = {"": {}, "_tch": dict(tch=True), "_full": dict(full=True), "_voice": dict(voice=True)}
+    last_error = api._fn("gmr1_hip_last_error")
+    for mine, flags in kinds.items():
+        with api.RxStream(1, sps=SPS, **flags) as s:
+            out = np.empty(max(s.max_records(0), 1), api.RX_RECORD)
+            big = np.empty(max(s.max_big(0), 1), api.RX_BIG_RECORD)
+            audio = np.empty(max(s.max_audio(0), 1), api.RX_AUDIO)
+            assert out.size > 1 and (big.size > 1) == (mine == "_full") and (audio.size > 1) == (mine == "_voice")
+
+            def push(tried):
+                """the device entry `tried` on this handle -> (return code, the counts it was given)"""
+                counts = [C.c_int(7)]
+                chunks = {"": (None,), "_tch": (None, None), "_full": (None, None, None), "_voice": (None, None)}[tried]
+                tail = ()
+                if tried in ("_full", "_voice"):
+                    extra = big if tried == "_full" else audio
+                    counts.append(C.c_int(7))
+                    tail = (extra.ctypes.data, extra.size, C.byref(counts[1]))
+                rc = api._fn("gmr1_hip_rx_stream_push%s_dev" % tried)(None, s._h, *chunks, 0, 0, 0, out.ctypes.data, out.size,
+                                                                      C.byref(counts[0]), *tail)
+                return rc, [c.value for c in counts]
+
+            for tried in kinds:
+                if tried == mine:
+                    continue
+                rc, counts = push(tried)
+                assert rc == -22 and not any(counts), (mine, tried, rc, counts)
+                want = "a handle of gmr1_hip_rx_stream_create%s takes gmr1_hip_rx_stream_push%s*, not gmr1_hip_rx_stream_push%s*" % (
+                    mine, mine, tried)
+                assert want.encode() in last_error(), (mine, tried, last_error())
+            rc, counts = push(mine)
+            assert rc == 0 and not any(counts), (mine, rc, counts, last_error())
+            status, chains, retained = s.status()
+            assert not status.any() and not chains.any() and not retained.any(), (mine, status, chains, retained)
