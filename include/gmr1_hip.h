@@ -419,7 +419,7 @@ int gmr1_hip_ddc(double samp_rate, int sps, const float *wide, uint64_t n_in, in
  * n_chans x 31.25 kHz is first resampled to that rate by a 32-phase arbitrary resampler (:413-417, :453-461:
  * pfb.arb_resampler_ccf(rate, taps=None, flt_size=32)) -- a branch that cannot run in the reference as written
  * (it reads self.samp_rate before anything sets it); built to its evident intent, with the library's own
- * prototype for the resampler (GNU Radio's default design is not restatable: csrc/capi_chan.cpp,
+ * prototype for the resampler (GNU Radio's default design is not restatable: csrc/chan_plan.h,
  * design_pre_resampler).  The multi-ARFCN synthesizer (:567-576) is not built.
  * gmr1_hip_channelize_plan reports sizes: n_mid = 2x oversampled samples per channel.
  * gmr1_hip_channelize_planar_dev writes the n_sel streams POLYPHASE-PLANAR, the layout

@@ -1,6 +1,6 @@
 // chan_select.h -- which form of the arbitrary resampler a launch gets (chan_kernels.hip: k_resamp, k_resamp2, k_resamp2w) and
 // whether the kernels can run the plan at all: the launchers' rule as a function of its inputs.  No HIP call and nothing
-// global, so tests/c/chan_select_host.cpp runs it without a GPU; capi_chan.cpp asks it when it makes a plan, so that a plan the
+// global, so tests/c/chan_select_host.cpp runs it without a GPU; chan_plan.h asks it when it makes a plan, so that a plan the
 // kernels cannot run is refused there (-EINVAL) and not at its first launch.
 #pragma once
 

@@ -142,12 +142,12 @@ def _form_name(row):
     return {"shared": "k_resamp2w"}.get(f, f)
 
 
-def _build(tmp_path, extra):
+def _build(tmp_path, extra, prog="chan_select_host"):
     if shutil.which("g++") is None:
         pytest.skip("no g++")
-    exe = str(tmp_path / "chan_select_host")
+    exe = str(tmp_path / prog)
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall"] + extra +
-                          ["-I" + os.path.join(ROOT, "osmo-gmr_amd", "csrc"), os.path.join(ROOT, "tests", "c", "chan_select_host.cpp"),
+                          ["-I" + os.path.join(ROOT, "osmo-gmr_amd", "csrc"), os.path.join(ROOT, "tests", "c", prog + ".cpp"),
                            "-o", exe])
     return exe
 
@@ -201,15 +201,19 @@ def test_direct_mode_search_over_the_10_khz_raster(tmp_path):
     """0.5 .. 8 Msps in steps of 10 kHz x sps 1 .. 16: the accepted plan with the widest two-outputs-per-lane window, the
     accepted plan with the widest window on the 96-tap bank, and the refused plans nearest above either window.  No plan of
     the 30-tap bank is refused anywhere on the raster (the program's "short_refused" line says so: -1), so three plans, not
-    four, join the GPU grid (chan_grid_cases.DDC_SEARCH)."""
+    four, join the GPU grid (chan_grid_cases.DDC_SEARCH).  The steps and banks the rule is fed are the library's own
+    (csrc/chan_plan.h through tests/c/chan_plan_host.cpp, which tests/test_chan_plan_host.py holds to chan_grid_cases): every
+    plan it makes and every plan it refuses for its span."""
     exe = _build(tmp_path, [])
+    cells = [(r * 10000.0, sps) for r in range(50, 801) for sps in range(1, 17)]
+    plans = _run(_build(tmp_path, [], "chan_plan_host"), ["ddc"], "".join("%.1f %d\n" % c for c in cells)).splitlines()
+    assert len(plans) == len(cells)
     lines = []
-    for r in range(50, 801):
-        fs = r * 10000.0
-        for sps in range(1, 17):
-            d = cg.direct_numbers(fs, sps)
-            if d is not None:
-                lines.append("%d %d %d %d %d" % (int(fs), sps, d[2].numerator, d[2].denominator, 30 if d[3] <= 30 else 96))
+    for (fs, sps), ln in zip(cells, plans):
+        head, _, text = ln.partition(" | ")
+        w = head.split()
+        if w[0] == "ok" or " spans " in text:
+            lines.append("%d %d %s %s %s" % (int(fs), sps, w[3], w[4], w[6]))
     out = _run(exe, ["search"], "\n".join(lines) + "\n")
     print(out)
     found = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in out.splitlines()}
