@@ -167,9 +167,11 @@ def facch3_encode(l2, bits_s, ciph=None):
     return out
 
 
-def facch3_decode(ebits):
+def facch3_decode(ebits, ciph=None):
     ebits = np.ascontiguousarray(ebits, np.int8).reshape(-1, 416)
     n = ebits.shape[0]
+    if ciph is not None:
+        ciph = np.ascontiguousarray(ciph, np.uint8).reshape(n, 384)
     l2 = np.zeros((n, 10), np.uint8)
     s = np.zeros((n, 32), np.uint8)
     crc = np.zeros(n, np.int32)
@@ -178,7 +180,8 @@ def facch3_decode(ebits):
     f.restype = C.c_int
     cv = C.c_int()
     for i in range(n):
-        crc[i] = f(_p(l2[i], C.c_uint8), _p(s[i], C.c_uint8), _p(ebits[i], C.c_int8), None, C.byref(cv))
+        crc[i] = f(_p(l2[i], C.c_uint8), _p(s[i], C.c_uint8), _p(ebits[i], C.c_int8),
+                   None if ciph is None else _p(ciph[i], C.c_uint8), C.byref(cv))
         conv[i] = cv.value
     return l2, s, crc, conv
 
