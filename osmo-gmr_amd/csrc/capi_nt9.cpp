@@ -1,8 +1,7 @@
 // capi_nt9.cpp -- C ABI of the NT9 burst decoders: FACCH9 (reference include/osmocom/gmr1/l1/facch9.h:39-41)
-// and TCH9 (include/osmocom/gmr1/l1/tch9.h:40-53).  The host builds, once per kind, the map that tells the
-// kernel where the soft bit of every coded bit of every trellis step sits in the burst (puncturing,
-// intra- and inter-burst de-interleaving, descrambling, demultiplexing folded together); everything per
-// burst runs on the GPU.
+// and TCH9 (include/osmocom/gmr1/l1/tch9.h:40-53).  The map that tells the kernel where the soft bit of every coded
+// bit of every trellis step sits in the burst is nt9_map.h's, built from l1_codes.h; this file uploads it once per
+// kind and device.  Everything per burst runs on the GPU.
 
 #include "capi_common.h"
 
@@ -13,86 +12,11 @@
 #include "../../include/osmocom/gmr1/l1/facch9.h"
 #include "../../include/osmocom/gmr1/l1/interleave.h"
 #include "../../include/osmocom/gmr1/l1/tch9.h"
+#include "nt9_map.h"
 
 using namespace gmr1;
 
 namespace {
-
-struct Punct { int r, L, N; uint8_t mask[15]; };       // mask 0 = punctured (punct.c)
-const Punct k5_12_P23 = {2, 3, 2, {0, 1, 1, 0, 1, 1}};
-const Punct k5_12_P25 = {2, 5, 2, {1, 0, 1, 1, 1, 0, 1, 1, 1, 1}};
-const Punct k5_12_Ps25 = {2, 5, 2, {1, 1, 1, 1, 1, 0, 1, 1, 1, 0}};
-const Punct k5_13_P25 = {2, 5, 3, {1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1, 1, 1, 0, 1}};
-const Punct k5_13_P15 = {1, 5, 3, {1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}};
-const Punct k5_13_Ps15 = {1, 5, 3, {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 1}};
-const Punct k5_15_P23 = {2, 3, 5, {1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0}};
-const Punct k5_15_P53 = {5, 3, 5, {1, 1, 1, 0, 1, 1, 0, 0, 1, 1, 1, 1, 1, 0, 0}};
-const Punct k5_15_Ps53 = {5, 3, 5, {1, 1, 1, 0, 0, 1, 0, 0, 1, 1, 1, 1, 1, 0, 1}};
-
-// gmr1_puncturer_generate (punct.c:48-133): punctured[ii] for the cl unpunctured coded bits
-std::vector<uint8_t> punctured_bits(int cl, int N, const Punct *pre, const Punct *mn, const Punct *post, int repeat)
-{
-	std::vector<uint8_t> p(cl, 0);
-	int ii = 0, lim = cl;
-	if (pre)
-		for (int ip = 0; ii < lim && ip < pre->L * N; ii++, ip++)
-			if (!pre->mask[ip]) p[ii] = 1;
-	if (post)
-		lim -= post->L * N;
-	for (int i = 0; i < repeat; i++)
-		for (int ip = 0; ii < lim && ip < mn->L * N; ii++, ip++)
-			if (!mn->mask[ip]) p[ii] = 1;
-	if (post) {
-		ii = lim;
-		for (int ip = 0; ii > 0 && ip < post->L * N && ii < cl; ii++, ip++)
-			if (!post->mask[ip]) p[ii] = 1;
-	}
-	return p;
-}
-
-struct Nt9Kind { int N, len, l2_bytes, intra, x_off, inter; };
-const Nt9Kind kKinds[4] = {
-	{5, 144, 18, 81, 0, 1},     // TCH9 2k4: k5_15, tch9.c:56-62
-	{3, 240, 30, 81, 0, 1},     // TCH9 4k8: k5_13, tch9.c:64-70
-	{2, 480, 60, 81, 0, 1},     // TCH9 9k6: k5_12, tch9.c:72-78
-	{2, 316, 38, 80, 4, 0},     // FACCH9:   k5_12 len 316, facch9.c:42-48, 4 + 4 pad bits
-};
-
-std::vector<uint32_t> build_map(int kind)
-{
-	const Nt9Kind &kd = kKinds[kind];
-	const int S = kd.len + 4, cl = S * kd.N;
-	std::vector<uint8_t> punct(cl, 0);
-	if (kind == 0) punct = punctured_bits(cl, 5, &k5_15_P53, &k5_15_P23, &k5_15_Ps53, 41);
-	if (kind == 1) punct = punctured_bits(cl, 3, &k5_13_P15, &k5_13_P25, &k5_13_Ps15, 41);
-	if (kind == 2) punct = punctured_bits(cl, 2, &k5_12_P25, &k5_12_P23, &k5_12_Ps25, 158);
-	// scrambler over the 648 positions of bits_epp_x (scramb.c:39-52)
-	bool scr[648];
-	{
-		uint16_t r = 0x4d4b;
-		for (int i = 0; i < 648; i++) {
-			const uint32_t b = ((r >> 14) ^ r) & 1u;
-			r = (uint16_t)((r << 1) | b);
-			scr[i] = b != 0;
-		}
-	}
-	std::vector<uint32_t> map(cl);
-	int q = 0;                                   // index into bits_c (the sent coded bits)
-	for (int ii = 0; ii < cl; ii++) {
-		if (punct[ii]) {
-			map[ii] = 0x80000000u;
-			continue;
-		}
-		// bits_c[q] = ep[intra * ((5 q) & 7) + (q >> 3)]   (gmr1_deinterleave_intra, interleave.c:73-87)
-		const int xi = kd.intra * ((5 * q) & 7) + (q >> 3) + kd.x_off;
-		const int back = kd.inter ? 2 - (xi % 3) : 0;      // gmr1_deinterleave_inter, N = 3 (interleave.c:163-186)
-		const int mi = xi < 52 ? xi : xi + 10;             // bits_my: 52 | sacch 10 | 596
-		const int ei = mi < 52 ? mi : mi + 4;              // bits_e:  52 | status 4 | 606
-		map[ii] = (uint32_t)ei | (scr[xi] ? 0x400u : 0u) | ((uint32_t)mi << 11) | ((uint32_t)back << 21);
-		q++;
-	}
-	return map;
-}
 
 std::mutex g_mu;
 struct DevMap { int device; int kind; uint32_t *d; };
@@ -108,7 +32,7 @@ int get_map(int kind, const uint32_t **out)
 			*out = m.d;
 			return 0;
 		}
-	const std::vector<uint32_t> map = build_map(kind);
+	const std::vector<uint32_t> map = nt9_build_map(kind);
 	uint32_t *d = nullptr;
 	HIP_TRY(hipMalloc(&d, map.size() * 4));
 	HIP_TRY(hipMemcpy(d, map.data(), map.size() * 4, hipMemcpyHostToDevice));
@@ -166,8 +90,8 @@ int nt9_kind_args(int kind, Nt9Args *a)
 	const uint32_t *map;
 	int r = get_map(kind, &map);
 	if (r) return r;
-	a->kind = kind; a->conv_acc = conv_acc(); a->N = kKinds[kind].N; a->len = kKinds[kind].len;
-	a->map = map; a->l2_bytes = kKinds[kind].l2_bytes;
+	a->kind = kind; a->conv_acc = conv_acc(); a->N = kNt9Kinds[kind].N; a->len = kNt9Kinds[kind].len;
+	a->map = map; a->l2_bytes = kNt9Kinds[kind].l2_bytes;
 	return 0;
 }
 }  // namespace gmr1
@@ -185,7 +109,7 @@ int nt9_host(int kind, int n, int seq_len, const int8_t *ebits, const uint8_t *c
 		return fail(-EINVAL, "nt9: ebits / l2 are required");
 	if (kind < 0 || kind > 3)
 		return fail(-EINVAL, "nt9: mode %d unknown", kind);
-	const int nb = kKinds[kind].l2_bytes;
+	const int nb = kNt9Kinds[kind].l2_bytes;
 	Stage sg;
 	const int8_t *d_e = sg.in(ebits, (size_t)n * 662);
 	const uint8_t *d_c = sg.in(ciph, (size_t)n * 658);

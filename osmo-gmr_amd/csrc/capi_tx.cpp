@@ -4,8 +4,10 @@
 //
 // The host's part is to write each chain down ONCE as an EncPlan -- the position map from payload bits to burst
 // bits (CRC tables, trellis-step windows, puncturing, interleavers, scrambler, multiplexing; the structure follows
-// the reference's encoders line by line, in index space instead of on data).  Every bit of every burst is then
-// computed on the GPU by k_encode (tx_kernels.hip); there is no CPU path.
+// the reference's encoders line by line, in index space instead of on data).  The codes themselves -- polynomials,
+// CRCs, puncturing masks and the puncturer, scrambler, interleaver positions -- are l1_codes.h's, the description the
+// decoders' tables are made from.  Every bit of every burst is then computed on the GPU by k_encode (tx_kernels.hip);
+// there is no CPU path.
 
 #include "capi_common.h"
 
@@ -25,6 +27,7 @@
 #include "../../include/osmocom/gmr1/l1/tch9.h"
 #include "../../include/osmocom/gmr1/l1/xch_dc12.h"
 #include "../../include/osmocom/gmr1/sdr/pi4cxpsk.h"
+#include "nt9_map.h"
 
 using namespace gmr1;
 
@@ -79,17 +82,11 @@ struct Builder {
 
 	// CRC of `n` payload-sourced bits (osmo_crcXXgen_set_bits, init 0 / no final xor: crc.c:36-63): the register is the
 	// xor of one table entry per set bit
-	void crc_table(uint16_t *tab, int bits, uint32_t poly, const std::vector<uint16_t> &src)
+	void crc_table(uint16_t *tab, const l1c::Crc &c, const std::vector<uint16_t> &src)
 	{
 		const int n = (int)src.size();
-		const uint32_t top = 1u << (bits - 1), mask = (top << 1) - 1;
-		for (int k = 0; k < n; k++) {
-			uint32_t crc = top;                                   // the unit vector's only set bit enters here
-			crc = ((crc << 1) ^ poly) & mask;
-			for (int i = k + 1; i < n; i++)
-				crc = ((crc & top) ? ((crc << 1) ^ poly) : (crc << 1)) & mask;
-			tab[src[k]] ^= (uint16_t)crc;
-		}
+		for (int k = 0; k < n; k++)
+			tab[src[k]] ^= (uint16_t)l1c::crc_unit(c, k, n);
 	}
 
 	// extended information word of one code: [K-1 preset | info | K-1 flush zeros]; returns the offset of step 0's window
@@ -170,19 +167,16 @@ Bits interleave_intra(const Bits &in, int off, int N)
 {
 	Bits out(8 * N);
 	for (int kc = 0; kc < 8 * N; kc++)
-		out[N * ((5 * kc) & 7) + (kc >> 3)] = in[off + kc];
+		out[l1c::intra_pos(N, kc)] = in[off + kc];
 	return out;
 }
 
-// gmr1_scramble_ubit (scramb.c:39-52, 83-93): 15-bit LFSR 0x4d4b, restarted for every call
+// gmr1_scramble_ubit (scramb.c:39-52, 83-93): the LFSR is restarted for every call
 void scramble(Bits &b, int off, int n)
 {
-	uint16_t r = 0x4d4b;
-	for (int i = 0; i < n; i++) {
-		const int bit = ((r >> 14) ^ r) & 1;
-		r = (uint16_t)((r << 1) | bit);
-		b[off + i].scr ^= bit;
-	}
+	l1c::Scrambler g;
+	for (int i = 0; i < n; i++)
+		b[off + i].scr ^= (int)g.next();
 }
 
 void cipher(Bits &b, int off, int n, int c0)
@@ -201,14 +195,9 @@ std::vector<uint16_t> lsb_bits(int first, int n)
 	return v;
 }
 
-const unsigned k5_12[2] = {0x19, 0x17};                          // conv.c:123-128
-const unsigned k5_13[3] = {0x15, 0x1b, 0x1f};                    // conv.c:148-154
-const unsigned k5_14[4] = {0x19, 0x17, 0x15, 0x1f};              // conv.c:174-181
-const unsigned k5_15[5] = {0x15, 0x1b, 0x1f, 0x1d, 0x17};        // conv.c:201-209
-const unsigned k9_13[3] = {0x1ed, 0x19b, 0x127};                 // conv.c:345-351
-const unsigned k7_tch3[2] = {0x6d, 0x4f};                        // conv.c:518-523
-
-Code make_code(int N, int K, int len, bool tb, const unsigned *polys)
+// a code of l1_codes.h's polynomials (N of them) over `len` information bits
+template <int N>
+Code make_code(int K, int len, bool tb, const unsigned (&polys)[N])
 {
 	Code c;
 	c.N = N; c.K = K; c.len = len; c.tail_biting = tb;
@@ -217,11 +206,20 @@ Code make_code(int N, int K, int len, bool tb, const unsigned *polys)
 	return c;
 }
 
-// 192 information bits + CRC16 (crc.c:58-63, poly 0x1021): BCCH, CCCH, xCH
+// per unpunctured coded bit of `c`: 1 = not sent, `mn` repeated over the whole stream (gmr1_puncturer_generate with
+// repeat 0 and no first / last block: tch3.c:48, xch_dc12.c:52)
+template <int M>
+void puncture_all(Code &c, const l1c::Punct<M> &mn)
+{
+	c.punct.assign((size_t)(c.len + (c.tail_biting ? 0 : c.K - 1)) * c.N, 0);
+	l1c::punctured_bits(c.punct.data(), (int)c.punct.size(), l1c::kNoScheme, l1c::scheme(mn), l1c::kNoScheme, 0);
+}
+
+// 192 information bits + CRC16 (crc.c:58-63): BCCH, CCCH, xCH
 std::vector<uint16_t> info_crc16(Builder &b, int n_bits)
 {
 	std::vector<uint16_t> info = lsb_bits(0, n_bits);
-	b.crc_table(b.P.crc_tab, 16, 0x1021, info);
+	b.crc_table(b.P.crc_tab, l1c::kCrc16, info);
 	for (int i = 0; i < 16; i++)
 		info.push_back(crc_a(15 - i));
 	return info;
@@ -234,7 +232,7 @@ enum PlanId { kPlBcch = 0, kPlCcch, kPlFacch3, kPlTch3M0, kPlTch3M1, kPlFacch9, 
 void plan_bcch_ccch(Builder &b, bool ccch)          // bcch.c:60-81, ccch.c:60-83
 {
 	b.P.n_in0 = 24;
-	const Code c = make_code(2, 5, 208, false, k5_12);
+	const Code c = make_code(5, 208, false, l1c::kK5_12);
 	const int base = b.add_word(5, false, info_crc16(b, 192));
 	const Bits coded = b.conv(c, base);                            // 424
 	const Bits il = interleave_intra(coded, 0, 53);
@@ -251,7 +249,7 @@ void plan_facch3(Builder &b)                        // facch3.c:65-116
 	b.P.n_in0 = 10;
 	b.P.n_aux0 = 32;
 	b.P.n_ciph = 384;
-	const Code c = make_code(4, 5, 92, false, k5_14);
+	const Code c = make_code(5, 92, false, l1c::kK5_14);
 	const int base = b.add_word(5, false, info_crc16(b, 76));
 	const Bits coded = b.conv(c, base);                            // 384
 	Bits cp(384);
@@ -270,21 +268,13 @@ void plan_facch3(Builder &b)                        // facch3.c:65-116
 	b.finish(e);
 }
 
-int tch3_perm(int kc)                               // tch3.c:60-76 (position of coded bit kc in the frame's 104 bits)
-{
-	const int ii = kc % 24, ij = kc / 24;
-	return ii < 8 ? ij + 5 * ii : ij + 4 * ii + 8;
-}
-
 void plan_tch3(Builder &b, int m)                   // tch3.c:78-118 with the conv_encode arguments the right way round
 {
 	b.P.n_in0 = 20;                                                // frame0 | frame1
 	b.P.n_aux0 = 4;
 	b.P.n_ciph = 208;
-	Code c = make_code(2, 7, 48, true, k7_tch3);
-	c.punct.assign(96, 0);
-	for (int i = 0; i < 24; i++)
-		c.punct[4 * i + 3] = 1;                                    // P(1;2), punct.c:239-248
+	Code c = make_code(7, 48, true, l1c::kTch3);
+	puncture_all(c, l1c::k5_12_P12);                               // P(1;2), punct.c:239-248
 	Bits epp(208);
 	for (int f = 0; f < 2; f++) {
 		std::vector<uint16_t> cls1(48), cls2(32);
@@ -297,7 +287,7 @@ void plan_tch3(Builder &b, int m)                   // tch3.c:78-118 with the co
 		append(cb, raw, 0, 32);                                    // 104
 		Bits ep(104);
 		for (int kc = 0; kc < 104; kc++)
-			ep[tch3_perm(kc)] = cb[kc];
+			ep[l1c::tch3_pos(kc)] = cb[kc];
 		for (int j = 0; j < 104; j++)
 			epp[m ? 104 * f + j : 2 * j + f] = ep[j];
 	}
@@ -309,34 +299,6 @@ void plan_tch3(Builder &b, int m)                   // tch3.c:78-118 with the co
 		e.push_back(aux_bit(j));
 	append(e, epp, 52, 156);
 	b.finish(e);
-}
-
-struct Punct { int L; uint8_t mask[15]; };          // mask 0 = punctured (punct.c)
-const Punct P12_23 = {3, {0, 1, 1, 0, 1, 1}}, P12_25 = {5, {1, 0, 1, 1, 1, 0, 1, 1, 1, 1}}, P12_s25 = {5, {1, 1, 1, 1, 1, 0, 1, 1, 1, 0}};
-const Punct P13_25 = {5, {1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1, 1, 1, 0, 1}}, P13_15 = {5, {1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}},
-            P13_s15 = {5, {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 1}};
-const Punct P15_23 = {3, {1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1, 1, 1, 1, 0}}, P15_53 = {3, {1, 1, 1, 0, 1, 1, 0, 0, 1, 1, 1, 1, 1, 0, 0}},
-            P15_s53 = {3, {1, 1, 1, 0, 0, 1, 0, 0, 1, 1, 1, 1, 1, 0, 1}};
-
-// gmr1_puncturer_generate (punct.c:48-133) as a flag per unpunctured coded bit
-std::vector<uint8_t> puncture(int cl, int N, const Punct *pre, const Punct *mn, const Punct *post, int repeat)
-{
-	std::vector<uint8_t> p(cl, 0);
-	int ii = 0, lim = cl;
-	if (pre)
-		for (int ip = 0; ii < lim && ip < pre->L * N; ii++, ip++)
-			if (!pre->mask[ip]) p[ii] = 1;
-	if (post)
-		lim -= post->L * N;
-	for (int i = 0; i < repeat; i++)
-		for (int ip = 0; ii < lim && ip < mn->L * N; ii++, ip++)
-			if (!mn->mask[ip]) p[ii] = 1;
-	if (post) {
-		ii = lim;
-		for (int ip = 0; ii > 0 && ip < post->L * N && ii < cl; ii++, ip++)
-			if (!post->mask[ip]) p[ii] = 1;
-	}
-	return p;
 }
 
 // the NT9 burst around 648 coded positions: scramble, SACCH, cipher, status (facch9.c:84-103, tch9.c:114-136)
@@ -363,7 +325,7 @@ void nt9_finish(Builder &b, Bits &x)
 void plan_facch9(Builder &b)                        // facch9.c:60-104
 {
 	b.P.n_in0 = 38;
-	const Code c = make_code(2, 5, 316, false, k5_12);
+	const Code c = make_code(5, 316, false, l1c::kK5_12);
 	const int base = b.add_word(5, false, info_crc16(b, 300));
 	const Bits coded = b.conv(c, base);                            // 640
 	const Bits il = interleave_intra(coded, 0, 80);
@@ -375,15 +337,13 @@ void plan_facch9(Builder &b)                        // facch9.c:60-104
 
 void plan_tch9(Builder &b, int mode)                // tch9.c:56-79, 81-137
 {
-	static const int len[3] = {144, 240, 480}, N[3] = {5, 3, 2};
-	Code c = make_code(N[mode], 5, len[mode], false, mode == 0 ? k5_15 : mode == 1 ? k5_13 : k5_12);
-	const int cl = (len[mode] + 4) * N[mode];
-	if (mode == 0) c.punct = puncture(cl, 5, &P15_53, &P15_23, &P15_s53, 41);
-	if (mode == 1) c.punct = puncture(cl, 3, &P13_15, &P13_25, &P13_s15, 41);
-	if (mode == 2) c.punct = puncture(cl, 2, &P12_25, &P12_23, &P12_s25, 158);
-	b.P.n_in0 = len[mode] / 8;
+	const int len = kNt9Kinds[mode].len;
+	Code c = mode == 0 ? make_code(5, len, false, l1c::kK5_15)
+	       : mode == 1 ? make_code(5, len, false, l1c::kK5_13) : make_code(5, len, false, l1c::kK5_12);
+	c.punct = nt9_punctured(mode);
+	b.P.n_in0 = len / 8;
 	b.P.depth = 3;
-	const int base = b.add_word(5, false, lsb_bits(0, len[mode]));
+	const int base = b.add_word(5, false, lsb_bits(0, len));
 	const Bits coded = b.conv(c, base);
 	if (coded.size() != 648)
 		abort();
@@ -398,15 +358,15 @@ void plan_rach(Builder &b)                          // rach.c:44-66, 78-136
 	b.P.n_in0 = 18;
 	b.P.n_in1 = 1;                                                 // the SB mask rides as payload byte 18
 	const std::vector<uint16_t> u1 = lsb_bits(0, 16), u2 = lsb_bits(16, 123);
-	b.crc_table(b.P.crc_tab, 8, 0x9b, u1);                         // crc.c:36-44
+	b.crc_table(b.P.crc_tab, l1c::kCrc8, u1);                      // crc.c:36-44
 	for (int i = 0; i < 8; i++)
 		b.P.crc_tab[144 + i] ^= (uint16_t)(1u << i);               // crc bit ^= sb_mask bit, rach.c:104-105
-	b.crc_table(b.P.crc_tab2, 12, 0x80f, u2);                      // crc.c:46-54
+	b.crc_table(b.P.crc_tab2, l1c::kCrc12, u2);                    // crc.c:46-54
 	std::vector<uint16_t> info = u2;
 	for (int i = 0; i < 12; i++) info.push_back(crc_b(11 - i));
 	info.insert(info.end(), u1.begin(), u1.end());
 	for (int i = 0; i < 8; i++) info.push_back(crc_a(7 - i));      // 159
-	Code c = make_code(4, 5, 159, false, k5_14);
+	Code c = make_code(5, 159, false, l1c::kK5_14);
 	c.punct.assign(163 * 4, 0);
 	for (int i = 0; i < 135; i++)
 		c.punct[4 * i + 2] = c.punct[4 * i + 3] = 1;
@@ -430,14 +390,9 @@ void plan_rach(Builder &b)                          // rach.c:44-66, 78-136
 
 void plan_xch(Builder &b)                           // xch_dc12.c:45-54, 64-84
 {
-	static const uint8_t p1213[39] = {                             // gmr1_punct_k9_13_P1213, punct.c:1105-1125
-		1, 1, 0, 1, 0, 1, 0, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1, 1, 1, 1, 1,
-	};
 	b.P.n_in0 = 24;
-	Code c = make_code(3, 9, 208, true, k9_13);
-	c.punct.assign(624, 0);
-	for (int ii = 0; ii < 624; ii++)
-		c.punct[ii] = p1213[ii % 39] == 0;
+	Code c = make_code(9, 208, true, l1c::kK9_13);
+	puncture_all(c, l1c::k9_13_P1213);                             // punct.c:1105-1125
 	const int base = b.add_word(9, true, info_crc16(b, 192));
 	const Bits coded = b.conv(c, base);                            // 432
 	Bits e = interleave_intra(coded, 0, 54);
@@ -669,15 +624,12 @@ int bitmap_host(int n_in, int n_out, int soft, const void *in, const std::vector
 	return sg.fetch();
 }
 
-std::vector<uint8_t> scramble_mask(int len)         // scramb.c:39-52: 15-bit LFSR, seed 0x4d4b
+std::vector<uint8_t> scramble_mask(int len)         // scramb.c:39-52
 {
 	std::vector<uint8_t> m((size_t)(len > 0 ? len : 0));
-	uint16_t r = 0x4d4b;
-	for (int i = 0; i < len; i++) {
-		const int b = ((r >> 14) ^ r) & 1;
-		r = (uint16_t)((r << 1) | b);
-		m[i] = (uint8_t)b;
-	}
+	l1c::Scrambler g;
+	for (uint8_t &b : m)
+		b = (uint8_t)g.next();
 	return m;
 }
 
@@ -895,7 +847,7 @@ void gmr1_interleave_intra(void *out, const void *in, int N)
 	if (N < 0) { (void)fail(-EINVAL, "gmr1_interleave_intra: N < 0"); return; }
 	std::vector<int32_t> perm((size_t)8 * N);
 	for (int kc = 0; kc < 8 * N; kc++)
-		perm[N * ((5 * kc) & 7) + (kc >> 3)] = kc;                 // interleave.c:48-61
+		perm[l1c::intra_pos(N, kc)] = kc;                          // interleave.c:48-61
 	(void)bitmap_host(8 * N, 8 * N, 0, in, &perm, nullptr, out, "gmr1_interleave_intra");
 }
 
@@ -904,7 +856,7 @@ void gmr1_deinterleave_intra(void *out, const void *in, int N)
 	if (N < 0) { (void)fail(-EINVAL, "gmr1_deinterleave_intra: N < 0"); return; }
 	std::vector<int32_t> perm((size_t)8 * N);
 	for (int kc = 0; kc < 8 * N; kc++)
-		perm[kc] = N * ((5 * kc) & 7) + (kc >> 3);                 // interleave.c:73-87
+		perm[kc] = l1c::intra_pos(N, kc);                          // interleave.c:73-87
 	(void)bitmap_host(8 * N, 8 * N, 0, in, &perm, nullptr, out, "gmr1_deinterleave_intra");
 }
 

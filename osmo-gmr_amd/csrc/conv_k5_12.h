@@ -2,6 +2,7 @@
 // syndromes, the demodulator's soft-bit tables), branch metrics, the 16-state K=5 rate-1/2 Viterbi decoders
 // (decode4_k5_12: four bursts a wave; decode1_k5_12_lat: one burst, latency shape), survivor walk + CRC16, L2 store.
 #pragma once
+#include "l1_codes.h"
 #include "wave_ops.h"
 
 namespace gmr1 {
@@ -17,22 +18,15 @@ struct StepTable { uint32_t w[2][kSteps12]; };
 static constexpr StepTable make_steps()
 {
 	StepTable t{};
+	const auto scr = l1c::scramble_seq<448>();        // scrambling sequence over the e-bit positions
 	for (int chain = 0; chain < 2; chain++) {
 		const int off = chain ? 4 : 0;
-		// scrambling sequence over the e-bit positions
-		bool scr[448] = {};
-		uint16_t r = 0x4d4b;
-		for (int i = 0; i < 448; i++) {
-			uint32_t b = ((r >> 14) ^ r) & 1u;
-			r = (uint16_t)((r << 1) | b);
-			scr[i] = b != 0;
-		}
 		for (int k = 0; k < kSteps12; k++) {
 			uint32_t w = 0;
 			for (int j = 0; j < 2; j++) {
 				const int kc = 2 * k + j;
-				const int ei = 53 * ((5 * kc) & 7) + (kc >> 3) + off;
-				w |= ((uint32_t)ei | (scr[ei] ? 0x400u : 0u)) << (16 * j);
+				const int ei = l1c::intra_pos(53, kc) + off;
+				w |= ((uint32_t)ei | (scr.bit[ei] ? 0x400u : 0u)) << (16 * j);
 			}
 			t.w[chain][k] = w;
 		}
@@ -91,17 +85,13 @@ constexpr uint32_t kAccLeadK5r2 = 127u * 2u * 5u / 2u;
 struct SynTable { uint16_t s[208]; };
 static constexpr SynTable make_syn()
 {
-	// CRC16 (poly 0x1021, init 0; reference src/l1/crc.c:58-63) is linear: the
+	// CRC16 (init 0; reference src/l1/crc.c:58-63) is linear: the
 	// check word of 192 message bits is the XOR of s[k] over the set bits k.
 	// s[192+i] folds the received CRC bit i (MSB first) in, so that the XOR over
 	// all 208 decoded bits is zero iff the check passes.
 	SynTable t{};
-	for (int k = 0; k < 192; k++) {
-		uint32_t crc = 0x8000u;
-		for (int i = k; i < 192; i++)
-			crc = (crc & 0x8000u) ? (((crc << 1) ^ 0x1021u) & 0xffffu) : ((crc << 1) & 0xffffu);
-		t.s[k] = (uint16_t)crc;
-	}
+	for (int k = 0; k < 192; k++)
+		t.s[k] = (uint16_t)l1c::crc_unit(l1c::kCrc16, k, 192);
 	for (int i = 0; i < 16; i++)
 		t.s[192 + i] = (uint16_t)(1u << (15 - i));
 	return t;
@@ -183,8 +173,9 @@ __device__ __attribute__((aligned(16))) const SbLut g_sb_lut1 = make_sb_lut1();
 // K=5 rate-1/2 code (g0 = 1+D^3+D^4, g1 = 1+D+D^2+D^4; reference src/l1/conv.c:123-145)
 __device__ __forceinline__ uint32_t out_k5_12(uint32_t s, uint32_t b)
 {
+	constexpr uint32_t g0 = l1c::kK5_12[0], g1 = l1c::kK5_12[1];
 	uint32_t reg = (s << 1) | b;
-	return ((uint32_t)(__popc(reg & 0x19u) & 1) << 1) | (uint32_t)(__popc(reg & 0x17u) & 1);
+	return ((uint32_t)(__popc(reg & g0) & 1) << 1) | (uint32_t)(__popc(reg & g1) & 1);
 }
 __device__ __forceinline__ uint32_t rotl4(uint32_t x, int r) { return ((x << r) | (x >> (4 - r))) & 15u; }
 
@@ -298,11 +289,7 @@ constexpr uint32_t kSentinel = 0xF0000000u;
 struct DecTable { uint32_t v[16]; };
 static constexpr uint32_t dec_out(uint32_t s, uint32_t b)
 {
-	const uint32_t reg = (s << 1) | b;
-	uint32_t p0 = reg & 0x19u, p1 = reg & 0x17u;
-	p0 ^= p0 >> 4; p0 ^= p0 >> 2; p0 ^= p0 >> 1;
-	p1 ^= p1 >> 4; p1 ^= p1 >> 2; p1 ^= p1 >> 1;
-	return ((p0 & 1u) << 1) | (p1 & 1u);
+	return l1c::conv_word(l1c::kK5_12, (s << 1) | b);
 }
 // the predecessor state a row location holds in phase ph (loc in the basis {8, 7, 2, 1})
 static constexpr uint32_t dec_state(uint32_t loc, int ph)

@@ -34,12 +34,8 @@ struct Syn92 { uint16_t s[92]; };
 static constexpr Syn92 make_syn92()
 {
 	Syn92 t{};
-	for (int k = 0; k < 76; k++) {
-		uint32_t crc = 0x8000u;
-		for (int i = k; i < 76; i++)
-			crc = (crc & 0x8000u) ? (((crc << 1) ^ 0x1021u) & 0xffffu) : ((crc << 1) & 0xffffu);
-		t.s[k] = (uint16_t)crc;
-	}
+	for (int k = 0; k < 76; k++)
+		t.s[k] = (uint16_t)l1c::crc_unit(l1c::kCrc16, k, 76);
 	for (int i = 0; i < 16; i++)
 		t.s[76 + i] = (uint16_t)(1u << (15 - i));
 	return t;
@@ -81,15 +77,7 @@ static constexpr int kF3Steps = 96;       // 92 bits + 4 flush
 struct K5r4Tab { uint32_t ov[16]; uint32_t hi[16]; };
 static constexpr uint32_t k5r4_out(uint32_t s, uint32_t b)
 {
-	const uint32_t reg = (s << 1) | b;
-	const uint32_t g[4] = {0x19u, 0x17u, 0x15u, 0x1fu};
-	uint32_t o = 0;
-	for (int i = 0; i < 4; i++) {
-		uint32_t p = reg & g[i];
-		p ^= p >> 4; p ^= p >> 2; p ^= p >> 1;
-		o = (o << 1) | (p & 1u);
-	}
-	return o;
+	return l1c::conv_word(l1c::kK5_14, (s << 1) | b);
 }
 static constexpr K5r4Tab make_k5r4()
 {
@@ -192,7 +180,7 @@ __device__ __forceinline__ void facch3_block(const Facch3Args &a, const uint8_t 
 		for (int j = 0; j < 4; j++) {
 			const int i = 4 * k + j;              // index into bits_c
 			const int burst = i & 3, kc = i >> 2;
-			const int p = 12 * ((5 * kc) & 7) + (kc >> 3);       // position in xmy / ep (0..95)
+			const int p = l1c::intra_pos(12, kc);                // position in xmy / ep (0..95)
 			const int e = p < 22 ? p : p + 8;
 			int v = s_eb[q][104 * burst + e];
 			bool flip = (c_scr.w[p >> 5] >> (p & 31)) & 1u;

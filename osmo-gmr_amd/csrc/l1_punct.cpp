@@ -1,4 +1,5 @@
-// l1_punct.cpp -- gmr1_puncturer_generate (reference src/l1/punct.c:48-133): host code, no GPU involved.
+// l1_punct.cpp -- gmr1_puncturer_generate (reference src/l1/punct.c:48-133): host code, no GPU involved.  The walk over
+// the first / main / last block is l1_codes.h's punctured_bits, the one the GPU path's maps and plans are built with.
 #include <errno.h>
 #include <stdlib.h>
 
@@ -6,6 +7,10 @@
 
 #include <osmocom/gmr1/l1/conv.h>
 #include <osmocom/gmr1/l1/punct.h>
+
+#include "l1_codes.h"
+
+using namespace gmr1;
 
 namespace {
 
@@ -21,6 +26,8 @@ int coded_length(const struct osmo_conv_code *code)
 	return n;
 }
 
+l1c::Scheme scheme(const struct gmr1_puncturer *p) { return p ? l1c::Scheme{p->L * p->N, p->mask} : l1c::kNoScheme; }
+
 }  // namespace
 
 extern "C" int gmr1_puncturer_generate(struct osmo_conv_code *code, const struct gmr1_puncturer *punct_pre,
@@ -34,41 +41,20 @@ extern "C" int gmr1_puncturer_generate(struct osmo_conv_code *code, const struct
 		return -EINVAL;
 
 	const int total = coded_length(code);
-	// the stretch the main scheme covers: what the first and last blocks leave
-	int body_end = total;
-	if (punct_post)
-		body_end -= punct_post->L * N;
-	if (!repeat) {
-		int body = body_end - (punct_pre ? punct_pre->L * N : 0);
-		const int d = punct_main->L * N;
-		repeat = (body + d - 1) / d;
-	}
+	std::vector<uint8_t> flag(total > 0 ? total : 0, 0);
+	l1c::punctured_bits(flag.data(), total, scheme(punct_pre), scheme(punct_main), scheme(punct_post), repeat);
+	size_t n = 0;
+	for (uint8_t f : flag)
+		n += f;
 
-	std::vector<int> out;
-	int pos = 0;
-	if (punct_pre)
-		for (int k = 0; k < punct_pre->L * N && pos < total; k++, pos++)
-			if (punct_pre->mask[k] == 0)
-				out.push_back(pos);
-	for (int r = 0; r < repeat; r++)
-		for (int k = 0; k < punct_main->L * N && pos < body_end; k++, pos++)
-			if (punct_main->mask[k] == 0)
-				out.push_back(pos);
-	if (punct_post) {
-		// the last block starts at body_end wherever the main scheme stopped (the reference's loop guard here is
-		// `position > 0`, punct.c:121-124: kept)
-		pos = body_end;
-		for (int k = 0; k < punct_post->L * N && pos > 0; k++, pos++)
-			if (punct_post->mask[k] == 0)
-				out.push_back(pos);
-	}
-
-	int *p = static_cast<int *>(malloc((out.size() + 1) * sizeof(int)));
+	int *p = static_cast<int *>(malloc((n + 1) * sizeof(int)));
 	if (!p)
 		return -ENOMEM;
-	for (size_t i = 0; i < out.size(); i++)
-		p[i] = out[i];
-	p[out.size()] = -1;
+	n = 0;
+	for (int i = 0; i < total; i++)
+		if (flag[i])
+			p[n++] = i;
+	p[n] = -1;
 	code->puncture = p;
 	return 0;
 }

@@ -7,7 +7,7 @@
 // row, with the packed [metric:16 | window decisions:16] word and the in-place butterfly (masks 8, 7, 2, 1)
 // of decode4_k5_12 (conv_k5_12.h).  What differs between the four is data:
 //
-//   * a per-kind MAP (built on the host, capi_nt9.cpp) that says, for every coded bit of every trellis
+//   * a per-kind MAP (built on the host, nt9_map.h) that says, for every coded bit of every trellis
 //     step, whether it was punctured and otherwise where its soft bit sits in the burst: status / SACCH
 //     demux, [decipher], descramble, TCH9's depth-3 inter-burst de-interleaver (a coded bit may come from
 //     this burst or one of the two before it in the channel's sequence) and the intra-burst de-interleaver
@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "gmr1_dev.h"
+#include "l1_codes.h"
 #include "tch9_follow.h"
 
 namespace gmr1 {
@@ -72,10 +73,7 @@ static constexpr Syn316 make_syn316()
 	for (int k = 0; k < 316; k++) {
 		uint32_t v = 0;
 		if (k < 300) {
-			uint32_t crc = 0x8000u;
-			for (int i = k; i < 300; i++)
-				crc = (crc & 0x8000u) ? (((crc << 1) ^ 0x1021u) & 0xffffu) : ((crc << 1) & 0xffffu);
-			v = crc;
+			v = l1c::crc_unit(l1c::kCrc16, k, 300);
 		} else {
 			v = 1u << (15 - (k - 300));
 		}
@@ -431,13 +429,7 @@ static constexpr uint32_t rach_x2e(int i)      // position in the de-multiplexed
 static constexpr RachMap make_rach_map()
 {
 	RachMap t{};
-	bool scr[494] = {};
-	uint32_t r = 0x4d4bu;
-	for (int i = 0; i < 494; i++) {
-		const uint32_t b = ((r >> 14) ^ r) & 1u;
-		r = ((r << 1) | b) & 0xffffu;
-		scr[i] = b != 0;
-	}
+	const auto scr = l1c::scramble_seq<494>();
 	for (int k = 0; k < kRachSteps; k++) {
 		for (int j = 0; j < 4; j++) {
 			uint32_t e = 0;
@@ -445,14 +437,14 @@ static constexpr RachMap make_rach_map()
 				e = kMapPunct;
 			} else if (k < 135) {
 				const int q = 2 * k + j;                                   // bits_c[0..269] = e2p (N = 33, last 6 as sent)
-				const int i2 = q < 264 ? 33 * ((5 * q) & 7) + (q >> 3) : q;
+				const int i2 = q < 264 ? l1c::intra_pos(33, q) : q;
 				const int xi = 112 + i2;
-				e = rach_x2e(xi) | (scr[xi] ? 0x400u : 0u);
+				e = rach_x2e(xi) | (scr.bit[xi] ? 0x400u : 0u);
 			} else {
 				const int qq = 4 * (k - 135) + j;                          // bits_c[270..381] = e1p (N = 14)
-				const int i1 = 14 * ((5 * qq) & 7) + (qq >> 3);
+				const int i1 = l1c::intra_pos(14, qq);
 				const int xa = i1, xb = i1 + 382;
-				e = rach_x2e(xa) | (scr[xa] ? 0x400u : 0u) | (rach_x2e(xb) << 11) | (scr[xb] ? 0x200000u : 0u) |
+				e = rach_x2e(xa) | (scr.bit[xa] ? 0x400u : 0u) | (rach_x2e(xb) << 11) | (scr.bit[xb] ? 0x200000u : 0u) |
 				    0x400000u;
 			}
 			t.m[4 * k + j] = e;
@@ -471,17 +463,11 @@ static constexpr SynRach make_syn_rach()
 	for (int k = 0; k < kRachLen; k++) {
 		uint32_t v = 0;
 		if (k < 123) {
-			uint32_t crc = 0x800u;
-			for (int i = k; i < 123; i++)
-				crc = (crc & 0x800u) ? (((crc << 1) ^ 0x80fu) & 0xfffu) : ((crc << 1) & 0xfffu);
-			v = crc;
+			v = l1c::crc_unit(l1c::kCrc12, k, 123);
 		} else if (k < 135) {
 			v = 1u << (11 - (k - 123));
 		} else if (k < 151) {
-			uint32_t crc = 0x80u;
-			for (int i = k - 135; i < 16; i++)
-				crc = (crc & 0x80u) ? (((crc << 1) ^ 0x9bu) & 0xffu) : ((crc << 1) & 0xffu);
-			v = crc << 16;
+			v = l1c::crc_unit(l1c::kCrc8, k - 135, 16) << 16;
 		} else {
 			v = (1u << (7 - (k - 151))) << 16;
 		}

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "gmr1_dev.h"
+#include "l1_codes.h"
 #include "wave_ops.h"
 
 namespace gmr1 {
@@ -14,12 +15,9 @@ struct ScrBits { uint32_t w[8]; };
 static constexpr ScrBits make_scr()
 {
 	ScrBits t{};
-	uint16_t r = 0x4d4b;
-	for (int i = 0; i < 256; i++) {
-		uint32_t b = ((r >> 14) ^ r) & 1u;
-		r = (uint16_t)((r << 1) | b);
-		t.w[i >> 5] |= b << (i & 31);
-	}
+	l1c::Scrambler g;
+	for (int i = 0; i < 256; i++)
+		t.w[i >> 5] |= g.next() << (i & 31);
 	return t;
 }
 
@@ -46,8 +44,7 @@ static constexpr T3Map make_t3map()
 	for (int m = 0; m < 2; m++)
 		for (int fr = 0; fr < 2; fr++)
 			for (int kc = 0; kc < 104; kc++) {
-				const int ii = kc % 24, ij = kc / 24;
-				const int kep = (ii < 8) ? (ij + 5 * ii) : (ij + 4 * ii + 8);   // bits_c[kc] = bits_ep[kep]
+				const int kep = l1c::tch3_pos(kc);                               // bits_c[kc] = bits_ep[kep]
 				const int q = m ? (104 * fr + kep) : ((kep << 1) + fr);          // index into epp / xmy
 				const uint32_t flip = (scr.w[q >> 5] >> (q & 31)) & 1u;
 				t.q[m][fr][kc] = (uint16_t)(q | (flip << 8));
@@ -132,11 +129,9 @@ __device__ __forceinline__ int tch3_c(const int8_t *__restrict__ e, const uint8_
 struct K7Tab { uint16_t o[2][32]; uint8_t st[2][32]; uint8_t loc_of[64]; };
 static constexpr uint32_t k7_out(uint32_t s, uint32_t b)
 {
+	constexpr uint32_t g0 = l1c::kTch3[0], g1 = l1c::kTch3[1];    // (as values: k7_pair_mask also runs on the device)
 	const uint32_t reg = (s << 1) | b;
-	uint32_t p0 = reg & 0x6du, p1 = reg & 0x4fu;
-	p0 ^= p0 >> 4; p0 ^= p0 >> 2; p0 ^= p0 >> 1;
-	p1 ^= p1 >> 4; p1 ^= p1 >> 2; p1 ^= p1 >> 1;
-	return ((p0 & 1u) << 1) | (p1 & 1u);
+	return (l1c::parity(reg & g0) << 1) | l1c::parity(reg & g1);
 }
 static constexpr K7Tab make_k7()
 {

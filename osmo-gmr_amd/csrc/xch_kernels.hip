@@ -22,6 +22,7 @@
 // subtracted, a second pass that records; best end state (lowest on ties); the survivor path is read
 // back through 13 chained 16-bit LDS reads (a window's first 8 decisions name the state it started in).
 #include "gmr1_dev.h"
+#include "l1_codes.h"
 
 namespace gmr1 {
 
@@ -42,24 +43,18 @@ struct XchMap { uint16_t m[3 * kXchLen]; };
 static constexpr XchMap make_xch_map()
 {
 	XchMap t{};
-	bool scr[432] = {};
-	uint32_t r = 0x4d4bu;                          // scramb.c:39-52
-	for (int i = 0; i < 432; i++) {
-		const uint32_t b = ((r >> 14) ^ r) & 1u;
-		r = ((r << 1) | b) & 0xffffu;
-		scr[i] = b != 0;
-	}
-	// gmr1_punct_k9_13_P1213 (0 = punctured), repeated by gmr1_puncturer_generate over 624 bits
-	const uint8_t p[39] = {1, 1, 0, 1, 0, 1, 0, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1, 1,
-	                       1, 1, 0, 1, 0, 1, 0, 1, 1, 1, 1, 1};
+	const auto scr = l1c::scramble_seq<432>();     // scramb.c:39-52
+	// gmr1_punct_k9_13_P1213, repeated by gmr1_puncturer_generate over the 624 bits (xch_dc12.c:52)
+	uint8_t punct[3 * kXchLen] = {};
+	l1c::punctured_bits(punct, 3 * kXchLen, l1c::kNoScheme, l1c::scheme(l1c::k9_13_P1213), l1c::kNoScheme, 0);
 	int q = 0;                                     // index into bits_c (the sent coded bits)
 	for (int ii = 0; ii < 3 * kXchLen; ii++) {
-		if (!p[ii % 39]) {
+		if (punct[ii]) {
 			t.m[ii] = 0x8000u;
 			continue;
 		}
-		const int ei = 54 * ((5 * q) & 7) + (q >> 3);    // gmr1_deinterleave_intra, interleave.c:73-87
-		t.m[ii] = (uint16_t)(ei | (scr[ei] ? 0x200 : 0));
+		const int ei = l1c::intra_pos(54, q);          // gmr1_deinterleave_intra, interleave.c:73-87
+		t.m[ii] = (uint16_t)(ei | (scr.bit[ei] ? 0x200 : 0));
 		q++;
 	}
 	return t;
@@ -72,15 +67,9 @@ __constant__ XchMap c_xch_map = make_xch_map();
 //   o[r][loc]   : code word (3 bits) of the own transition per phase, 3 bits each
 //   st[r][loc]  : state held in phase 0;  loc_of[state] = r * 64 + loc
 struct K9Tab { uint32_t o[4][64]; uint8_t st[4][64]; uint8_t loc_of[256]; };
-static constexpr uint32_t parity9(uint32_t v)
-{
-	v ^= v >> 8; v ^= v >> 4; v ^= v >> 2; v ^= v >> 1;
-	return v & 1u;
-}
 static constexpr uint32_t k9_out(uint32_t s, uint32_t b)
 {
-	const uint32_t reg = (s << 1) | b;             // bit i = D^i
-	return (parity9(reg & 0x1edu) << 2) | (parity9(reg & 0x19bu) << 1) | parity9(reg & 0x127u);
+	return l1c::conv_word(l1c::kK9_13, (s << 1) | b);      // bit i = D^i
 }
 static constexpr K9Tab make_k9()
 {
@@ -124,10 +113,7 @@ static constexpr Syn208 make_syn208()
 	for (int k = 0; k < kXchLen; k++) {
 		uint32_t v = 0;
 		if (k < 192) {
-			uint32_t crc = 0x8000u;
-			for (int i = k; i < 192; i++)
-				crc = (crc & 0x8000u) ? (((crc << 1) ^ 0x1021u) & 0xffffu) : ((crc << 1) & 0xffffu);
-			v = crc;
+			v = l1c::crc_unit(l1c::kCrc16, k, 192);
 		} else {
 			v = 1u << (15 - (k - 192));
 		}
