@@ -461,6 +461,43 @@ int gmr1_hip_chan_stream_push(struct gmr1_hip_chan_stream *h, const float *wide,
                               float *out, uint64_t out_stride, uint64_t *n_out);
 int gmr1_hip_chan_stream_destroy(struct gmr1_hip_chan_stream *h);
 
+/* The same front ends on captures as radios and archives hold them: `wide` is interleaved I, Q of the format named by fmt --
+ * GMR1_HIP_IQ_F32 (float, 8 bytes per complex sample), _S16 (int16_t, 4 bytes: a USRP's sc16) or _S8 (int8_t, 2 bytes) -- and
+ * a sample's value is its integer x 2^-15 (S16) or x 2^-7 (S8), so -32768 and -128 are -1.0.  The integers are read by the
+ * first kernel of the chain itself (a quarter or a half of the float's bytes, uploaded by the host forms and read on the
+ * device); only a sample rate off the n_chans x 31.25 kHz grid converts to float first, in front of its pre-resampler.
+ * The conversion is exact, so every output of an _iq call or push sequence is BIT-IDENTICAL to the float entry's on
+ * (float)v x 2^-k, and a streamed integer capture equals the one-shot integer call.  Everything else -- outputs, counts,
+ * strides, refusals, threading, stream ordering, -ENODEV without a device -- is the float entry's, and with GMR1_HIP_IQ_F32 an
+ * _iq entry IS the float entry.  Any other fmt: -EINVAL, before anything is allocated.  `wide` needs the alignment of one
+ * complex sample only (4 bytes S16, 2 bytes S8): a _dev pointer may lie any number of samples into an allocation.
+ * A stream handle has one format for life: _create_iq sets it (the plain _create calls make F32 handles), _push_iq* read
+ * `wide` in it; the float _push* on a handle of another format are refused (-EINVAL, the handle stays as it was).
+ * gmr1_hip_iq_sample_bytes: 8 / 4 / 2 bytes per complex sample, -EINVAL for any other fmt; host arithmetic, no device
+ * needed.  Unsigned (offset-binary) 8-bit samples are not a format: their centre is a convention of the source. */
+enum { GMR1_HIP_IQ_F32 = 0, GMR1_HIP_IQ_S16 = 1, GMR1_HIP_IQ_S8 = 2 };
+int gmr1_hip_iq_sample_bytes(int fmt);
+int gmr1_hip_channelize_iq_dev(void *stream, double samp_rate, int sps, int fmt, const void *wide, uint64_t n_in,
+                               float rotation, int n_sel, const int32_t *chan_idx,
+                               float *out, uint64_t out_stride, uint64_t *n_out);
+int gmr1_hip_channelize_iq(double samp_rate, int sps, int fmt, const void *wide, uint64_t n_in, float rotation,
+                           int n_sel, const int32_t *chan_idx, float *out, uint64_t out_stride, uint64_t *n_out);
+int gmr1_hip_channelize_planar_iq_dev(void *stream, double samp_rate, int sps, int fmt, const void *wide, uint64_t n_in,
+                                      float rotation, int n_sel, const int32_t *chan_idx,
+                                      float *out_planes, uint64_t out_stride, uint64_t plane_stride, uint64_t *n_out);
+int gmr1_hip_ddc_iq_dev(void *stream, double samp_rate, int sps, int fmt, const void *wide, uint64_t n_in, int n_sel,
+                        const double *freq_hz, float *out, uint64_t out_stride, uint64_t *n_out);
+int gmr1_hip_ddc_iq(double samp_rate, int sps, int fmt, const void *wide, uint64_t n_in, int n_sel,
+                    const double *freq_hz, float *out, uint64_t out_stride, uint64_t *n_out);
+int gmr1_hip_channelize_stream_create_iq(double samp_rate, int sps, int fmt, float rotation, int n_sel,
+                                         const int32_t *chan_idx, struct gmr1_hip_chan_stream **h);
+int gmr1_hip_ddc_stream_create_iq(double samp_rate, int sps, int fmt, int n_sel, const double *freq_hz,
+                                  struct gmr1_hip_chan_stream **h);
+int gmr1_hip_chan_stream_push_iq_dev(void *stream, struct gmr1_hip_chan_stream *h, const void *wide, uint64_t n_in,
+                                     float *out, uint64_t out_stride, uint64_t *n_out);
+int gmr1_hip_chan_stream_push_iq(struct gmr1_hip_chan_stream *h, const void *wide, uint64_t n_in,
+                                 float *out, uint64_t out_stride, uint64_t *n_out);
+
 /* ------------------------------------------------------------------------
  * The gmr1_rx receive loop over many BCCH carriers (reference src/gmr1_rx.c:605-895 and
  * main() :897-975, one process per capture file there).

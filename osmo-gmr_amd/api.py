@@ -107,6 +107,16 @@ SIGNATURES = {
     "gmr1_hip_chan_stream_push_dev": (I, P, P, P, U64, P, U64, P),
     "gmr1_hip_chan_stream_push": (I, P, P, U64, P, U64, P),
     "gmr1_hip_chan_stream_destroy": (I, P),
+    "gmr1_hip_iq_sample_bytes": (I, I),
+    "gmr1_hip_channelize_iq_dev": (I, P, D, I, I, P, U64, F, I, P, P, U64, P),
+    "gmr1_hip_channelize_iq": (I, D, I, I, P, U64, F, I, P, P, U64, P),
+    "gmr1_hip_channelize_planar_iq_dev": (I, P, D, I, I, P, U64, F, I, P, P, U64, U64, P),
+    "gmr1_hip_ddc_iq_dev": (I, P, D, I, I, P, U64, I, P, P, U64, P),
+    "gmr1_hip_ddc_iq": (I, D, I, I, P, U64, I, P, P, U64, P),
+    "gmr1_hip_channelize_stream_create_iq": (I, D, I, I, F, I, P, P),
+    "gmr1_hip_ddc_stream_create_iq": (I, D, I, I, I, P, P),
+    "gmr1_hip_chan_stream_push_iq_dev": (I, P, P, P, U64, P, U64, P),
+    "gmr1_hip_chan_stream_push_iq": (I, P, P, U64, P, U64, P),
     "gmr1_hip_rx_run_dev": (I, P, I, I, P, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_run": (I, I, I, P, U64, P, P, P, P, I, P, P, P),
     "gmr1_hip_rx_stream_create": (I, I, I, P, P),
@@ -1245,6 +1255,82 @@ def channelize_planar_dev(stream, wide_ptr, n_in, samp_rate, channels, out_ptr, 
     return no.value
 
 
+# the same on captures as radios and archives hold them (gmr1_hip.h: GMR1_HIP_IQ_*)
+IQ_F32, IQ_S16, IQ_S8 = 0, 1, 2
+_IQ_DTYPES = {IQ_S16: np.int16, IQ_S8: np.int8}
+
+
+def iq_sample_bytes(fmt):
+    """gmr1_hip_iq_sample_bytes: bytes per complex sample of a format (no device needed)"""
+    n = _fn("gmr1_hip_iq_sample_bytes")(fmt)
+    if n < 0:
+        raise Gmr1HipError(f"gmr1_hip_iq_sample_bytes failed with {n}: fmt={fmt}")
+    return n
+
+
+def _iq(wide, fmt=None):
+    """a host capture and its format: (n, 2) int16 / int8 arrays are S16 / S8 (the format is the dtype's), anything else
+    complex64; fmt given: the array must be of that format -> (array, fmt, complex samples)"""
+    a = np.asarray(wide)
+    got = next((f for f, dt in _IQ_DTYPES.items() if a.dtype == dt), IQ_F32)
+    if fmt is not None and fmt != got:
+        raise TypeError("a format %d capture, not dtype %s" % (fmt, a.dtype))
+    if got == IQ_F32:
+        a = _arr(a, np.complex64, -1)
+        return a, got, a.size
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("an integer capture is an (n, 2) array of I, Q, not shape %s" % (a.shape,))
+    a = np.ascontiguousarray(a)
+    return a, got, a.shape[0]
+
+
+def channelize_iq(wide, samp_rate, channels, sps=4, rotation=0.0):
+    """gmr1_hip_channelize_iq: host capture, (n, 2) int16 / int8 or complex64 -> (len(channels), n_out) complex64"""
+    wide, fmt, n = _iq(wide)
+    ch = _arr(channels, np.int32)
+    _, _, n_out = channelize_plan(samp_rate, sps, n)
+    out = np.zeros((ch.size, n_out), np.complex64)
+    no = C.c_uint64()
+    _call("gmr1_hip_channelize_iq", samp_rate, sps, fmt, _p(wide), n, rotation, ch.size, _p(ch), _p(out), n_out, C.byref(no))
+    return out
+
+
+def ddc_iq(wide, samp_rate, freqs_hz, sps=4):
+    """gmr1_hip_ddc_iq: host capture, (n, 2) int16 / int8 or complex64 -> (len(freqs_hz), n_out) complex64"""
+    wide, fmt, n = _iq(wide)
+    freqs = _arr(freqs_hz, np.float64)
+    _, _, _, n_out = ddc_plan(samp_rate, sps, n)
+    out = np.zeros((freqs.size, max(n_out, 1)), np.complex64)
+    got = C.c_uint64()
+    _call("gmr1_hip_ddc_iq", samp_rate, sps, fmt, _p(wide), n, freqs.size, _p(freqs), _p(out), out.shape[1], C.byref(got))
+    return out[:, :got.value]
+
+
+def channelize_iq_dev(stream, fmt, wide_ptr, n_in, samp_rate, channels, out_ptr, out_stride, sps=4, rotation=0.0):
+    ch = _arr(channels, np.int32)
+    no = C.c_uint64()
+    _call("gmr1_hip_channelize_iq_dev", stream, samp_rate, sps, fmt, wide_ptr, n_in, rotation, ch.size, _p(ch), out_ptr,
+          out_stride, C.byref(no))
+    return no.value
+
+
+def channelize_planar_iq_dev(stream, fmt, wide_ptr, n_in, samp_rate, channels, out_ptr, out_stride, plane_stride, sps=4,
+                             rotation=0.0):
+    ch = _arr(channels, np.int32)
+    no = C.c_uint64()
+    _call("gmr1_hip_channelize_planar_iq_dev", stream, samp_rate, sps, fmt, wide_ptr, n_in, rotation, ch.size, _p(ch), out_ptr,
+          out_stride, plane_stride, C.byref(no))
+    return no.value
+
+
+def ddc_iq_dev(stream, fmt, wide_ptr, n_in, samp_rate, freqs_hz, out_ptr, out_stride, sps=4):
+    freqs = _arr(freqs_hz, np.float64)
+    got = C.c_uint64()
+    _call("gmr1_hip_ddc_iq_dev", stream, samp_rate, sps, fmt, wide_ptr, n_in, freqs.size, _p(freqs), out_ptr, out_stride,
+          C.byref(got))
+    return got.value
+
+
 class _LibHandle(_Handle):
     """an opaque handle the library made (self._h), given back to `_destroy_fn` once"""
 
@@ -1257,25 +1343,27 @@ class _LibHandle(_Handle):
 class ChanStream(_LibHandle):
     """gmr1_hip_chan_stream_*: the channelizer (or, from ChanStream.direct, the direct mode) over a capture pushed piece
     by piece.  Each push returns the outputs that have become computable; all pushes' outputs, concatenated per stream, are
-    identical to one channelize() / ddc() call on the samples pushed so far."""
+    identical to one channelize() / ddc() call on the samples pushed so far.  fmt: what the pushes hold (IQ_F32, IQ_S16,
+    IQ_S8), for the handle's life."""
     _destroy_fn = "gmr1_hip_chan_stream_destroy"
 
-    def __init__(self, samp_rate, channels, sps=4, rotation=0.0, _handle=None, _n_sel=None):
+    def __init__(self, samp_rate, channels, sps=4, rotation=0.0, _handle=None, _n_sel=None, fmt=IQ_F32):
         self._h = C.c_void_p()
+        self.fmt = fmt
         if _handle is not None:
             self._h, self.n_sel = _handle, _n_sel
             return
         ch = _arr(channels, np.int32)
-        _call("gmr1_hip_channelize_stream_create", samp_rate, sps, rotation, ch.size, _p(ch), C.byref(self._h))
+        _call("gmr1_hip_channelize_stream_create_iq", samp_rate, sps, fmt, rotation, ch.size, _p(ch), C.byref(self._h))
         self.n_sel = ch.size
 
     @classmethod
-    def direct(cls, samp_rate, freqs_hz, sps=4):
-        """gmr1_hip_ddc_stream_create: the recorder script's direct mode, carriers at freqs_hz from the centre."""
+    def direct(cls, samp_rate, freqs_hz, sps=4, fmt=IQ_F32):
+        """gmr1_hip_ddc_stream_create_iq: the recorder script's direct mode, carriers at freqs_hz from the centre."""
         freqs = _arr(freqs_hz, np.float64)
         h = C.c_void_p()
-        _call("gmr1_hip_ddc_stream_create", samp_rate, sps, freqs.size, _p(freqs), C.byref(h))
-        return cls(None, None, _handle=h, _n_sel=freqs.size)
+        _call("gmr1_hip_ddc_stream_create_iq", samp_rate, sps, fmt, freqs.size, _p(freqs), C.byref(h))
+        return cls(None, None, _handle=h, _n_sel=freqs.size, fmt=fmt)
 
     def out_len(self, n_in):
         """outputs per stream the next push of n_in samples will give"""
@@ -1284,18 +1372,18 @@ class ChanStream(_LibHandle):
         return n.value
 
     def push(self, wide):
-        """host complex64 samples -> (n_sel, n_new) complex64"""
-        wide = _arr(wide, np.complex64, -1)
-        n_new = self.out_len(wide.size)
+        """host samples in the handle's format (complex64, or (n, 2) int16 / int8) -> (n_sel, n_new) complex64"""
+        wide, _, n = _iq(wide, self.fmt)
+        n_new = self.out_len(n)
         out = np.zeros((self.n_sel, max(n_new, 1)), np.complex64)
         got = C.c_uint64()
-        _call("gmr1_hip_chan_stream_push", self._h, _p(wide), wide.size, _p(out), out.shape[1], C.byref(got))
+        _call("gmr1_hip_chan_stream_push_iq", self._h, _p(wide), n, _p(out), out.shape[1], C.byref(got))
         return out[:, :got.value]
 
     def push_dev(self, stream, wide_ptr, n_in, out_ptr, out_stride):
-        """device pointers, enqueued on `stream` (not waited for) -> outputs written per stream"""
+        """device pointers (wide in the handle's format), enqueued on `stream` (not waited for) -> outputs written per stream"""
         got = C.c_uint64()
-        _call("gmr1_hip_chan_stream_push_dev", stream, self._h, wide_ptr, n_in, out_ptr, out_stride, C.byref(got))
+        _call("gmr1_hip_chan_stream_push_iq_dev", stream, self._h, wide_ptr, n_in, out_ptr, out_stride, C.byref(got))
         return got.value
 
 

@@ -90,6 +90,7 @@ struct gmr1_hip_chan_stream {
 	mutable std::mutex mu;               // one push at a time
 	int device = -1;
 	bool direct = false;                 // gmr1_hip_ddc_stream_create
+	int fmt = kIqF32;                    // what a push's `wide` holds (iq_format.h), for life
 	int n_sel = 0;
 	float rotation = 0.0f;
 	const ChanPlan *cp = nullptr;
@@ -108,7 +109,8 @@ struct gmr1_hip_chan_stream {
 	hipEvent_t ev = nullptr;             // recorded behind the last push
 	hipStream_t last = nullptr;
 	bool pushed = false;
-	GrowBuf h_in, h_out;                 // gmr1_hip_chan_stream_push's device copies
+	GrowBuf h_in, h_out;                 // gmr1_hip_chan_stream_push's device copies (h_in in the handle's format)
+	GrowBuf conv;                        // off the grid, an integer push's samples as float2: the pre-resampler reads floats
 	~gmr1_hip_chan_stream()
 	{
 		if (d_slot) (void)hipFree(d_slot);
@@ -149,16 +151,23 @@ int stream_finish_create(std::unique_ptr<gmr1_hip_chan_stream> &h, gmr1_hip_chan
 }
 
 // the device part of a push; the caller holds h->mu and has validated everything
-int stream_push(hipStream_t st, gmr1_hip_chan_stream *h, const float2 *wide, uint64_t n_in, float2 *out, uint64_t out_stride)
+int stream_push(hipStream_t st, gmr1_hip_chan_stream *h, const void *wide, uint64_t n_in, float2 *out, uint64_t out_stride)
 {
 	const uint64_t N0 = h->N, N1 = N0 + n_in;
 	const StreamCounts c0 = stream_counts(h, N0), c1 = stream_counts(h, N1);
 	if (h->pushed && st != h->last)
 		HIP_TRY(hipStreamWaitEvent(st, h->ev, 0));
 	const long long na = (long long)(c1.a - c0.a), nb = (long long)(c1.b - c0.b);
+	int r, fmt = h->fmt;
+	if (fmt != kIqF32 && !h->direct && h->cp->pre && n_in > 0) {
+		// the one chain that converts up front: everything below, the kept tail included, then sees floats
+		if ((r = h->conv.reserve(n_in * sizeof(float2)))) return r;
+		HIP_TRY(launch_iq_convert(wide, fmt, (long long)n_in, static_cast<float2 *>(h->conv.p), st));
+		wide = h->conv.p;
+		fmt = kIqF32;
+	}
 	Span in = reads(h->xt, N0, N1);      // the wideband chunk behind the retained samples: the caller's, never copied
-	in.x = wide; in.x_stride = 0;
-	int r;
+	in.x = static_cast<const float2 *>(wide); in.x_stride = 0; in.fmt = fmt;
 	if (h->a.p && (r = stage_reserve(h->a, na, st))) return r;
 	if (h->b.p && (r = stage_reserve(h->b, nb, st))) return r;
 	if (!h->direct) {
@@ -188,6 +197,7 @@ int stream_push(hipStream_t st, gmr1_hip_chan_stream *h, const float2 *wide, uin
 	if (n_in > 0) {
 		KeepTail &j = keep.job[keep.n++];
 		j.dst = h->xt.p; j.a = h->xt.p; j.b = wide; j.na = h->xt.L; j.nb = (long long)n_in; j.L = h->xt.L; j.rows = 1;
+		keep.b_fmt = fmt;                    // kept as float2: converted as it is kept
 	}
 	if (h->a.p)
 		stage_keep(keep, h->a, na);
@@ -201,8 +211,9 @@ int stream_push(hipStream_t st, gmr1_hip_chan_stream *h, const float2 *wide, uin
 	return 0;
 }
 
-// the checks every push makes before it touches the handle: -EINVAL leaves the stream as it was
-int stream_check(gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in, const float *out, uint64_t out_stride,
+// the checks every push makes before it touches the handle: -EINVAL leaves the stream as it was.  as_f32: the push came
+// through an entry whose `wide` is const float *
+int stream_check(gmr1_hip_chan_stream *h, bool as_f32, const void *wide, uint64_t n_in, const float *out, uint64_t out_stride,
                  uint64_t *n_new)
 {
 	DevState *s;
@@ -214,6 +225,8 @@ int stream_check(gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in, cons
 	HIP_TRY(hipGetDevice(&dev));
 	if (dev != h->device)
 		return fail(-EINVAL, "chan_stream: the handle belongs to device %d, the current device is %d", h->device, dev);
+	if (as_f32 && h->fmt != kIqF32)
+		return fail(-EINVAL, "chan_stream: the handle reads format %d: push it with gmr1_hip_chan_stream_push_iq*", h->fmt);
 	if (!wide)
 		return fail(-EINVAL, "chan_stream: wide is required");
 	if (n_in > (uint64_t)1 << 40)
@@ -233,12 +246,13 @@ int stream_check(gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in, cons
 
 extern "C" {
 
-int gmr1_hip_channelize_stream_create(double samp_rate, int sps, float rotation, int n_sel, const int32_t *chan_idx,
-                                      struct gmr1_hip_chan_stream **out)
+int gmr1_hip_channelize_stream_create_iq(double samp_rate, int sps, int fmt, float rotation, int n_sel,
+                                         const int32_t *chan_idx, struct gmr1_hip_chan_stream **out)
 {
 	DevState *s;
 	int r = dev_state(&s);
 	if (r) return r;
+	if ((r = checked_fmt("channelize_stream", fmt))) return r;
 	if (!out || n_sel < 0 || (n_sel && !chan_idx))
 		return fail(-EINVAL, "channelize_stream: chan_idx / handle are required");
 	const ChanPlan *p;
@@ -249,7 +263,7 @@ int gmr1_hip_channelize_stream_create(double samp_rate, int sps, float rotation,
 		return r;
 	std::unique_ptr<gmr1_hip_chan_stream> h(new gmr1_hip_chan_stream);
 	HIP_TRY(hipGetDevice(&h->device));
-	h->n_sel = n_sel; h->rotation = rotation; h->cp = p; h->rs = &p->rs; h->rs_bank = p->d_bank; h->rs_in = &h->b;
+	h->fmt = fmt; h->n_sel = n_sel; h->rotation = rotation; h->cp = p; h->rs = &p->rs; h->rs_bank = p->d_bank; h->rs_in = &h->b;
 	// history: the filterbank reaches ntaps + n_chans / 2 inputs behind its first new instant (n_blocks n_chans + n_chans
 	// covers it); the pre-resampler its taps and one step
 	const int l_pfb = (p->n_blocks + 1) * p->n_chans;
@@ -265,11 +279,19 @@ int gmr1_hip_channelize_stream_create(double samp_rate, int sps, float rotation,
 	return stream_finish_create(h, out);
 }
 
-int gmr1_hip_ddc_stream_create(double samp_rate, int sps, int n_sel, const double *freq_hz, struct gmr1_hip_chan_stream **out)
+int gmr1_hip_channelize_stream_create(double samp_rate, int sps, float rotation, int n_sel, const int32_t *chan_idx,
+                                      struct gmr1_hip_chan_stream **out)
+{
+	return gmr1_hip_channelize_stream_create_iq(samp_rate, sps, kIqF32, rotation, n_sel, chan_idx, out);
+}
+
+int gmr1_hip_ddc_stream_create_iq(double samp_rate, int sps, int fmt, int n_sel, const double *freq_hz,
+                                  struct gmr1_hip_chan_stream **out)
 {
 	DevState *s;
 	int r = dev_state(&s);
 	if (r) return r;
+	if ((r = checked_fmt("ddc_stream", fmt))) return r;
 	if (!out || n_sel < 0 || (n_sel && !freq_hz))
 		return fail(-EINVAL, "ddc_stream: freq_hz / handle are required");
 	const DdcPlan *p;
@@ -277,7 +299,7 @@ int gmr1_hip_ddc_stream_create(double samp_rate, int sps, int n_sel, const doubl
 		return r;
 	std::unique_ptr<gmr1_hip_chan_stream> h(new gmr1_hip_chan_stream);
 	HIP_TRY(hipGetDevice(&h->device));
-	h->direct = true; h->n_sel = n_sel; h->dp = p; h->rs = &p->rs; h->rs_bank = p->d_bank; h->rs_in = p->d2 > 1 ? &h->b : &h->a;
+	h->direct = true; h->fmt = fmt; h->n_sel = n_sel; h->dp = p; h->rs = &p->rs; h->rs_bank = p->d_bank; h->rs_in = p->d2 > 1 ? &h->b : &h->a;
 	const int l_rs = resamp_history(p->rs);
 	const int l_fir1 = (int)p->taps1.size() + p->d1 + 1;
 	if ((r = stage_init(h->xt, (int)up_to((size_t)l_fir1, 64), 1)) ||
@@ -294,6 +316,11 @@ int gmr1_hip_ddc_stream_create(double samp_rate, int sps, int n_sel, const doubl
 	return stream_finish_create(h, out);
 }
 
+int gmr1_hip_ddc_stream_create(double samp_rate, int sps, int n_sel, const double *freq_hz, struct gmr1_hip_chan_stream **out)
+{
+	return gmr1_hip_ddc_stream_create_iq(samp_rate, sps, kIqF32, n_sel, freq_hz, out);
+}
+
 int gmr1_hip_chan_stream_out_len(const struct gmr1_hip_chan_stream *h, uint64_t n_in, uint64_t *n_out)
 {
 	DevState *s;
@@ -306,38 +333,37 @@ int gmr1_hip_chan_stream_out_len(const struct gmr1_hip_chan_stream *h, uint64_t 
 	return 0;
 }
 
-int gmr1_hip_chan_stream_push_dev(void *stream, struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in,
-                                  float *out, uint64_t out_stride, uint64_t *n_out)
+static int push_dev_impl(void *stream, struct gmr1_hip_chan_stream *h, bool as_f32, const void *wide, uint64_t n_in,
+                         float *out, uint64_t out_stride, uint64_t *n_out)
 {
 	std::unique_lock<std::mutex> lk;
 	if (h)
 		lk = std::unique_lock<std::mutex>(h->mu);
 	uint64_t n_new = 0;
-	int r = stream_check(h, wide, n_in, out, out_stride, &n_new);
+	int r = stream_check(h, as_f32, wide, n_in, out, out_stride, &n_new);
 	if (r) return r;
-	if ((r = stream_push((hipStream_t)stream, h, reinterpret_cast<const float2 *>(wide), n_in, reinterpret_cast<float2 *>(out),
-	                     out_stride)))
+	if ((r = stream_push((hipStream_t)stream, h, wide, n_in, reinterpret_cast<float2 *>(out), out_stride)))
 		return r;
 	if (n_out) *n_out = n_new;
 	return 0;
 }
 
-int gmr1_hip_chan_stream_push(struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in, float *out,
-                              uint64_t out_stride, uint64_t *n_out)
+static int push_host_impl(struct gmr1_hip_chan_stream *h, bool as_f32, const void *wide, uint64_t n_in, float *out,
+                          uint64_t out_stride, uint64_t *n_out)
 {
 	std::unique_lock<std::mutex> lk;
 	if (h)
 		lk = std::unique_lock<std::mutex>(h->mu);
 	uint64_t n_new = 0;
-	int r = stream_check(h, wide, n_in, out, out_stride, &n_new);
+	int r = stream_check(h, as_f32, wide, n_in, out, out_stride, &n_new);
 	if (r) return r;
 	const size_t out_rows = h->n_sel > 0 && n_new > 0 ? (size_t)h->n_sel : 0;
-	if ((r = h->h_in.reserve(n_in * sizeof(float2))) || (r = h->h_out.reserve(out_rows * n_new * sizeof(float2))))
+	const size_t in_bytes = n_in * (size_t)iq_sample_bytes(h->fmt);      // the upload is the format's bytes
+	if ((r = h->h_in.reserve(in_bytes)) || (r = h->h_out.reserve(out_rows * n_new * sizeof(float2))))
 		return r;
 	if (n_in)
-		HIP_TRY(hipMemcpyAsync(h->h_in.p, wide, n_in * sizeof(float2), hipMemcpyHostToDevice, nullptr));
-	if ((r = stream_push(nullptr, h, static_cast<const float2 *>(h->h_in.p ? h->h_in.p : h->xt.p), n_in,
-	                     static_cast<float2 *>(h->h_out.p), n_new)))
+		HIP_TRY(hipMemcpyAsync(h->h_in.p, wide, in_bytes, hipMemcpyHostToDevice, nullptr));
+	if ((r = stream_push(nullptr, h, h->h_in.p ? h->h_in.p : h->xt.p, n_in, static_cast<float2 *>(h->h_out.p), n_new)))
 		return r;
 	if (out_rows)
 		HIP_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float2), h->h_out.p, n_new * sizeof(float2), n_new * sizeof(float2),
@@ -345,6 +371,30 @@ int gmr1_hip_chan_stream_push(struct gmr1_hip_chan_stream *h, const float *wide,
 	HIP_TRY(hipStreamSynchronize(nullptr));
 	if (n_out) *n_out = n_new;
 	return 0;
+}
+
+int gmr1_hip_chan_stream_push_dev(void *stream, struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in,
+                                  float *out, uint64_t out_stride, uint64_t *n_out)
+{
+	return push_dev_impl(stream, h, true, wide, n_in, out, out_stride, n_out);
+}
+
+int gmr1_hip_chan_stream_push_iq_dev(void *stream, struct gmr1_hip_chan_stream *h, const void *wide, uint64_t n_in,
+                                     float *out, uint64_t out_stride, uint64_t *n_out)
+{
+	return push_dev_impl(stream, h, false, wide, n_in, out, out_stride, n_out);
+}
+
+int gmr1_hip_chan_stream_push(struct gmr1_hip_chan_stream *h, const float *wide, uint64_t n_in, float *out,
+                              uint64_t out_stride, uint64_t *n_out)
+{
+	return push_host_impl(h, true, wide, n_in, out, out_stride, n_out);
+}
+
+int gmr1_hip_chan_stream_push_iq(struct gmr1_hip_chan_stream *h, const void *wide, uint64_t n_in, float *out,
+                                 uint64_t out_stride, uint64_t *n_out)
+{
+	return push_host_impl(h, false, wide, n_in, out, out_stride, n_out);
 }
 
 int gmr1_hip_chan_stream_destroy(struct gmr1_hip_chan_stream *h)

@@ -5,6 +5,7 @@
 
 #include "capi_common.h"
 #include "chan_plan.h"
+#include "iq_format.h"
 
 #pragma GCC visibility push(hidden)
 namespace gmr1 {
@@ -42,14 +43,18 @@ int select_slots(int nch, int n_sel, const int32_t *chan_idx, std::vector<int32_
 
 // What one launch of a stage covers.  One-shot: st zeroed, n_in / n_out the call's counts, rows n_in and n_out apart
 // whatever the strides say (only the resampler's output stride is read).  A push: x the new samples, st.xt / xt0 / x0 / o0
-// set, n_in / n_out the global ends; the stage puts the strides where its kernel reads them.
+// set, n_in / n_out the global ends; the stage puts the strides where its kernel reads them.  fmt: what x holds (iq_format.h)
+// -- float2 is its type in F32 only; the filterbank and stage 1 of the direct mode read the others, nothing else does.
 struct Span {
 	const float2 *x;
 	long long n_in, x_stride;
 	float2 *y;
 	long long n_out, y_stride;
 	StreamIdx st;
+	int fmt = kIqF32;
 };
+// -EINVAL for a format that is none of GMR1_HIP_IQ_* (`who` names the entry in the message)
+int checked_fmt(const char *who, int fmt);
 // an arbitrary resampler over n_slots rows (rotation: the pre-resampler's; planar_sps > 0: polyphase-planar output)
 int run_resamp(hipStream_t st, const RsStage &rs, const float2 *bank, int n_slots, const Span &s, float rotation = 0.0f,
                int planar_sps = 0, long long plane_stride = 0);

@@ -32,6 +32,7 @@
 #include "gmr1_dev.h"
 #include "chan_select.h"
 #include "fast_math.h"
+#include "iq_format.h"
 #include "profile_env.h"
 
 namespace gmr1 {
@@ -60,13 +61,24 @@ __device__ __forceinline__ float lane_xor(float v)
 	else return dppf_mov<0xB1>(v);
 }
 
+// sample s of a capture in format FMT (iq_format.h): the float2 read the kernels always had, or the load rule
+template <int FMT>
+__device__ __forceinline__ float2 cap_ld(const float2 *x, long long s)
+{
+	if constexpr (FMT == kIqF32)
+		return x[s];
+	else
+		return iq_load<FMT, float2>(x, s);
+}
+
 // sample s (global index) of a streamed stage's input row: the retained tail below st.x0, the new samples from there, zeros
-// outside [st.xt0, end) (gmr1_dev.h, StreamIdx)
+// outside [st.xt0, end) (gmr1_dev.h, StreamIdx).  FMT: the new samples' format (iq_format.h); the tail is float2 in every one
+template <int FMT = kIqF32>
 __device__ __forceinline__ float2 stream_ld(const float2 *x, const float2 *xt, const StreamIdx &st, long long s, long long end)
 {
 	if (s < st.xt0 || s >= end)
 		return make_float2(0.f, 0.f);
-	return s < st.x0 ? xt[s - st.xt0] : x[s - st.x0];
+	return s < st.x0 ? xt[s - st.xt0] : cap_ld<FMT>(x, s - st.x0);
 }
 
 // ---- packed single precision (v_pk_*_f32: two multiply-adds per lane and instruction, the rate the vector peak is quoted
@@ -142,7 +154,9 @@ __device__ __forceinline__ pf_v2f pf_partner(pf_v2f v)
 }
 
 // STREAM: the instants [st.o0, T) of a streamed run (the waves start at the even instant at or below st.o0)
-template <bool ROT, bool STREAM>
+// FMT: the capture's format (iq_format.h).  load_block is the only read of it: a lane's S16 sample is one dword, a block
+// one coalesced 256-byte load; S8 one 2-byte load per lane.  Everything behind the load is the same code in every format
+template <bool ROT, bool STREAM, int FMT = kIqF32>
 __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 {
 	__shared__ float2 tile[64 * (kPfbTile + 1)];
@@ -187,11 +201,32 @@ __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 	auto load_block = [&](long long b) -> pf_v2f {
 		const long long s = 64 * b + r;
 		float2 v = make_float2(0.f, 0.f);
+		if constexpr (FMT != kIqF32 && !STREAM) {
+			// Only the load is under the range test, as in the float form: converted there, the conversion is the load's first use
+			// and sits right behind it -- every block then waits out its trip to memory instead of travelling two blocks ahead
+			// (S16 measured that way: 0.288 against the float's 0.217 ms, profiles/r11a; the S8 pair of bytes is still taken apart
+			// under the test: DESIGN 8).  A stored zero converts to the 0.0 a sample out of range is.
+			typename IqStored<FMT>::type raw = {0, 0};
+			const bool in = b >= 0 && s < a.n_in;
+			if (in)
+				raw = iq_fetch<FMT>(a.x, s);
+			v = iq_value<float2>(raw);
+			if (ROT && in) {
+				const double ph = (double)a.rotation * (double)s;
+				const float fr = (float)(ph - 6.283185307179586 * rint(ph * 0.15915494309189535));
+				float sn, cs;
+				__sincosf(fr, &sn, &cs);
+				v = make_float2(v.x * cs - v.y * sn, v.x * sn + v.y * cs);
+			}
+			return (pf_v2f){v.x, v.y};
+		}
 		if (STREAM || (b >= 0 && s < a.n_in)) {
 			if constexpr (STREAM)
-				v = stream_ld(a.x, a.st.xt, a.st, s, a.n_in);
-			else
+				v = stream_ld<FMT>(a.x, a.st.xt, a.st, s, a.n_in);
+			else if constexpr (FMT == kIqF32)
 				v = a.x[s];
+			else
+				v = iq_load<FMT, float2>(a.x, s);
 			if (ROT) {
 				// e^{j rotation s}: the angle reduced in double so that long captures keep their phase
 				const double ph = (double)a.rotation * (double)s;
@@ -294,7 +329,7 @@ __global__ __launch_bounds__(64) void k_pfb64(PfbArgs a)
 static constexpr int kAnyTile = 16;          // instants per work-group
 static constexpr int kAnyThreads = 256;
 
-template <bool ROT, bool STREAM>
+template <bool ROT, bool STREAM, int FMT = kIqF32>
 __global__ __launch_bounds__(kAnyThreads) void k_pfb_any(PfbArgs a)
 {
 	extern __shared__ float2 lds_any[];
@@ -326,7 +361,7 @@ __global__ __launch_bounds__(kAnyThreads) void k_pfb_any(PfbArgs a)
 					continue;
 				if (STREAM && sidx < a.st.xt0)
 					break;
-				float2 x = STREAM ? stream_ld(a.x, a.st.xt, a.st, sidx, a.n_in) : a.x[sidx];
+				float2 x = STREAM ? stream_ld<FMT>(a.x, a.st.xt, a.st, sidx, a.n_in) : cap_ld<FMT>(a.x, sidx);
 				if (ROT) {
 					const double ph = (double)a.rotation * (double)sidx;
 					const float fr = (float)(ph - 6.283185307179586 * rint(ph * 0.15915494309189535));
@@ -365,9 +400,20 @@ __global__ __launch_bounds__(kAnyThreads) void k_pfb_any(PfbArgs a)
 	}
 }
 
+// the filterbank's instantiations by [streamed][rotation][format]
+using PfbKernel = void (*)(PfbArgs);
+#define GMR1_PFB_FMTS(K, ROT, STREAM) {K<ROT, STREAM, kIqF32>, K<ROT, STREAM, kIqS16>, K<ROT, STREAM, kIqS8>}
+static const PfbKernel kPfb64[2][2][3] = {{GMR1_PFB_FMTS(k_pfb64, false, false), GMR1_PFB_FMTS(k_pfb64, true, false)},
+                                          {GMR1_PFB_FMTS(k_pfb64, false, true), GMR1_PFB_FMTS(k_pfb64, true, true)}};
+static const PfbKernel kPfbAny[2][2][3] = {{GMR1_PFB_FMTS(k_pfb_any, false, false), GMR1_PFB_FMTS(k_pfb_any, true, false)},
+                                           {GMR1_PFB_FMTS(k_pfb_any, false, true), GMR1_PFB_FMTS(k_pfb_any, true, true)}};
+#undef GMR1_PFB_FMTS
+
 hipError_t launch_pfb(const PfbArgs &a, hipStream_t stream)
 {
 	const bool strm = a.st.xt != nullptr;
+	if (iq_sample_bytes(a.fmt) < 0)
+		return hipErrorInvalidValue;
 	const long long t_lo = strm ? a.st.o0 : 0;
 	if (a.T <= t_lo)
 		return hipSuccess;
@@ -379,27 +425,13 @@ hipError_t launch_pfb(const PfbArgs &a, hipStream_t stream)
 		const long long grid = (a.T - t_lo + kAnyTile - 1) / kAnyTile;
 		const size_t lds = (size_t)(kAnyTile * (a.n_chans + 1) + a.n_chans) * sizeof(float2);
 		const bool rot = a.rotation != 0.0f;
-		if (strm && rot)
-			hipLaunchKernelGGL((k_pfb_any<true, true>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
-		else if (strm)
-			hipLaunchKernelGGL((k_pfb_any<false, true>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
-		else if (rot)
-			hipLaunchKernelGGL((k_pfb_any<true, false>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
-		else
-			hipLaunchKernelGGL((k_pfb_any<false, false>), dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
+		hipLaunchKernelGGL(kPfbAny[strm][rot][a.fmt], dim3((unsigned)grid), dim3(kAnyThreads), lds, stream, a);
 		return hipGetLastError();
 	}
 	const int steps = strm ? kPfbStepsStream : kPfbSteps;
 	const long long grid = (a.T - (t_lo & ~1LL) + steps - 1) / steps;
 	const bool rot = a.rotation != 0.0f;
-	if (strm && rot)
-		hipLaunchKernelGGL((k_pfb64<true, true>), dim3((unsigned)grid), dim3(64), 0, stream, a);
-	else if (strm)
-		hipLaunchKernelGGL((k_pfb64<false, true>), dim3((unsigned)grid), dim3(64), 0, stream, a);
-	else if (rot)
-		hipLaunchKernelGGL((k_pfb64<true, false>), dim3((unsigned)grid), dim3(64), 0, stream, a);
-	else
-		hipLaunchKernelGGL((k_pfb64<false, false>), dim3((unsigned)grid), dim3(64), 0, stream, a);
+	hipLaunchKernelGGL(kPfb64[strm][rot][a.fmt], dim3((unsigned)grid), dim3(64), 0, stream, a);
 	return hipGetLastError();
 }
 
@@ -1072,7 +1104,7 @@ void k_resamp2w(ResampArgs a, long long P, long long Q, int nch)
 // ---------------------------------------------------------------------------
 static constexpr int kDdcOut = 256;
 
-template <bool STREAM>
+template <bool STREAM, int FMT = kIqF32>
 __global__ __launch_bounds__(256) void k_ddc_fir(DdcFirArgs a)
 {
 	extern __shared__ __align__(16) unsigned char ddc_lds[];
@@ -1089,9 +1121,9 @@ __global__ __launch_bounds__(256) void k_ddc_fir(DdcFirArgs a)
 	for (int i = tid; i < span; i += 256) {
 		const long long n = first + i;
 		if constexpr (STREAM)
-			xs[i] = stream_ld(x, xt, a.st, n, a.n_in);
+			xs[i] = stream_ld<FMT>(x, xt, a.st, n, a.n_in);
 		else
-			xs[i] = (n >= 0 && n < a.n_in) ? x[n] : make_float2(0.f, 0.f);
+			xs[i] = (n >= 0 && n < a.n_in) ? cap_ld<FMT>(x, n) : make_float2(0.f, 0.f);
 	}
 	__syncthreads();
 	const long long m = m0 + tid;
@@ -1126,6 +1158,8 @@ __global__ __launch_bounds__(256) void k_ddc_fir(DdcFirArgs a)
 // (the stage buffers' [tail | new samples] moved to the front).  O(L) per row: the history a stage needs, never a chunk.
 // All of a push's stages in one launch (blockIdx.y: the job): each launch is ~4 us of a push that is 20-70 us.
 // ---------------------------------------------------------------------------
+// FMT: the format b is read in (iq_format.h); what is kept is float2
+template <int FMT = kIqF32>
 __global__ __launch_bounds__(256) void k_keep_tail(KeepTailArgs ka)
 {
 	extern __shared__ float2 keep_lds[];
@@ -1135,7 +1169,7 @@ __global__ __launch_bounds__(256) void k_keep_tail(KeepTailArgs ka)
 		return;
 	for (int i = threadIdx.x; i < j.L; i += 256) {
 		const long long g = g0 + i;
-		keep_lds[i] = g < j.na ? j.a[row * j.a_stride + g] : j.b[row * j.b_stride + (g - j.na)];
+		keep_lds[i] = g < j.na ? j.a[row * j.a_stride + g] : iq_load<FMT, float2>(j.b, row * j.b_stride + (g - j.na));
 	}
 	__syncthreads();
 	for (int i = threadIdx.x; i < j.L; i += 256)
@@ -1156,7 +1190,44 @@ hipError_t launch_keep_tail(const KeepTailArgs &a, hipStream_t stream)
 	}
 	if (rows == 0 || L == 0)
 		return hipSuccess;
-	hipLaunchKernelGGL(k_keep_tail, dim3((unsigned)rows, (unsigned)a.n), dim3(256), (size_t)L * sizeof(float2), stream, a);
+	const dim3 grid((unsigned)rows, (unsigned)a.n);
+	if (a.b_fmt == kIqF32)
+		hipLaunchKernelGGL(k_keep_tail<kIqF32>, grid, dim3(256), (size_t)L * sizeof(float2), stream, a);
+	else if (a.b_fmt == kIqS16)
+		hipLaunchKernelGGL(k_keep_tail<kIqS16>, grid, dim3(256), (size_t)L * sizeof(float2), stream, a);
+	else if (a.b_fmt == kIqS8)
+		hipLaunchKernelGGL(k_keep_tail<kIqS8>, grid, dim3(256), (size_t)L * sizeof(float2), stream, a);
+	else
+		return hipErrorInvalidValue;
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_iq_convert -- an integer capture to float2, sample by sample through the load rule.  The one place a capture is
+// converted ahead of its first stage: off the grid that stage is the pre-resampler, whose k_resamp2 form brings its windows
+// in by LDS-DMA, as the bytes they are in memory.  4 or 2 bytes in, 8 out per sample, one wideband stream.
+// ---------------------------------------------------------------------------
+template <int FMT>
+__global__ __launch_bounds__(256) void k_iq_convert(const void *src, long long n, float2 *dst)
+{
+	const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (s < n)
+		dst[s] = iq_load<FMT, float2>(src, s);
+}
+
+hipError_t launch_iq_convert(const void *src, int fmt, long long n, float2 *dst, hipStream_t stream)
+{
+	if (n <= 0)
+		return hipSuccess;
+	if ((n + 255) / 256 > 0x7fffffffLL)
+		return hipErrorInvalidValue;
+	const dim3 grid((unsigned)((n + 255) / 256));
+	if (fmt == kIqS16)
+		hipLaunchKernelGGL(k_iq_convert<kIqS16>, grid, dim3(256), 0, stream, src, n, dst);
+	else if (fmt == kIqS8)
+		hipLaunchKernelGGL(k_iq_convert<kIqS8>, grid, dim3(256), 0, stream, src, n, dst);
+	else
+		return hipErrorInvalidValue;
 	return hipGetLastError();
 }
 
@@ -1173,14 +1244,17 @@ hipError_t launch_ddc_fir(const DdcFirArgs &a, hipStream_t stream)
 	const size_t lds = ((size_t)a.ntaps + (size_t)kDdcOut * a.decim + a.ntaps) * sizeof(float2);
 	if (lds > 150 * 1024)
 		return hipErrorInvalidValue;
-	const void *fn = strm ? reinterpret_cast<const void *>(k_ddc_fir<true>) : reinterpret_cast<const void *>(k_ddc_fir<false>);
+	// (an integer capture is stage 1's: one stream for every carrier)
+	if (iq_sample_bytes(a.fmt) < 0 || (a.fmt != kIqF32 && a.in_stride != 0))
+		return hipErrorInvalidValue;
+	using Kernel = void (*)(DdcFirArgs);
+	static const Kernel kern[2][3] = {{k_ddc_fir<false, kIqF32>, k_ddc_fir<false, kIqS16>, k_ddc_fir<false, kIqS8>},
+	                                  {k_ddc_fir<true, kIqF32>, k_ddc_fir<true, kIqS16>, k_ddc_fir<true, kIqS8>}};
+	const Kernel fn = kern[strm][a.fmt];
 	if (lds > 64 * 1024)
-		(void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 	const dim3 grid((unsigned)((a.n_out - m_lo + kDdcOut - 1) / kDdcOut), (unsigned)a.n_sel);
-	if (strm)
-		hipLaunchKernelGGL(k_ddc_fir<true>, grid, dim3(256), lds, stream, a);
-	else
-		hipLaunchKernelGGL(k_ddc_fir<false>, grid, dim3(256), lds, stream, a);
+	hipLaunchKernelGGL(fn, grid, dim3(256), lds, stream, a);
 	return hipGetLastError();
 }
 

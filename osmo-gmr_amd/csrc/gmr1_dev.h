@@ -319,12 +319,13 @@ struct PfbArgs {
 	long long n_in;            // wideband samples
 	long long T;               // output instants = n_in / (n_chans / 2)
 	float rotation;            // optional pre-rotation, rad / sample
-	const float2 *x;           // wideband capture
+	const float2 *x;           // wideband capture (fmt: float2 is its type only in GMR1_HIP_IQ_F32)
 	const float *taps;         // prototype low-pass, ntaps floats
 	const int32_t *slot;       // n_chans entries: output slot of channel k or -1
 	float2 *y;                 // n_slots x T, 2x oversampled channel streams
 	const int32_t *sel;        // n_sel selected channel indices (slot order), used by the generic kernel
 	int n_sel;
+	int fmt;                   // format of x (iq_format.h); a streamed run's tail st.xt is float2 in every format
 	StreamIdx st;              // streamed run: n_in and T are global ends
 };
 struct ResampArgs {
@@ -353,6 +354,7 @@ constexpr int kDdcMaxTaps = 256;
 struct DdcFirArgs {
 	int n_sel;                 // carriers
 	int decim, ntaps;
+	int fmt;                   // format of x (iq_format.h): stage 1 only; st.xt is float2 in every format
 	long long n_in, n_out;     // samples per stream in / out (n_out = n_in / decim)
 	long long in_stride;       // complex samples between input streams; 0: every carrier reads the same (wideband) stream
 	const float2 *x;
@@ -363,19 +365,25 @@ struct DdcFirArgs {
 };
 hipError_t launch_ddc_fir(const DdcFirArgs &a, hipStream_t stream);
 // a streamed run's retained history, all of a push's stages in one launch: per job and row r < rows, the last L samples of
-// (a[r a_stride + [0, na)] ++ b[r b_stride + [0, nb)]) to dst[r dst_stride + [0, L)]; dst may be a
+// (a[r a_stride + [0, na)] ++ b[r b_stride + [0, nb)]) to dst[r dst_stride + [0, L)]; dst may be a.  b is read in b_fmt
+// (iq_format.h; the wideband input's job is the one that has a b) and kept as float2: it is converted as it is kept
 constexpr int kKeepTailMax = 4096, kKeepJobs = 3;
 struct KeepTail {
 	float2 *dst;
-	const float2 *a, *b;
+	const float2 *a;
+	const void *b;
 	long long dst_stride, a_stride, b_stride, na, nb;
 	int L, rows;
 };
 struct KeepTailArgs {
 	KeepTail job[kKeepJobs];
 	int n;
+	int b_fmt;
 };
 hipError_t launch_keep_tail(const KeepTailArgs &a, hipStream_t stream);
+// n samples of an integer capture to float2 (k_iq_convert): off the grid only, where the pre-resampler's windows travel
+// as raw bytes (k_resamp2's LDS-DMA) and so need floats in memory
+hipError_t launch_iq_convert(const void *src, int fmt, long long n, float2 *dst, hipStream_t stream);
 
 // The streaming receive loop's staging (k_rx_stage, rx_stream_kernels.hip): per carrier, [kept tail of the source
 // buffer | the caller's chunk] -> the destination buffer, and the carrier's chain states rebased onto it.

@@ -4,6 +4,9 @@
     python tools/isa_diff.py HEAD --profile           # the -DGMR1_HIP_PROFILE build
     python tools/isa_diff.py HEAD rx_kernels.hip      # one translation unit
     python tools/isa_diff.py HEAD --resources k_rx4   # also the register/spill/LDS metadata of matching kernels, both sides
+    python tools/isa_diff.py HEAD --rename ELi0EEEvNS_7PfbArgsE=EEEvNS_7PfbArgsE
+                                                      # a kernel that gained a template parameter: its <..., 0> form is
+                                                      # compared with REV's (a substring of the mangled name, new -> old)
 csrc/ and include/ of REV are taken out of git into a temporary directory, every .hip of both trees is compiled to device-only
 assembly with build.py's flags, and the output is compared kernel by kernel: the code from the kernel's symbol to the end of the
 function, its .amdhsa_kernel block, its resource symbols and its metadata entry.  The assembly carries no file names or line
@@ -84,6 +87,8 @@ def main():
     ap.add_argument("--profile", action="store_true", help="compile with -DGMR1_HIP_PROFILE")
     ap.add_argument("--resources", metavar="KERNEL",
                     help="print the register, spill and LDS metadata of kernels whose name, demangled or mangled, contains KERNEL")
+    ap.add_argument("--rename", metavar="NEW=OLD", action="append", default=[],
+                    help="replace NEW by OLD in the working tree's assembly before comparing (mangled-name substrings)")
     a = ap.parse_args()
     extra = ["-DGMR1_HIP_PROFILE"] if a.profile else []
     with tempfile.TemporaryDirectory() as td:
@@ -102,6 +107,8 @@ def main():
             sys.exit(str(e))
     kern = {"old": {}, "new": {}}
     for (side, _, f), t in zip(jobs, texts):
+        for r in a.rename if side == "new" else ():
+            t = t.replace(*r.split("=", 1))
         for sym, text in split_kernels(t).items():
             kern[side][(f, sym)] = text
     keys = sorted(set(kern["old"]) | set(kern["new"]))
