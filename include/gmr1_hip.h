@@ -121,7 +121,8 @@ int gmr1_hip_get_conv_decoder(void);
 
 /* ---- normal-burst demodulation (any burst type, one type per call) ------- */
 /* iq: interleaved float32 I/Q; burst i occupies iq[offset[i] .. offset[i]+in_len) (complex samples).
- * Optional outputs may be NULL.  ebits is n x ebits_stride int8, ssyms n x bt.len float. */
+ * Optional outputs may be NULL.  ebits is n rows of bt.ebits int8, ebits_stride (>= bt.ebits) bytes apart: what lies
+ * between two rows is left as it was.  ssyms is n x bt.len float. */
 int gmr1_hip_demod_batch_dev(void *stream, int burst_id, int n, int sps, int in_len,
                              const float *iq, const uint64_t *offset, const float *freq_shift,
                              int8_t *ebits, int ebits_stride, int32_t *sync_id,

@@ -116,7 +116,8 @@ int demod_host_impl(int type, const DevBurst &ht, const DevBurst *custom,
 	const uint64_t *d_off = sg.in(offset, (size_t)n);
 	const float *d_fs = sg.in(freq_shift, (size_t)n);
 	int32_t *d_rv = sg.out(rv, (size_t)n);
-	int8_t *d_eb = sg.out(ebits, (size_t)n * ebits_stride);
+	// rows further apart than the soft bits fill: what lies between them is the caller's, and comes back as it was
+	int8_t *d_eb = ebits_stride > ht.ebits ? sg.inout(ebits, (size_t)n * ebits_stride) : sg.out(ebits, (size_t)n * ebits_stride);
 	int32_t *d_sid = sg.out(sync_id, (size_t)n);
 	float *d_toa = sg.out(toa, (size_t)n);
 	float *d_fe = sg.out(freq_err, (size_t)n);

@@ -1876,9 +1876,12 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 		int8_t *eb = L.eb + q * (GEN ? EBROW : 432);
 		row_chain |= kind << q;
 		if (!found) {
+			// (demodulation only: a row's soft bits and nothing behind them, which is the caller's where the rows lie
+			// further apart; the fused path's rows of 432 are zero beyond the format's soft bits)
 			if (io.ebits)
 				for (int i = lane; i < a.ebits_stride; i += 64)
-					io.ebits[(size_t)g * a.ebits_stride + i] = 0;
+					if (!GEN || i < bt.ebits)
+						io.ebits[(size_t)g * a.ebits_stride + i] = 0;
 			if constexpr (GEN)                                  // (a fused decoder reads the LDS row)
 				for (int i = lane; i < EBROW / 4; i += 64)
 					reinterpret_cast<uint32_t *>(eb)[i] = 0;
@@ -1904,6 +1907,12 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 		Bt -= rintf(Bt);
 		const float A2 = At * 2048.0f, B2 = Bt * 2048.0f;
 		const float scale = (float)(1 << nbits);
+		// demodulation only: the soft symbols that go out are formed about the reference's mean (window_mean_serial)
+		float2 mref = make_float2(avr, avi);
+		if constexpr (GEN) {
+			if (gss)
+				mref = window_mean_serial(a.iq + io.offset[g], a.in_len[0]);
+		}
 #pragma unroll
 		for (int r = 0; r < NSYM; r++) {
 			const int i = lane + 64 * r;
@@ -1926,8 +1935,14 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 			const float th2 = fmaf(A2, (float)i, fmaf(at, 2048.0f, B2));
 			if (gss) {
 				float th = th2 * (1.0f / 2048.0f);
+				bool zero_ss = zero;
+				if constexpr (GEN) {
+					const float xr = cur.x[r].x - mref.x, xi = cur.x[r].y - mref.y;
+					th = fmaf(A2, (float)i, fmaf(atan2_turns(xi, xr), 2048.0f, B2)) * (1.0f / 2048.0f);
+					zero_ss = !(cur.ok & (1 << r)) || (xr == 0.0f && xi == 0.0f);
+				}
 				th -= rintf(th);
-				gss[i] = zero ? 0.0f : th * scale;
+				gss[i] = zero_ss ? 0.0f : th * scale;
 			}
 			const int ord = ordv[r];
 			if (ord >= 0) {
@@ -1945,7 +1960,8 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 			const int neb = bt.ebits;
 			int8_t *ge = io.ebits + (size_t)g * a.ebits_stride;
 			for (int i = lane; i < a.ebits_stride; i += 64)
-				ge[i] = i < neb ? eb[i] : (int8_t)0;
+				if (!GEN || i < neb)
+					ge[i] = i < neb ? eb[i] : (int8_t)0;
 		}
 	}
 	if (GEN || (a.dbg_stop && a.dbg_stop < 7))

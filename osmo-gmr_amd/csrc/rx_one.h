@@ -243,7 +243,8 @@ __device__ int demod_one(int type, const float2 *__restrict__ in, int in_len, in
 	const int nbits = bt.nbits;
 	const int blen = bt.len;
 
-	load_normalise<NPL>(in, in_len, L, lane);
+	float avr, avi, inv_sd;
+	load_normalise_stats<NPL>(in, in_len, L, lane, avr, avi, inv_sd);
 	if (dbg_stop == 1) return -100;
 
 	// per-sample derotation step (pi4cxpsk.c:539)
@@ -392,6 +393,19 @@ __device__ int demod_one(int type, const float2 *__restrict__ in, int in_len, in
 	static_assert(NSYM * 64 >= kMaxLen, "the soft-symbol loop covers every format's length");
 	const float inv_dd = (float)(1 << nbits) / (2.0f * kPif);
 	const int mask = (1 << nbits) - 1;
+	// the soft symbols that go out are formed about the reference's mean (window_mean_serial): what a normalised sample
+	// moves by.  (Not behind the fractional delay, which has mixed the window's samples.)
+	const bool ref_mean = g_ssyms != nullptr && !frac_on;
+	float2 dm = make_float2(0.f, 0.f);
+	if (ref_mean) {
+		const float2 m = window_mean_serial(in, in_len);
+		dm = make_float2((avr - m.x) * inv_sd, (avi - m.y) * inv_sd);
+	}
+	auto soft_symbol = [&](float2 x, int i, int j) -> float {
+		float th = atan2_fast(x.y, x.x) + reduce_2pi(fs * (float)j);
+		th = reduce_2pi(fmaf(rps, (float)i, th) - psi);
+		return (x.x == 0.0f && x.y == 0.0f) ? 0.0f : th * inv_dd;   // cargf(0) = 0
+	};
 #pragma unroll
 	for (int r = 0; r < NSYM; r++) {
 		if (64 * r >= blen)
@@ -401,11 +415,9 @@ __device__ int demod_one(int type, const float2 *__restrict__ in, int in_len, in
 			continue;
 		const int j = i * sps + d;
 		const float2 x = pick(j);
-		float th = atan2_fast(x.y, x.x) + reduce_2pi(fs * (float)j);
-		th = reduce_2pi(fmaf(rps, (float)i, th) - psi);
-		const float sv = (x.x == 0.0f && x.y == 0.0f) ? 0.0f : th * inv_dd;   // cargf(0) = 0
+		const float sv = soft_symbol(x, i, j);
 		if (g_ssyms)
-			g_ssyms[i] = sv;
+			g_ssyms[i] = (ref_mean && j >= 0 && j < in_len) ? soft_symbol(make_float2(x.x + dm.x, x.y + dm.y), i, j) : sv;
 		const int ord = bt.ord_of_sym[i];
 		if (ord >= 0) {
 			const float svr2 = roundf(sv);
@@ -508,7 +520,8 @@ __global__ __launch_bounds__(64) void k_rx(RxArgs a, int max_in_len, int max_len
 		if (a.ebits) {
 			const int neb = c_types[type].ebits;
 			int8_t *ge = a.ebits + (size_t)g * a.ebits_stride;
-			for (int i = lane; i < a.ebits_stride; i += 64)
+			// (demodulation only: what lies behind a row's soft bits is the caller's; the fused rows of 432 are zero there)
+			for (int i = lane; i < (DECODE ? a.ebits_stride : neb); i += 64)
 				ge[i] = (rv == 0 && i < neb) ? eb[i] : (int8_t)0;
 		}
 		if (rv && gss)

@@ -329,6 +329,23 @@ __device__ __forceinline__ void window_stats_q(const float2 (&v)[16], int in_len
 	inv_o = __builtin_amdgcn_rcpf(stddev);
 }
 
+// The window's mean as the reference forms it (osmo_cxvec_sig_normalize): ONE fp32 sum in sample order, then a true division.
+// Under a constant offset of the burst's own amplitude that sum ends about 1e-6 from the exact mean, the wave's tree sums
+// within 1e-7 of it -- and a sample that all but vanishes once the mean is out (a guard symbol's noise, 1e-3 of the burst)
+// turns the difference into 1e-4 ... 5e-4 of a soft-symbol step.  Soft SYMBOLS are held to the reference's to 1e-4, so the
+// callers that write them out form them about this mean; nothing else uses it (soft bits come from symbols that carry
+// energy), and a call without the soft-symbol output never runs it.  Every lane walks the same addresses.
+__device__ __forceinline__ float2 window_mean_serial(const float2 *__restrict__ in, int in_len)
+{
+	float sr = 0.f, si = 0.f;
+	for (int i = 0; i < in_len; i++) {
+		const float2 v = in[i];
+		sr += v.x;
+		si += v.y;
+	}
+	return make_float2(sr / (float)in_len, si / (float)in_len);
+}
+
 // burst_energy() of the caller (gmr1_rx.c:172-182): sum |x|^2 over [len>>5, len - len>>5) of the RAW
 // window, divided by len.  Only the receive driver asks for it (RxArgs::energy); the window was
 // read a moment ago, so this second read is served by L1 / L2.

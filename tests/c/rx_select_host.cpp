@@ -141,11 +141,29 @@ int check_fused_rules()
 	return 0;
 }
 
+// A test's own cells, "type:extra:n" each (a built-in burst id, in_len = len * 4 + extra at 4 samples per symbol, n bursts):
+// one line "type extra n impl stage_samples" per cell, what demod_kernel_choice gives the product's call
+int report_cells(int argc, char **argv)
+{
+	for (int i = 1; i < argc; i++) {
+		int type, extra, n;
+		if (std::sscanf(argv[i], "%d:%d:%d", &type, &extra, &n) != 3 || type < 0 || type >= GMR1_HIP_N_BURSTS || extra < 0 || n < 0) {
+			std::printf("FAIL: cell '%s' is not type:extra:n\n", argv[i]);
+			return 1;
+		}
+		const DevBurst &ht = g_types[type];
+		int stage = -1;
+		const int impl = demod_kernel_choice(ht, n, 4, ht.len * 4 + extra, 0, &stage);
+		std::printf("%d %d %d %d %d\n", type, extra, n, impl, stage);
+	}
+	return 0;
+}
+
 }  // namespace
 
-int main()
+int main(int argc, char **argv)
 {
-	if (build_types() || check_kernel_choice() || check_fused_rules())
+	if (build_types() || check_kernel_choice() || check_fused_rules() || report_cells(argc, argv))
 		return 1;
 	std::printf("ok\n");
 	return 0;

@@ -12,10 +12,12 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
+BUILDS = pytest.mark.parametrize("extra", ([], SAN), ids=("plain", "asan_ubsan"))
 
 
-@pytest.mark.parametrize("extra", ([], SAN), ids=("plain", "asan_ubsan"))
-def test_kernel_choice_and_fused_rules_on_the_builtin_tables(tmp_path, extra):
+def run_rx_select_host(tmp_path, extra, args=()):
+    """tests/c/rx_select_host.cpp built with the compiler flags `extra` and run with `args` -> the lines it printed; its
+    own checks ran first, and the last line is their "ok" """
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     csrc = os.path.join(ROOT, "osmo-gmr_amd", "csrc")
@@ -25,5 +27,12 @@ def test_kernel_choice_and_fused_rules_on_the_builtin_tables(tmp_path, extra):
                            os.path.join(ROOT, "tests", "c", "rx_select_host.cpp"), os.path.join(csrc, "host_tables.cpp"),
                            "-o", exe])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    res = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert res.returncode == 0 and res.stdout.strip() == "ok", res.stdout + res.stderr
+    res = subprocess.run([exe] + list(args), capture_output=True, text=True, env=env)
+    lines = res.stdout.split("\n")
+    assert res.returncode == 0 and lines[-2:] == ["ok", ""], res.stdout + res.stderr
+    return lines[:-2]
+
+
+@BUILDS
+def test_kernel_choice_and_fused_rules_on_the_builtin_tables(tmp_path, extra):
+    assert run_rx_select_host(tmp_path, extra) == []
