@@ -319,13 +319,6 @@ int codec_init_list(hipStream_t st, int n, const int32_t *call, void *state, int
 	return 0;
 }
 
-// a slot per frame, a sink block per call, each from a 128-byte boundary
-size_t tch3_audio_scratch_bytes(int n_calls, int n_frames)
-{
-	auto up = [](size_t x) { return (x + 127) & ~(size_t)127; };
-	return up((size_t)n_frames * 4) + up((size_t)n_calls * kAudioBytes);
-}
-
 int tch3_audio_enqueue(hipStream_t st, void *scratch, int n_calls, const int32_t *first, int n_frames,
                        const struct gmr1_hip_tch3_frame *frames, const uint32_t *fn, const uint64_t *label, void *codec_state,
                        struct gmr1_hip_rx_audio *out, int max_out, int32_t *call_base, int32_t *n_out)
@@ -333,12 +326,12 @@ int tch3_audio_enqueue(hipStream_t st, void *scratch, int n_calls, const int32_t
 	AmbeAudioArgs a;
 	int r = dev_tab(&a.tab, &a.big, &a.libm);
 	if (r) return r;
-	unsigned char *d = static_cast<unsigned char *>(scratch);
+	const AudioScratch o(scratch, (size_t)n_calls, (size_t)n_frames);
 	Tch3AudioArgs c;
 	std::memset(&c, 0, sizeof(c));
 	c.n_calls = n_calls; c.n_frames = n_frames; c.max_out = max_out;
 	c.first = first; c.frames = frames; c.fn = fn; c.label = label; c.out = out;
-	c.slot = reinterpret_cast<int32_t *>(d);
+	c.slot = o.slot;
 	c.call_base = call_base; c.n_out = n_out;
 	HIP_TRY(launch_tch3f_audio(c, st));
 	a.n_calls = n_calls;
@@ -348,7 +341,7 @@ int tch3_audio_enqueue(hipStream_t st, void *scratch, int n_calls, const int32_t
 	a.rec = reinterpret_cast<const uint8_t *>(frames);
 	a.slot = c.slot;
 	a.out = reinterpret_cast<unsigned char *>(out);
-	a.sink = d + (((size_t)n_frames * 4 + 127) & ~(size_t)127);
+	a.sink = reinterpret_cast<unsigned char *>(o.sink);
 	a.state = static_cast<AmbeState *>(codec_state);
 	a.tone_n = kAmbeFrameSamples;
 	a.dbg = 0;
@@ -536,11 +529,9 @@ int gmr1_hip_tch3_frames_to_audio_dev(void *stream, int n_calls, const int32_t *
 		return 0;
 	}
 	if ((r = tch3_pcm_prepare())) return r;
-	WsLease lease;
-	if ((r = lease.acquire(s, st))) return r;
-	Arena ws;                                      // the start of the device's workspace
-	if ((r = ws.init(tch3_audio_scratch_bytes(n_calls, n_frames)))) return r;
-	return tch3_audio_enqueue(st, ws.base, n_calls, first, n_frames, frames, fn, label, codec_state, out, max_out, nullptr, n_out);
+	return with_scratch(s, st, tch3_audio_scratch_bytes(n_calls, n_frames), [&](void *ws) {
+		return tch3_audio_enqueue(st, ws, n_calls, first, n_frames, frames, fn, label, codec_state, out, max_out, nullptr, n_out);
+	});
 }
 
 // ---- the reference's own calls (include/osmocom/gmr1/codec/codec.h:37-45) ----

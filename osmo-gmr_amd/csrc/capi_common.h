@@ -13,6 +13,7 @@
 
 #include "gmr1_dev.h"
 #include "host_tables.h"
+#include "scratch_layouts.h"
 
 namespace gmr1 {
 
@@ -118,17 +119,17 @@ int dbg_stop_env();
 int l1_dev(hipStream_t st, int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv);
 int l1_host(int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv);
 
-// gmr1_hip_tch3_follow_batch_dev on scratch of the caller's (capi_tch3_follow.cpp): tch3_follow_scratch_bytes(n_frames) of
-// device memory on a 128-byte boundary.  The arguments are not checked; the caller holds a WsLease.
-size_t tch3_follow_scratch_bytes(int n_frames);
+// gmr1_hip_tch3_follow_batch_dev on scratch of the caller's (capi_tch3_follow.cpp): tch3_follow_scratch_bytes(n_frames)
+// (scratch_layouts.h) of device memory on a 128-byte boundary.  The arguments are not checked; the caller holds a WsLease.
 int tch3_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, const float *iq, const int32_t *first,
                         int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                         struct gmr1_hip_tch3_state *state, struct gmr1_hip_tch3_frame *out);
 
 // The speech decoder over the TCH3 follower's records (capi_ambe.cpp), shared by gmr1_hip_tch3_frames_to_pcm* and
 // gmr1_hip_tch3_voice_batch*.  _check: counts, required pointers (codec_state only where state_required), flag bits outside
-// flags_known, alignment -- needs no device.  _first_check: first[] is a partition of 0..n_frames (host memory).  _prepare: the
-// decoder's tables are on the current device (the first use uploads and builds them).  _fresh: gmr1_hip_codec_init_dev.
+// flags_known, alignment -- needs no device.  _first_check: first[] is a partition of 0..n_frames (host memory; every
+// follower's host form asks it under its own name).  _prepare: the decoder's tables are on the current device (the first
+// use uploads and builds them).  _fresh: gmr1_hip_codec_init_dev.
 // _enqueue: one launch on `st`, device pointers, arguments not checked.
 int tch3_pcm_check(const char *who, int n_calls, const int32_t *first, int n_frames, const void *frames, const void *codec_state,
                    bool state_required, int flags, int flags_known, const void *pcm);
@@ -139,26 +140,34 @@ int tch3_pcm_enqueue(hipStream_t st, int n_calls, const int32_t *first, int n_fr
                      void *codec_state, int16_t *pcm, int32_t *rv);
 
 // The follower's records closed up into audio blocks (capi_ambe.cpp; the rule: tch3_audio.h): what
-// gmr1_hip_tch3_frames_to_audio_dev runs, on scratch of the caller's -- tch3_audio_scratch_bytes of device memory on a
-// 128-byte boundary -- with the arguments not checked.  call_base (optional, device, n_calls entries): the blocks in front
+// gmr1_hip_tch3_frames_to_audio_dev runs, on scratch of the caller's -- tch3_audio_scratch_bytes (scratch_layouts.h) of
+// device memory on a 128-byte boundary -- with the arguments not checked.  call_base (optional, device, n_calls entries): the blocks in front
 // of each call.  codec_init_list: gmr1_hip_codec_init_list_dev.
-size_t tch3_audio_scratch_bytes(int n_calls, int n_frames);
 int tch3_audio_enqueue(hipStream_t st, void *scratch, int n_calls, const int32_t *first, int n_frames,
                        const struct gmr1_hip_tch3_frame *frames, const uint32_t *fn, const uint64_t *label, void *codec_state,
                        struct gmr1_hip_rx_audio *out, int max_out, int32_t *call_base, int32_t *n_out);
 int codec_init_list(hipStream_t st, int n, const int32_t *call, void *state, int flags);
 
 // gmr1_hip_tch9_follow_batch_dev on scratch of the caller's (capi_tch9_follow.cpp), under the same terms
-size_t tch9_follow_scratch_bytes(int n_frames);
 int tch9_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,
                         int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                         struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out);
 
 // Device scratch of a traffic pass: one carve-up of the grow-only device workspace (none of the kernels the
-// passes launch uses it) instead of dozens of hipMalloc / hipFree pairs per call.
+// passes launch uses it) instead of dozens of hipMalloc / hipFree pairs per call.  No byte count is summed for it: a pass
+// is written once and run twice (sized_by) -- on the arena measuring, when it has no memory, take() only adds up and a
+// Stage on it copies nothing; then on memory of the size that took.
 struct Arena {
 	unsigned char *base = nullptr;
 	size_t cap = 0, off = 0;
+	bool measures = false;
+	template <class F> int sized_by(F &&pass)
+	{
+		base = nullptr; cap = ~(size_t)0; off = 0; measures = true;
+		pass(*this);
+		const int r = init(off);
+		return r ? r : pass(*this);
+	}
 	int init(size_t bytes)
 	{
 		DevState *ds;
@@ -167,17 +176,18 @@ struct Arena {
 		void *ws;
 		r = dev_workspace(ds, bytes + 256, &ws);
 		if (r) return r;
-		base = reinterpret_cast<unsigned char *>(((uintptr_t)ws + 127) & ~(uintptr_t)127);
+		base = reinterpret_cast<unsigned char *>(up128((uintptr_t)ws));
 		cap = bytes;
 		off = 0;
+		measures = false;
 		return 0;
 	}
 	void *take(size_t n)
 	{
-		n = ((n ? n : 1) + 127) & ~(size_t)127;
+		n = up128(n ? n : 1);
 		if (off + n > cap)
 			return nullptr;
-		void *p = base + off;
+		void *p = measures ? static_cast<void *>(this) : base + off;      // (measuring: a pointer nobody follows)
 		off += n;
 		return p;
 	}
@@ -200,12 +210,12 @@ public:
 	// uploaded
 	template <typename T> const T *in(const T *h, size_t n)
 	{
-		T *d = h ? dev<T>(n) : nullptr;
+		T *d = h || measures() ? dev<T>(n) : nullptr;
 		if (d) copy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
 		return d;
 	}
 	// copied back by fetch()
-	template <typename T> T *out(T *h, size_t n) { return h ? out_always(h, n) : nullptr; }
+	template <typename T> T *out(T *h, size_t n) { return h || measures() ? out_always(h, n) : nullptr; }
 	// an output the kernel writes whether the caller wants it or not: copied back by fetch() if h is not null
 	template <typename T> T *out_always(T *h, size_t n)
 	{
@@ -221,7 +231,9 @@ public:
 		return d;
 	}
 	// fetch() copies the n elements at d, which lie in a buffer of this stage, to h (nothing if h is null)
-	template <typename T> void back(T *h, const T *d, size_t n) { if (h && d) backs_.push_back({h, d, n * sizeof(T)}); }
+	template <typename T> void back(T *h, const T *d, size_t n) { if (h && d && !measures()) backs_.push_back({h, d, n * sizeof(T)}); }
+	// on a measuring Arena: every buffer is charged for, a null or empty host side too, and nothing is copied or booked
+	bool measures() const { return arena_ && arena_->measures; }
 
 	int err() const
 	{
@@ -248,7 +260,7 @@ private:
 	void note(const char *what, hipError_t e) { if (e_ == hipSuccess && e != hipSuccess) { e_ = e; what_ = what; } }
 	void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
 	{
-		if (e_ != hipSuccess) return;
+		if (e_ != hipSuccess || measures()) return;
 		if (arena_) note("hipMemcpyAsync", hipMemcpyAsync(dst, src, bytes, kind, st_));
 		else note("hipMemcpy", hipMemcpy(dst, src, bytes, kind));
 	}
@@ -272,5 +284,31 @@ private:
 	std::vector<void *> owned_;
 	std::vector<Back> backs_;
 };
+
+// One turn on the device's workspace: leases it for `st`, hands enqueue(scratch) `bytes` of it, gives the lease back on return
+template <class F> int with_scratch(DevState *s, hipStream_t st, size_t bytes, F &&enqueue)
+{
+	WsLease lease;
+	int r = lease.acquire(s, st);
+	if (r) return r;
+	Arena ws;
+	if ((r = ws.init(bytes))) return r;
+	return enqueue(static_cast<void *>(ws.base));
+}
+
+// The device copies of what a call follower's host form is handed: the samples and the per-frame arrays (the bits form has
+// neither samples nor windows: null, nothing staged), the calls' states in and out, the records out.
+template <class State, class Frame> struct FollowStaged {
+	const float *iq; const int32_t *first; const uint64_t *off; const float *fs; const uint32_t *fn;
+	State *state; Frame *out;
+};
+template <class State, class Frame>
+FollowStaged<State, Frame> stage_follow(Stage &sg, int n_calls, const float *iq, uint64_t iq_len, const int32_t *first, int n_frames,
+                                        const uint64_t *off, const float *fs, const uint32_t *fn, State *state, Frame *out)
+{
+	const size_t n = (size_t)n_frames;
+	return {sg.in(iq, (size_t)iq_len * 2), sg.in(first, (size_t)n_calls + 1), sg.in(off, n), sg.in(fs, n), sg.in(fn, n),
+	        sg.inout(state, (size_t)n_calls), sg.out(out, n)};
+}
 
 }  // namespace gmr1

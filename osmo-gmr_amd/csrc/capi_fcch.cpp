@@ -357,8 +357,6 @@ int acq_spare(size_t n, hipStream_t st, const float2 **out)
 	return 0;
 }
 
-size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
-
 int acq_check(int tab, int n, int sps, const float *iq, const uint64_t *offset, const uint64_t *length, const void *out)
 {
 	if (tab < 0 || tab >= kFcchTabs)
@@ -399,50 +397,25 @@ int fcch_acquire_enqueue(hipStream_t st, int tab, int n, int sps, const float *i
 	const int flen = kFcchBuiltin[tab]->len * sps;
 	const int wl1 = (330 * 23400 * sps) / 1000, wl3 = (650 * 23400 * sps) / 1000;
 	const size_t S = (size_t)n * kAcqPeaks;
-	// one block: [per carrier ... | per slot ...]
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t at = o; o += up128(bytes); return at; };
-	const size_t o_base = take(n * 8), o_len = take(n * 8), o_stat = take(n * 4), o_align = take(n * 4), o_ba = take(n * 4),
-	             o_ferr = take(n * 4), o_can3 = take(n * 4), o_off = take(S * 8), o_peaks = take(S * 4), o_toa1 = take(n * 4),
-	             o_rv1 = take(n * 4), o_ftoa = take(n * 4), o_fe = take(n * 4), o_count = take(n * 4), o_ctoa = take(S * 4),
-	             o_cfe = take(S * 4), o_snr = take(S * 4), o_live = take(S * 4), o_fs = take(S * 4);
-	const size_t total = o;
 	unsigned char *d;
-	if ((r = acq_scratch(0, total, &d))) return r;
+	if ((r = acq_scratch(0, AcqScratch(nullptr, (size_t)n, kAcqPeaks).bytes, &d))) return r;
+	const AcqScratch o(d, (size_t)n, kAcqPeaks);
 	const float2 *spare;
 	if ((r = acq_spare((size_t)wl3, st, &spare))) return r;
-	auto D = [&](size_t at) { return d + at; };
 
 	AcqArgs g;
 	std::memset(&g, 0, sizeof(g));
 	g.n = n; g.sps = sps; g.flen = flen; g.wl3 = wl3;
 	// (both are 8-byte aligned, so the difference is whole samples; windows are iq + offset in 64-bit arithmetic)
 	g.spare = (uint64_t)((uintptr_t)spare - (uintptr_t)iq) / sizeof(float2);
-	g.base = reinterpret_cast<uint64_t *>(D(o_base));
-	g.len = reinterpret_cast<uint64_t *>(D(o_len));
-	g.stat = reinterpret_cast<int32_t *>(D(o_stat));
-	g.align = reinterpret_cast<int32_t *>(D(o_align));
-	g.base_align = reinterpret_cast<int32_t *>(D(o_ba));
-	g.ferr = reinterpret_cast<float *>(D(o_ferr));
-	g.can3 = reinterpret_cast<int32_t *>(D(o_can3));
-	g.toa1 = reinterpret_cast<const int32_t *>(D(o_toa1));
-	g.rv1 = reinterpret_cast<const int32_t *>(D(o_rv1));
-	g.ftoa = reinterpret_cast<const int32_t *>(D(o_ftoa));
-	g.fe = reinterpret_cast<const float *>(D(o_fe));
-	g.peaks = reinterpret_cast<int32_t *>(D(o_peaks));
-	g.count = reinterpret_cast<int32_t *>(D(o_count));
-	g.ctoa = reinterpret_cast<const int32_t *>(D(o_ctoa));
-	g.cfe = reinterpret_cast<const float *>(D(o_cfe));
-	g.off = reinterpret_cast<uint64_t *>(D(o_off));
-	g.fs = reinterpret_cast<float *>(D(o_fs));
-	g.live = reinterpret_cast<int32_t *>(D(o_live));
-	uint64_t *d_off = g.off;
-	float *d_fs = g.fs;
+	g.base = o.base; g.len = o.len; g.stat = o.stat; g.align = o.align; g.base_align = o.base_align; g.ferr = o.ferr;
+	g.can3 = o.can3; g.toa1 = o.toa1; g.rv1 = o.rv1; g.ftoa = o.ftoa; g.fe = o.fe; g.peaks = o.peaks; g.count = o.count;
+	g.ctoa = o.ctoa; g.cfe = o.cfe; g.off = o.off; g.fs = o.fs; g.live = o.live;
 	AcqIo io;
 	std::memset(&io, 0, sizeof(io));
 	io.offset = offset; io.length = length; io.start = start;
 	io.wl1 = wl1;
-	io.snr = reinterpret_cast<const float *>(D(o_snr));
+	io.snr = o.snr;
 	io.out = out;
 	HIP_TRY(launch_acq_begin(g, io, st));
 
@@ -461,11 +434,9 @@ int fcch_acquire_enqueue(hipStream_t st, int tab, int n, int sps, const float *i
 		return t;
 	};
 	// fcch_single_init (gmr1_rx.c:605-639): rough over 330 ms, then fine
-	if ((r = fcch_rough_tail(st, tab, n, sps, wl1, iq, d_off, nullptr, reinterpret_cast<int32_t *>(D(o_toa1)),
-	                         reinterpret_cast<int32_t *>(D(o_rv1)), tail(1, false)))) return r;
+	if ((r = fcch_rough_tail(st, tab, n, sps, wl1, iq, o.off, nullptr, o.toa1, o.rv1, tail(1, false)))) return r;
 	if (unfused) HIP_TRY(launch_acq_glue(1, g, st));
-	if ((r = fcch_fine_tail(st, tab, 0, n, sps, iq, d_off, nullptr, reinterpret_cast<int32_t *>(D(o_ftoa)),
-	                        reinterpret_cast<float *>(D(o_fe)), nullptr, tail(2, false)))) return r;
+	if ((r = fcch_fine_tail(st, tab, 0, n, sps, iq, o.off, nullptr, o.ftoa, o.fe, nullptr, tail(2, false)))) return r;
 	if (unfused) HIP_TRY(launch_acq_glue(2, g, st));
 	// fcch_multi_process (gmr1_rx.c:643-744); a carrier shorter than 650 ms can only fail here: where the host knows the
 	// lengths the sweep runs over the others (where it does not, over everything: such a carrier's window is the spare one)
@@ -476,23 +447,20 @@ int fcch_acquire_enqueue(hipStream_t st, int tab, int n, int sps, const float *i
 	const bool all3 = (int)k3.size() == n;
 	if (!k3.empty()) {
 		if (all3) {
-			if ((r = fcch_rough_multi_tail(st, tab, n, sps, wl3, iq, d_off, d_fs, reinterpret_cast<int32_t *>(D(o_peaks)),
-			                               kAcqPeaks, reinterpret_cast<int32_t *>(D(o_count)), tail(3, false)))) return r;
+			if ((r = fcch_rough_multi_tail(st, tab, n, sps, wl3, iq, o.off, o.fs, o.peaks, kAcqPeaks, o.count,
+			                               tail(3, false)))) return r;
 		} else {
 			// mixed lengths: the long-enough carriers one by one at their own slots (rare; captures come in equal lengths)
 			for (int k : k3)
-				if ((r = gmr1_hip_fcch_rough_multi_batch_dev(st, tab, 1, sps, wl3, iq, d_off + k, d_fs + k,
-				                                             reinterpret_cast<int32_t *>(D(o_peaks)) + (size_t)k * kAcqPeaks, kAcqPeaks,
-				                                             reinterpret_cast<int32_t *>(D(o_count)) + k))) return r;
+				if ((r = gmr1_hip_fcch_rough_multi_batch_dev(st, tab, 1, sps, wl3, iq, o.off + k, o.fs + k,
+				                                             o.peaks + (size_t)k * kAcqPeaks, kAcqPeaks, o.count + k))) return r;
 		}
 	}
 	// (mixed lengths, or no carrier long enough: the step that lays out the candidate slots runs as its own launch)
 	if (unfused || !all3) HIP_TRY(launch_acq_glue(3, g, st));
-	if ((r = fcch_fine_tail(st, tab, 0, (int)S, sps, iq, d_off, d_fs, reinterpret_cast<int32_t *>(D(o_ctoa)),
-	                        reinterpret_cast<float *>(D(o_cfe)), nullptr, tail(4, true)))) return r;
+	if ((r = fcch_fine_tail(st, tab, 0, (int)S, sps, iq, o.off, o.fs, o.ctoa, o.cfe, nullptr, tail(4, true)))) return r;
 	if (unfused) HIP_TRY(launch_acq_glue(4, g, st));
-	if ((r = fcch_fine_tail(st, tab, 1, (int)S, sps, iq, d_off, d_fs, nullptr, nullptr, reinterpret_cast<float *>(D(o_snr)),
-	                        tail(0, true)))) return r;
+	if ((r = fcch_fine_tail(st, tab, 1, (int)S, sps, iq, o.off, o.fs, nullptr, nullptr, o.snr, tail(0, true)))) return r;
 	HIP_TRY(launch_acq_decide(g, io, st));
 	return 0;
 }

@@ -72,28 +72,26 @@ int RxRun::acquire()
 	int n_tp = 0;
 	auto stamp = [&] { if (timing && n_tp < 6) tp[n_tp++] = RxClock::now(); };
 	stamp();
-	// one block, device and pinned host mirror: [offset | length | results]
-	const size_t o_len = up128((size_t)A * 8), o_res = o_len + up128((size_t)A * 8);
-	const size_t total = o_res + (size_t)A * sizeof(gmr1_hip_fcch_acq);
+	// one block, device and pinned host mirror
+	const size_t total = AcqBlock(nullptr, (size_t)A).bytes;
 	unsigned char *d, *h;
 	if ((r = acq_scratch(1, total, &d))) return r;
 	if ((r = host_log(total, &h))) return r;
-	std::memcpy(h, offset, (size_t)A * 8);
-	std::memcpy(h + o_len, length, (size_t)A * 8);
-	HIP_TRY(hipMemcpyAsync(d, h, o_res, hipMemcpyHostToDevice, st));
+	const AcqBlock da(d, (size_t)A), ha(h, (size_t)A);
+	std::memcpy(ha.offset, offset, (size_t)A * 8);
+	std::memcpy(ha.length, length, (size_t)A * 8);
+	HIP_TRY(hipMemcpyAsync(da.offset, ha.offset, da.up_bytes, hipMemcpyHostToDevice, st));
 	stamp();
-	if ((r = fcch_acquire_enqueue(st, 0, A, sps, iq, reinterpret_cast<const uint64_t *>(d),
-	                              reinterpret_cast<const uint64_t *>(d + o_len), nullptr, length,
-	                              reinterpret_cast<gmr1_hip_fcch_acq *>(d + o_res)))) return r;
+	if ((r = fcch_acquire_enqueue(st, 0, A, sps, iq, da.offset, da.length, nullptr, length, da.results))) return r;
 	stamp();
-	HIP_TRY(hipMemcpyAsync(h + o_res, d + o_res, (size_t)A * sizeof(gmr1_hip_fcch_acq), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(ha.results, da.results, (size_t)A * sizeof(gmr1_hip_fcch_acq), hipMemcpyDeviceToHost, st));
 	stamp();
 	HIP_TRY(hipStreamSynchronize(st));
 	stamp();
 	if (timing)
 		fprintf(stderr, "acquire: prepare + first copy %.1f us, launches %.1f us, copy back enqueued %.1f us, waited %.1f us\n",
 		        us_between(tp[0], tp[1]), us_between(tp[1], tp[2]), us_between(tp[2], tp[3]), us_between(tp[3], tp[4]));
-	const gmr1_hip_fcch_acq *res = reinterpret_cast<const gmr1_hip_fcch_acq *>(h + o_res);
+	const gmr1_hip_fcch_acq *res = ha.results;
 	for (int i = 0; i < A; i++) {
 		if (res[i].status) { stat[i] = res[i].status; continue; }
 		for (int j = 0; j < res[i].n_chains; j++)
@@ -139,43 +137,42 @@ struct LoopLayout {
 	// pointers, on the pinned mirror the host the same names for the front part.  Returns the bytes taken.
 	size_t carve(unsigned char *base, RxLoopArgs *la)
 	{
-		uintptr_t q = (uintptr_t)base;
-		auto take = [&](size_t n) { void *p = (void *)q; q += up128(n); return p; };
+		Carve c(base);
 		const size_t nrec = (size_t)nc * rec_stride, nslot = (size_t)nc * c_stride;
 		std::memset(la, 0, sizeof(*la));
 		la->rec_stride = rec_stride;
 		la->max_rounds = max_rounds;
 		la->c_stride = c_stride;
-		la->rec = static_cast<gmr1_hip_rx_record *>(take(nrec * sizeof(gmr1_hip_rx_record)));
-		la->n_rounds = static_cast<int32_t *>(take(((size_t)nc * 3 + 1) * 4));
+		la->rec = c.take<gmr1_hip_rx_record>(nrec);
+		la->n_rounds = c.take<int32_t>((size_t)nc * 3 + 1);
 		la->n_rec = la->n_rounds + nc;
 		la->n_frames = la->n_rec + nc;
-		la->state = static_cast<RxLoopState *>(take((size_t)nc * sizeof(RxLoopState)));
+		la->state = c.take<RxLoopState>((size_t)nc);
 		if (want_ctx) {
-			la->rec_frame = static_cast<int32_t *>(take(nrec * 4));
-			la->rec_minen = static_cast<float *>(take(nrec * 4));
-			la->flog = static_cast<RxLoopFrame *>(take((size_t)nc * max_frames * sizeof(RxLoopFrame)));
+			la->rec_frame = c.take<int32_t>(nrec);
+			la->rec_minen = c.take<float>(nrec);
+			la->flog = c.take<RxLoopFrame>((size_t)nc * max_frames);
 			la->flog_stride = max_frames;
 		}
-		mirrored = (size_t)(q - (uintptr_t)base);
-		la->rounds = static_cast<RxLoopRound *>(take((size_t)nc * max_rounds * sizeof(RxLoopRound)));
-		la->n_ccch = static_cast<int32_t *>(take((size_t)nc * 4));
-		la->fin = static_cast<int32_t *>(take((size_t)nc * 4));
-		la->slice_end = static_cast<int32_t *>(take(up128((size_t)nc * 4) * (kLoopSlices + 1)));
-		la->c_off = static_cast<uint64_t *>(take(nslot * 8));
-		la->c_fs = static_cast<float *>(take(nslot * 4));
-		la->c_kind = static_cast<uint8_t *>(take(nslot));
-		la->c_meta = static_cast<RxLoopCcch *>(take(nslot * sizeof(RxLoopCcch)));
-		la->c_l2 = static_cast<uint8_t *>(take(nslot * 24));
-		la->c_crc = static_cast<int32_t *>(take(nslot * 4));
-		la->c_conv = static_cast<int32_t *>(take(nslot * 4));
-		la->c_rv = static_cast<int32_t *>(take(nslot * 4));
-		la->c_en = static_cast<float *>(take(nslot * 4));
+		mirrored = c.bytes();
+		la->rounds = c.take<RxLoopRound>((size_t)nc * max_rounds);
+		la->n_ccch = c.take<int32_t>((size_t)nc);
+		la->fin = c.take<int32_t>((size_t)nc);
+		la->slice_end = c.take<int32_t>(up128((size_t)nc * 4) / 4 * (kLoopSlices + 1));
+		la->c_off = c.take<uint64_t>(nslot);
+		la->c_fs = c.take<float>(nslot);
+		la->c_kind = c.take<uint8_t>(nslot);
+		la->c_meta = c.take<RxLoopCcch>(nslot);
+		la->c_l2 = c.take<uint8_t>(nslot * 24);
+		la->c_crc = c.take<int32_t>(nslot);
+		la->c_conv = c.take<int32_t>(nslot);
+		la->c_rv = c.take<int32_t>(nslot);
+		la->c_en = c.take<float>(nslot);
 		if (pack) {
-			la->packed = static_cast<gmr1_hip_rx_record *>(take(nrec * sizeof(gmr1_hip_rx_record)));
+			la->packed = c.take<gmr1_hip_rx_record>(nrec);
 			la->n_packed = la->n_frames + nc;
 		}
-		return (size_t)(q - (uintptr_t)base);
+		return c.bytes();
 	}
 };
 
@@ -302,7 +299,7 @@ int RxRun::frame_loop()
 	unsigned char *h;
 	if ((r = host_log(lay.mirrored, &h))) return r;
 	RxLoopArgs la, ha;
-	lay.carve(reinterpret_cast<unsigned char *>(((uintptr_t)ws + 127) & ~(uintptr_t)127), &la);
+	lay.carve(reinterpret_cast<unsigned char *>(up128((uintptr_t)ws)), &la);
 	lay.carve(h, &ha);
 	if ((r = loop_launch(*this, lay, la, ha, t_start))) return r;
 	loop_collect(*this, lay, ha);

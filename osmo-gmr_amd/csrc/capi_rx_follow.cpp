@@ -51,20 +51,21 @@ struct Tch3Batch {
 // one invocation: staged, rx_tch3_init on the states where they lie, the follower, b.got on the host (one synchronisation,
 // which also comes ahead of the next invocation's staging: the vectors are reused).  d_codec: the calls' decoders, for a
 // pass that gives audio -- made fresh for the very calls rx_tch3_init runs on, then run over the frames where they lie;
-// the block counts come back with b.got.
+// the block counts come back with b.got.  On a measuring arena it stages (nothing) and launches nothing.
 int tch3_invoke(hipStream_t st, Arena &arena, int n_calls, int sps, const float *tch, gmr1_hip_tch3_state *d_state, Tch3Batch &b,
                 void *d_codec)
 {
 	int r = 0;
 	const size_t n = b.item.size(), n_assign = b.a_call.size();
+	const bool live = !arena.measures;
 	b.got.resize(n);
 	Stage sg(st, &arena);
 	if (n_assign) {
 		const int32_t *d_call = sg.in(b.a_call.data(), n_assign), *d_p = sg.in(b.a_p.data(), n_assign);
 		const float *d_en = sg.in(b.a_en.data(), n_assign);
 		if ((r = sg.err())) return r;
-		if ((r = gmr1_hip_tch3_state_assign_batch_dev(st, (int)n_assign, d_call, d_p, d_en, d_state))) return r;
-		if (d_codec && (r = codec_init_list(st, (int)n_assign, d_call, d_codec, 0))) return r;
+		if (live && (r = gmr1_hip_tch3_state_assign_batch_dev(st, (int)n_assign, d_call, d_p, d_en, d_state))) return r;
+		if (live && d_codec && (r = codec_init_list(st, (int)n_assign, d_call, d_codec, 0))) return r;
 	}
 	b.d_audio = nullptr;
 	b.call_base.assign((size_t)n_calls + 1, 0);
@@ -76,20 +77,19 @@ int tch3_invoke(hipStream_t st, Arena &arena, int n_calls, int sps, const float 
 		gmr1_hip_tch3_frame *d_got = sg.out(b.got.data(), n);
 		unsigned char *scratch = sg.dev<unsigned char>(tch3_follow_scratch_bytes((int)n));
 		if ((r = sg.err())) return r;
-		r = tch3_follow_enqueue(st, scratch, n_calls, sps, rx_tch3_in_len(sps), tch, d_first, (int)n, d_off, d_fs, d_fn, d_state, d_got);
-		if (r) return r;
+		if (live && (r = tch3_follow_enqueue(st, scratch, n_calls, sps, rx_tch3_in_len(sps), tch, d_first, (int)n, d_off, d_fs, d_fn,
+		                                     d_state, d_got))) return r;
 		if (d_codec) {
 			const uint64_t *d_label = sg.in(b.label.data(), (size_t)n_calls);
 			int32_t *d_base = sg.out(b.call_base.data(), (size_t)n_calls + 1);
 			b.d_audio = sg.dev<gmr1_hip_rx_audio>(n);
 			unsigned char *a_scratch = sg.dev<unsigned char>(tch3_audio_scratch_bytes(n_calls, (int)n));
 			if ((r = sg.err())) return r;
-			r = tch3_audio_enqueue(st, a_scratch, n_calls, d_first, (int)n, d_got, d_fn, d_label, d_codec, b.d_audio, (int)n, d_base,
-			                       d_base + n_calls);
-			if (r) return r;
+			if (live && (r = tch3_audio_enqueue(st, a_scratch, n_calls, d_first, (int)n, d_got, d_fn, d_label, d_codec, b.d_audio,
+			                                    (int)n, d_base, d_base + n_calls))) return r;
 		}
 	}
-	return sg.fetch();
+	return live ? sg.fetch() : 0;
 }
 
 // frame order within a chain: BCCH / CCCH of a frame come before its TCH records
@@ -141,28 +141,23 @@ int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t
 	const int nt = (int)titems.size();
 	if (!nt && (h_state0 || !plan.any_event))
 		return 0;
-	// the states if they start here, first[] and an assignment per call, per frame 56 B staged and the follower's scratch;
-	// no invocation has more than nt frames
-	// with audio: the decoders if they start here, a label and a block count per call, a block per frame, the close-up's scratch
 	const size_t codec_bytes = gmr1_hip_codec_state_bytes();
 	const bool own_codec = voice && !voice->d_codec;
-	const size_t voice_bytes = !voice ? 0 : (own_codec ? up128((size_t)n_calls * codec_bytes) : 0) + up128((size_t)n_calls * 8) +
-	                           up128(((size_t)n_calls + 1) * 4) + up128((size_t)nt * sizeof(gmr1_hip_rx_audio)) +
-	                           tch3_audio_scratch_bytes(n_calls, nt) + 2 * 128;
 	if (voice && (r = tch3_pcm_prepare())) return r;  // the decoder's tables, before anything is enqueued
-	Arena arena;
-	if ((r = arena.init((h_state0 ? (size_t)n_calls * sizeof(gmr1_hip_tch3_state) + 128 : 0) + ((size_t)n_calls + 1) * 4 +
-	                    (size_t)n_calls * 12 + (size_t)nt * 56 + 10 * 128 + tch3_follow_scratch_bytes(nt) + voice_bytes))) return r;
 	void *d_codec = voice ? voice->d_codec : nullptr;
-	if (h_state0 || own_codec) {
-		Stage s0(st, &arena);
-		if (h_state0)
-			d_state = const_cast<gmr1_hip_tch3_state *>(s0.in(h_state0, (size_t)n_calls));
-		// (no decoder is read before an assignment made it fresh: frames are handed in from a call's first assignment on)
-		if (own_codec)
-			d_codec = s0.dev<unsigned char>((size_t)n_calls * codec_bytes);
-		if ((r = s0.err())) return r;
-	}
+	// What the pass keeps: the states and the decoders if they start here (no decoder is read before an assignment made it
+	// fresh: frames are handed in from a call's first assignment on).  Measuring, the largest invocation comes behind that:
+	// none has more than n_calls assignments or nt frames.
+	Tch3Batch b;
+	b.first.resize((size_t)n_calls + 1); b.a_call.resize((size_t)n_calls); b.item.resize((size_t)nt);
+	auto keep = [&](Arena &ar) -> int {
+		Stage s0(st, &ar);
+		if (h_state0) d_state = const_cast<gmr1_hip_tch3_state *>(s0.in(h_state0, (size_t)n_calls));
+		if (own_codec) d_codec = s0.dev<unsigned char>((size_t)n_calls * codec_bytes);
+		return ar.measures ? tch3_invoke(st, ar, n_calls, sps, tch, d_state, b, d_codec) : s0.err();
+	};
+	Arena arena;
+	if ((r = arena.sized_by(keep))) return r;
 	const size_t arena_kept = arena.off;
 	// where the blocks go (rx_follow.h): straight to the caller when one invocation has them all
 	const bool direct = voice && tch3_voice_invocations(plan) <= 1;
@@ -170,8 +165,6 @@ int tch3_follow_chains(hipStream_t st, int sps, const float *tch, const uint16_t
 	std::vector<Kept> kept;
 	std::vector<size_t> next(plan.start.begin(), plan.start.end() - 1);   // per call: its first item no invocation has taken yet
 	std::vector<char> touched((size_t)n_calls, 0);
-	Tch3Batch b;
-	b.first.resize((size_t)n_calls + 1);
 	for (size_t g = 0; g < plan.n_gen; g++) {
 		b.item.clear(); b.t_off.clear(); b.t_fs.clear(); b.t_fn.clear();
 		b.a_call.clear(); b.a_p.clear(); b.a_en.clear();
@@ -280,18 +273,19 @@ int RxRun::tch3_pass()
 namespace {
 
 // The FACCH9 / TCH9 jobs `jobs` of the demodulated items: keystreams, the two decodes, and the big records in frame order
-// per chain.  sg is the pass's stage; h_eb holds the items' demodulated bits (662 each).
+// per chain.  sg is the pass's stage; h_eb: the items' demodulated bits (662 each).  bound: measuring, with no jobs: as many
+// jobs in all and of either kind, which no split of the pass's frames into jobs exceeds in any take.
 int tch9_decode_jobs(hipStream_t st, Stage &sg, const uint16_t *arfcn, const uint8_t *kc, const std::vector<RxChain> &chains,
                      std::vector<RxWalk> &walks, const std::vector<Nt9Item> &items9, const Tch9Jobs &jobs,
-                     const std::vector<int8_t> &h_eb)
+                     const std::vector<int8_t> &h_eb, int bound = 0)
 {
 	int r = 0;
 	const std::vector<int> &fj = jobs.facch, &tj = jobs.tch;
-	const int nf = (int)fj.size(), nt9 = (int)tj.size(), nj = nf + nt9;
+	const int nf = bound + (int)fj.size(), nt9 = bound + (int)tj.size(), nj = bound ? bound : nf + nt9;
 	std::vector<int8_t> eb((size_t)nj * 662);
 	std::vector<uint8_t> keys((size_t)nj * 8, 0);
 	std::vector<uint32_t> fns(nj);
-	for (int i = 0; i < nj; i++) {
+	for (int i = 0; i < (int)(fj.size() + tj.size()); i++) {
 		const int k = i < nf ? fj[i] : tj[i - nf];
 		std::memcpy(&eb[(size_t)i * 662], &h_eb[(size_t)k * 662], 662);
 		if (kc) std::memcpy(&keys[(size_t)i * 8], kc + (size_t)chains[items9[k].chain].a * 8, 8);
@@ -305,7 +299,9 @@ int tch9_decode_jobs(hipStream_t st, Stage &sg, const uint16_t *arfcn, const uin
 	uint8_t *d_ks = sg.dev<uint8_t>((size_t)nj * 658);
 	uint8_t *d_l2f = sg.dev<uint8_t>((size_t)nf * 38), *d_l2t = sg.dev<uint8_t>((size_t)nt9 * 60);
 	int32_t *d_crc = sg.dev<int32_t>((size_t)nf), *d_cvf = sg.dev<int32_t>((size_t)nf), *d_cvt = sg.dev<int32_t>((size_t)nt9);
-	if ((r = sg.err())) return r;
+	// all runs in one launch: every burst knows its position in its own run (jobs.pos lives until the synchronisation below)
+	const int32_t *d_pos = nt9 ? sg.in(jobs.pos.data(), (size_t)nt9) : nullptr;
+	if ((r = sg.err()) || sg.measures()) return r;
 	r = gmr1_hip_a5_batch_dev(st, nj, 1, 658, d_k, d_fn, d_ks, nullptr);
 	if (r) return r;
 	if (nf) {
@@ -317,9 +313,6 @@ int tch9_decode_jobs(hipStream_t st, Stage &sg, const uint16_t *arfcn, const uin
 		sg.queue_backs();
 	}
 	if (nt9) {
-		// all runs in one launch: every burst knows its position in its own run (jobs.pos lives until the synchronisation below)
-		const int32_t *d_pos = sg.in(jobs.pos.data(), (size_t)nt9);
-		if ((r = sg.err())) return r;
 		r = tch9_runs_dev_impl(st, 2 /* GMR1_TCH9_9k6, gmr1_rx.c:333 */, nt9, d_pos, d_e2 + (size_t)nf * 662,
 		                       d_ks + (size_t)nf * 658, d_l2t, d_cvt);
 		if (r) return r;
@@ -370,10 +363,6 @@ int tch9_follow_chains(hipStream_t st, int sps, const float *csd, const uint16_t
 	const int n9 = (int)items9.size();
 	if (!n9)
 		return 0;
-	// demodulation 682 B per frame, keystreams and decodes at most 662 + 8 + 4 + 658 + 64 B per frame
-	Arena arena;
-	if ((r = arena.init((size_t)n9 * 2300 + 64 * 1024))) return r;
-	Stage sg(st, &arena);
 	std::vector<uint64_t> off9(n9);
 	std::vector<float> fs9(n9);
 	for (int k = 0; k < n9; k++) {
@@ -383,19 +372,27 @@ int tch9_follow_chains(hipStream_t st, int sps, const float *csd, const uint16_t
 	}
 	std::vector<int8_t> h_eb((size_t)n9 * 662);
 	std::vector<int32_t> h_sid(n9), h_rv(n9);
-	const uint64_t *d_o = sg.in(off9.data(), (size_t)n9);
-	const float *d_f = sg.in(fs9.data(), (size_t)n9);
-	int8_t *d_eb = sg.out(h_eb.data(), (size_t)n9 * 662);
-	int32_t *d_sid = sg.out(h_sid.data(), (size_t)n9);
-	int32_t *d_rv = sg.out(h_rv.data(), (size_t)n9);
-	if ((r = sg.err())) return r;
-	r = demod_dev_energy(st, GMR1_HIP_NT9, n9, sps, rx_tch9_in_len(sps), csd, d_o, d_f, d_eb, 662, d_sid, nullptr, nullptr, d_rv);
-	if (r) return r;
-	if ((r = sg.fetch())) return r;
-	const Tch9Jobs jobs = tch9_plan_jobs(items9, h_sid.data(), h_rv.data());
-	if (jobs.facch.empty() && jobs.tch.empty())
-		return 0;
-	return tch9_decode_jobs(st, sg, arfcn, kc, chains, walks, items9, jobs, h_eb);
+	// the pass: the demodulation and, behind it, the decodes of the frames that ask for one.  Run first on a measuring arena,
+	// with every frame asking for both decodes, it sizes the arena it then runs on.
+	auto pass = [&](Arena &arena) -> int {
+		Stage sg(st, &arena);
+		const uint64_t *d_o = sg.in(off9.data(), (size_t)n9);
+		const float *d_f = sg.in(fs9.data(), (size_t)n9);
+		int8_t *d_eb = sg.out(h_eb.data(), (size_t)n9 * 662);
+		int32_t *d_sid = sg.out(h_sid.data(), (size_t)n9);
+		int32_t *d_rv = sg.out(h_rv.data(), (size_t)n9);
+		if ((r = sg.err())) return r;
+		if (arena.measures) return tch9_decode_jobs(st, sg, arfcn, kc, chains, walks, items9, Tch9Jobs(), h_eb, n9);
+		r = demod_dev_energy(st, GMR1_HIP_NT9, n9, sps, rx_tch9_in_len(sps), csd, d_o, d_f, d_eb, 662, d_sid, nullptr, nullptr, d_rv);
+		if (r) return r;
+		if ((r = sg.fetch())) return r;
+		const Tch9Jobs jobs = tch9_plan_jobs(items9, h_sid.data(), h_rv.data());
+		if (jobs.facch.empty() && jobs.tch.empty())
+			return 0;
+		return tch9_decode_jobs(st, sg, arfcn, kc, chains, walks, items9, jobs, h_eb);
+	};
+	Arena arena;
+	return arena.sized_by(pass);
 }
 
 // ---- TCH9 follow-up of one push of the streaming loop -------------------------------------------
@@ -452,51 +449,51 @@ int tch9_follow_push(hipStream_t st, int sps, const float *csd, const uint16_t *
 		fs[k] = -x.freq_err;
 		fn[k] = (uint32_t)x.fn;
 	}
-	// the calls' states, seven index arrays of at most a word per call, per frame 16 B staged, the follower's 80 B and a big
-	// record of 80 B, the count, the follower's scratch
+	// the pass: the calls' states, the index arrays, the frames, the follower's frames and their big records, the count, the
+	// follower's scratch.  Run first on a measuring arena, it sizes the arena it then runs on.
+	auto pass = [&](Arena &arena) -> int {
+		Stage sg(st, &arena);
+		gmr1_hip_tch9_state *d_call = sg.dev<gmr1_hip_tch9_state>((size_t)n_seg);
+		const int32_t *d_first = sg.in(first.data(), first.size());
+		const int32_t *d_at = sg.in(at.data(), at.size()), *d_own = sg.in(own.data(), own.size());
+		const int32_t *d_fresh = sg.in(fresh.data(), fresh.size());
+		const int32_t *d_back_at = sg.in(back_at.data(), back_at.size()), *d_back_own = sg.in(back_own.data(), back_own.size());
+		const uint32_t *d_label = sg.in(label.data(), label.size());
+		const uint64_t *d_off = sg.in(off.data(), (size_t)n);
+		const float *d_fs = sg.in(fs.data(), (size_t)n);
+		const uint32_t *d_fn = sg.in(fn.data(), (size_t)n);
+		gmr1_hip_tch9_frame *d_got = sg.dev<gmr1_hip_tch9_frame>((size_t)n);
+		gmr1_hip_rx_big_record *d_big = sg.dev<gmr1_hip_rx_big_record>((size_t)n);
+		int32_t h_count = 0;
+		int32_t *d_count = sg.dev<int32_t>(1);
+		unsigned char *scratch = sg.dev<unsigned char>(tch9_follow_scratch_bytes(n));
+		if ((r = sg.err()) || arena.measures) return r;
+		HIP_TRY(launch_tch9f_move(n_seg, d_call, d_at, d_state, d_own, st));
+		HIP_TRY(launch_tch9f_assign((int)fresh.size(), d_fresh, d_call, st));
+		if (n) {
+			r = tch9_follow_enqueue(st, scratch, n_seg, sps, rx_tch9_in_len(sps), 2 /* GMR1_TCH9_9k6, gmr1_rx.c:333 */, csd, d_first, n,
+			                        d_off, d_fs, d_fn, d_call, d_got);
+			if (r) return r;
+		}
+		HIP_TRY(launch_tch9f_move((int)back_at.size(), d_state, d_back_own, d_call, d_back_at, st));
+		if (!n)
+			return sg.fetch();                        // (the staged arrays are the host's until the stream is through)
+		Tch9BigArgs ba;
+		std::memset(&ba, 0, sizeof(ba));
+		ba.n_calls = n_seg; ba.n_frames = n; ba.max_out = n;
+		ba.first = d_first; ba.frames = d_got; ba.label = d_label; ba.out = d_big; ba.n_out = d_count;
+		HIP_TRY(launch_tch9f_big(ba, st));
+		sg.back(&h_count, d_count, 1);
+		if ((r = sg.fetch())) return r;
+		*n_big = h_count;
+		const int fit = std::min((int)h_count, max_big);
+		if (fit > 0)
+			HIP_TRY(hipMemcpyAsync(big_out, d_big, (size_t)fit * sizeof(gmr1_hip_rx_big_record), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		return 0;
+	};
 	Arena arena;
-	if ((r = arena.init(up128((size_t)n_seg * sizeof(gmr1_hip_tch9_state)) + 7 * up128(((size_t)n_seg + 1) * 4) +
-	                    up128((size_t)n * 8) + 2 * up128((size_t)n * 4) + 2 * up128((size_t)n * 80) + 16 * 128 +
-	                    tch9_follow_scratch_bytes(n)))) return r;
-	Stage sg(st, &arena);
-	gmr1_hip_tch9_state *d_call = sg.dev<gmr1_hip_tch9_state>((size_t)n_seg);
-	const int32_t *d_first = sg.in(first.data(), first.size());
-	const int32_t *d_at = sg.in(at.data(), at.size()), *d_own = sg.in(own.data(), own.size());
-	const int32_t *d_fresh = sg.in(fresh.data(), fresh.size());
-	const int32_t *d_back_at = sg.in(back_at.data(), back_at.size()), *d_back_own = sg.in(back_own.data(), back_own.size());
-	const uint32_t *d_label = sg.in(label.data(), label.size());
-	const uint64_t *d_off = sg.in(off.data(), (size_t)n);
-	const float *d_fs = sg.in(fs.data(), (size_t)n);
-	const uint32_t *d_fn = sg.in(fn.data(), (size_t)n);
-	gmr1_hip_tch9_frame *d_got = sg.dev<gmr1_hip_tch9_frame>((size_t)n);
-	gmr1_hip_rx_big_record *d_big = sg.dev<gmr1_hip_rx_big_record>((size_t)n);
-	int32_t h_count = 0;
-	int32_t *d_count = sg.dev<int32_t>(1);
-	unsigned char *scratch = sg.dev<unsigned char>(tch9_follow_scratch_bytes(n));
-	if ((r = sg.err())) return r;
-	HIP_TRY(launch_tch9f_move(n_seg, d_call, d_at, d_state, d_own, st));
-	HIP_TRY(launch_tch9f_assign((int)fresh.size(), d_fresh, d_call, st));
-	if (n) {
-		r = tch9_follow_enqueue(st, scratch, n_seg, sps, rx_tch9_in_len(sps), 2 /* GMR1_TCH9_9k6, gmr1_rx.c:333 */, csd, d_first, n,
-		                        d_off, d_fs, d_fn, d_call, d_got);
-		if (r) return r;
-	}
-	HIP_TRY(launch_tch9f_move((int)back_at.size(), d_state, d_back_own, d_call, d_back_at, st));
-	if (!n)
-		return sg.fetch();                        // (the staged arrays are the host's until the stream is through)
-	Tch9BigArgs ba;
-	std::memset(&ba, 0, sizeof(ba));
-	ba.n_calls = n_seg; ba.n_frames = n; ba.max_out = n;
-	ba.first = d_first; ba.frames = d_got; ba.label = d_label; ba.out = d_big; ba.n_out = d_count;
-	HIP_TRY(launch_tch9f_big(ba, st));
-	sg.back(&h_count, d_count, 1);
-	if ((r = sg.fetch())) return r;
-	*n_big = h_count;
-	const int fit = std::min((int)h_count, max_big);
-	if (fit > 0)
-		HIP_TRY(hipMemcpyAsync(big_out, d_big, (size_t)fit * sizeof(gmr1_hip_rx_big_record), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return arena.sized_by(pass);
 }
 
 }  // namespace gmr1

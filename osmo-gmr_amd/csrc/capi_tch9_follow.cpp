@@ -43,44 +43,12 @@ int samples_check(int n_calls, int sps, int in_len, int mode, const float *iq, c
 	return 0;
 }
 
-int first_check(int n_calls, const int32_t *first, int n_frames)
-{
-	if (first[0] != 0 || first[n_calls] != n_frames)
-		return fail(-EINVAL, "tch9_follow: first[] must run from 0 to n_frames");
-	for (int c = 0; c < n_calls; c++)
-		if (first[c + 1] < first[c])
-			return fail(-EINVAL, "tch9_follow: first[%d] decreases", c + 1);
-	return 0;
-}
-
-size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
-
-// where the follower's scratch of n frames lies, from a 128-byte boundary: the demodulator's outputs (from-samples form),
-// the plan, keystreams, decodes
-struct Follow9Scratch {
-	size_t eb, sid, rv, cls, need, src, call, ks, fl2, tl2, fcrc, fcv, tcv, bytes;
-	explicit Follow9Scratch(size_t n)
-	{
-		size_t o = 0;
-		auto take = [&](size_t b) { const size_t at = o; o += up128(b); return at; };
-		eb = take(n * 662); sid = take(n * 4); rv = take(n * 4);
-		cls = take(n); need = take(n); src = take(n * 12); call = take(n * 4); ks = take(n * 658);
-		fl2 = take(n * 64); tl2 = take(n * 64); fcrc = take(n * 4); fcv = take(n * 4); tcv = take(n * 4);
-		bytes = o;
-	}
-};
-
 // The follower, enqueued on `st`; every pointer is device memory.  The caller has checked the arguments and holds a WsLease;
-// `scratch` is Follow9Scratch(n_frames).bytes of device memory on a 128-byte boundary.
-int bits_enqueue(hipStream_t st, void *scratch, int n_calls, int mode, const int32_t *first, int n_frames, const int8_t *ebits,
-                 const int32_t *sync_id, const int32_t *rv, const uint32_t *fn, struct gmr1_hip_tch9_state *state,
-                 struct gmr1_hip_tch9_frame *out)
+// `o` names tch9_follow_scratch_bytes(n_frames) of device memory on a 128-byte boundary.
+int bits_enqueue(hipStream_t st, const Follow9Scratch &o, int n_calls, int mode, const int32_t *first, int n_frames,
+                 const int8_t *ebits, const int32_t *sync_id, const int32_t *rv, const uint32_t *fn,
+                 struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
 {
-	const Follow9Scratch o((size_t)n_frames);
-	unsigned char *d = static_cast<unsigned char *>(scratch);
-	auto I32 = [&](size_t at) { return reinterpret_cast<int32_t *>(d + at); };
-	auto U8 = [&](size_t at) { return reinterpret_cast<uint8_t *>(d + at); };
-
 	Nt9Args f, t;
 	std::memset(&f, 0, sizeof(f));
 	std::memset(&t, 0, sizeof(t));
@@ -92,9 +60,9 @@ int bits_enqueue(hipStream_t st, void *scratch, int n_calls, int mode, const int
 	std::memset(&a, 0, sizeof(a));
 	a.n_calls = n_calls; a.n_frames = n_frames; a.l2_bytes = t.l2_bytes;
 	a.first = first; a.ebits = ebits; a.sync_id = sync_id; a.rv = rv; a.fn = fn; a.state = state; a.out = out;
-	a.cls = U8(o.cls); a.need = U8(o.need); a.src = I32(o.src); a.call_of = I32(o.call);
-	a.ks = U8(o.ks); a.fa_l2 = U8(o.fl2); a.t_l2 = U8(o.tl2);
-	a.fa_crc = I32(o.fcrc); a.fa_conv = I32(o.fcv); a.t_conv = I32(o.tcv);
+	a.cls = o.cls; a.need = o.need; a.src = o.src; a.call_of = o.call;
+	a.ks = o.ks; a.fa_l2 = o.fl2; a.t_l2 = o.tl2;
+	a.fa_crc = o.fcrc; a.fa_conv = o.fcv; a.t_conv = o.tcv;
 
 	// A. classes and sources, call by call (a frame no call owns -- first[] is the caller's device memory -- asks for nothing)
 	HIP_TRY(hipMemsetAsync(a.need, 0, (size_t)n_frames, st));
@@ -107,8 +75,8 @@ int bits_enqueue(hipStream_t st, void *scratch, int n_calls, int mode, const int
 	f.need = t.need = a.need; f.src = t.src = a.src; f.src_call = t.src_call = a.call_of;
 	f.held = t.held = reinterpret_cast<const int8_t *>(state) + offsetof(gmr1_hip_tch9_state, held);
 	f.held_stride = t.held_stride = sizeof(gmr1_hip_tch9_state);
-	f.want = kT9NeedFacch; f.l2 = U8(o.fl2); f.crc = I32(o.fcrc); f.conv = I32(o.fcv);
-	t.want = kT9NeedTch; t.l2 = U8(o.tl2); t.conv = I32(o.tcv);
+	f.want = kT9NeedFacch; f.l2 = o.fl2; f.crc = o.fcrc; f.conv = o.fcv;
+	t.want = kT9NeedTch; t.l2 = o.tl2; t.conv = o.tcv;
 	HIP_TRY(launch_nt9_jobs(f, st));
 	HIP_TRY(launch_nt9_jobs(t, st));
 
@@ -117,31 +85,19 @@ int bits_enqueue(hipStream_t st, void *scratch, int n_calls, int mode, const int
 	return 0;
 }
 
-// the NT9 demodulator into the scratch's own slots, then the follower on them
-int samples_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,
-                    int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
-                    struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
-{
-	const Follow9Scratch o((size_t)n_frames);
-	unsigned char *d = static_cast<unsigned char *>(scratch);
-	int8_t *eb = reinterpret_cast<int8_t *>(d + o.eb);
-	int32_t *sid = reinterpret_cast<int32_t *>(d + o.sid), *rv = reinterpret_cast<int32_t *>(d + o.rv);
-	int r = demod_dev_energy(st, GMR1_HIP_NT9, n_frames, sps, in_len, iq, offset, freq_shift, eb, 662, sid, nullptr, nullptr, rv);
-	if (r) return r;
-	return bits_enqueue(st, scratch, n_calls, mode, first, n_frames, eb, sid, rv, fn, state, out);
-}
-
 }  // namespace
 
 namespace gmr1 {
 
-size_t tch9_follow_scratch_bytes(int n_frames) { return Follow9Scratch((size_t)n_frames).bytes; }
-
+// the NT9 demodulator into the scratch's own slots, then the follower on them
 int tch9_follow_enqueue(hipStream_t st, void *scratch, int n_calls, int sps, int in_len, int mode, const float *iq, const int32_t *first,
                         int n_frames, const uint64_t *offset, const float *freq_shift, const uint32_t *fn,
                         struct gmr1_hip_tch9_state *state, struct gmr1_hip_tch9_frame *out)
 {
-	return samples_enqueue(st, scratch, n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	const Follow9Scratch o(scratch, (size_t)n_frames);
+	int r = demod_dev_energy(st, GMR1_HIP_NT9, n_frames, sps, in_len, iq, offset, freq_shift, o.eb, 662, o.sid, nullptr, nullptr, o.rv);
+	if (r) return r;
+	return bits_enqueue(st, o, n_calls, mode, first, n_frames, o.eb, o.sid, o.rv, fn, state, out);
 }
 
 }  // namespace gmr1
@@ -181,11 +137,10 @@ int gmr1_hip_tch9_follow_bits_batch_dev(void *stream, int n_calls, int mode, con
 	DevState *s;
 	if ((r = dev_state(&s))) return r;
 	if (n_calls == 0 || n_frames == 0) return 0;
-	WsLease lease;
-	if ((r = lease.acquire(s, (hipStream_t)stream))) return r;
-	Arena ws;                                      // the start of the device's workspace
-	if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
-	return bits_enqueue((hipStream_t)stream, ws.base, n_calls, mode, first, n_frames, ebits, sync_id, rv, fn, state, out);
+	hipStream_t st = (hipStream_t)stream;
+	return with_scratch(s, st, tch9_follow_scratch_bytes(n_frames), [&](void *ws) {
+		return bits_enqueue(st, Follow9Scratch(ws, (size_t)n_frames), n_calls, mode, first, n_frames, ebits, sync_id, rv, fn, state, out);
+	});
 }
 
 int gmr1_hip_tch9_follow_bits_batch(int n_calls, int mode, const int32_t *first, int n_frames, const int8_t *ebits,
@@ -194,27 +149,21 @@ int gmr1_hip_tch9_follow_bits_batch(int n_calls, int mode, const int32_t *first,
 {
 	int r = bits_check(n_calls, mode, first, n_frames, ebits, sync_id, fn, state, out);
 	if (r) return r;
-	if ((r = first_check(n_calls, first, n_frames))) return r;
+	if ((r = tch3_pcm_first_check("tch9_follow", n_calls, first, n_frames))) return r;
 	DevState *s;
 	if ((r = dev_state(&s))) return r;
 	if (n_calls == 0 || n_frames == 0) return 0;
 	Stage sg;
-	const int32_t *d_first = sg.in(first, (size_t)n_calls + 1);
+	const auto d = stage_follow(sg, n_calls, nullptr, 0, first, n_frames, nullptr, nullptr, fn, state, out);
 	const int8_t *d_eb = sg.in(ebits, (size_t)n_frames * 662);
 	const int32_t *d_sid = sg.in(sync_id, (size_t)n_frames);
 	const int32_t *d_rv = sg.in(rv, (size_t)n_frames);
-	const uint32_t *d_fn = sg.in(fn, (size_t)n_frames);
-	struct gmr1_hip_tch9_state *d_state = sg.inout(state, (size_t)n_calls);
-	struct gmr1_hip_tch9_frame *d_out = sg.out(out, (size_t)n_frames);
 	if ((r = sg.err())) return r;
-	{
-		WsLease lease;
-		if ((r = lease.acquire(s, nullptr))) return r;
-		Arena ws;
-		if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
-		if ((r = bits_enqueue(nullptr, ws.base, n_calls, mode, d_first, n_frames, d_eb, d_sid, d_rv, d_fn, d_state, d_out)))
-			return r;
-	}
+	r = with_scratch(s, nullptr, tch9_follow_scratch_bytes(n_frames), [&](void *ws) {
+		return bits_enqueue(nullptr, Follow9Scratch(ws, (size_t)n_frames), n_calls, mode, d.first, n_frames, d_eb, d_sid, d_rv, d.fn,
+		                    d.state, d.out);
+	});
+	if (r) return r;
 	return sg.fetch();
 }
 
@@ -227,12 +176,10 @@ int gmr1_hip_tch9_follow_batch_dev(void *stream, int n_calls, int sps, int in_le
 	DevState *s;
 	if ((r = dev_state(&s))) return r;
 	if (n_calls == 0 || n_frames == 0) return 0;
-	WsLease lease;
-	if ((r = lease.acquire(s, (hipStream_t)stream))) return r;
-	Arena ws;
-	if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
-	return samples_enqueue((hipStream_t)stream, ws.base, n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn,
-	                       state, out);
+	hipStream_t st = (hipStream_t)stream;
+	return with_scratch(s, st, tch9_follow_scratch_bytes(n_frames), [&](void *ws) {
+		return tch9_follow_enqueue(st, ws, n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn, state, out);
+	});
 }
 
 int gmr1_hip_tch9_follow_batch(int n_calls, int sps, int in_len, int mode, const float *iq, uint64_t iq_len,
@@ -241,29 +188,18 @@ int gmr1_hip_tch9_follow_batch(int n_calls, int sps, int in_len, int mode, const
 {
 	int r = samples_check(n_calls, sps, in_len, mode, iq, first, n_frames, offset, freq_shift, fn, state, out);
 	if (r) return r;
-	if ((r = first_check(n_calls, first, n_frames))) return r;
+	if ((r = tch3_pcm_first_check("tch9_follow", n_calls, first, n_frames))) return r;
 	if ((r = bursts_fit(n_frames, offset, in_len, iq_len))) return r;
 	DevState *s;
 	if ((r = dev_state(&s))) return r;
 	if (n_calls == 0 || n_frames == 0) return 0;
 	Stage sg;
-	const float *d_iq = sg.in(iq, (size_t)iq_len * 2);
-	const int32_t *d_first = sg.in(first, (size_t)n_calls + 1);
-	const uint64_t *d_off = sg.in(offset, (size_t)n_frames);
-	const float *d_fs = sg.in(freq_shift, (size_t)n_frames);
-	const uint32_t *d_fn = sg.in(fn, (size_t)n_frames);
-	struct gmr1_hip_tch9_state *d_state = sg.inout(state, (size_t)n_calls);
-	struct gmr1_hip_tch9_frame *d_out = sg.out(out, (size_t)n_frames);
+	const auto d = stage_follow(sg, n_calls, iq, iq_len, first, n_frames, offset, freq_shift, fn, state, out);
 	if ((r = sg.err())) return r;
-	{
-		WsLease lease;
-		if ((r = lease.acquire(s, nullptr))) return r;
-		Arena ws;
-		if ((r = ws.init(Follow9Scratch((size_t)n_frames).bytes))) return r;
-		if ((r = samples_enqueue(nullptr, ws.base, n_calls, sps, in_len, mode, d_iq, d_first, n_frames, d_off, d_fs, d_fn, d_state,
-		                         d_out)))
-			return r;
-	}
+	r = with_scratch(s, nullptr, tch9_follow_scratch_bytes(n_frames), [&](void *ws) {
+		return tch9_follow_enqueue(nullptr, ws, n_calls, sps, in_len, mode, d.iq, d.first, n_frames, d.off, d.fs, d.fn, d.state, d.out);
+	});
+	if (r) return r;
 	return sg.fetch();
 }
 

@@ -111,8 +111,6 @@ int tch9_follow_push(hipStream_t st, int sps, const float *csd, const uint16_t *
                      const std::vector<RxWalk> &walks, gmr1_hip_tch9_state *d_state, Tch9CallCarry *carry,
                      gmr1_hip_rx_big_record *big_out, int max_big, int *n_big);
 
-inline size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
-
 // what a carrier's records carry: its ARFCN, or its index
 inline uint16_t rx_label(const uint16_t *arfcn, int a) { return arfcn ? arfcn[a] : (uint16_t)a; }
 
