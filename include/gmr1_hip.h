@@ -317,6 +317,46 @@ int gmr1_hip_rach_encode_batch_dev(void *stream, int n, const uint8_t *rach, con
 int gmr1_hip_rach_encode_batch(int n, const uint8_t *rach, const uint8_t *sb_mask, uint8_t *ebits);
 int gmr1_hip_mod_batch_dev(void *stream, int burst_id, int sync_id, int n, const uint8_t *ebits, float *out);
 int gmr1_hip_mod_batch(int burst_id, int sync_id, int n, const uint8_t *ebits, float *out);
+/* The shaped modulator: symbols at one sample per symbol to demodulator-ready windows at sps samples per symbol, on the
+ * device -- the pulse (raised cosine: what a demodulator behind a channelizer sees; root raised cosine: what a transmitter
+ * sends; roll-off 0.35, cut at +-span symbols), a fraction of a sample of delay, a carrier offset, a phase and a level.
+ * No framing, no overlapping bursts, no noise: a caller who wants noise adds it to the windows.
+ *   shape:      symbols n x len complex float32 (gmr1_hip_mod_batch's output, DKAB symbols, anything)
+ *   mod_shaped: ebits n x (ebits of the burst format), sync_id per burst (NULL: sequence 0): the modulator and the shaper
+ *               in one launch, float for float what shape gives on gmr1_hip_mod_batch's symbols
+ * offset and in_len are those of gmr1_hip_demod_batch*: burst b's window is out[2*offset[b] .. 2*(offset[b] + in_len)), and
+ * the same offset array and buffer go straight into the demodulator on the same stream.  Windows must not overlap.
+ * Per burst, each array optional (NULL: 0, 0, 0, 0, 1): start, the window sample symbol 0 lands on (it may be negative or
+ * past the window: the body is clipped at both ends); frac, a further delay in samples (the true arrival time is
+ * start + frac); cfo in radians per sample; phase0 in radians; gain, linear.  With s[j] = 0 outside 0..len, window sample
+ * k = 0..in_len is, for q = k - (start - span*sps), i = q div sps, p = q mod sps:
+ *   x[k] = gain e^{j(phase0 + cfo k)} sum_{m=-span..span} s[i - span - m] g(m + (p - frac) / sps)
+ * where 0 <= q < (len + 2 span) sps, and 0 elsewhere: every window is written in full.  The coefficients are evaluated in
+ * double and rounded to float once; the phase is formed and the sum is taken in float.
+ * -EINVAL, before anything is written: sps outside 1..16, span outside 1..8, an unknown pulse or burst_id, len outside
+ * 1..2048, in_len < 1, n < 0, a NULL symbols / ebits / offset / out; the host forms also refuse a window that leaves the
+ * out_len samples of out, windows that overlap and a sync_id outside the format's sequences (the _dev forms cannot see the
+ * arrays: there a burst with such a sync_id has no symbols, and the rest is the caller's).  n == 0 returns 0.
+ * _dev: device pointers, asynchronous on `stream`. */
+enum gmr1_hip_pulse { GMR1_HIP_PULSE_RC = 0, GMR1_HIP_PULSE_RRC = 1 };   /* roll-off 0.35 both */
+int gmr1_hip_shape_batch_dev(void *stream, int n, int len, int sps, int pulse, int span, int in_len,
+                             const float *symbols, const uint64_t *offset, const int32_t *start,
+                             const float *frac, const float *cfo, const float *phase0, const float *gain,
+                             float *out, uint64_t out_len);
+int gmr1_hip_shape_batch(int n, int len, int sps, int pulse, int span, int in_len,
+                         const float *symbols, const uint64_t *offset, const int32_t *start,
+                         const float *frac, const float *cfo, const float *phase0, const float *gain,
+                         float *out, uint64_t out_len);
+int gmr1_hip_mod_shaped_batch_dev(void *stream, int burst_id, int n, int sps, int pulse, int span, int in_len,
+                                  const uint8_t *ebits, const int32_t *sync_id,
+                                  const uint64_t *offset, const int32_t *start,
+                                  const float *frac, const float *cfo, const float *phase0, const float *gain,
+                                  float *out, uint64_t out_len);
+int gmr1_hip_mod_shaped_batch(int burst_id, int n, int sps, int pulse, int span, int in_len,
+                              const uint8_t *ebits, const int32_t *sync_id,
+                              const uint64_t *offset, const int32_t *start,
+                              const float *frac, const float *cfo, const float *phase0, const float *gain,
+                              float *out, uint64_t out_len);
 /* The position map (payload bits -> burst bits) the encoder kernel evaluates for one chain, copied into buf as
  * struct EncPlan of osmo-gmr_amd/csrc/gmr1_dev.h; returns its size (buf may be NULL) or -EINVAL.  Host-only,
  * works without a GPU: tests/test_tx_plan.py evaluates it bit by bit against the CPU oracle. */

@@ -83,6 +83,10 @@ SIGNATURES = {
     "gmr1_hip_rach_encode_batch": (I, I, P, P, P),
     "gmr1_hip_mod_batch_dev": (I, P, I, I, I, P, P),
     "gmr1_hip_mod_batch": (I, I, I, I, P, P),
+    "gmr1_hip_shape_batch_dev": (I, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, U64),
+    "gmr1_hip_shape_batch": (I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, U64),
+    "gmr1_hip_mod_shaped_batch_dev": (I, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, U64),
+    "gmr1_hip_mod_shaped_batch": (I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, U64),
     "gmr1_hip_encoder_plan": (I, I, P, I),
     "gmr1_hip_fcch_rough_batch_dev": (I, P, I, I, I, I, P, P, P, P, P),
     "gmr1_hip_fcch_rough_batch": (I, I, I, I, I, P, U64, P, P, P, P),
@@ -1796,6 +1800,70 @@ def mod_batch(burst, ebits, sync_id=0):
     out = np.zeros((eb.shape[0], b.len), np.complex64)
     _call("gmr1_hip_mod_batch", bid, sync_id, eb.shape[0], _p(eb), _p(out))
     return out
+
+
+PULSE_RC, PULSE_RRC = 0, 1
+PULSES = {"rc": PULSE_RC, "rrc": PULSE_RRC}
+
+
+def _shape_windows(n, in_len, offset, out, impair):
+    """The shaping calls' window arguments -> (uint64 offset, complex64 out, what to return, the five per-burst arrays):
+    offset None = windows back to back; out None = a fresh array that exactly holds them (returned as (n, in_len)), else
+    the caller's flat complex64 array, written in place (what lies between the windows stays) and returned as it is."""
+    offset = np.arange(n, dtype=np.uint64) * np.uint64(max(in_len, 0)) if offset is None else _arr(offset, np.uint64)
+    if out is None:
+        out = np.zeros(int(offset.max()) + in_len if n else 0, np.complex64)
+        ret = out.reshape(n, in_len) if out.size == n * in_len else out
+    else:
+        if not (isinstance(out, np.ndarray) and out.dtype == np.complex64 and out.flags.c_contiguous):
+            raise TypeError("out: a contiguous complex64 array, written in place")
+        ret = out
+    types = (np.int32, np.float32, np.float32, np.float32, np.float32)
+    per = [None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, t), (n,))) for a, t in zip(impair, types)]
+    return offset, out, ret, per
+
+
+def shape_batch(symbols, sps, in_len, *, pulse="rc", span=5, offset=None, start=None, frac=None, cfo=None, phase0=None,
+                gain=None, out=None):
+    """gmr1_hip_shape_batch: symbols (n, len) complex64 at one sample per symbol -> (n, in_len) complex64 windows at sps
+    samples per symbol (offset = arange(n) * in_len unless given: then the flat buffer the windows lie in).  Per burst, a
+    scalar or (n,), None = 0 / 0 / 0 / 0 / 1: start (window sample of symbol 0), frac (samples), cfo (rad / sample), phase0
+    (rad), gain.  pulse: "rc" | "rrc" (roll-off 0.35), cut at +-span symbols."""
+    sym = _arr(symbols, np.complex64)
+    sym = sym.reshape(-1, sym.shape[-1] if sym.ndim else 1)
+    n, length = sym.shape
+    offset, out, ret, per = _shape_windows(n, in_len, offset, out, (start, frac, cfo, phase0, gain))
+    _call("gmr1_hip_shape_batch", n, length, sps, PULSES.get(pulse, pulse), span, in_len, _p(sym), _p(offset),
+          *[_p(a) for a in per], _p(out), out.size)
+    return ret
+
+
+def mod_shaped_batch(burst, ebits, sps, in_len, *, sync_id=None, pulse="rc", span=5, offset=None, start=None, frac=None,
+                     cfo=None, phase0=None, gain=None, out=None):
+    """gmr1_hip_mod_shaped_batch: ebits (n, burst.ebits) ubits -> windows as shape_batch(mod_batch(burst, ebits), ...) gives
+    them, float for float, in one launch; sync_id: a scalar or (n,), the training sequence of each burst (None: 0)."""
+    bid = _burst_id(burst)
+    b = burst_info(bid)
+    eb = _arr(ebits, np.uint8, (-1, b.ebits))
+    n = eb.shape[0]
+    sid = None if sync_id is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sync_id, np.int32), (n,)))
+    offset, out, ret, per = _shape_windows(n, in_len, offset, out, (start, frac, cfo, phase0, gain))
+    _call("gmr1_hip_mod_shaped_batch", bid, n, sps, PULSES.get(pulse, pulse), span, in_len, _p(eb), _p(sid), _p(offset),
+          *[_p(a) for a in per], _p(out), out.size)
+    return ret
+
+
+def shape_batch_dev(stream, n, length, sps, pulse, span, in_len, symbols, offset, start, frac, cfo, phase0, gain, out, out_len):
+    """gmr1_hip_shape_batch_dev on device memory (addresses, None for an array left out): enqueues on `stream` and returns"""
+    _call("gmr1_hip_shape_batch_dev", stream, n, length, sps, pulse, span, in_len, symbols, offset, start, frac, cfo, phase0,
+          gain, out, out_len)
+
+
+def mod_shaped_batch_dev(stream, burst, n, sps, pulse, span, in_len, ebits, sync_id, offset, start, frac, cfo, phase0, gain,
+                         out, out_len):
+    """gmr1_hip_mod_shaped_batch_dev on device memory (addresses, None for an array left out): enqueues and returns"""
+    _call("gmr1_hip_mod_shaped_batch_dev", stream, _burst_id(burst), n, sps, pulse, span, in_len, ebits, sync_id, offset, start,
+          frac, cfo, phase0, gain, out, out_len)
 
 
 def encode_single(chain, *args):

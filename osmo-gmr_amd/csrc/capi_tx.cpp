@@ -11,6 +11,7 @@
 
 #include "capi_common.h"
 
+#include <algorithm>
 #include <cmath>
 #include <mutex>
 #include <vector>
@@ -28,6 +29,7 @@
 #include "../../include/osmocom/gmr1/l1/xch_dc12.h"
 #include "../../include/osmocom/gmr1/sdr/pi4cxpsk.h"
 #include "nt9_map.h"
+#include "tx_pulse.h"
 
 using namespace gmr1;
 
@@ -541,6 +543,17 @@ int mod_plan(const gmr1_hip_burst_flat &f, int sync_id, std::vector<int16_t> *ou
 	return 0;
 }
 
+// osmo_cxvec_rotate: sample i times e^{j (rotation * i)}, phase and phasor in single precision
+std::vector<float2> mod_rot(const gmr1_hip_burst_flat &f)
+{
+	std::vector<float2> rot((size_t)f.len);
+	for (int i = 0; i < f.len; i++) {
+		const float ph = f.rotation * (float)i;
+		rot[i] = make_float2(cosf(ph), sinf(ph));
+	}
+	return rot;
+}
+
 int mod_dev(hipStream_t st, const gmr1_hip_burst_flat &f, int sync_id, int n, const uint8_t *ebits, float *out)
 {
 	DevState *s;
@@ -553,12 +566,7 @@ int mod_dev(hipStream_t st, const gmr1_hip_burst_flat &f, int sync_id, int n, co
 	if (r) return fail(r, "mod: unsupported burst description or sync_id %d", sync_id);
 	if (n == 0)
 		return 0;
-	// osmo_cxvec_rotate: sample i times e^{j (rotation * i)}, phase and phasor in single precision
-	std::vector<float2> rot((size_t)f.len);
-	for (int i = 0; i < f.len; i++) {
-		const float ph = f.rotation * (float)i;
-		rot[i] = make_float2(cosf(ph), sinf(ph));
-	}
+	const std::vector<float2> rot = mod_rot(f);
 	Stage sg(st);
 	int16_t *d_p = sg.dev<int16_t>(plan.size());
 	float2 *d_r = sg.dev<float2>(rot.size());
@@ -597,6 +605,154 @@ int builtin_flat(int burst_id, gmr1_hip_burst_flat *f)
 		return fail(-EINVAL, "mod: burst id %d unknown", burst_id);
 	tables_init();
 	return flatten(kBuiltin[burst_id], f, kBuiltinName[burst_id]);
+}
+
+// ---- shaped modulator (k_shape; tx_pulse.h) -----------------------------------------------------------------------
+// the modulator's tables of a built-in format on the current device, every sync sequence's plan: uploaded once and kept,
+// so the _dev entries only enqueue
+struct ModTab { int device, id, n_sync; int16_t *plan; float2 *rot; };
+std::vector<ModTab> g_mod_tabs;
+
+int mod_tables(int burst_id, const gmr1_hip_burst_flat &f, ModTab *out)
+{
+	int dev = 0;
+	HIP_TRY(hipGetDevice(&dev));
+	std::lock_guard<std::mutex> lk(g_mu);
+	for (const ModTab &t : g_mod_tabs)
+		if (t.device == dev && t.id == burst_id) {
+			*out = t;
+			return 0;
+		}
+	std::vector<int16_t> plans, one;
+	for (int s = 0; s < f.n_sync; s++) {
+		const int r = mod_plan(f, s, &one);
+		if (r) return fail(r, "mod_shaped: unsupported burst description");
+		plans.insert(plans.end(), one.begin(), one.end());
+	}
+	const std::vector<float2> rot = mod_rot(f);
+	ModTab t = {dev, burst_id, f.n_sync, nullptr, nullptr};
+	HIP_TRY(hipMalloc(&t.plan, plans.size() * sizeof(int16_t)));
+	HIP_TRY(hipMalloc(&t.rot, rot.size() * sizeof(float2)));
+	HIP_TRY(hipMemcpy(t.plan, plans.data(), plans.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(t.rot, rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice));
+	g_mod_tabs.push_back(t);
+	*out = t;
+	return 0;
+}
+
+// where the symbols of a shaping call come from: memory (symbols) or a built-in format's burst bits (ebits)
+struct ShapeSrc {
+	const char *who;
+	bool bits;
+	int burst_id;                      // bits: the built-in format ...
+	gmr1_hip_burst_flat f;             // ... and its description (shape_check fills it in)
+	const float *symbols;
+	const uint8_t *ebits;
+	const int32_t *sync_id;
+};
+
+// what both forms refuse without looking at an array; fills in src->f and *len for a built-in format
+int shape_check(ShapeSrc *src, int n, int *len, int sps, int pulse, int span, int in_len, const uint64_t *offset, const float *out)
+{
+	if (src->bits) {
+		if (src->burst_id < 0 || src->burst_id >= GMR1_HIP_N_BURSTS)
+			return fail(-EINVAL, "%s: burst id %d unknown", src->who, src->burst_id);
+		const int r = builtin_flat(src->burst_id, &src->f);
+		if (r) return r;
+		*len = src->f.len;
+	}
+	if (shape_args_bad(n, *len, sps, pulse, span, in_len))
+		return fail(-EINVAL, "%s: n %d, len %d (1..%d), sps %d (1..%d), pulse %d, span %d (1..%d) or in_len %d is out of range", src->who,
+		            n, *len, kShapeMaxLen, sps, kShapeMaxSps, pulse, span, kShapeMaxSpan, in_len);
+	if (n > 0 && (!(src->bits ? (const void *)src->ebits : (const void *)src->symbols) || !offset || !out))
+		return fail(-EINVAL, "%s: %s, offset and out are required", src->who, src->bits ? "ebits" : "symbols");
+	return 0;
+}
+
+// every pointer is device memory; the arguments have passed shape_check
+int shape_enqueue(hipStream_t st, const ShapeSrc &src, int n, int len, int sps, int pulse, int span, int in_len,
+                  const uint64_t *offset, const int32_t *start, const float *frac, const float *cfo, const float *phase0,
+                  const float *gain, float *out)
+{
+	ShapeArgs a;
+	std::memset(&a, 0, sizeof(a));
+	a.n = n; a.len = len; a.sps = sps; a.pulse = pulse; a.span = span; a.in_len = in_len;
+	if (src.bits) {
+		ModTab t;
+		const int r = mod_tables(src.burst_id, src.f, &t);
+		if (r) return r;
+		a.nbits = src.f.nbits; a.n_ebits = src.f.ebits; a.n_sync = t.n_sync;
+		a.plan = t.plan; a.rot = t.rot; a.ebits = src.ebits; a.sync_id = src.sync_id;
+	} else {
+		a.symbols = reinterpret_cast<const float2 *>(src.symbols);
+	}
+	a.offset = offset; a.start = start; a.frac = frac; a.cfo = cfo; a.phase0 = phase0; a.gain = gain;
+	a.out = reinterpret_cast<float2 *>(out);
+	HIP_TRY(launch_shape(a, st));
+	return 0;
+}
+
+int shape_dev(hipStream_t st, ShapeSrc src, int n, int len, int sps, int pulse, int span, int in_len,
+              const uint64_t *offset, const int32_t *start, const float *frac, const float *cfo, const float *phase0,
+              const float *gain, float *out)
+{
+	int r = shape_check(&src, n, &len, sps, pulse, span, in_len, offset, out);
+	if (r) return r;
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n == 0)
+		return 0;
+	return shape_enqueue(st, src, n, len, sps, pulse, span, in_len, offset, start, frac, cfo, phase0, gain, out);
+}
+
+// host pointers.  The arrays are in reach here, so the windows are checked: inside out_len, pairwise disjoint; and every
+// sync_id names a sequence of the format.  Only the windows are copied back, so what lies between them in out stays.
+int shape_host(ShapeSrc src, int n, int len, int sps, int pulse, int span, int in_len,
+               const uint64_t *offset, const int32_t *start, const float *frac, const float *cfo, const float *phase0,
+               const float *gain, float *out, uint64_t out_len)
+{
+	int r = shape_check(&src, n, &len, sps, pulse, span, in_len, offset, out);
+	if (r) return r;
+	std::vector<uint64_t> order(offset, offset + n);
+	for (int b = 0; b < n; b++) {
+		if (offset[b] > out_len || (uint64_t)in_len > out_len - offset[b])
+			return fail(-EINVAL, "%s: window %d leaves the %llu samples of out", src.who, b, (unsigned long long)out_len);
+		if (src.bits && src.sync_id && (src.sync_id[b] < 0 || src.sync_id[b] >= src.f.n_sync))
+			return fail(-EINVAL, "%s: burst %d asks for sync sequence %d of %d", src.who, b, (int)src.sync_id[b], src.f.n_sync);
+	}
+	std::sort(order.begin(), order.end());
+	for (int b = 1; b < n; b++)
+		if (order[b] - order[b - 1] < (uint64_t)in_len)
+			return fail(-EINVAL, "%s: the windows at samples %llu and %llu overlap", src.who, (unsigned long long)order[b - 1],
+			            (unsigned long long)order[b]);
+	DevState *s;
+	if ((r = dev_state(&s))) return r;
+	if (n == 0)
+		return 0;
+	// the device copy of out covers the windows' hull; the offsets are taken relative to its first sample
+	const uint64_t lo = order.front(), hull = order.back() + (uint64_t)in_len - lo;
+	std::vector<uint64_t> rel(offset, offset + n);
+	for (uint64_t &o : rel)
+		o -= lo;
+	Stage sg;
+	const size_t nn = (size_t)n;
+	ShapeSrc d = src;
+	d.symbols = sg.in(src.symbols, nn * (size_t)len * 2);
+	d.ebits = src.bits ? sg.in(src.ebits, nn * (size_t)src.f.ebits) : nullptr;
+	d.sync_id = sg.in(src.sync_id, nn);
+	const uint64_t *d_off = sg.in(rel.data(), nn);
+	const int32_t *d_start = sg.in(start, nn);
+	const float *d_frac = sg.in(frac, nn), *d_cfo = sg.in(cfo, nn), *d_ph = sg.in(phase0, nn), *d_gain = sg.in(gain, nn);
+	float *d_out = sg.dev<float>((size_t)hull * 2);
+	if ((r = sg.err())) return r;
+	for (int b = 0, first = 0; b < n; b++)          // one copy back per run of windows that touch
+		if (b + 1 == n || order[b + 1] - order[b] > (uint64_t)in_len) {
+			sg.back(out + 2 * order[first], d_out + 2 * (order[first] - lo), (size_t)(order[b] + (uint64_t)in_len - order[first]) * 2);
+			first = b + 1;
+		}
+	r = shape_enqueue(nullptr, d, n, len, sps, pulse, span, in_len, d_off, d_start, d_frac, d_cfo, d_ph, d_gain, d_out);
+	if (r) return r;
+	return sg.fetch();
 }
 
 // ---- stand-alone primitives -------------------------------------------------------------------------------------
@@ -741,6 +897,43 @@ int gmr1_hip_mod_batch(int burst_id, int sync_id, int n, const uint8_t *ebits, f
 	int r = builtin_flat(burst_id, &f);
 	if (r) return r;
 	return mod_host(f, sync_id, n, ebits, out);
+}
+
+int gmr1_hip_shape_batch_dev(void *stream, int n, int len, int sps, int pulse, int span, int in_len,
+                             const float *symbols, const uint64_t *offset, const int32_t *start,
+                             const float *frac, const float *cfo, const float *phase0, const float *gain,
+                             float *out, uint64_t out_len)
+{
+	(void)out_len;                             // the windows are on the device: the host form checks them against it
+	ShapeSrc src = {"shape_batch_dev", false, -1, {}, symbols, nullptr, nullptr};
+	return shape_dev((hipStream_t)stream, src, n, len, sps, pulse, span, in_len, offset, start, frac, cfo, phase0, gain, out);
+}
+int gmr1_hip_shape_batch(int n, int len, int sps, int pulse, int span, int in_len,
+                         const float *symbols, const uint64_t *offset, const int32_t *start,
+                         const float *frac, const float *cfo, const float *phase0, const float *gain,
+                         float *out, uint64_t out_len)
+{
+	ShapeSrc src = {"shape_batch", false, -1, {}, symbols, nullptr, nullptr};
+	return shape_host(src, n, len, sps, pulse, span, in_len, offset, start, frac, cfo, phase0, gain, out, out_len);
+}
+int gmr1_hip_mod_shaped_batch_dev(void *stream, int burst_id, int n, int sps, int pulse, int span, int in_len,
+                                  const uint8_t *ebits, const int32_t *sync_id,
+                                  const uint64_t *offset, const int32_t *start,
+                                  const float *frac, const float *cfo, const float *phase0, const float *gain,
+                                  float *out, uint64_t out_len)
+{
+	(void)out_len;
+	ShapeSrc src = {"mod_shaped_batch_dev", true, burst_id, {}, nullptr, ebits, sync_id};
+	return shape_dev((hipStream_t)stream, src, n, 0, sps, pulse, span, in_len, offset, start, frac, cfo, phase0, gain, out);
+}
+int gmr1_hip_mod_shaped_batch(int burst_id, int n, int sps, int pulse, int span, int in_len,
+                              const uint8_t *ebits, const int32_t *sync_id,
+                              const uint64_t *offset, const int32_t *start,
+                              const float *frac, const float *cfo, const float *phase0, const float *gain,
+                              float *out, uint64_t out_len)
+{
+	ShapeSrc src = {"mod_shaped_batch", true, burst_id, {}, nullptr, ebits, sync_id};
+	return shape_host(src, n, 0, sps, pulse, span, in_len, offset, start, frac, cfo, phase0, gain, out, out_len);
 }
 
 // ---- the reference's own single calls; the void ones report a device failure through gmr1_hip_last_error() ----

@@ -593,6 +593,24 @@ struct ModArgs {
 };
 hipError_t launch_mod(const ModArgs &a, hipStream_t stream);
 
+// the shaped modulator (k_shape, tx_kernels.hip; the arithmetic: tx_pulse.h): n bursts of len symbols to n windows of
+// in_len samples, burst b's at out + offset[b].  The symbols come from memory (symbols) or, when ebits is set, from
+// burst bits through the modulator's tables.  Every per-burst array but offset may be null.
+struct ShapeArgs {
+	int n, len, sps, pulse, span, in_len;
+	const float2 *symbols;             // n x len, or null: from bits
+	int nbits, n_ebits, n_sync;        // from bits: the format's bits per symbol, ubits per burst, sync sequences
+	const int16_t *plan;               // n_sync x len entries, as ModArgs::plan per sequence
+	const float2 *rot;                 // len entries, as ModArgs::rot
+	const uint8_t *ebits;              // n x n_ebits ubits
+	const int32_t *sync_id;            // per burst (null: 0); outside 0..n_sync the burst has no symbols
+	const uint64_t *offset;            // per burst: first sample of its window in out
+	const int32_t *start;              // window sample of symbol 0 (null: 0)
+	const float *frac, *cfo, *phase0, *gain;     // samples, rad / sample, rad, linear (null: 0, 0, 0, 1)
+	float2 *out;
+};
+hipError_t launch_shape(const ShapeArgs &a, hipStream_t stream);
+
 // the stand-alone layer-1 primitives (scrambler, intra- / inter-burst interleaver) as one gather kernel:
 // out[i] = in[perm ? perm[i] : i], then xor (ubits) or negate (sbits) where mask[i] is set
 struct BitMapArgs {

@@ -1,6 +1,7 @@
 // tx_kernels.hip -- transmit direction for gfx950: the layer-1 channel encoders (reference src/l1/bcch.c:60-81,
 // ccch.c:60-83, facch3.c:65-116, tch3.c:60-118, facch9.c:60-104, tch9.c:81-137, rach.c:78-136, xch_dc12.c:64-84)
-// and the pi/4-CxPSK modulator (reference src/sdr/pi4cxpsk.c:741-799).
+// and the pi/4-CxPSK modulator (reference src/sdr/pi4cxpsk.c:741-799); past where the reference ends, the shaped
+// modulator k_shape (symbols or burst bits to windows at sps samples per symbol: see above the kernel, and tx_pulse.h).
 //
 // k_encode: one unit per wave, four units per workgroup.  Nothing in a GMR-1 coder depends on the data: CRC,
 // convolutional code (all feed-forward), puncturing, intra- / inter-burst interleaving, scrambling, ciphering
@@ -27,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gmr1_dev.h"
+#include "tx_pulse.h"
 
 namespace gmr1 {
 
@@ -131,6 +133,30 @@ hipError_t launch_encode(const EncArgs &a, hipStream_t stream)
 // so the "multiply by the rotation" of osmo_cxvec_rotate is written out as the complex product the CPU computes
 // (the zeros of the operand matter only for the sign of a zero); the rotation phasors e^{j rotation i} are a
 // per-format table the host evaluates with the CPU's own cosf / sinf, so the symbols match a CPU build bit for bit.
+// symbol i of a burst: plan entry p (-1 guard, 0..3 training symbol, 4 + k data symbol from ebu[k ...]) times the phasor r
+__device__ __forceinline__ float2 mod_symbol(int p, const uint8_t *ebu, int nbits, float2 r)
+{
+	float2 v = make_float2(0.f, 0.f);
+	if (p >= 0) {
+		int sym = p;
+		if (p >= 4) {
+			const uint8_t *eb = ebu + (p - 4);
+			if (nbits == 2) {
+				const int bv = ((eb[0] & 1) << 1) | (eb[1] & 1);
+				sym = bv ^ (bv >> 1);             // 00 01 10 11 -> 0 1 3 2 (the '.bits' table of pi4cxpsk.c:87-107)
+			} else {
+				sym = eb[0] & 1;
+			}
+		}
+		if (nbits == 2)
+			v = make_float2((sym & 1) ? 0.f : ((sym & 2) ? -1.f : 1.f), (sym & 1) ? ((sym & 2) ? -1.f : 1.f) : 0.f);
+		else
+			v = make_float2((sym & 1) ? -1.f : 1.f, 0.f);
+	}
+	const float c = r.x, s = r.y;
+	return make_float2(v.x * c - v.y * s, v.x * s + v.y * c);
+}
+
 __global__ __launch_bounds__(256) void k_mod(ModArgs a)
 {
 	const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one burst per wave, symbols strided over its lanes
@@ -138,29 +164,8 @@ __global__ __launch_bounds__(256) void k_mod(ModArgs a)
 		return;
 	const uint8_t *ebu = a.ebits + u * a.n_ebits;
 	float2 *outu = a.out + u * a.len;
-	for (int i = threadIdx.x & 63; i < a.len; i += 64) {
-		const int p = a.plan[i];
-		float2 v = make_float2(0.f, 0.f);
-		if (p >= 0) {
-			int sym = p;
-			if (p >= 4) {
-				const uint8_t *eb = ebu + (p - 4);
-				if (a.nbits == 2) {
-					const int bv = ((eb[0] & 1) << 1) | (eb[1] & 1);
-					sym = bv ^ (bv >> 1);             // 00 01 10 11 -> 0 1 3 2 (the '.bits' table of pi4cxpsk.c:87-107)
-				} else {
-					sym = eb[0] & 1;
-				}
-			}
-			if (a.nbits == 2)
-				v = make_float2((sym & 1) ? 0.f : ((sym & 2) ? -1.f : 1.f), (sym & 1) ? ((sym & 2) ? -1.f : 1.f) : 0.f);
-			else
-				v = make_float2((sym & 1) ? -1.f : 1.f, 0.f);
-		}
-		const float2 r = a.rot[i];
-		const float c = r.x, s = r.y;
-		outu[i] = make_float2(v.x * c - v.y * s, v.x * s + v.y * c);
-	}
+	for (int i = threadIdx.x & 63; i < a.len; i += 64)
+		outu[i] = mod_symbol(a.plan[i], ebu, a.nbits, a.rot[i]);
 }
 
 hipError_t launch_mod(const ModArgs &a, hipStream_t stream)
@@ -168,6 +173,105 @@ hipError_t launch_mod(const ModArgs &a, hipStream_t stream)
 	if (a.n <= 0 || a.len <= 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_mod, dim3((unsigned)((a.n + 3) / 4)), dim3(256), 0, stream, a);
+	return hipGetLastError();
+}
+
+// ---- shaped modulator: symbols (from memory, or from burst bits as k_mod makes them) to demodulator-ready windows at
+// sps samples per symbol: the pulse at a fractional delay, a carrier offset, a phase and a level (tx_pulse.h states the
+// pulse and the index rule; synth.shape_bursts / synth_windows are the numpy statement the tests compare with).
+// One wave per burst.  Per burst, in LDS: the symbols between 2 span zeros on either side, and the (2 span + 1) sps
+// coefficients, which depend on frac alone, evaluated in fp64 and rounded once.  Per sample: 2 span + 1 complex-by-real
+// multiply-adds from LDS, the phase phase0 + cfo k in fp32 (two roundings, as numpy's) through the accurate sincosf
+// (|phase| reaches hundreds of radians on the long windows), the rotation and the gain.  A lane takes the two samples of a
+// 16-byte unit of the output (the unit grid is that of the ADDRESS, so a window that starts on an odd sample has a single
+// sample at either end) and the wave stores 1 KiB contiguous, streaming: nothing here is read again by this kernel.
+// The whole window is written, zeros outside the body included; windows are disjoint by contract, so no atomics.
+typedef float sh_v4f __attribute__((ext_vector_type(4)));
+typedef float sh_v2f __attribute__((ext_vector_type(2)));
+
+__host__ __device__ inline size_t shape_wave_lds(int len, int span, int sps)
+{
+	return ((size_t)shape_padded_len(len, span) * sizeof(float2) + (size_t)pulse_coefs(span, sps) * sizeof(float) + 15) & ~(size_t)15;
+}
+
+template <bool BITS>
+__global__ __launch_bounds__(256) void k_shape(ShapeArgs a)
+{
+	extern __shared__ __align__(16) unsigned char shape_lds[];
+	const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const long long u = (long long)blockIdx.x * (blockDim.x >> 6) + w;
+	if (u >= a.n)
+		return;                               // waves are independent: no workgroup barrier below
+	const int span = a.span, sps = a.sps, len = a.len, in_len = a.in_len;
+	const int npad = shape_padded_len(len, span), ncoef = pulse_coefs(span, sps);
+	float2 *sp = reinterpret_cast<float2 *>(shape_lds + (size_t)w * shape_wave_lds(len, span, sps));
+	float *cf = reinterpret_cast<float *>(sp + npad);
+
+	const double fr = a.frac ? (double)a.frac[u] : 0.0;
+	for (int c = lane; c < ncoef; c += 64)
+		cf[c] = pulse_coef(a.pulse, c / sps - span, c % sps, fr, sps);
+	const uint8_t *ebu = nullptr;
+	const int16_t *plan = nullptr;
+	if (BITS) {
+		const int sid = a.sync_id ? a.sync_id[u] : 0;
+		if (sid >= 0 && sid < a.n_sync) {
+			plan = a.plan + (size_t)sid * len;
+			ebu = a.ebits + u * a.n_ebits;
+		}
+	}
+	for (int j = lane; j < npad; j += 64) {
+		const int s = j - 2 * span;
+		float2 v = make_float2(0.f, 0.f);
+		if (s >= 0 && s < len) {
+			if (!BITS)
+				v = a.symbols[u * len + s];
+			else if (plan)
+				v = mod_symbol(plan[s], ebu, a.nbits, a.rot[s]);
+		}
+		sp[j] = v;
+	}
+	WAVE_SYNC();
+
+	const int start = a.start ? a.start[u] : 0;
+	const float cfo = a.cfo ? a.cfo[u] : 0.f, ph0 = a.phase0 ? a.phase0[u] : 0.f, gain = a.gain ? a.gain[u] : 1.f;
+	const uint32_t magic = shape_div_magic(sps);
+	auto sample = [&](int k) -> float2 {
+		int i, p;
+		if (k < 0 || k >= in_len || !shape_index(k, start, span, sps, len, magic, &i, &p))
+			return make_float2(0.f, 0.f);
+		const float2 b = shape_body<float2>(sp, cf, i, p, span, sps);
+		float s, c;
+		sincosf(__fadd_rn(ph0, __fmul_rn(cfo, (float)k)), &s, &c);
+		return make_float2(gain * (b.x * c - b.y * s), gain * (b.x * s + b.y * c));
+	};
+	float2 *outu = a.out + a.offset[u];
+	const int odd = (int)((reinterpret_cast<uintptr_t>(outu) >> 3) & 1u);     // the window starts in the upper half of a unit
+	for (int t = lane; 2 * t - odd < in_len; t += 64) {
+		const int k = 2 * t - odd;
+		const float2 x0 = sample(k), x1 = sample(k + 1);
+		if (k >= 0 && k + 1 < in_len)
+			__builtin_nontemporal_store((sh_v4f){x0.x, x0.y, x1.x, x1.y}, reinterpret_cast<sh_v4f *>(outu + k));
+		else if (k >= 0)
+			__builtin_nontemporal_store((sh_v2f){x0.x, x0.y}, reinterpret_cast<sh_v2f *>(outu + k));
+		else
+			__builtin_nontemporal_store((sh_v2f){x1.x, x1.y}, reinterpret_cast<sh_v2f *>(outu + k + 1));
+	}
+}
+
+hipError_t launch_shape(const ShapeArgs &a, hipStream_t stream)
+{
+	if (a.n <= 0)
+		return hipSuccess;
+	// four bursts a workgroup, fewer where the symbols of four do not fit the 64 KiB a launch gets without asking
+	const size_t per = shape_wave_lds(a.len, a.span, a.sps);
+	const int waves = (int)(4 * per <= 65536 ? 4 : 65536 / per);
+	if (waves < 1)
+		return hipErrorInvalidValue;
+	const unsigned blocks = (unsigned)(((long long)a.n + waves - 1) / waves);
+	if (a.ebits)
+		hipLaunchKernelGGL(k_shape<true>, dim3(blocks), dim3(64 * waves), per * waves, stream, a);
+	else
+		hipLaunchKernelGGL(k_shape<false>, dim3(blocks), dim3(64 * waves), per * waves, stream, a);
 	return hipGetLastError();
 }
 
