@@ -6,6 +6,12 @@ for the fresh streams of tests/test_oracle_ambe.py, as one 64-bit digest per 160
     <key>_clean          [n] uint64   gmr1_codec_decode_frame entered on a zeroed stack
     <key>_rv             [n] int32    its return values
     <key>_pcm            [n] uint64   the reference's program gmr1_ambe_decode on the same file (not for "rejected")
+and per family of aimed streams (tests/ambe_aimed.py; T.aimed_streams(): "orbit", "histories", "levels", "tones"), over its
+channels one after the other, every channel on a decoder of its own:
+    aimed_<family>_frames_digest  uint64   the input frames, one digest per 16 frames of a channel
+    aimed_<family>_clean          uint64   gmr1_codec_decode_frame entered on a zeroed stack: one digest per frame, for
+                                           "histories" (61 752 frames) one per 16 frames of a channel (T.AIMED_BLOCK)
+    aimed_<family>_rv             int32    its return values, per frame
 """
 import os
 import sys
@@ -30,5 +36,10 @@ for key, fr, program in jobs:
     if program:
         assert len(prog) == len(fr)
         out[key + "_pcm"] = T.frame_digests(prog)
+for key, chans in T.aimed_streams().items():
+    clean, rv = T.aimed_reference(key)
+    out["aimed_%s_frames_digest" % key] = T.block_digests(chans, T.AIMED_FRAMES_BLOCK)
+    out["aimed_%s_clean" % key] = T.block_digests(clean, T.AIMED_BLOCK[key])
+    out["aimed_%s_rv" % key] = rv.astype(np.int32)
 np.savez_compressed(os.path.join(HERE, "ambe_ref_digests.npz"), **out)
 print("wrote", os.path.join(HERE, "ambe_ref_digests.npz"), os.path.getsize(os.path.join(HERE, "ambe_ref_digests.npz")), "bytes")

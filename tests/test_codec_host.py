@@ -43,13 +43,13 @@ def test_fundamental_tables_are_the_oracles_powf_on_the_oracles_arguments(tab):
     f0log = [_orc_f("orc_ambe_f0log_sf1", C.c_int(p)) for p in range(128)] + [np.float32(0.0)]
     for p in range(128):
         assert tab["f0_sf1"][p] == _orc_f("orc_ambe_pow2", C.c_float(f0log[p]))
-    rng = np.random.default_rng(0)
-    picks = [(b, p, r) for b in (0, 1, 63, 127, 128) for p in (0, 1, 64, 123, 127) for r in range(4)]
-    picks += [tuple(int(x) for x in rng.integers(0, (129, 128, 4))) for _ in range(3000)]
-    picks += [(p, p, r) for p in range(128) for r in range(4)]          # equal pitches: the other branch
-    for b, p, r in picks:
-        x = _orc_f("orc_ambe_f0log_sf0", C.c_float(f0log[b]), C.c_float(f0log[p]), C.c_int(r))
-        assert tab["f0_sf0"][b, p, r] == _orc_f("orc_ambe_pow2", C.c_float(x)), (b, p, r)
+    # every entry: 129 previous pitches (128 = none yet: log2 f0 = 0) x 128 pitches x 4 rules, the equal-pitch branch among them
+    lib = oracle_lib.lib()
+    lib.orc_ambe_f0log_sf0.restype = lib.orc_ambe_pow2.restype = C.c_float
+    want = np.array([lib.orc_ambe_pow2(C.c_float(lib.orc_ambe_f0log_sf0(C.c_float(f0log[b]), C.c_float(f0log[p]), C.c_int(r))))
+                     for b in range(129) for p in range(128) for r in range(4)], np.float32).reshape(129, 128, 4)
+    differ = np.argwhere(tab["f0_sf0"].view(np.uint32) != want.view(np.uint32))
+    assert want.size == 66048 and len(differ) == 0, differ[:5]
 
 
 def test_tone_amplitudes_and_generator_jumps(tab):

@@ -4,13 +4,20 @@ The vocoder is the one part of the reference that compiles from its own sources 
 PINNED: bit-identical PCM is required against (a) outputs of the reference's program committed under tests/golden/
 and (b) the reference built on the spot, on fresh streams -- or, where its sources are absent, that build's outputs on the
 same streams as tests/golden/ambe_ref_digests.npz stores them (a 64-bit digest per frame, written by
-tests/golden/make_ambe_ref_digests.py and pinned to the build by the last test below wherever the sources are present)."""
+tests/golden/make_ambe_ref_digests.py and pinned to the build by the last test below wherever the sources are present).
+
+The aimed streams of tests/ambe_aimed.py (tests/test_ambe_aimed_host.py compares the oracle with the reference on them) have
+their reference outputs here too: aimed_streams(), aimed_reference()."""
+import ctypes as C
+import functools
 import hashlib
 import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+import ambe_aimed as A
 import ambe_streams as S
 import oracle_lib
 import ref_codec
@@ -49,6 +56,69 @@ def reference_outputs(key, fr, program=True):
     g = np.load(DIGESTS)
     assert np.array_equal(g[key + "_frames_digest"], frame_digests(fr)), "stream changed"
     return g[key + "_clean"], g[key + "_rv"], (g[key + "_pcm"] if program else None)
+
+
+# ---- the aimed streams: families of channels, every channel a fresh decoder ----
+
+# frames per stored digest of the reference's samples: `histories` is 61 752 frames, stored per block of 16 to keep the file
+# small; the digests of the input frames (there to notice a changed generator, not to compare) are per 16 frames throughout
+AIMED_BLOCK = {"orbit": 1, "histories": 16, "levels": 1, "tones": 1}
+AIMED_FRAMES_BLOCK = 16
+
+
+def oracle_vuv_table():
+    return np.ctypeslib.as_array((C.c_uint16 * 64).in_dll(oracle_lib.lib(), "orc_ambe_vuv")).copy()
+
+
+@functools.lru_cache(None)
+def aimed_streams():
+    """family -> its channels, a list of [n, 10] (lengths differ)"""
+    lv, tn = A.levels(), A.tones_batch()
+    return {"orbit": list(A.orbit(oracle_vuv_table())), "histories": list(A.histories()),
+            "levels": [lv[c] for c in A.level_cases()], "tones": [tn[k] for k in A.TONE_STREAMS]}
+
+
+def decode_channels(decode, chans):
+    """[decode(channel) for every channel], each on a decoder of its own; on several threads (the C calls release the
+    interpreter lock; one frame first, alone, so that tables built at first use are built once)"""
+    decode(chans[0][:1])
+    with ThreadPoolExecutor(max(1, min(8, len(os.sched_getaffinity(0))))) as ex:
+        return list(ex.map(decode, chans))
+
+
+def block_digests(chans, block):
+    """One 64-bit digest per `block` rows of every channel (a channel's last block may be short; no block spans two
+    channels); block = 1 is frame_digests of the channels one after the other."""
+    return np.array([int.from_bytes(hashlib.blake2b(np.ascontiguousarray(c[i:i + block]).tobytes(), digest_size=8).digest(), "little")
+                     for c in chans for i in range(0, len(c), block)], np.uint64)
+
+
+_aimed_reference = {}
+
+
+def aimed_reference(key):
+    """The reference entered on a zeroed stack over the channels of family `key` -> (clean, rv [all frames]): clean is the
+    list of the channels' pcm where the reference is built here, else the stored digests per AIMED_BLOCK[key] frames."""
+    if key not in _aimed_reference:
+        chans = aimed_streams()[key]
+        if ref_codec.available():
+            res = decode_channels(ref_codec.decode_clean_stack, chans)
+            _aimed_reference[key] = ([p for p, _ in res], np.concatenate([r for _, r in res]))
+        else:
+            if not os.path.exists(DIGESTS):
+                pytest.skip("neither the reference's sources nor tests/golden/ambe_ref_digests.npz")
+            g = np.load(DIGESTS)
+            assert np.array_equal(g["aimed_%s_frames_digest" % key], block_digests(chans, AIMED_FRAMES_BLOCK)), "stream changed"
+            _aimed_reference[key] = (g["aimed_%s_clean" % key], g["aimed_%s_rv" % key])
+    return _aimed_reference[key]
+
+
+def aimed_differing(key, pcm_chans, clean):
+    """How many frames (blocks of frames, where only digests of blocks are known) of the channels' pcm differ from `clean`,
+    and of how many."""
+    if isinstance(clean, list):
+        return sum(int((p != c).any(1).sum()) for p, c in zip(pcm_chans, clean)), sum(len(c) for c in clean)
+    return int((block_digests(pcm_chans, AIMED_BLOCK[key]) != clean).sum()), len(clean)
 
 
 def same_frames(pcm, ref):
@@ -190,3 +260,9 @@ def test_stored_digests_are_the_reference_built_here():
         assert np.array_equal(g[key + "_clean"], frame_digests(clean)) and np.array_equal(g[key + "_rv"], rv), key
         if program:      # the program's few stack-dependent frames (see above) are allowed to move with the C library
             assert (g[key + "_pcm"] != frame_digests(prog)).sum() <= len(fr) // 200, key
+    for key, chans in aimed_streams().items():
+        clean, rv = aimed_reference(key)
+        assert isinstance(clean, list)
+        assert np.array_equal(g["aimed_%s_frames_digest" % key], block_digests(chans, AIMED_FRAMES_BLOCK)), key
+        assert np.array_equal(g["aimed_%s_clean" % key], block_digests(clean, AIMED_BLOCK[key])), key
+        assert np.array_equal(g["aimed_%s_rv" % key], rv), key
