@@ -320,7 +320,8 @@ int gmr1_hip_mod_batch(int burst_id, int sync_id, int n, const uint8_t *ebits, f
 /* The shaped modulator: symbols at one sample per symbol to demodulator-ready windows at sps samples per symbol, on the
  * device -- the pulse (raised cosine: what a demodulator behind a channelizer sees; root raised cosine: what a transmitter
  * sends; roll-off 0.35, cut at +-span symbols), a fraction of a sample of delay, a carrier offset, a phase and a level.
- * No framing, no overlapping bursts, no noise: a caller who wants noise adds it to the windows.
+ * No framing, no overlapping bursts, no noise: a caller who wants noise adds it to the windows, or hands the windows to
+ * gmr1_hip_carrier_mix* below, which places them on a carrier, overlapping where they must, over a noise floor.
  *   shape:      symbols n x len complex float32 (gmr1_hip_mod_batch's output, DKAB symbols, anything)
  *   mod_shaped: ebits n x (ebits of the burst format), sync_id per burst (NULL: sequence 0): the modulator and the shaper
  *               in one launch, float for float what shape gives on gmr1_hip_mod_batch's symbols
@@ -357,6 +358,64 @@ int gmr1_hip_mod_shaped_batch(int burst_id, int n, int sps, int pulse, int span,
                               const uint64_t *offset, const int32_t *start,
                               const float *frac, const float *cfo, const float *phase0, const float *gain,
                               float *out, uint64_t out_len);
+/* FCCH chirp windows: the one window kind the shaper cannot make.  A window writer under exactly the window contract of
+ * gmr1_hip_shape_batch*: offset, in_len, start, frac, cfo, phase0, gain, out and out_len mean what they mean there, every
+ * window is written in full, windows must not overlap, the NULL defaults are the same (0, 0, 0, 0, 1).  fcch_type: 0, 1, 2
+ * as in the FCCH entries below; freq and len are those of gmr1_fcch_burst, gmr1_fcch3_lband_burst, gmr1_fcch3_sband_burst.
+ * For q = k - start, 0 <= q < len sps:
+ *   t = (q - frac) / sps - len / 2,   x[k] = gain e^{j(phase0 + cfo k)} sqrt(2) cos(freq 2 pi / len t^2)
+ * and 0 elsewhere.  The chirp value is evaluated in double and rounded to float once, as the pulse coefficients are; the
+ * rotation is the shaper's (phase formed in float), so a chirp and a burst given the same cfo / phase0 rotate alike.
+ * -EINVAL, before anything is written: fcch_type outside 0..2, sps outside 1..16, in_len < 1, n < 0, a NULL offset / out;
+ * the host form also refuses a window that leaves out_len and windows that overlap.  n == 0 returns 0.
+ * _dev: device pointers, asynchronous on `stream`. */
+int gmr1_hip_fcch_chirp_batch_dev(void *stream, int fcch_type, int n, int sps, int in_len,
+                                  const uint64_t *offset, const int32_t *start,
+                                  const float *frac, const float *cfo, const float *phase0, const float *gain,
+                                  float *out, uint64_t out_len);
+int gmr1_hip_fcch_chirp_batch(int fcch_type, int n, int sps, int in_len,
+                              const uint64_t *offset, const int32_t *start,
+                              const float *frac, const float *cfo, const float *phase0, const float *gain,
+                              float *out, uint64_t out_len);
+/* The carrier mixer: windows (the outputs of shape / mod_shaped / fcch_chirp, any layout, complex float32 in seg_iq) to
+ * CARRIERS -- continuous streams with the windows overlap-added at absolute sample positions, a carrier offset and a noise
+ * floor: what the FCCH acquisition, gmr1_hip_rx_run*, the streaming handles and the call followers read.  Which burst goes
+ * where (the frame schedule) is the caller's.
+ * Carrier c owns segments seg_first[c] .. seg_first[c + 1]; segment s is seg_iq[seg_src[s] .. seg_src[s] + seg_len[s]) and
+ * its first sample lands on absolute sample seg_pos[s].  Carrier c is out[out_offset[c] .. out_offset[c] + length[c])
+ * (gmr1_hip_rx_run*'s arrays) and its sample k has the absolute index n = first[c] + k (first NULL: 0).  Its value:
+ *   1. acc = 0; for the carrier's segments IN LIST ORDER, each one with pos <= n < pos + len adds seg_iq[src + (n - pos)],
+ *      one float add per component.  List order is the summation order: the result is reproducible bit for bit.
+ *   2. if cfo[c] != 0 (radians per sample, double; NULL: 0): theta = cfo n formed in double, reduced to [-pi, pi] in double,
+ *      rounded to float, through the accurate sincosf; acc = acc e^{j theta} in float.  (n passes 2^23 within 90 s at four
+ *      samples per symbol: a float phase is not an option.)  cfo == 0 skips the step.
+ *   3. if sigma[c] != 0 (deviation per component, so the noise power is 2 sigma^2; NULL: 0): acc += sigma z(seed, id, n), id =
+ *      noise_id[c] (NULL: c).  z: Philox4x32-10 with key = (seed low, seed high) and counter = (j low, j high, id, 0),
+ *      j = n >> 1; words w0, w1 belong to sample 2 j and w2, w3 to sample 2 j + 1; with (wa, wb) the sample's words,
+ *      u1 = ((wa >> 8) + 1) 2^-24, u2 = (wb >> 8) 2^-24, r = sqrtf(-2 logf(u1)), z = r (cospi(2 u2) + j sinpi(2 u2)).
+ *      The noise is not rotated (it is circular).  sigma == 0 skips the step.
+ *   4. every sample of every carrier is written, zeros where nothing lands; nothing else in out is touched.
+ * z depends on the absolute index alone, and segments are clipped to the carrier (pos may be negative or past its end): a
+ * carrier made in pieces (first = 0, a, b, ...) is sample for sample the carrier made in one call, so a stream of any
+ * length needs bounded memory and can feed the streaming handles push by push.
+ * Required of the caller, each carrier: segments sorted by pos, non-decreasing, and seg_len <= max_seg_len (the kernel finds
+ * a sample's segments by a search over pos).  seg_first NULL (host form: n_seg == 0): no segments, noise and zeros only.
+ * -EINVAL, before anything is written: n_carriers < 0, a NULL out_offset / length / out, segments present with a NULL
+ * seg_iq / seg_src / seg_pos / seg_len or max_seg_len == 0; the host form, which sees the arrays, also: segments not sorted
+ * or longer than max_seg_len, a segment that leaves seg_iq_len, seg_first not non-decreasing from 0 to n_seg, carriers that
+ * overlap in out or leave out_len, length[c] > max_length, a negative or non-finite sigma.  n_carriers == 0 returns 0.
+ * _dev: device pointers, asynchronous on `stream`, no scratch.  The host form copies seg_iq and the arrays in and the
+ * carriers out (what lies between them in out stays). */
+#define GMR1_HIP_CARRIER_MIX_TILE 1024      /* samples a work-group of the mixer owns (for tests of its edges) */
+int gmr1_hip_carrier_mix_dev(void *stream, int n_carriers, const float *seg_iq, const int32_t *seg_first,
+                             const uint64_t *seg_src, const int64_t *seg_pos, const uint32_t *seg_len, uint32_t max_seg_len,
+                             const uint64_t *out_offset, const uint64_t *length, uint64_t max_length, const int64_t *first,
+                             const float *sigma, const double *cfo, const uint32_t *noise_id, uint64_t seed, float *out);
+int gmr1_hip_carrier_mix(int n_carriers, const float *seg_iq, uint64_t seg_iq_len, int n_seg, const int32_t *seg_first,
+                         const uint64_t *seg_src, const int64_t *seg_pos, const uint32_t *seg_len, uint32_t max_seg_len,
+                         const uint64_t *out_offset, const uint64_t *length, uint64_t max_length, const int64_t *first,
+                         const float *sigma, const double *cfo, const uint32_t *noise_id, uint64_t seed,
+                         float *out, uint64_t out_len);
 /* The position map (payload bits -> burst bits) the encoder kernel evaluates for one chain, copied into buf as
  * struct EncPlan of osmo-gmr_amd/csrc/gmr1_dev.h; returns its size (buf may be NULL) or -EINVAL.  Host-only,
  * works without a GPU: tests/test_tx_plan.py evaluates it bit by bit against the CPU oracle. */

@@ -87,6 +87,10 @@ SIGNATURES = {
     "gmr1_hip_shape_batch": (I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, U64),
     "gmr1_hip_mod_shaped_batch_dev": (I, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, U64),
     "gmr1_hip_mod_shaped_batch": (I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, U64),
+    "gmr1_hip_fcch_chirp_batch_dev": (I, P, I, I, I, I, P, P, P, P, P, P, P, U64),
+    "gmr1_hip_fcch_chirp_batch": (I, I, I, I, I, P, P, P, P, P, P, P, U64),
+    "gmr1_hip_carrier_mix_dev": (I, P, I, P, P, P, P, P, U32, P, P, U64, P, P, P, P, U64, P),
+    "gmr1_hip_carrier_mix": (I, I, P, U64, I, P, P, P, P, U32, P, P, U64, P, P, P, P, U64, P, U64),
     "gmr1_hip_encoder_plan": (I, I, P, I),
     "gmr1_hip_fcch_rough_batch_dev": (I, P, I, I, I, I, P, P, P, P, P),
     "gmr1_hip_fcch_rough_batch": (I, I, I, I, I, P, U64, P, P, P, P),
@@ -1864,6 +1868,68 @@ def mod_shaped_batch_dev(stream, burst, n, sps, pulse, span, in_len, ebits, sync
     """gmr1_hip_mod_shaped_batch_dev on device memory (addresses, None for an array left out): enqueues and returns"""
     _call("gmr1_hip_mod_shaped_batch_dev", stream, _burst_id(burst), n, sps, pulse, span, in_len, ebits, sync_id, offset, start,
           frac, cfo, phase0, gain, out, out_len)
+
+
+def fcch_chirp_batch(n, sps, in_len, *, fcch_type="fcch", offset=None, start=None, frac=None, cfo=None, phase0=None, gain=None,
+                     out=None):
+    """gmr1_hip_fcch_chirp_batch: n windows of in_len complex64 samples, each holding one FCCH dual chirp at sps samples per
+    symbol, under shape_batch's window arguments (offset, out, and per window start / frac / cfo / phase0 / gain)."""
+    offset, out, ret, per = _shape_windows(n, in_len, offset, out, (start, frac, cfo, phase0, gain))
+    _call("gmr1_hip_fcch_chirp_batch", _fcch_id(fcch_type), n, sps, in_len, _p(offset), *[_p(a) for a in per], _p(out), out.size)
+    return ret
+
+
+def fcch_chirp_batch_dev(stream, fcch_type, n, sps, in_len, offset, start, frac, cfo, phase0, gain, out, out_len):
+    """gmr1_hip_fcch_chirp_batch_dev on device memory (addresses, None for an array left out): enqueues and returns"""
+    _call("gmr1_hip_fcch_chirp_batch_dev", stream, _fcch_id(fcch_type), n, sps, in_len, offset, start, frac, cfo, phase0, gain,
+          out, out_len)
+
+
+CARRIER_MIX_TILE = 1024       # GMR1_HIP_CARRIER_MIX_TILE
+
+
+def carrier_mix(seg_iq, seg_first, seg_src, seg_pos, seg_len, length, *, out_offset=None, first=None, sigma=None, cfo=None,
+                noise_id=None, seed=0, max_seg_len=None, max_length=None, out=None):
+    """gmr1_hip_carrier_mix: the windows in seg_iq (flat complex64: what shape_batch / mod_shaped_batch / fcch_chirp_batch
+    wrote) to carriers.  Carrier c owns segments seg_first[c] .. seg_first[c + 1] (seg_first None: no segments), segment s is
+    seg_iq[seg_src[s] : seg_src[s] + seg_len[s]] landing on absolute sample seg_pos[s] (sorted per carrier); carrier c has
+    length[c] samples from absolute sample first[c] (None: 0) and gets the noise sigma[c] (None: 0) of stream noise_id[c]
+    (None: c) under `seed`, and the carrier offset cfo[c] in radians per sample (None: 0).  out_offset None: carriers back to
+    back; out None: a fresh array that exactly holds them, else the caller's flat complex64 array, written in place.
+    Returns the array; with out None and one carrier or equal lengths, shaped (n_carriers, length)."""
+    length = _arr(length, np.uint64, -1)
+    n = length.size
+    seg_iq = _arr(seg_iq, np.complex64, -1)
+    seg_first, seg_src = _arr(seg_first, np.int32), _arr(seg_src, np.uint64)
+    seg_pos, seg_len = _arr(seg_pos, np.int64), _arr(seg_len, np.uint32)
+    n_seg = 0 if seg_first is None or seg_src is None else seg_src.size
+    if max_seg_len is None:
+        max_seg_len = int(seg_len.max()) if n_seg else 0
+    if max_length is None:
+        max_length = int(length.max()) if n else 0
+    if out_offset is None:
+        out_offset = (np.cumsum(length) - length).astype(np.uint64)
+    out_offset = _arr(out_offset, np.uint64, -1)
+    if out is None:
+        out = np.zeros(int((out_offset + length).max()) if n else 0, np.complex64)
+        ret = out.reshape(n, -1) if n and out.size == n * int(length[0]) and (length == length[0]).all() else out
+    else:
+        if not (isinstance(out, np.ndarray) and out.dtype == np.complex64 and out.flags.c_contiguous):
+            raise TypeError("out: a contiguous complex64 array, written in place")
+        ret = out
+    per = [None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, t), (n,)))
+           for a, t in ((first, np.int64), (sigma, np.float32), (cfo, np.float64), (noise_id, np.uint32))]
+    _call("gmr1_hip_carrier_mix", n, _p(seg_iq), 0 if seg_iq is None else seg_iq.size, n_seg, _p(seg_first), _p(seg_src),
+          _p(seg_pos), _p(seg_len), max_seg_len, _p(out_offset), _p(length), max_length, *[_p(a) for a in per], seed, _p(out),
+          out.size)
+    return ret
+
+
+def carrier_mix_dev(stream, n_carriers, seg_iq, seg_first, seg_src, seg_pos, seg_len, max_seg_len, out_offset, length, max_length,
+                    first, sigma, cfo, noise_id, seed, out):
+    """gmr1_hip_carrier_mix_dev on device memory (addresses, None for an array left out): enqueues on `stream` and returns"""
+    _call("gmr1_hip_carrier_mix_dev", stream, n_carriers, seg_iq, seg_first, seg_src, seg_pos, seg_len, max_seg_len, out_offset,
+          length, max_length, first, sigma, cfo, noise_id, seed, out)
 
 
 def encode_single(chain, *args):

@@ -285,6 +285,18 @@ private:
 	std::vector<Back> backs_;
 };
 
+// The output of a host form that writes n windows of in_len samples into the caller's array (the shaping calls, the FCCH
+// chirps): check() refuses a window that leaves out_len and windows that overlap; stage() gives the device copy of the
+// windows' hull and the offsets relative to it, and books one copy back per run of windows that touch -- so what lies
+// between the windows in the caller's array stays.
+struct HostWindows {
+	std::vector<uint64_t> order;       // the offsets, sorted
+	int check(const char *who, int n, int in_len, const uint64_t *offset, uint64_t out_len);
+	float *stage(Stage &sg, int in_len, const uint64_t *offset, float *out, const uint64_t **d_offset);     // n > 0
+private:
+	std::vector<uint64_t> rel_;
+};
+
 // One turn on the device's workspace: leases it for `st`, hands enqueue(scratch) `bytes` of it, gives the lease back on return
 template <class F> int with_scratch(DevState *s, hipStream_t st, size_t bytes, F &&enqueue)
 {

@@ -713,43 +713,26 @@ int shape_host(ShapeSrc src, int n, int len, int sps, int pulse, int span, int i
 {
 	int r = shape_check(&src, n, &len, sps, pulse, span, in_len, offset, out);
 	if (r) return r;
-	std::vector<uint64_t> order(offset, offset + n);
-	for (int b = 0; b < n; b++) {
-		if (offset[b] > out_len || (uint64_t)in_len > out_len - offset[b])
-			return fail(-EINVAL, "%s: window %d leaves the %llu samples of out", src.who, b, (unsigned long long)out_len);
+	HostWindows win;
+	if ((r = win.check(src.who, n, in_len, offset, out_len))) return r;
+	for (int b = 0; b < n; b++)
 		if (src.bits && src.sync_id && (src.sync_id[b] < 0 || src.sync_id[b] >= src.f.n_sync))
 			return fail(-EINVAL, "%s: burst %d asks for sync sequence %d of %d", src.who, b, (int)src.sync_id[b], src.f.n_sync);
-	}
-	std::sort(order.begin(), order.end());
-	for (int b = 1; b < n; b++)
-		if (order[b] - order[b - 1] < (uint64_t)in_len)
-			return fail(-EINVAL, "%s: the windows at samples %llu and %llu overlap", src.who, (unsigned long long)order[b - 1],
-			            (unsigned long long)order[b]);
 	DevState *s;
 	if ((r = dev_state(&s))) return r;
 	if (n == 0)
 		return 0;
-	// the device copy of out covers the windows' hull; the offsets are taken relative to its first sample
-	const uint64_t lo = order.front(), hull = order.back() + (uint64_t)in_len - lo;
-	std::vector<uint64_t> rel(offset, offset + n);
-	for (uint64_t &o : rel)
-		o -= lo;
 	Stage sg;
 	const size_t nn = (size_t)n;
 	ShapeSrc d = src;
 	d.symbols = sg.in(src.symbols, nn * (size_t)len * 2);
 	d.ebits = src.bits ? sg.in(src.ebits, nn * (size_t)src.f.ebits) : nullptr;
 	d.sync_id = sg.in(src.sync_id, nn);
-	const uint64_t *d_off = sg.in(rel.data(), nn);
 	const int32_t *d_start = sg.in(start, nn);
 	const float *d_frac = sg.in(frac, nn), *d_cfo = sg.in(cfo, nn), *d_ph = sg.in(phase0, nn), *d_gain = sg.in(gain, nn);
-	float *d_out = sg.dev<float>((size_t)hull * 2);
+	const uint64_t *d_off;
+	float *d_out = win.stage(sg, in_len, offset, out, &d_off);
 	if ((r = sg.err())) return r;
-	for (int b = 0, first = 0; b < n; b++)          // one copy back per run of windows that touch
-		if (b + 1 == n || order[b + 1] - order[b] > (uint64_t)in_len) {
-			sg.back(out + 2 * order[first], d_out + 2 * (order[first] - lo), (size_t)(order[b] + (uint64_t)in_len - order[first]) * 2);
-			first = b + 1;
-		}
 	r = shape_enqueue(nullptr, d, n, len, sps, pulse, span, in_len, d_off, d_start, d_frac, d_cfo, d_ph, d_gain, d_out);
 	if (r) return r;
 	return sg.fetch();

@@ -611,6 +611,40 @@ struct ShapeArgs {
 };
 hipError_t launch_shape(const ShapeArgs &a, hipStream_t stream);
 
+// FCCH chirp windows (k_chirp, tx_kernels.hip; the arithmetic: tx_pulse.h): n windows of in_len samples under the shaper's
+// window contract, each holding one dual chirp of len symbols at sps samples per symbol
+struct ChirpArgs {
+	int n, len, sps, in_len;
+	double freq;                       // the burst description's, as a double
+	const uint64_t *offset;            // per window: its first sample in out
+	const int32_t *start;              // window sample of the chirp's sample 0 (null: 0)
+	const float *frac, *cfo, *phase0, *gain;     // as ShapeArgs
+	float2 *out;
+};
+hipError_t launch_chirp(const ChirpArgs &a, hipStream_t stream);
+
+// the carrier mixer (k_carrier_mix, carrier_kernels.hip; the noise and the phase: carrier_noise.h): per carrier, the
+// overlap-add of its segments of seg_iq in list order, a rotation by cfo n, noise, over length[c] samples from absolute
+// sample first[c].  Every pointer is device memory.
+struct MixArgs {
+	int n_carriers;
+	const float2 *seg_iq;
+	const int32_t *seg_first;          // n_carriers + 1, or null: no segments at all
+	const uint64_t *seg_src;           // per segment: its first sample in seg_iq,
+	const long long *seg_pos;          //   the absolute sample that lands on (non-decreasing within a carrier),
+	const uint32_t *seg_len;           //   its samples (at most max_seg_len)
+	uint32_t max_seg_len;
+	const uint64_t *out_offset, *length;   // per carrier: where it lies in out
+	uint64_t max_length;
+	const long long *first;            // null: 0
+	const float *sigma;                // null: 0
+	const double *cfo;                 // null: 0
+	const uint32_t *noise_id;          // null: the carrier's index
+	uint64_t seed;
+	float2 *out;
+};
+hipError_t launch_carrier_mix(const MixArgs &a, hipStream_t stream);
+
 // the stand-alone layer-1 primitives (scrambler, intra- / inter-burst interleaver) as one gather kernel:
 // out[i] = in[perm ? perm[i] : i], then xor (ubits) or negate (sbits) where mask[i] is set
 struct BitMapArgs {

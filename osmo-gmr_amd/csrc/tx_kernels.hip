@@ -275,6 +275,52 @@ hipError_t launch_shape(const ShapeArgs &a, hipStream_t stream)
 	return hipGetLastError();
 }
 
+// ---- FCCH chirp windows: the one window kind the shaper cannot make (a real chirp, no symbols and no pulse), under the
+// shaper's window contract and with its rotation and gain, so that a chirp and a burst given the same cfo / phase0 rotate
+// alike.  One wave per window, a lane takes the two samples of a 16-byte unit of the output, stores are streaming: as
+// k_shape.  Per sample: the chirp in fp64 (tx_pulse.h: chirp_value; a cos and a handful of multiplies, on windows of a
+// few hundred samples every 320 ms of carrier -- nothing a table would pay for), the phase in fp32, the accurate sincosf.
+__global__ __launch_bounds__(256) void k_chirp(ChirpArgs a)
+{
+	const int lane = threadIdx.x & 63;
+	const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (u >= a.n)
+		return;
+	const int in_len = a.in_len;
+	const int start = a.start ? a.start[u] : 0;
+	const double fr = a.frac ? (double)a.frac[u] : 0.0;
+	const float cfo = a.cfo ? a.cfo[u] : 0.f, ph0 = a.phase0 ? a.phase0[u] : 0.f, gain = a.gain ? a.gain[u] : 1.f;
+	auto sample = [&](int k) -> float2 {
+		long long q;
+		if (k < 0 || k >= in_len || !chirp_index(k, start, a.sps, a.len, &q))
+			return make_float2(0.f, 0.f);
+		const float v = chirp_value(a.freq, a.len, a.sps, q, fr);
+		float s, c;
+		sincosf(__fadd_rn(ph0, __fmul_rn(cfo, (float)k)), &s, &c);
+		return make_float2(gain * (v * c), gain * (v * s));
+	};
+	float2 *outu = a.out + a.offset[u];
+	const int odd = (int)((reinterpret_cast<uintptr_t>(outu) >> 3) & 1u);     // the window starts in the upper half of a unit
+	for (int t = lane; 2 * t - odd < in_len; t += 64) {
+		const int k = 2 * t - odd;
+		const float2 x0 = sample(k), x1 = sample(k + 1);
+		if (k >= 0 && k + 1 < in_len)
+			__builtin_nontemporal_store((sh_v4f){x0.x, x0.y, x1.x, x1.y}, reinterpret_cast<sh_v4f *>(outu + k));
+		else if (k >= 0)
+			__builtin_nontemporal_store((sh_v2f){x0.x, x0.y}, reinterpret_cast<sh_v2f *>(outu + k));
+		else
+			__builtin_nontemporal_store((sh_v2f){x1.x, x1.y}, reinterpret_cast<sh_v2f *>(outu + k + 1));
+	}
+}
+
+hipError_t launch_chirp(const ChirpArgs &a, hipStream_t stream)
+{
+	if (a.n <= 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_chirp, dim3((unsigned)(((long long)a.n + 3) / 4)), dim3(256), 0, stream, a);
+	return hipGetLastError();
+}
+
 // ---- stand-alone primitives: gmr1_scramble_{sbit,ubit} (scramb.c:62-93), gmr1_{de,}interleave_intra
 // (interleave.c:48-87), gmr1_{de,}interleave_inter (interleave.c:128-190): a gather plus an optional sign / bit flip
 __global__ __launch_bounds__(256) void k_bitmap(BitMapArgs a)

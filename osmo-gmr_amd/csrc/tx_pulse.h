@@ -109,6 +109,28 @@ GMR1_HD V shape_body(const V *padded, const float *coef, int i, int p, int span,
 	return V{re, im};
 }
 
+// ---- the FCCH dual chirp (k_chirp; gmr1_hip_fcch_chirp_batch*): synth.fcch_dual_chirp, operation for operation.
+// Sample q = 0 .. len sps of a chirp of len symbols delayed by frac samples: sqrt(2) cos(freq 2 pi / len t^2) at
+// t = (q - frac) / sps - len / 2 symbols, evaluated in double and rounded to float once, as the pulse coefficients are.
+GMR1_HD float chirp_value(double freq, int len, int sps, long long q, double frac)
+{
+	const double t = ((double)q - frac) / (double)sps - (double)len / 2.0;
+	return (float)(sqrt(2.0) * cos(freq * 2 * kPulsePi / (double)len * t * t));
+}
+
+// window sample k of a chirp whose sample 0 lands on window sample start: 0 if k lies outside the chirp, else 1 and q
+GMR1_HD int chirp_index(int k, int start, int sps, int len, long long *q)
+{
+	*q = (long long)k - (long long)start;
+	return *q >= 0 && *q < (long long)len * sps;
+}
+
+// what the chirp entries refuse (include/gmr1_hip.h): 0 if the arguments are in range
+GMR1_HD int chirp_args_bad(int fcch_type, int n, int sps, int in_len)
+{
+	return fcch_type < 0 || fcch_type > 2 || n < 0 || sps < 1 || sps > kShapeMaxSps || in_len < 1;
+}
+
 // the arguments every entry refuses (include/gmr1_hip.h): 0 if they are in range
 GMR1_HD int shape_args_bad(int n, int len, int sps, int pulse, int span, int in_len)
 {
