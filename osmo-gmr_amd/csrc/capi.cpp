@@ -29,6 +29,7 @@ FcchTables g_fcch_tables;
 }  // namespace
 
 DevBurst g_host_types[kNumTypes];
+Rx4Ord4 g_host_ord4;
 
 int fail(int code, const char *fmt, ...)
 {
@@ -104,6 +105,7 @@ static int host_types_build()
 		if (rv)
 			return fail(rv, "built-in burst table %d is inconsistent", i);
 	}
+	make_ord4(g_host_types, &g_host_ord4);
 	fcch_tables_init(&g_fcch_tables);
 	g_host_types_ready = true;
 	return 0;
@@ -126,6 +128,7 @@ int dev_state(DevState **out)
 		if (rv)
 			return rv;
 		HIP_TRY(upload_types(g_host_types, 0, kNumTypes, nullptr));
+		HIP_TRY(upload_rx4_operands(&g_host_ord4, nullptr));
 		HIP_TRY(upload_fcch_tables(&g_fcch_tables, nullptr));
 		HIP_TRY(hipStreamSynchronize(nullptr));
 		s.ready = true;

@@ -13,6 +13,7 @@
 
 #include "gmr1_dev.h"
 #include "host_tables.h"
+#include "rx4_operands.h"
 #include "scratch_layouts.h"
 
 namespace gmr1 {
@@ -61,6 +62,7 @@ private:
 };
 
 extern DevBurst g_host_types[kNumTypes];
+extern Rx4Ord4 g_host_ord4;      // the fused batch kernel's packed view of the BCCH / DC6 descriptors, made with them (rx4_operands.h)
 // guards the descriptor-table slots caller-defined burst types are uploaded into (one demodulator slot, four detector
 // slots): held from the upload until the kernel that reads them has finished
 std::mutex &custom_slots_mutex();

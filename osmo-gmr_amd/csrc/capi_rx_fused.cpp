@@ -25,6 +25,8 @@ int rx_fused_base_args(int sps, RxArgs *a, int min_sps)
 		if (!fused_format_matches(g_host_types[kFusedType[k]], k))
 			return fail(-EINVAL, "rx_bcch_ccch: burst table %d does not have the training layout the kernel is built for",
 			            kFusedType[k]);
+	if (!fused_operands_match(g_host_types, g_host_ord4, kHostSteps4))
+		return fail(-EINVAL, "rx_bcch_ccch: the packed per-lane operand tables do not say what the burst and step tables say");
 	a->stage_samples = fused_stage_samples(g_host_types, sps);
 	return 0;
 }

@@ -3,37 +3,16 @@
 // (decode4_k5_12: four bursts a wave; decode1_k5_12_lat: one burst, latency shape), survivor walk + CRC16, L2 store.
 #pragma once
 #include "l1_codes.h"
+#include "rx4_operands.h"
 #include "wave_ops.h"
 
 namespace gmr1 {
 
-static constexpr int kSteps12 = 212;              // 208 data + 4 flush steps (BCCH/CCCH)
-
-// Per trellis step of the BCCH / CCCH chain: where the two soft bits of the step
-// sit in the burst's e-bit order and whether the scrambler flips them
-//   bits  0..9  index of c[2k]   bit 10 its scrambling bit
-//   bits 16..25 index of c[2k+1] bit 26 its scrambling bit
-// (interleave.c:73-87 with N=53, scramb.c:39-73; CCCH: 4 leading pad bits, ccch.c:95-96)
-struct StepTable { uint32_t w[2][kSteps12]; };
-static constexpr StepTable make_steps()
-{
-	StepTable t{};
-	const auto scr = l1c::scramble_seq<448>();        // scrambling sequence over the e-bit positions
-	for (int chain = 0; chain < 2; chain++) {
-		const int off = chain ? 4 : 0;
-		for (int k = 0; k < kSteps12; k++) {
-			uint32_t w = 0;
-			for (int j = 0; j < 2; j++) {
-				const int kc = 2 * k + j;
-				const int ei = l1c::intra_pos(53, kc) + off;
-				w |= ((uint32_t)ei | (scr.bit[ei] ? 0x400u : 0u)) << (16 * j);
-			}
-			t.w[chain][k] = w;
-		}
-	}
-	return t;
-}
+// the trellis-step descriptors (kSteps12, StepTable, make_steps) and their per-lane packing are written down in
+// rx4_operands.h, which the host reads as well
 __constant__ StepTable c_steps = make_steps();
+// a lane's four descriptors of a chain as one 16-byte load (the fused batch kernel's request ahead of pass 2)
+__device__ const Rx4Steps4 g_steps4 = make_steps4(make_steps());
 
 // Viterbi input cost of one soft bit, libosmocore's generic decoder: ((in -+ 127)^2) >> 9, and 0 for
 // an erasure (in == 0).  Index = soft bit as uint8, + 256 when the scrambler flips it (the flipped
@@ -201,19 +180,18 @@ __device__ __forceinline__ void branch_metrics_k5_12(const int8_t *__restrict__ 
 // the four bursts of a fused wave at once: every lane owns steps lane + 64 it of each burst, and the
 // three dependent fetches (step descriptor -> soft bits -> cost words) are each issued for all 16
 // (burst, step) pairs before anything waits -- three memory round trips per wave instead of 48
-template <bool ACC = false>
-__device__ __forceinline__ void branch_metrics4_k5_12(const int8_t *__restrict__ eb, int eb_stride, int row_ok,
-                                                      int row_chain, uint32_t *__restrict__ bm, int lane)
+// (steps(c, it): the descriptor of step lane + 64 it of chain c, 0 beyond the last step; the two forms below say where from)
+template <bool ACC, class Steps>
+__device__ __forceinline__ void branch_metrics4_k5_12_from(const int8_t *__restrict__ eb, int eb_stride, int row_ok,
+                                                           int row_chain, uint32_t *__restrict__ bm, int lane, Steps steps)
 {
 	const CostTable &ct = ACC ? c_cost_acc : c_cost;
 	uint32_t st[2][4];
 #pragma unroll
 	for (int c = 0; c < 2; c++)
 #pragma unroll
-		for (int it = 0; it < 4; it++) {
-			const int k = lane + 64 * it;
-			st[c][it] = k < kSteps12 ? c_steps.w[c][k] : 0u;
-		}
+		for (int it = 0; it < 4; it++)
+			st[c][it] = steps(c, it);
 	uint32_t ia[4][4], ib[4][4];
 #pragma unroll
 	for (int q = 0; q < 4; q++) {
@@ -244,6 +222,30 @@ __device__ __forceinline__ void branch_metrics4_k5_12(const int8_t *__restrict__
 				bm[q * kSteps12 + k] = ok ? va[q][it] + vb[q][it] : 0u;
 		}
 	}
+}
+
+// the descriptors read from c_steps here, a memory trip of their own in front of the other two
+template <bool ACC = false>
+__device__ __forceinline__ void branch_metrics4_k5_12(const int8_t *__restrict__ eb, int eb_stride, int row_ok,
+                                                      int row_chain, uint32_t *__restrict__ bm, int lane)
+{
+	branch_metrics4_k5_12_from<ACC>(eb, eb_stride, row_ok, row_chain, bm, lane, [&](int c, int it) -> uint32_t {
+		const int k = lane + 64 * it;
+		return k < kSteps12 ? c_steps.w[c][k] : 0u;
+	});
+}
+
+// the descriptors already in registers: st0 / st1 = the lane's g_steps4 entries of chain 0 / 1, which the caller asked for
+// ahead of its own waits
+template <bool ACC = false>
+__device__ __forceinline__ void branch_metrics4_k5_12(const int8_t *__restrict__ eb, int eb_stride, int row_ok,
+                                                      int row_chain, uint32_t *__restrict__ bm, int lane,
+                                                      const uint4 st0, const uint4 st1)
+{
+	branch_metrics4_k5_12_from<ACC>(eb, eb_stride, row_ok, row_chain, bm, lane, [&](int c, int it) -> uint32_t {
+		const uint4 v = c ? st1 : st0;
+		return it == 0 ? v.x : (it == 1 ? v.y : (it == 2 ? v.z : v.w));
+	});
 }
 
 // ---------------------------------------------------------------------------

@@ -668,6 +668,9 @@ hipError_t launch_rx_tch3(const RxArgs &a, const Tch3Args &t, hipStream_t stream
 // launchers (rx_kernels.hip and the files it includes)
 // descriptors live in __constant__ memory of the current device
 hipError_t upload_types(const DevBurst *host, int first, int count, hipStream_t stream);
+// the fused batch kernel's packed per-lane view of the BCCH / DC6 descriptors (rx4_operands.h), device memory of the current device
+struct Rx4Ord4;
+hipError_t upload_rx4_operands(const Rx4Ord4 *host, hipStream_t stream);
 hipError_t launch_rx(const RxArgs &a, bool decode, int max_in_len, hipStream_t stream);
 // interleaved sample array -> polyphase-planar (sample s to out[(s % sps) * plane_stride + s / sps])
 hipError_t launch_to_planar(const float2 *in, float2 *out, unsigned long long n, int sps, long long plane_stride, hipStream_t stream);

@@ -7,6 +7,8 @@
 //   conv_k5_12.h         the layer-1 chain: constant tables (trellis steps, costs, CRC syndromes, soft-bit tables), branch
 //                        metrics, decode4_k5_12 / decode1_k5_12_lat, survivor walk + CRC16, store_l2
 //                        (reference src/l1/bcch.c:83-103, src/l1/ccch.c:87-107 and libosmocore's osmo_conv_decode)
+//   rx4_operands.h       (through conv_k5_12.h; no HIP in it) the trellis-step table's maker and the packed per-lane tables
+//                        k_rx4 asks for in batches behind pass 1 (g_ord4, g_steps4), with the checks the host runs on them
 //   rx_window.h          the one-burst LDS carve-up; window HBM -> registers -> LDS, statistics, burst energy
 //   rx_one.h             sync_search, demod_one and k_rx: pi/4-CxPSK demodulation, one burst per wavefront; with DECODE four
 //                        bursts back to back and the layer-1 chain behind them
@@ -63,6 +65,10 @@ __constant__ DevBurst c_types[kNumTypes];
 #include "rx_window.h"
 
 namespace gmr1 {
+
+// where the soft bits of a lane's four symbols go, BCCH and DC6 (rx4_operands.h; upload_rx4_operands fills it from the
+// host's burst tables, next to c_types)
+__device__ Rx4Ord4 g_ord4;
 
 #include "rx_one.h"
 
@@ -148,6 +154,11 @@ hipError_t upload_types(const DevBurst *host, int first, int count, hipStream_t 
 	if (e != hipSuccess)
 		return e;
 	return hipMemcpyToSymbolAsync(HIP_SYMBOL(c_coef0), src, sizeof(g_coef0), 0, hipMemcpyDeviceToDevice, stream);
+}
+
+hipError_t upload_rx4_operands(const Rx4Ord4 *host, hipStream_t stream)
+{
+	return hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ord4), host, sizeof(Rx4Ord4), 0, hipMemcpyHostToDevice, stream);
 }
 
 // Sync correlation of the fused path's two formats with everything static: chunks of T0, T1, T2 training symbols
@@ -660,7 +671,18 @@ struct Rx4Switches : P {
 	static constexpr bool AHEAD = P::EARLY && QX;
 	static constexpr int TOUCH = AHEAD ? GMR1_EXP_RX4_TOUCH : 0;
 	static constexpr bool H_ROW = AHEAD, ONE_LOAD = AHEAD;
+	// OPS_AHEAD (with AHEAD, whose scalars name each burst's kind): what pass 2, the branch metrics and the decoder read per
+	// lane that is fixed for the launch goes out in batches, ahead of the waits it used to stand behind.  Where the lane's
+	// four symbols' soft bits go (g_ord4, one 8-byte load a burst) is asked for with the soft-bit table's two loads, right
+	// behind the sync rows: one memory trip where pass 2 made one per burst.  The lane's step descriptors (g_steps4, one
+	// 16-byte load a chain) go out inside the pass-2 loop (kRx4StepsAt), the decoder's constants in front of the branch
+	// metrics' gathers.  The other instantiations read c_types' ord_of_sym, c_steps and the constants where they always did
+	// (profiles/r14a_rx4_waits_behind_pass1.txt has both lists of waits).
+	static constexpr bool OPS_AHEAD = AHEAD;
 };
+
+// OPS_AHEAD: the pass-2 iteration (bursts run 3, 2, 1, 0) at whose head the step descriptors are asked for
+constexpr int kRx4StepsAt = 1;
 
 template <class Cfg>
 __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int stage_samples, int cw, int g0, int n_end,
@@ -672,7 +694,7 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 	constexpr bool SMALL = C::SMALL, QL = C::QL, QX = C::QX, PREFETCH_NEXT = C::PREFETCH_NEXT, UB_OVER = C::UB_OVER;
 	constexpr int NSYM = C::NSYM, NCHK = C::NCHK, NSH = C::NSH;
 	constexpr int TOUCH = C::TOUCH;
-	constexpr bool AHEAD = C::AHEAD, H_ROW = C::H_ROW;
+	constexpr bool AHEAD = C::AHEAD, H_ROW = C::H_ROW, OPS_AHEAD = C::OPS_AHEAD;
 	const int row = lane >> 4, col = lane & 15;
 	const int sps = SPS ? SPS : a.sps;
 	const int cwh = FAC ? cw / 2 : cw;                // lags per correlation array
@@ -1815,6 +1837,8 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 	// the soft-bit table overlays the pass-1 data (fused: where the branch metrics go after pass 2; demodulation
 	// only: behind the soft-bit rows, which themselves overlay the correlation the rows above were reading)
 	const unsigned char *lut = lds_raw + (GEN ? 4 * EBROW : 0);
+	uint2 ord4_q[4] = {};                              // OPS_AHEAD: burst q's g_ord4 entry of this lane
+	uint4 st4[2] = {};                                 // OPS_AHEAD: this lane's g_steps4 entries, both chains
 	if constexpr (LAT) {
 		lut = pre->lut;                             // the work-group's resident copy
 		WSYNC();
@@ -1823,6 +1847,13 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 		unsigned char *const lutw = lds_raw + (GEN ? 4 * EBROW : 0);
 		const uint4 *__restrict__ lut_src = reinterpret_cast<const uint4 *>(FAC ? g_sb_lut1.v : g_sb_lut.v);
 		const uint4 lut_a = lut_src[lane], lut_b = lut_src[lane + 64];
+		if constexpr (OPS_AHEAD) {
+			// (behind the table's loads, which are needed first: loads come back in order)
+			const uint2 *__restrict__ ord_src = reinterpret_cast<const uint2 *>(g_ord4.v);
+#pragma unroll
+			for (int q = 0; q < 4; q++)
+				ord4_q[q] = ord_src[(uint32_t)((kind_s[q] ? 64 : 0) + lane)];      // (kind_s: scalars, 0 / 1)
+		}
 		WSYNC();
 		reinterpret_cast<uint4 *>(lutw)[lane] = lut_a;
 		reinterpret_cast<uint4 *>(lutw)[lane + 64] = lut_b;
@@ -1835,6 +1866,16 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 #pragma unroll
 	for (int q = 3; q >= 0; q--) {
 		const int g = g0 + q;
+		if constexpr (OPS_AHEAD) {
+			// the step descriptors, for the branch metrics behind this loop: eight registers that do not fit beside the
+			// four bursts' kept phases in front of it (spills), and do once two bursts' phases are used up
+			if (q == kRx4StepsAt) {
+				const uint4 *__restrict__ st_src = reinterpret_cast<const uint4 *>(g_steps4.w);
+#pragma unroll
+				for (int c = 0; c < 2; c++)
+					st4[c] = st_src[(uint32_t)(64 * c + lane)];
+			}
+		}
 		Sym4 cur;
 		if constexpr (LAT) {
 			if (q != 0)
@@ -1896,7 +1937,12 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 #pragma unroll
 		for (int r = 0; r < NSYM; r++) {
 			const int i = lane + 64 * r;
-			ordv[r] = i < blen ? bt.ord_of_sym[i] : -1;
+			if constexpr (OPS_AHEAD) {
+				const uint32_t pair = r < 2 ? ord4_q[q].x : ord4_q[q].y;       // int16 r of the entry, sign-extended
+				ordv[r] = (r & 1) ? (int)pair >> 16 : (int)(pair << 16) >> 16;
+			} else {
+				ordv[r] = i < blen ? bt.ord_of_sym[i] : -1;
+			}
 		}
 		// phase of symbol i in TURNS: arg(x_i) + fs (i sps + d) + rps i - psi  =  arg(x_i) + A i + B
 		// (pi4cxpsk.c:351-371 derotation, :574-588 frequency / phase correction, folded into one fma), carried
@@ -1989,6 +2035,12 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 #ifdef GMR1_HIP_PROFILE
 		dpre.stamp = io.stamp;
 #endif
+	} else if constexpr (OPS_AHEAD) {
+		// the decoder's per-lane constants are asked for in front of the branch metrics' gathers, not behind them
+		dpre.dc = c_dec.v[col];
+		dpre.sy0 = *reinterpret_cast<const uint4 *>(&c_syn_rows.w[col][0]);
+		dpre.sy1 = *reinterpret_cast<const uint4 *>(&c_syn_rows.w[col][4]);
+		branch_metrics4_k5_12<ACC>(L.eb, 432, row_ok, row_chain, L.bm, lane, st4[0], st4[1]);
 	} else {
 		branch_metrics4_k5_12<ACC>(L.eb, 432, row_ok, row_chain, L.bm, lane);
 	}
@@ -2002,7 +2054,7 @@ __device__ __forceinline__ void rx4_body(const RxArgs &a, const RxIo io, int sta
 	if constexpr (LAT)
 		decode1_k5_12_lat<ACC>(pre->vtab, L.surv, L.ubits, lane, syn, fae, &dpre);
 	else
-		decode4_k5_12<ACC>(L.bm, L.surv, L.ubits, lane, syn, fae, nullptr);
+		decode4_k5_12<ACC>(L.bm, L.surv, L.ubits, lane, syn, fae, OPS_AHEAD ? &dpre : nullptr);
 	GMR1_STAMP(7);
 	if (col == 0 && row_live) {
 		if ((row_ok >> row) & 1) {

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "gmr1_dev.h"
+#include "rx4_operands.h"
 
 namespace gmr1 {
 
@@ -56,6 +57,7 @@ inline int demod_kernel_choice(const DevBurst &ht, int n, int sps, int in_len, i
 
 // the two formats of the fused path, by kind
 constexpr int kFusedType[2] = {GMR1_HIP_BCCH, GMR1_HIP_DC6};
+static_assert(kFusedType[0] == kRx4Type[0] && kFusedType[1] == kRx4Type[1], "the packed operand tables are made for the fused path's formats");
 
 // The fused kernels unroll the sync correlation for these two formats (corr_fixed, rx_kernels.hip) and carry both formats'
 // geometry and training symbols as constants (Fmt<false>, rx_kernels.hip; nb.c:36-62, 94-120): is `bt` what they hold for `kind`?
@@ -77,6 +79,16 @@ inline bool fused_format_matches(const DevBurst &bt, int kind)
 inline bool fused_formats_match(const DevBurst types[kNumTypes])
 {
 	return fused_format_matches(types[kFusedType[0]], 0) && fused_format_matches(types[kFusedType[1]], 1);
+}
+
+// The batch kernel reads where a lane's soft bits go and its trellis-step descriptors from packed per-lane copies (g_ord4,
+// g_steps4: rx4_operands.h) instead of c_types' ord_of_sym and c_steps: do the copies say what the originals say?
+// kHostSteps4 is the host's rendering of the table the kernels are compiled with.
+constexpr StepTable kHostSteps = make_steps();
+constexpr Rx4Steps4 kHostSteps4 = make_steps4(kHostSteps);
+inline bool fused_operands_match(const DevBurst types[kNumTypes], const Rx4Ord4 &ord4, const Rx4Steps4 &steps4)
+{
+	return rx4_ord4_matches(types, ord4) && rx4_steps4_matches(kHostSteps, steps4);
 }
 
 // LDS samples of the sync-chunk windows, sum over chunks of len*sps + w - 1: the larger of the two formats'
