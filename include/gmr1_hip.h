@@ -417,7 +417,7 @@ int gmr1_hip_carrier_mix(int n_carriers, const float *seg_iq, uint64_t seg_iq_le
                          const float *sigma, const double *cfo, const uint32_t *noise_id, uint64_t seed,
                          float *out, uint64_t out_len);
 /* The position map (payload bits -> burst bits) the encoder kernel evaluates for one chain, copied into buf as
- * struct EncPlan of osmo-gmr_amd/csrc/gmr1_dev.h; returns its size (buf may be NULL) or -EINVAL.  Host-only,
+ * struct EncPlan of osmo-gmr_amd/csrc/enc_plan.h; returns its size (buf may be NULL) or -EINVAL.  Host-only,
  * works without a GPU: tests/test_tx_plan.py evaluates it bit by bit against the CPU oracle. */
 enum gmr1_hip_enc_chain {
 	GMR1_HIP_ENC_BCCH = 0, GMR1_HIP_ENC_CCCH, GMR1_HIP_ENC_FACCH3, GMR1_HIP_ENC_TCH3_M0, GMR1_HIP_ENC_TCH3_M1,

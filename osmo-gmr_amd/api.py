@@ -1706,13 +1706,13 @@ def gsmtap_pack_big(record, with_arfcn=False) -> bytes:
     return _gsmtap("gmr1_hip_gsmtap_pack_big", record, RX_BIG_RECORD, with_arfcn, 96)
 
 
-# ---- transmit direction: channel encoders and modulator (csrc/capi_tx.cpp, tx_kernels.hip) ----------------
+# ---- transmit direction: channel encoders and modulator (csrc/capi_encode.cpp, capi_mod.cpp, capi_tx_ref.cpp, tx_kernels.hip) ----------------
 ENC_CHAINS = ("bcch", "ccch", "facch3", "tch3_m0", "tch3_m1", "facch9", "tch9_2k4", "tch9_4k8", "tch9_9k6", "rach",
               "xch_dc12")
 
 
 def encoder_plan(chain):
-    """The position map of one encoder chain (struct EncPlan of csrc/gmr1_dev.h) as a dict of numpy arrays.
+    """The position map of one encoder chain (struct EncPlan of csrc/enc_plan.h) as a dict of numpy arrays.
     Host-only: works without a GPU."""
     cid = ENC_CHAINS.index(chain) if isinstance(chain, str) else int(chain)
     f = _fn("gmr1_hip_encoder_plan")

@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libgmr1_hip.so")
 ARCH = "gfx950"
 
 HIP_SOURCES = ["rx_kernels.hip", "fcch_kernels.hip", "l1_kernels.hip", "tch_kernels.hip", "chan_kernels.hip", "nt9_kernels.hip", "xch_kernels.hip", "tx_kernels.hip", "carrier_kernels.hip", "ambe_kernels.hip", "util_kernels.hip", "rx_stream_kernels.hip", "tch3_follow_kernels.hip", "tch9_follow_kernels.hip"]
-CXX_SOURCES = ["capi.cpp", "capi_demod.cpp", "capi_one.cpp", "capi_rx_fused.cpp", "capi_fcch.cpp", "capi_l1.cpp", "capi_detect.cpp", "capi_rx.cpp", "capi_tch.cpp", "capi_chan.cpp", "capi_chan_stream.cpp", "capi_nt9.cpp", "capi_xch.cpp", "capi_tx.cpp", "capi_carrier.cpp", "host_tables.cpp", "l1_tables.cpp", "l1_punct.cpp", "capi_shard.cpp", "capi_ambe.cpp", "ambe_tables.cpp", "capi_tch3_follow.cpp", "capi_rx_follow.cpp", "capi_rx_stream.cpp", "capi_gsmtap.cpp", "capi_tch9_follow.cpp"]
+CXX_SOURCES = ["capi.cpp", "capi_demod.cpp", "capi_one.cpp", "capi_rx_fused.cpp", "capi_fcch.cpp", "capi_l1.cpp", "capi_detect.cpp", "capi_rx.cpp", "capi_tch.cpp", "capi_chan.cpp", "capi_chan_stream.cpp", "capi_nt9.cpp", "capi_xch.cpp", "capi_encode.cpp", "capi_mod.cpp", "capi_tx_ref.cpp", "enc_plan.cpp", "capi_carrier.cpp", "host_tables.cpp", "l1_tables.cpp", "l1_punct.cpp", "capi_shard.cpp", "capi_ambe.cpp", "ambe_tables.cpp", "capi_tch3_follow.cpp", "capi_rx_follow.cpp", "capi_rx_stream.cpp", "capi_gsmtap.cpp", "capi_tch9_follow.cpp"]
 
 # (the sources use designated initialisers, C++20, which hipcc and g++ take at -std=c++17 without a warning)
 COMMON = [

@@ -5,35 +5,31 @@
 
 #include "chan_chain.h"
 
-#include <deque>
+#include <utility>
 
 #include "../../include/gmr1_hip.h"
+#include "dev_cache.h"
 
 using namespace gmr1;
 
 namespace {
 
-std::mutex g_plan_mu;
-std::deque<ChanPlan> g_plans;       // addresses stay valid as plans are added
-std::deque<DdcPlan> g_ddc_plans;
+typedef std::pair<double, int> RateSps;
+DevCache<RateSps, ChanPlan> g_plans;
+DevCache<RateSps, DdcPlan> g_ddc_plans;
 
-template <typename T, typename D> int upload(D **dst, const std::vector<T> &v)
-{
-	static_assert(sizeof(T) == sizeof(D), "uploaded as it lies");
-	HIP_TRY(hipMalloc(dst, v.size() * sizeof(T)));
-	HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-	return 0;
-}
-
-int upload(ChanPlan &p)
+// a plan's device copies; what was uploaded is freed if a later upload fails
+int upload_plan(ChanPlan &p)
 {
 	int r;
-	if ((r = upload(&p.d_taps, p.taps)) || (r = upload(&p.d_bank, p.bank)))
-		return r;
-	return p.pre ? upload(&p.d_pre_bank, p.pre_bank) : 0;
+	if (!(r = upload(&p.d_taps, p.taps)) && !(r = upload(&p.d_bank, p.bank)) && p.pre)
+		r = upload(&p.d_pre_bank, p.pre_bank);
+	if (r)
+		(void)hipFree(p.d_taps), (void)hipFree(p.d_bank);
+	return r;
 }
 
-int upload(DdcPlan &p)
+int upload_plan(DdcPlan &p)
 {
 	std::vector<F2> t2(p.taps2.size());
 	for (size_t i = 0; i < t2.size(); i++)
@@ -41,30 +37,20 @@ int upload(DdcPlan &p)
 	int r;
 	if (!t2.empty() && (r = upload(&p.d_taps2, t2)))
 		return r;
-	return upload(&p.d_bank, p.bank);
+	if ((r = upload(&p.d_bank, p.bank)))
+		(void)hipFree(p.d_taps2);
+	return r;
 }
 
 // the cached plan of (rate, sps, current device), or a new one: its numbers, then its device copies
-template <typename Plan> int cached_plan(std::deque<Plan> &plans, double samp_rate, int sps, const Plan **out)
+template <typename Plan> int cached_plan(DevCache<RateSps, Plan> &plans, double samp_rate, int sps, const Plan **out)
 {
 	int dev = 0;
 	HIP_TRY(hipGetDevice(&dev));
-	std::lock_guard<std::mutex> lk(g_plan_mu);
-	for (const Plan &p : plans)
-		if (p.samp_rate == samp_rate && p.sps == sps && p.device == dev) {
-			*out = &p;
-			return 0;
-		}
-	Plan p;
-	std::string why;
-	if (!plan_numbers(samp_rate, sps, &p, &why))
-		return fail(-EINVAL, "%s", why.c_str());
-	p.device = dev;
-	int r = upload(p);
-	if (r) return r;
-	plans.push_back(std::move(p));
-	*out = &plans.back();
-	return 0;
+	return plans.get(dev, RateSps(samp_rate, sps), out, [&](Plan *p) {
+		std::string why;
+		return plan_numbers(samp_rate, sps, p, &why) ? upload_plan(*p) : fail(-EINVAL, "%s", why.c_str());
+	});
 }
 
 }  // namespace

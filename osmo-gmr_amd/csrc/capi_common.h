@@ -33,6 +33,22 @@ int conv_acc();
 			                    hipGetErrorString(e_));                                \
 	} while (0)
 
+// a vector to a new device buffer, as it lies (blocking): what the per-device caches' makers upload with (dev_cache.h).
+// Frees the buffer if the copy fails; *dst is null after any failure.
+template <typename T, typename D> static int upload(D **dst, const std::vector<T> &v)
+{
+	static_assert(sizeof(T) == sizeof(D), "uploaded as it lies");
+	*dst = nullptr;
+	HIP_TRY(hipMalloc(dst, v.size() * sizeof(T)));
+	const hipError_t e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+	if (e != hipSuccess) {
+		(void)hipFree(*dst);
+		*dst = nullptr;
+		return fail(e == hipErrorNoDevice ? -ENODEV : -EIO, "upload: hipMemcpy: %s", hipGetErrorString(e));
+	}
+	return 0;
+}
+
 struct DevState {
 	bool ready = false;       // constant tables uploaded to this device
 	void *ws = nullptr;       // grow-only scratch for kernels that need workspace
@@ -116,6 +132,16 @@ int demod_host_impl(int type, const DevBurst &ht, const DevBurst *custom,
                     float *toa, float *freq_err, float *ssyms, int32_t *rv);
 // the profiling switch GMR1_HIP_DBG_STOP (RxArgs::dbg_stop; 0 in the product build), read once (capi_demod.cpp)
 int dbg_stop_env();
+
+// One encode of n units of chain `id` (enc_plan.h's PlanId) through k_encode (capi_encode.cpp): what a chain does not take
+// stays null.  encode_dev: device pointers, enqueued on `st`.  encode_host: host pointers staged through HBM, blocking.
+struct EncIo { const uint8_t *in0, *in1, *aux0, *aux1, *ciph; uint8_t *ebits; };
+#pragma GCC visibility push(hidden)
+int encode_dev(hipStream_t st, int id, int n, int seq_len, const EncIo &io, const char *what);
+int encode_host(int id, int n, int seq_len, const EncIo &io, const char *what);
+// the chain of a gmr1_tch9_mode, -1 for none (capi_encode.cpp)
+int tch9_plan(int mode);
+#pragma GCC visibility pop
 
 // BCCH / CCCH batch decode, chain = kChainBcch / kChainCcch (capi_l1.cpp): device pointers; host pointers, blocking
 int l1_dev(hipStream_t st, int chain, int n, const int8_t *ebits, uint8_t *l2, int32_t *crc, int32_t *conv);

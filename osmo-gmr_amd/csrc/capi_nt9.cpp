@@ -5,40 +5,27 @@
 
 #include "capi_common.h"
 
-#include <mutex>
-#include <vector>
-
 #include "../../include/gmr1_hip.h"
 #include "../../include/osmocom/gmr1/l1/facch9.h"
 #include "../../include/osmocom/gmr1/l1/interleave.h"
 #include "../../include/osmocom/gmr1/l1/tch9.h"
+#include "dev_cache.h"
 #include "nt9_map.h"
 
 using namespace gmr1;
 
 namespace {
 
-std::mutex g_mu;
-struct DevMap { int device; int kind; uint32_t *d; };
-std::vector<DevMap> g_maps;
+DevCache<int, uint32_t *> g_maps;
 
 int get_map(int kind, const uint32_t **out)
 {
 	int dev = 0;
 	HIP_TRY(hipGetDevice(&dev));
-	std::lock_guard<std::mutex> lk(g_mu);
-	for (const DevMap &m : g_maps)
-		if (m.device == dev && m.kind == kind) {
-			*out = m.d;
-			return 0;
-		}
-	const std::vector<uint32_t> map = nt9_build_map(kind);
-	uint32_t *d = nullptr;
-	HIP_TRY(hipMalloc(&d, map.size() * 4));
-	HIP_TRY(hipMemcpy(d, map.data(), map.size() * 4, hipMemcpyHostToDevice));
-	g_maps.push_back({dev, kind, d});
-	*out = d;
-	return 0;
+	uint32_t *const *d;
+	const int r = g_maps.get(dev, kind, &d, [kind](uint32_t **m) { return upload(m, nt9_build_map(kind)); });
+	if (!r) *out = *d;
+	return r;
 }
 
 int nt9_dev(hipStream_t st, int kind, int n, int seq_len, const int8_t *ebits, const uint8_t *ciph,
@@ -179,10 +166,9 @@ int gmr1_facch9_decode(uint8_t *l2, sbit_t *bits_sacch, sbit_t *bits_status,
 }
 
 // ---- the reference's stateful single-burst TCH9 call (tch9.h:47-50, interleave.h:40-56) -----------------
-// The history the depth-3 de-interleaver needs is kept as the previous two bursts AS RECEIVED (662 soft
-// bits + 658 key stream bits each); every call decodes the three-burst sequence on the GPU, where the
-// de-interleaving is part of the gather (nt9_kernels.hip), and returns the newest burst's outputs.
-static constexpr int kIlSlot = 662 + 658;
+// The history the depth-3 de-interleaver needs is kept as the previous two bursts AS RECEIVED (kNt9IlSlot,
+// nt9_map.h); every call decodes the three-burst sequence on the GPU, where the de-interleaving is part of
+// the gather (nt9_kernels.hip), and returns the newest burst's outputs.
 
 int gmr1_interleaver_init(struct gmr1_interleaver *il, int N, int K)
 {
@@ -191,7 +177,7 @@ int gmr1_interleaver_init(struct gmr1_interleaver *il, int N, int K)
 	std::memset(il, 0, sizeof(*il));
 	if (N != 3 || K != 648)
 		return fail(-EINVAL, "gmr1_interleaver_init: only the (3, 648) geometry of TCH9 is provided");
-	uint8_t *b = static_cast<uint8_t *>(std::calloc(2, kIlSlot));
+	uint8_t *b = static_cast<uint8_t *>(std::calloc(2, kNt9IlSlot));
 	if (!b)
 		return fail(-ENOMEM, "gmr1_interleaver_init: out of memory");
 	il->N = N;
@@ -211,14 +197,13 @@ void gmr1_interleaver_fini(struct gmr1_interleaver *il)
 void gmr1_tch9_decode(uint8_t *l2, sbit_t *bits_sacch, sbit_t *bits_status, const sbit_t *bits_e,
                       enum gmr1_tch9_mode mode, const ubit_t *ciph, struct gmr1_interleaver *il, int *conv_rv)
 {
-	static const int kBytes[3] = {18, 30, 60};
 	if (!l2 || !bits_e || !il || !il->bits_cpp || il->N != 3 || il->K != 648 || (int)mode < 0 || (int)mode > 2) {
 		(void)fail(-EINVAL, "gmr1_tch9_decode: bad argument");
 		return;
 	}
-	const int nb = kBytes[(int)mode];
+	const int nb = kNt9Kinds[(int)mode].l2_bytes;
 	// sequence = [burst n-2, burst n-1, this burst]; slot (n & 1) holds burst n-2
-	uint8_t *older = il->bits_cpp + (size_t)(il->n & 1) * kIlSlot, *newer = il->bits_cpp + (size_t)((il->n + 1) & 1) * kIlSlot;
+	uint8_t *older = il->bits_cpp + (size_t)(il->n & 1) * kNt9IlSlot, *newer = il->bits_cpp + (size_t)((il->n + 1) & 1) * kNt9IlSlot;
 	int8_t seq_e[3 * 662];
 	uint8_t seq_c[3 * 658];
 	std::memcpy(seq_e, older, 662);

@@ -15,12 +15,10 @@ static_assert(kPlanMaxChans == kPfbMaxChans && kPlanMaxBlocks == kPfbMaxBlocks &
 static_assert(sizeof(F2) == sizeof(float2), "F2 is uploaded as float2");
 
 struct ChanPlan : ChanNumbers {
-	int device = -1;
 	float *d_taps = nullptr;
 	float2 *d_bank = nullptr, *d_pre_bank = nullptr;
 };
 struct DdcPlan : DdcNumbers {
-	int device = -1;
 	float2 *d_taps2 = nullptr;               // real taps as (t, 0)
 	float2 *d_bank = nullptr;
 };

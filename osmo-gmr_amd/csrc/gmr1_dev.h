@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "enc_plan.h"
 #include "gmr1_hip.h"
 #include "rx_loop.h"
 
@@ -554,24 +555,8 @@ hipError_t launch_xch(const XchArgs &a, hipStream_t stream);
 // ---- transmit direction (tx_kernels.hip): the channel encoders and the 1-sample-per-symbol modulator ------
 // Every GMR-1 channel coder is a fixed GF(2)-linear map from payload bits to burst bits (CRC, feed-forward
 // convolutional code, puncturing, interleavers, scrambler, multiplexing).  The host writes that map down once
-// per channel as an EncPlan (capi_tx.cpp); one generic kernel evaluates it, one unit (burst, or group of four
-// FACCH3 bursts) per wave.
-constexpr int kEncMaxIn = 64;          // payload bytes of one unit (TCH9 9k6: 60)
-constexpr int kEncMaxExt = 512;        // bits of the extended information word (TCH9 9k6: 480 + 8)
-constexpr int kEncMaxOut = 672;        // burst bits of one unit (NT9: 662)
-struct EncPlan {
-	int32_t n_in0, n_in1;              // payload bytes per unit: first / second input array
-	int32_t n_ext;                     // extended information word: [K-1 preset bits | info + CRC | flush zeros] ...
-	int32_t n_out;                     // burst bits written per unit
-	int32_t n_aux0, n_aux1;            // multiplexed-in bits per unit (status / SACCH): first / second array
-	int32_t n_ciph;                    // keystream bits per unit
-	int32_t depth;                     // 1, or 3: inter-burst interleaver (bursts n, n-1, n-2 of a run)
-	uint32_t poly[8];                  // window masks over K consecutive bits of the extended word
-	uint16_t crc_tab[kEncMaxIn * 8];   // what payload bit b adds to CRC register A (the CRCs are linear: init 0, no final xor)
-	uint16_t crc_tab2[kEncMaxIn * 8];  // the same for CRC register B (RACH: CRC12), else zeros
-	uint16_t ext_src[kEncMaxExt];      // where every bit of the extended word comes from (see tx_kernels.hip)
-	uint32_t out[kEncMaxOut];          // descriptor of every burst bit (see tx_kernels.hip)
-};
+// per channel as an EncPlan (enc_plan.h, enc_plan.cpp); one generic kernel evaluates it, one unit (burst, or group of
+// four FACCH3 bursts) per wave.
 struct EncArgs {
 	int n;                             // units
 	int seq_len;                       // depth 3: units per interleaver run (state starts empty at each run)

@@ -1,7 +1,7 @@
 // l1_tables.cpp -- the code description objects of libgmr1-l1's API (reference include/osmocom/gmr1/l1/conv.h:36-44,
 // l1/punct.h:54-106, l1/crc.h:36-38), exported for consumers that drive libosmocore's own encoder / decoder with them.
 // They are expanded at compile time from l1_codes.h, the description the GPU path reads as well: the kernels' table
-// makers, the NT9 gather maps (nt9_map.h) and the encoder plans (capi_tx.cpp) take their polynomials, masks and CRCs
+// makers, the NT9 gather maps (nt9_map.h) and the encoder plans (enc_plan.cpp) take their polynomials, masks and CRCs
 // from the same header.
 //
 // A trellis is its generator polynomials (bit i = D^i; the output word has g0 in its MSB), a puncturing scheme is the

@@ -17,6 +17,11 @@ constexpr Nt9Kind kNt9Kinds[4] = {
 	{2, 316, 38, 80, 4, 0},     // FACCH9:   k5_12 len 316, facch9.c:42-48, 4 + 4 pad bits
 };
 
+// One of the two private slots behind gmr1_interleaver::bits_cpp (gmr1_interleaver_init, capi_nt9.cpp), which the stateful
+// single-burst TCH9 calls keep their history of two bursts in.  gmr1_tch9_decode: a burst as received, 662 soft bits then
+// the 658 key stream bits.  gmr1_tch9_encode (capi_tx_ref.cpp): a burst's payload, the first l2_bytes of the slot.
+constexpr int kNt9IlSlot = 662 + 658;
+
 // per unpunctured coded bit of the kind's (len + 4) * N: 1 = not sent (FACCH9 punctures nothing)
 inline std::vector<uint8_t> nt9_punctured(int kind)
 {

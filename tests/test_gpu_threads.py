@@ -74,3 +74,63 @@ def test_two_threads_share_the_device_workspace(gpu_api, orc, pkg):
         t.join(500)
     assert not errs, errs
     assert out.get("a") and out.get("b")
+
+
+def test_four_threads_make_their_first_transmit_calls_together(gpu_api, orc, pkg):
+    """Four threads leave a barrier into four different calls, each of which asks a per-device cache (csrc/dev_cache.h) for a
+    table it builds and uploads on first use: a BCCH encoder plan, the TCH9 9k6 plan, the BCCH format's modulator tables, an
+    NT9 gather map.  Run alone, these are the process's first such calls, so the four builds race; within the suite the
+    lookups do.  Every result is what the oracle gives; the shaped windows lie within test_gpu_mod_shaped's derived bound of
+    its float64 restatement over the oracle's symbols."""
+    from test_gpu_mod_shaped import restate
+    rng = np.random.default_rng(41)
+    l2_b = rng.integers(0, 256, (5, 24), dtype=np.uint8)
+    l2_t = rng.integers(0, 256, (6, 60), dtype=np.uint8)
+    sa, stt = rng.integers(0, 2, (6, 10), dtype=np.uint8), rng.integers(0, 2, (6, 4), dtype=np.uint8)
+    ciph = rng.integers(0, 2, (6, 658), dtype=np.uint8)
+    info = gpu_api.burst_info("bcch")
+    bits = rng.integers(0, 2, (3, info.ebits), dtype=np.uint8)
+    sps, span, in_len = 4, 4, info.len * 4 + 16
+    start = np.array([8, 6, 10], np.int32)
+    l2_d = rng.integers(0, 256, (6, 30), dtype=np.uint8)
+    c_d = rng.integers(0, 2, (6, 658), dtype=np.uint8)
+    hard = np.concatenate([orc.tch9_encode_seq(l2_d[r:r + 3], 1, sa[r:r + 3], stt[r:r + 3], c_d[r:r + 3]) for r in (0, 3)])
+    eb = (127 * (1 - 2 * hard.astype(np.int16))).astype(np.int8)
+    with gpu_api.conv_decoder(gpu_api.CONV_GENERIC), orc.conv_mode(0):
+        want = {
+            "bcch": orc.bcch_encode(l2_b),
+            "tch9": np.concatenate([orc.tch9_encode_seq(l2_t[r:r + 3], 2, sa[r:r + 3], stt[r:r + 3], ciph[r:r + 3]) for r in (0, 3)]),
+            "nt9": [np.concatenate([orc.tch9_decode_seq(eb[r:r + 3], 1, c_d[r:r + 3])[k] for r in (0, 3)]) for k in range(4)],
+        }
+        sym = np.stack([orc.mod("bcch", bits[i], 0) for i in range(3)])
+        shaped, bound = restate(pkg.synth, sym, sps, in_len, "rc", span, start=start)
+        calls = {
+            "bcch": lambda: gpu_api.bcch_encode_batch(l2_b),
+            "tch9": lambda: gpu_api.tch9_encode_batch(l2_t, 2, 3, sa, stt, ciph),
+            "mod": lambda: gpu_api.mod_shaped_batch("bcch", bits, sps, in_len, span=span, start=start),
+            "nt9": lambda: gpu_api.tch9_decode_batch(eb, 1, 3, c_d),
+        }
+        go = threading.Barrier(len(calls))
+        got, errs = {}, []
+
+        def run(name):
+            try:
+                go.wait()
+                got[name] = calls[name]()
+            except BaseException as e:      # noqa: BLE001 - reported by the main thread
+                errs.append((name, repr(e)))
+
+        ts = [threading.Thread(target=run, args=(name,)) for name in calls]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join(60)
+    assert not errs, errs
+    assert sorted(got) == sorted(calls)
+    assert np.array_equal(got["bcch"], want["bcch"])
+    assert np.array_equal(got["tch9"], want["tch9"])
+    assert np.array_equal(want["nt9"][0][2::3], l2_d[0::3]), "the oracle's own decode gives back what was sent"
+    for g, w in zip(got["nt9"], want["nt9"]):
+        assert np.array_equal(g, w)
+    assert bound.max() > 0 and not got["mod"][bound == 0].any()
+    assert (np.abs(got["mod"].astype(np.complex128) - shaped) <= bound).all()

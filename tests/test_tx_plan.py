@@ -1,4 +1,4 @@
-"""The encoder position maps (struct EncPlan, built on the host by csrc/capi_tx.cpp) evaluated bit by bit in
+"""The encoder position maps (struct EncPlan, built on the host by csrc/enc_plan.cpp) evaluated bit by bit in
 numpy -- the same three steps k_encode runs (tx_kernels.hip) -- against the CPU oracle's encoders.  No GPU needed:
 this pins the host logic of the transmit direction; tests/test_gpu_tx.py runs the kernel itself."""
 import numpy as np
