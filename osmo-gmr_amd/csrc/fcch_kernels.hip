@@ -534,8 +534,12 @@ __global__ __launch_bounds__(256) void k_fcch_sweep(FcchRoughArgs a)
 				double var = dq / n - (ar * ar + ai * ai);
 				if (var < 0.0) var = 0.0;
 				float sd = sqrtf((float)var);
-				if (sd == 0.0f) sd = 1.0f;
-				s_stat[2] = 1.0f / sd;
+				// (no deviation: the reference's normalised window is then all zero and so is every lag's energy; here the raw
+				// sum and the mean's correction below would cancel only to rounding and leave energies of 1e-14, which
+				// rough_multi took for a signal: count 0 for a constant window, not -EINVAL.  var comes from float32 partials, so
+				// a window whose offset is a thousand times its signal can end here too: its answer was rounding before as well.
+				// k_fcch_corr and k_fcch_fine subtract the mean sample by sample, exactly: they keep sd = 1)
+				s_stat[2] = sd == 0.0f ? 0.0f : 1.0f / sd;
 				s_stat[0] = (float)ar * rr - (float)ai * ri;
 				s_stat[1] = (float)ar * ri + (float)ai * rr;
 				s_have = have ? 1 : 0;
@@ -784,8 +788,8 @@ __global__ __launch_bounds__(256) void k_fcch_energy(FcchRoughArgs a, int kEnerg
 			double var = dq / n - (ar * ar + ai * ai);
 			if (var < 0.0) var = 0.0;
 			float sd = sqrtf((float)var);
-			if (sd == 0.0f) sd = 1.0f;
-			s_stat[2] = 1.0f / sd;
+			// (no deviation: the window is its mean, every energy is 0 -- see k_fcch_sweep)
+			s_stat[2] = sd == 0.0f ? 0.0f : 1.0f / sd;
 			// mu * sum_n r[n] e^{j fs n}
 			s_stat[0] = (float)ar * rr - (float)ai * ri;
 			s_stat[1] = (float)ar * ri + (float)ai * rr;

@@ -9,37 +9,7 @@ import acq_cases as ac
 
 pytestmark = pytest.mark.gpu
 
-INT_FIELDS = ("status", "n_chains", "n_cand", "align", "base_align")
-
-
-def _check(name, got, want):
-    """one record against the oracle's: integers equal, frequencies within 1e-4, SNR within 2e-4 relative (the bounds of
-    tests/test_gpu_fcch.py for the single stages), unused slots exactly 0"""
-    for k in INT_FIELDS:
-        assert int(got[k]) == int(want[k]), (name, k, int(got[k]), int(want[k]))
-    nc = int(want["n_chains"])
-    assert list(got["chain_align"]) == list(want["chain_align"]), (name, got["chain_align"], want["chain_align"])
-    assert abs(float(got["freq_err"]) - float(want["freq_err"])) < 1e-4, (name, got["freq_err"], want["freq_err"])
-    for j in range(nc):
-        g, w = float(got["chain_freq_err"][j]), float(want["chain_freq_err"][j])
-        assert abs(g - w) < 1e-4, (name, j, g, w)
-        g, w = float(got["chain_snr"][j]), float(want["chain_snr"][j])
-        assert abs(g - w) <= 2e-4 * max(1.0, abs(w)), (name, j, g, w)
-    for k in ("chain_align", "chain_freq_err", "chain_snr"):
-        assert not got[k][nc:].view(np.uint32).any(), (name, k, got[k])
-    if int(want["status"]):
-        assert not bytes(got.tobytes()[4:]).strip(b"\0"), name
-
-
-def _expect(orc, cases, sps=ac.SPS, which="fcch"):
-    """[(name, samples, start)] -> the oracle's records; every survivor decision in them is at least MARGIN off its threshold"""
-    want = []
-    for name, x, start in cases:
-        rec, margins = ac.expected(orc, x, sps, start, which)
-        for m in margins:
-            assert min(m) >= ac.MARGIN, (name, m)
-        want.append(rec)
-    return want
+_check, _expect = ac.check_record, ac.expected_all
 
 
 @pytest.fixture(scope="module")
